@@ -16,8 +16,15 @@ Workloads (`--workload`; default c3 on one GPU, c5 on several): c2 = greedy deco
 beamed decode (configs[2]), c4 = train step of configs[3], c5 = configs[4]'s shape (8192 lines per GPU per step, decoded in
 1024-line batches, one all-gather per step), page = the OCR-D processor's call (wrapper/transcode.py:110-115 with the
 defaults of wrapper/ocrd-tool.json: depth 2, width 512, V 640, one page of 40 confusion-network lines, 256 hypotheses per
-step, alignments requested).  The default one-GPU run also times c2, c4 and page after the headline's timed region (child
-processes, bounded) and reports them under "other_workloads".
+step, alignments requested).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes time of its own: the roofline
+(HIP events around launches of the dominant kernel, inside the timed region), per-kernel times of one extra untimed step, the
+CPU baseline, the train step's vendor-GEMM calibration and, on one GPU with the default workload, c2, c4, page and c3 under
+`--arithmetic fp32` after the headline's timed region (child processes, bounded) under "other_workloads".
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64; the inputs are
+seeded, so two builds can be compared array for array).
 
 Prints ONE JSON line on rank 0.
 """
@@ -45,6 +52,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3           # MI355X_MICROARCH.md, v_mfma_f32_32x32x2
 PEAK_BF16_MFMA_TFLOPS = 2516.6         # dense bf16: 16x the fp32-input rate (v_mfma_f32_32x32x16_bf16: 32 768 FLOP in 32 cycles per SIMD at 2.4 GHz)
 PEAK_HBM_BYTES_PER_S = 8.0e12          # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 METRIC = 'corrected chars/sec (whole node) at beam=8, depth-4 width-512, 100-char lines'
+DUMP_BUDGET_BYTES = 64 << 20           # --dump-outputs: larger outputs are written as a fixed, seeded sample of their lines
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -400,6 +408,72 @@ def cpu_baseline(cfg, emb, lines, batch_size, fast, length=LENGTH, budget_s=60.0
 
 
 # ------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step handed its caller
+# ------------------------------------------------------------------------------------------------------
+def decode_output_arrays(texts, probs, scores, aligns=None):
+    """The return values of `correct_lines` as finite arrays with one row per line: `chars` = the strings' code points (-1 past a
+    line's end), `lengths` = the strings' lengths, `probs` = the per-character probabilities (0 past the end), `scores`; where
+    alignments were returned, `alignments` = every line's rows one after the other (zero-padded to the widest; the NaN entries
+    of a row -- a window past the end of the line -- as 0), `alignment_nan` = how many NaN entries each row had, and
+    `alignment_rows` = how many rows each line has."""
+    import numpy as np
+    n = len(texts)
+    width = max([len(t) for t in texts] + [len(p) for p in probs] + [1])
+    chars, prob = np.full((n, width), -1.0), np.zeros((n, width))
+    for j, (t, p) in enumerate(zip(texts, probs)):
+        chars[j, :len(t)] = np.frombuffer(t.encode('utf-32-le', 'surrogatepass'), np.uint32)
+        prob[j, :len(p)] = p
+    out = {'chars': chars, 'lengths': np.array([len(t) for t in texts], np.float64), 'probs': prob,
+           'scores': np.asarray(scores, np.float64)}
+    if aligns is not None and any(len(a) for a in aligns):
+        dense = [np.asarray(a, np.float32).reshape(len(a), -1) if len(a) else np.zeros((0, 1), np.float32) for a in aligns]
+        cols = max(d.shape[1] for d in dense)
+        rows = np.concatenate([np.pad(d, ((0, 0), (0, cols - d.shape[1]))) for d in dense])
+        out['alignments'] = np.where(np.isnan(rows), np.float32(0), rows)
+        out['alignment_nan'] = np.isnan(rows).sum(axis=1).astype(np.float64)
+        out['alignment_rows'] = np.array([len(d) for d in dense], np.float64)
+    return out
+
+
+def train_output_arrays(loss, norm, weights, per_tensor=16384):
+    """What the train step returns (loss, gradient norm) and a fixed, seeded sample of the weights it updated: up to
+    `per_tensor` values of every tensor, tensors in name order, concatenated."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    parts = []
+    for name in sorted(weights):
+        w = np.asarray(weights[name], np.float32).ravel()
+        parts.append(w[np.sort(rng.choice(w.size, per_tensor, replace=False))] if w.size > per_tensor else w)
+    return {'loss': np.array([loss], np.float64), 'grad_norm': np.array([norm], np.float64),
+            'weights_sample': np.concatenate(parts)}
+
+
+def write_outputs(path, arrays, per_line=()):
+    """Save every array as path/<name>.npy.  Where they would exceed DUMP_BUDGET_BYTES, the arrays named in `per_line` (one row
+    per line) keep a fixed, seeded sample of their rows, and `sampled_lines.npy` lists which."""
+    import numpy as np
+    line_bytes = sum(arrays[k].nbytes for k in per_line)
+    other = sum(a.nbytes for a in arrays.values()) - line_bytes
+    if line_bytes + other > DUMP_BUDGET_BYTES and per_line:
+        n = len(arrays[per_line[0]])
+        k = max(1, int(n * (DUMP_BUDGET_BYTES - other - 8 * n) // line_bytes))
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        arrays = dict(arrays, **{name: arrays[name][rows] for name in per_line})
+        arrays['sampled_lines'] = rows.astype(np.float64)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the budget of %d' % (sum(a.nbytes for a in arrays.values()), DUMP_BUDGET_BYTES))
+    bad = [name for name, a in arrays.items() if a.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise TypeError('--dump-outputs writes float32 / float64 only, not %s' % bad)
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise ValueError('--dump-outputs: not finite: %s' % bad)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+# ------------------------------------------------------------------------------------------------------
 def train_bench(args):
     """BASELINE configs[3]: depth 4, width 512, teacher-forced train step (forward + backward + clip + Adam) on 512
     lines of 100 characters (targets = sources with 5 % substitutions), dropout 0.2.  One GPU."""
@@ -466,23 +540,27 @@ def train_bench(args):
         loss, norm = one_step()
     eng.synchronize()
     elapsed = time.perf_counter() - t0
-    # the GEMMs' own time: a second pass over the same steps with HIP events around every launch (kept out of the timed
-    # region: ~1300 event pairs per step keep consecutive kernels from overlapping and cost 6.5 ms of a 75 ms step)
-    eng.profile(True)
-    for _ in range(args.steps):
-        one_step()
-    eng.synchronize()
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, train_output_arrays(loss, norm, eng.train_weights()))
+    if args.full:
+        # the GEMMs' own time: a second pass over the same steps with HIP events around every launch (kept out of the timed
+        # region: ~1300 event pairs per step keep consecutive kernels from overlapping and cost 6.5 ms of a 75 ms step)
+        eng.profile(True)
+        for _ in range(args.steps):
+            one_step()
+        eng.synchronize()
     if facade is not None:
         facade.close()
         os.unlink(tmp.name)
-    pl, pg, ps = eng.profile_read('lstm_gemm'), eng.profile_read('gemm'), eng.profile_read('lstm_gemm_small')
-    pp = eng.profile_read('persist')
-    eng.profile(False)
+    if args.full:
+        pl, pg, ps = eng.profile_read('lstm_gemm'), eng.profile_read('gemm'), eng.profile_read('lstm_gemm_small')
+        pp = eng.profile_read('persist')
+        eng.profile(False)
     # calibration, outside the timed region: the same step with the plain whole-sequence contractions handed to the vendor's
     # library (hipBLASLt, option "vendor_gemm"; never the default, never in `value`)
     vendor_default = int(os.environ.get('CASV_OPT_VENDOR_GEMM', '0'))
     calibration = None
-    if facade is None and not vendor_default and not os.environ.get('CASV_BENCH_NO_CALIBRATION'):    # (the variable: profiles of the default path alone)
+    if args.full and facade is None and not vendor_default and not os.environ.get('CASV_BENCH_NO_CALIBRATION'):    # (the variable: profiles of the default path alone)
         eng.set_option('vendor_gemm', 1)
         for _ in range(2):
             one_step()
@@ -494,9 +572,8 @@ def train_bench(args):
         calibration = {'vendor_gemm_ms_per_step': 1e3 * (time.perf_counter() - t1) / args.steps,
                        'note': 'plain whole-sequence contractions through hipBLASLt instead of csrc/gemm.hip; everything else unchanged'}
         eng.set_option('vendor_gemm', 0)
-    fl, ms = pl['flops'] + pg['flops'] + ps['flops'] + pp['flops'], pl['ms'] + pg['ms'] + ps['ms'] + pp['ms']
     cpu = None
-    if not args.no_cpu_baseline and facade is None:
+    if args.full and not args.no_cpu_baseline and facade is None:
         # the oracle's train step (numpy fp32: forward, hand-derived BPTT, clip, Adam) on a bounded sample of the same batch, host cores
         from oracle import make_weights as oracle_weights
         from oracle.train import forward_backward, adam_step
@@ -528,7 +605,7 @@ def train_bench(args):
                           'over this command, all kernels of a step, not a measurement of this run' % (tj.get('round', '?'), tj.get('commit', '?')))
     except Exception:
         pass
-    emit(json.dumps({
+    line = {
         'metric': 'trained chars/sec (1 GPU), depth-4 width-512 teacher-forced train step, 100-char lines',
         'value': B * LENGTH * args.steps / elapsed, 'unit': 'chars/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -537,14 +614,18 @@ def train_bench(args):
                    'batches': 'read from a TSV file and vectorised by the worker thread of train() (training.prefetch)' if args.facade
                               else 'one synthetic batch, resident on the host', 'last_loss': loss, 'last_grad_norm': norm,
                    'vendor_gemm': vendor_default},
-        'calibration': calibration, 'cpu_baseline': cpu,
-        'roofline': {'bound': 'mfma', 'kernel': 'all GEMMs of the step (incl. the persistent recurrences: %.1f ms in %d launches)' % (pp['ms'] / max(args.steps, 1), pp['launches'] // max(args.steps, 1)), 'achieved': fl / max(ms, 1e-9) / 1e9,
-                     'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': fl / max(ms, 1e-9) / 1e9 / PEAK_F32_MFMA_TFLOPS,
-                     'traffic': traffic, 'traffic_per': 'train step (all kernels)', 'traffic_source': traffic_source,
-                     'launches': pl['launches'] + pg['launches'] + ps['launches'] + pp['launches'],
-                     # the whole step priced with SURVEY.md section 8(d)'s ~133 MFLOP per trained character
-                     'whole_path': {'flop_per_char': 133e6,
-                                    'frac': B * LENGTH * args.steps / elapsed * 133e6 / 1e12 / PEAK_F32_MFMA_TFLOPS}}}))
+        'calibration': calibration, 'cpu_baseline': cpu}
+    if args.full:
+        fl, ms = pl['flops'] + pg['flops'] + ps['flops'] + pp['flops'], pl['ms'] + pg['ms'] + ps['ms'] + pp['ms']
+        line['roofline'] = {
+            'bound': 'mfma', 'kernel': 'all GEMMs of the step (incl. the persistent recurrences: %.1f ms in %d launches)' % (pp['ms'] / max(args.steps, 1), pp['launches'] // max(args.steps, 1)), 'achieved': fl / max(ms, 1e-9) / 1e9,
+            'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': fl / max(ms, 1e-9) / 1e9 / PEAK_F32_MFMA_TFLOPS,
+            'traffic': traffic, 'traffic_per': 'train step (all kernels)', 'traffic_source': traffic_source,
+            'launches': pl['launches'] + pg['launches'] + ps['launches'] + pp['launches'],
+            # the whole step priced with SURVEY.md section 8(d)'s ~133 MFLOP per trained character
+            'whole_path': {'flop_per_char': 133e6,
+                           'frac': B * LENGTH * args.steps / elapsed * 133e6 / 1e12 / PEAK_F32_MFMA_TFLOPS}}
+    emit(json.dumps(line))
     return 0
 
 
@@ -651,7 +732,7 @@ def decode_bench(args):
         cfg = weights = None
 
         def decode(chunk):
-            return chunk, [[1.0] * len(t) for t in chunk], [0.0] * len(chunk)
+            return chunk, [[1.0] * len(t) for t in chunk], [0.0] * len(chunk), [[] for _ in chunk]
         sync_dev = lambda: None
     else:
         s2s, cfg, weights = make_model(local_rank, wl['depth'], wl['width'], wl['n'], wl['emb'], V)
@@ -683,9 +764,8 @@ def decode_bench(args):
                         if len(a):
                             alignment2path(a, sum(max((len(x[0]) for x in c), default=0) for c in line), len(text), 1. / V)
                     t_realign[0] += time.perf_counter() - t0
-                return out, probs, scores
-            out, probs, scores, al = s2s.correct_lines(chunk, fast=wl['fast'], greedy=wl['fast'], alignments=want_align)
-            return out, probs, scores
+                return out, probs, scores, al
+            return s2s.correct_lines(chunk, fast=wl['fast'], greedy=wl['fast'], alignments=want_align)
         sync_dev = eng.synchronize
     t_gather = [0.0]
 
@@ -698,18 +778,18 @@ def decode_bench(args):
             eng.records_append(k * batch)
 
     def step():
-        out_lines, probs, scores = [], [], []
+        out_lines, probs, scores, aligns = [], [], [], []
         if dist_on and records == 'device':
             eng.records_reset(per_rank, S)
         if dry or wl.get('confmat') or len(chunks) == 1:
             for k, chunk in enumerate(chunks):
-                o, p, s = decode(chunk)
+                o, p, s, a = decode(chunk)
                 append_records(k)
-                out_lines += o; probs += p; scores += s
+                out_lines += o; probs += p; scores += s; aligns += a
         else:
             # several batches per step (configs[4]): batch k + 1 is vectorised and decoded while the strings of batch k are built
-            for o, p, s, _ in s2s.correct_batches(chunks, fast=wl['fast'], greedy=wl['fast'], alignments=want_align, after_decode=append_records):
-                out_lines += o; probs += p; scores += s
+            for o, p, s, a in s2s.correct_batches(chunks, fast=wl['fast'], greedy=wl['fast'], alignments=want_align, after_decode=append_records):
+                out_lines += o; probs += p; scores += s; aligns += a
         if dist_on:
             # fixed-width records (characters, probabilities, length, score) -> RCCL all-gather
             t0 = time.perf_counter()
@@ -721,7 +801,7 @@ def decode_bench(args):
                 got = comm.all_gather_records(rec, len(all_lines)) if comm else sharding.all_gather_records(rec, len(all_lines), device=device)
             t_gather[0] += time.perf_counter() - t0
             return got
-        return out_lines
+        return out_lines, probs, scores, aligns
 
     def sync():
         sync_dev()
@@ -752,7 +832,7 @@ def decode_bench(args):
             for _ in range(n):
                 for chunk in chunks:
                     yield (chunk, chunk) if confmat else chunk
-        out_lines, last = [], None
+        out, last = ([], [], [], []), None
         for k, (o, p, sc, al) in enumerate(s2s.correct_batches(batches(), fast=fast, greedy=fast, alignments=want_align)):
             if confmat and want_align:
                 from cor_asv_ann_amd.realign import alignment2path
@@ -761,14 +841,15 @@ def decode_bench(args):
                     if len(a):
                         alignment2path(a, sum(max((len(x[0]) for x in c), default=0) for c in line), len(text), 1. / V)
                 t_realign[0] += time.perf_counter() - t1
-            out_lines += o
+            for acc, part in zip(out, (o, p, sc, al)):
+                acc += part
             if (k + 1) % len(chunks) == 0:
-                last, out_lines = out_lines, []
+                last, out = out, ([], [], [], [])
         return last
 
     dom = 'lstm_gemm' if (args.workload != 'c2' or split_mode) else 'persist'
     run_steps(args.warmup)
-    if eng:
+    if eng and args.full:
         # HIP events around launches of the dominant kernel, on the library's stream: around every 13th of them (level 3) --
         # an event pair keeps the next launch from overlapping the kernel's tail, which costs ~8 us per pair: around every
         # launch (level 2) the timed region of c3 is 2 % slower than without events
@@ -783,8 +864,15 @@ def decode_bench(args):
     sync()
     elapsed = time.perf_counter() - t0
     realign_ms = 1e3 * t_realign[0] / max(args.steps, 1)
+    if rank == 0 and args.dump_outputs:
+        got = last
+        if dist_on:                    # the gathered records of every rank's lines -> the strings, probabilities and scores again
+            idx, prob, length, score, _ = sharding.unpack_records(last)
+            got = (sharding.records_to_strings(idx, length, make_vocabulary(V)[1]), [prob[j, :length[j]] for j in range(len(idx))],
+                   score, None)
+        write_outputs(args.dump_outputs, decode_output_arrays(*got), per_line=('chars', 'lengths', 'probs', 'scores'))
     prof, others = None, {}
-    if eng:
+    if eng and args.full:
         prof = eng.profile_read(dom)
         eng.profile(1)                 # one extra, untimed step with events around every kernel class
         run_steps(1)
@@ -906,7 +994,7 @@ def decode_bench(args):
             rl['whole_path']['frac_bf16'] = 6.0 * chars / elapsed * xpc / 1e12 / world / PEAK_BF16_MFMA_TFLOPS
         if others:
             result['kernel_ms_per_step'] = {k: v['ms'] for k, v in others.items()}     # from one extra untimed step
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and not dry:
             beam = {('rejection_threshold' if k == 'rejection' else k): wl[k] for k in ('rejection', 'beam_width_in', 'beam_threshold_in') if k in wl}
             try:
                 result['cpu_baseline'] = cpu_baseline(cfg, wl['emb'], all_lines[:256], wl['n'] if not wl['fast'] else 256, wl['fast'], L,
@@ -923,7 +1011,7 @@ def decode_bench(args):
         s2s.engine.close()              # free the device memory before the other workloads run as child processes
         s2s.engine = None
     if rank == 0:
-        if world == 1 and not dist_on and args.workload == 'c3' and not args.no_others and not dry:
+        if world == 1 and not dist_on and args.workload == 'c3' and args.full and not args.no_others and not dry:
             result['other_workloads'] = other_workloads(not args.no_cpu_baseline)
         emit(json.dumps(result))
     return 0
@@ -939,7 +1027,7 @@ def other_workloads(with_cpu_baseline=True):
                         # the headline's workload with every launch on the fp32-input matrix instruction (the library's only arithmetic
                         # until round 5; Sequence2Sequence.arithmetic = 'fp32'): the figure beside the default's
                         ('c3_fp32', ['--steps', '5', '--warmup', '2', '--arithmetic', 'fp32'])):
-        cmd = [sys.executable, os.path.abspath(__file__), '--workload', name.split('_')[0], '--no-others'] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), '--workload', name.split('_')[0], '--full', '--no-others'] + extra
         cmd += ['--cpu-budget', '8'] if name in ('c2', 'c4', 'page') and with_cpu_baseline else ['--no-cpu-baseline']
         env = {k: v for k, v in os.environ.items() if not k.startswith('CASV_BENCH_')}
         try:
@@ -1003,7 +1091,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=60.0, help='seconds of host time for the cpu_baseline sample')
-    ap.add_argument('--no-others', action='store_true', help='do not time c2 / c4 / page after the default c3 run')
+    ap.add_argument('--full', action='store_true', help='also measure what takes time of its own: roofline, per-kernel times, CPU baseline, '
+                    'calibration and, after the default c3 run, c2 / c4 / page / c3 under fp32 (the plain run times the steps only)')
+    ap.add_argument('--no-others', action='store_true', help='--full: do not time c2 / c4 / page after the default c3 run')
     ap.add_argument('--pipeline', type=int, default=1, help='1 GPU: 1 = the steps run through correct_batches (vectorising, device and '
                     'string building of neighbouring steps overlap, as in predict()), 0 = one correct_lines call after the other')
     ap.add_argument('--graph', type=int, default=0, help='replay the decode step from a hipGraph')
@@ -1025,9 +1115,14 @@ def main():
                     help='A/B measurements: process-wide override of every launch of the decode path (library option split_bf16; 0 = fp32-input, '
                          '1 = split operands on 128x128 tiles, 2 = on 256x256 tiles where they fill the chip)')
     ap.add_argument('--dump-records', default=None, help='rank 0 saves the gathered records of the last step to this .npy file (tests)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, save what the last one handed its caller as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB: a fixed, seeded sample of the lines beyond that)')
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be positive')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be positive and --warmup not negative')
     if args.workload is None:
         # BASELINE configs[4] is what the multi-GPU metric is quoted on: 64k lines over 8 GPUs = 8192 per GPU per step
         args.workload = 'c5' if (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1) else 'c3'

@@ -19,16 +19,16 @@ run() {  # name, rocprof args..., -- program args
 export CASV_BENCH_NO_CALIBRATION=1
 for what in $WHAT; do
   if [ $what = stats ]; then
-    run c3_stats --kernel-trace --stats --output-format csv -d $OUT/c3 -o c3 -- python3 bench.py --steps 5 --warmup 2 --no-others --no-cpu-baseline
-    run c3_fp32_stats --kernel-trace --stats --output-format csv -d $OUT/c3_fp32 -o c3_fp32 -- python3 bench.py --steps 3 --warmup 1 --no-others --no-cpu-baseline --arithmetic fp32
-    run c2_stats --kernel-trace --stats --output-format csv -d $OUT/c2 -o c2 -- python3 bench.py --workload c2 --steps 20 --warmup 3 --no-others --no-cpu-baseline
-    run c4_stats --kernel-trace --stats --output-format csv -d $OUT/c4 -o c4 -- python3 bench.py --workload c4 --steps 5 --warmup 2 --no-others --no-cpu-baseline
-    run page_stats --kernel-trace --stats --output-format csv -d $OUT/page -o page -- python3 bench.py --workload page --steps 3 --warmup 1 --no-others --no-cpu-baseline
+    run c3_stats --kernel-trace --stats --output-format csv -d $OUT/c3 -o c3 -- python3 bench.py --steps 5 --warmup 2 --full --no-others --no-cpu-baseline
+    run c3_fp32_stats --kernel-trace --stats --output-format csv -d $OUT/c3_fp32 -o c3_fp32 -- python3 bench.py --steps 3 --warmup 1 --full --no-others --no-cpu-baseline --arithmetic fp32
+    run c2_stats --kernel-trace --stats --output-format csv -d $OUT/c2 -o c2 -- python3 bench.py --workload c2 --steps 20 --warmup 3 --full --no-others --no-cpu-baseline
+    run c4_stats --kernel-trace --stats --output-format csv -d $OUT/c4 -o c4 -- python3 bench.py --workload c4 --steps 5 --warmup 2 --full --no-others --no-cpu-baseline
+    run page_stats --kernel-trace --stats --output-format csv -d $OUT/page -o page -- python3 bench.py --workload page --steps 3 --warmup 1 --full --no-others --no-cpu-baseline
   fi
   if [ $what = pmc ]; then
     for w in c3 page c4 c2; do
-      run ${w}_fetch --pmc FETCH_SIZE --output-format csv -d $OUT/${w}_fetch -o fetch -- python3 bench.py --workload $w --steps 1 --warmup 1 --no-others --no-cpu-baseline
-      run ${w}_write --pmc WRITE_SIZE --output-format csv -d $OUT/${w}_write -o write -- python3 bench.py --workload $w --steps 1 --warmup 1 --no-others --no-cpu-baseline
+      run ${w}_fetch --pmc FETCH_SIZE --output-format csv -d $OUT/${w}_fetch -o fetch -- python3 bench.py --workload $w --steps 1 --warmup 1 --full --no-others --no-cpu-baseline
+      run ${w}_write --pmc WRITE_SIZE --output-format csv -d $OUT/${w}_write -o write -- python3 bench.py --workload $w --steps 1 --warmup 1 --full --no-others --no-cpu-baseline
     done
     f() { find $OUT/$1 -name "*counter_collection.csv" | head -1; }
     python3 profiles/pmc_traffic.py $(f c3_fetch) $(f c3_write) gemm_split256_kernel split256_gemm_traffic.json 2 > $OUT/c3_traffic.txt 2>&1

@@ -1,8 +1,8 @@
 """Stress of the persistent kernels' hand-offs: many decodes of random shapes, each compared bit for bit with the per-step
 kernels, while a second model handle keeps the GPU busy with beamed decodes on another stream (uneven load on the CUs)."""
-import sys, time, threading
+import os, sys, time, threading
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cor_asv_ann_amd.synthetic import ModelConfig, make_weights, make_lines
 from cor_asv_ann_amd.engine import HipEngine
 

@@ -180,7 +180,7 @@ def test_bench_two_ranks_on_one_gpu():
     """The real N-rank path of bench.py (two processes, each with its own model handle, decoding their shards on
     the same card; gloo carries the gather because two RCCL ranks cannot share a device)."""
     code, lines, err = _run_bench({'CASV_BENCH_BACKEND': 'gloo', 'CASV_BENCH_SAME_DEVICE': '1'},
-                                  '--gpus', '2', '--steps', '1', '--warmup', '1', '--lines-per-gpu', '64')
+                                  '--gpus', '2', '--steps', '1', '--warmup', '1', '--lines-per-gpu', '64', '--full')
     assert code == 0, err
     out = lines[0]
     assert out['n_gpus'] == 2 and out['gathered_records'] == 128 and out['data'] == 'synthetic'
@@ -363,3 +363,89 @@ def test_eight_ranks_of_configs4_rehearsed_without_a_device(tmp_path):
     # (a sanity bound on a shared 8-CPU container, eight processes on eight CPUs: the figure that matters is printed above)
     assert packing8[4] <= 1.5 * alone + 30.0 and packing8[-1] <= 3.0 * alone + 120.0, (alone, packing8)
 
+
+
+def test_bench_dumps_what_the_last_step_returned(tmp_path):
+    """`--dump-outputs DIR`, dry (every line comes back as its own correction): one finite float array per returned value --
+    strings as code points and lengths, probabilities, scores --, every line in order, the same bits from a second run; the
+    gathered records of two ranks give the same arrays."""
+    from cor_asv_ann_amd.synthetic import make_lines
+    import bench
+    env = {'CASV_BENCH_DRY_RUN': '1', 'CASV_BENCH_BACKEND': 'gloo'}
+    runs = [(str(tmp_path / 'a'), '1'), (str(tmp_path / 'b'), '1'), (str(tmp_path / 'c'), '2')]
+    for out, gpus in runs:
+        code, lines, err = _run_bench(env, '--gpus', gpus, '--steps', '3', '--warmup', '1', '--lines-per-gpu', '6', '--dump-outputs', out)
+        assert code == 0, err
+        assert lines[0]['steps'] == 3 and lines[0]['ms_per_step'] > 0 and 'cpu_baseline' not in lines[0]
+    wl = bench.WORKLOADS['c3']
+    want = make_lines(6, wl['length'], wl['seed'], voc_size=wl['voc'])[0]
+    names = ('chars', 'lengths', 'probs', 'scores')
+    got = {k: np.load(os.path.join(runs[0][0], k + '.npy')) for k in names}
+    assert sorted(os.listdir(runs[0][0])) == sorted(k + '.npy' for k in names)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    ends = np.arange(got['chars'].shape[1])[None, :] >= got['lengths'][:, None]
+    text = lambda chars: [''.join(chr(int(c)) for c in row if c >= 0) for row in chars]
+    assert text(got['chars']) == want
+    assert np.array_equal(ends, got['chars'] < 0) and (got['probs'][~ends] == 1.0).all() and (got['probs'][ends] == 0).all()
+    for k, a in got.items():
+        assert np.array_equal(np.load(os.path.join(runs[1][0], k + '.npy')), a), k
+    # two ranks (configs[4]'s workload): the 12 lines of the global job, from the gathered records
+    two = {k: np.load(os.path.join(runs[2][0], k + '.npy')) for k in names}
+    wl = bench.WORKLOADS['c5']
+    assert text(two['chars']) == make_lines(12, wl['length'], wl['seed'], voc_size=wl['voc'])[0]
+    assert all(np.isfinite(a).all() for a in two.values()) and (two['lengths'] == 101).all()
+    assert np.array_equal(two['probs'] > 0, two['chars'] >= 0) and (two['scores'] == 0).all()
+    # alignments (the page call): a window past the end of the line is an all-NaN row; it is dumped as zeros and counted
+    from cor_asv_ann_amd.realign import SparseAlignment
+    al = SparseAlignment(np.array([0, -1], np.int32), np.array([[0.25, 0.75], [0.0, 0.0]], np.float32), 3)
+    assert np.isnan(np.asarray(al)[1]).all()
+    arr = bench.decode_output_arrays(['ab', ''], [[0.5, 0.5], []], [0.1, 0.0], [al, []])
+    assert all(np.isfinite(a).all() for a in arr.values())
+    assert arr['alignments'].tolist() == [[0.25, 0.75, 0.0], [0.0, 0.0, 0.0]] and arr['alignment_nan'].tolist() == [0, 3]
+    assert arr['alignment_rows'].tolist() == [2, 0] and arr['lengths'].tolist() == [2, 0]
+
+
+def test_bench_dump_keeps_a_seeded_sample_beyond_its_budget(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 20000)
+    arrays = {'chars': np.arange(1000 * 10, dtype=np.float64).reshape(1000, 10), 'scores': np.arange(1000, dtype=np.float64),
+              'loss': np.ones(3)}
+    for d in ('a', 'b'):
+        bench.write_outputs(str(tmp_path / d), arrays, per_line=('chars', 'scores'))
+    rows = np.load(str(tmp_path / 'a' / 'sampled_lines.npy'))
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))) <= 20000 + 4 * 128    # (+ .npy headers)
+    assert 0 < len(rows) < 1000 and np.array_equal(rows, np.unique(rows))
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'scores.npy')), rows)
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'chars.npy'))[:, 0], rows * 10)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'sampled_lines.npy')), rows)
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / 'c'), {'idx': np.zeros(4, np.int32)})
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / 'c'), {'probs': np.array([0.5, np.nan])})
+    assert not os.path.exists(str(tmp_path / 'c'))
+
+
+@pytest.mark.gpu
+def test_bench_dump_is_what_correct_lines_returns():
+    """`bench.py --workload page --dump-outputs DIR` (confusion-network lines, alignments requested, steps through correct_batches)
+    writes what `correct_lines` of the same model returns for the same lines."""
+    import tempfile
+    from cor_asv_ann_amd.synthetic import make_confmat_lines
+    import bench
+    wl = bench.WORKLOADS['page']
+    with tempfile.TemporaryDirectory() as out:
+        code, lines, err = _run_bench({}, '--workload', 'page', '--steps', '2', '--warmup', '0', '--dump-outputs', out)
+        assert code == 0, err
+        assert lines[0]['steps'] == 2 and 'roofline' not in lines[0] and 'kernel_ms_per_step' not in lines[0]
+        got = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    s2s, _, _ = bench.make_model(0, wl['depth'], wl['width'], wl['n'], wl['emb'], wl['voc'])
+    s2s.rejection_threshold, s2s.beam_width_in, s2s.beam_threshold_in = wl['rejection'], wl['beam_width_in'], wl['beam_threshold_in']
+    page = make_confmat_lines(wl['lines'], wl['length'], wl['seed'], voc_size=wl['voc'])
+    o, p, s, a = s2s.correct_lines(page, conf=page, fast=False, greedy=False, alignments=True)
+    s2s.engine.close()
+    want = bench.decode_output_arrays(o, p, s, a)
+    assert sorted(got) == sorted(want) and 'alignments' in got
+    for k in want:
+        assert got[k].shape == want[k].shape and got[k].dtype == want[k].dtype, k
+        assert np.isfinite(got[k]).all() and np.allclose(got[k], want[k], rtol=1e-6, atol=0), k
+    assert np.array_equal(got['chars'], want['chars'])
