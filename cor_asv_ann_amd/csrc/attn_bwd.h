@@ -19,7 +19,9 @@
 
 namespace casv {
 
-template <bool HANDOFF, int DEFER = 0>       // DEFER bits: 1 = d_enc, 2 = du summed behind the recurrence
+// ORDERED (per-step kernel of the "deterministic" train step): the d_enc / du read-modify-writes as plain loads and stores -- each
+// address has one writer per launch, and the launches of the steps follow each other on the stream, so the sums run in step order
+template <bool HANDOFF, int DEFER = 0, bool ORDERED = false>       // DEFER bits: 1 = d_enc, 2 = du summed behind the recurrence
 __device__ __forceinline__ void attention_bwd_sample(const AttnBwdArgs& p, const int b, const bool active, const int tid, const int nthr,
                                                      float* s_dx, float* s_da, float* s_ds, float* s_av) {
     const int lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
@@ -59,7 +61,10 @@ __device__ __forceinline__ void attention_bwd_sample(const AttnBwdArgs& p, const
         float* de = p.d_enc + (long long)b * p.enc_line + (long long)s_lo * p.enc_time;
         for (int i = 0; i < cnt; ++i) {
             const float av = s_av[i];
-            for (int c = tid; c < C; c += nthr) atomicAdd(de + (long long)i * p.enc_time + c, av * s_dx[c]);
+            for (int c = tid; c < C; c += nthr) {
+                if (ORDERED) de[(long long)i * p.enc_time + c] += av * s_dx[c];
+                else atomicAdd(de + (long long)i * p.enc_time + c, av * s_dx[c]);
+            }
         }
     }
     // energies: th = tanh(wq + u_s); dva += dscore*th ; dpre = dscore*va*(1-th^2) -> du_s, dwq
@@ -76,7 +81,10 @@ __device__ __forceinline__ void attention_bwd_sample(const AttnBwdArgs& p, const
             const float ds = s_ds[i];
             dva += ds * th;
             const float dpre = ds * v * (1.0f - th * th);
-            if (!(DEFER & 2) && i < cnt) atomicAdd(p.du + off0 + (long long)i * p.u_time, dpre);
+            if (!(DEFER & 2) && i < cnt) {
+                if (ORDERED) p.du[off0 + (long long)i * p.u_time] += dpre;
+                else atomicAdd(p.du + off0 + (long long)i * p.u_time, dpre);
+            }
             dwq += dpre;
         }
         if (HANDOFF) store_sc1(p.dwq + (long long)b * W + j, dwq);

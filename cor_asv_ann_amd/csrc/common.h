@@ -160,9 +160,15 @@ struct TnArgs {
     int out_zeroed;      // C = with a split K: the caller has cleared C already
     float* colsum;       // optional [Mstore]: += sum_k A[k][m] (the bias gradient that goes with a weight gradient)
     int nsplit;          // set by launch_gemm_tn: K shares of the launch
+    float* part;         // ordered form (launch_gemm_tn_ordered): K share z stores its partial tile at part[z][Mstore][N] ...
+    float* colpart;      // ... and its column sums at colpart[z][Mstore]; a second pass adds the shares in z order
 };
 void launch_gemm_tn(const TnArgs& g, hipStream_t stream);
 bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream);      // the same contraction on bf16x3-split operands (gemm_tn_split.hip); false: no such form for the shape
+// The same contraction with its sums in a fixed order (the train step's "deterministic" option): K shares chosen from the shape alone,
+// each share's partial stored, then added in share order -- no float atomics.  Needs gemm_tn_ordered_floats(g) floats at `ws`.
+size_t gemm_tn_ordered_floats(const TnArgs& g);
+void launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream);
 void launch_gemm(int epi, const GemmArgs& g, hipStream_t stream);
 void launch_gemm_batch(int epi, const GemmBatch& b, hipStream_t stream);
 void launch_gemm_skinny(int epi, const GemmBatch& b, int ksplit, int rows, hipStream_t stream);
@@ -192,6 +198,14 @@ void gemm_split_prepare(const float* Bt, int N, int K, hipStream_t stream);    /
 void gemm_split_invalidate(const float* Bt);     // drops the pre-split image of a weight buffer (call where it changes or is released); nullptr: all
 bool launch_gemm_split256(int epi, const GemmBatch& b, hipStream_t stream);     // false: not launched (the caller takes another path)
 int gemm_split_bf16();                     // the calling thread's current arithmetic (SplitScope)
+int gemm_ordered_enter(int on);            // 1: the calling thread's launches sum in a fixed order (no split-K, no float atomics); returns the previous
+int gemm_ordered();
+struct OrderedScope {
+    int prev;
+    explicit OrderedScope(bool on) : prev(gemm_ordered_enter(on ? 1 : 0)) {}
+    ~OrderedScope() { gemm_ordered_enter(prev); }
+    OrderedScope(const OrderedScope&) = delete; OrderedScope& operator=(const OrderedScope&) = delete;
+};
 long gemm_split_epoch();                   // changes whenever the option or a pre-split weight image does (key of captured step graphs)
 void gemm_split_bump_epoch();
 

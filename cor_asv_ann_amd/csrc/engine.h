@@ -143,6 +143,7 @@ struct casv_model {
     int arith = -1;                                       // option "arithmetic": -1 by entry point (arithmetic_of), 0 fp32-input chain, 1 / 2 split-bf16 everywhere
     bool vendor_gemm = false;                             // calibration only: the train step's plain whole-sequence contractions through hipBLASLt (vendor_gemm.hip)
     bool fused_backward = true;                           // train step: cell backward fused into the step's data GEMM (gemm_bwd.hip)
+    bool deterministic = false;                           // train step: every sum in a fixed order ("Reproducible training")
     const int* skip_nact = nullptr;                       // beam decode: live rows per line, handed to the step's kernels when
     int skip_group = 0;                                   // skipping can pay (wide beams, or a line has finished); rows per line
     // the captured step graph of the last decode configuration (option "graph"): kept across calls, rebuilt when the

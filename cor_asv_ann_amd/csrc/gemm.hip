@@ -804,6 +804,11 @@ void set_gemm_split_override(int v) { v = v < -1 ? -1 : v > 2 ? 2 : v; if (v != 
 int gemm_split_override() { return g_split_override; }
 int gemm_split_enter(int mode) { const int prev = t_split_bf16; t_split_bf16 = mode < 0 ? 0 : mode > 2 ? 2 : mode; return prev; }
 int gemm_split_bf16() { return t_split_bf16; }
+// Ordered sums (the train step's "deterministic" option): while set, no launch of the calling thread splits K
+// over workgroups -- every element is ONE k-ordered chain, nothing is added atomically, whatever the shape asks for.
+static thread_local int t_ordered = 0;
+int gemm_ordered_enter(int on) { const int prev = t_ordered; t_ordered = on ? 1 : 0; return prev; }
+int gemm_ordered() { return t_ordered; }
 
 static int count_ktiles(const GemmArgs& g) {
     int ktiles = 0;
@@ -826,6 +831,7 @@ static GemmPlan plan_gemm(int epi, const GemmBatch& b) {
     for (int j = 0; j < b.count; ++j)
         if (b.g[j].step_ptr || b.g[j].ksplit == 0 || b.g[j].ksplit == 1 || b.g[j].ksplit != b.g[0].ksplit || b.g[j].Ktot != b.g[0].Ktot ||
             b.g[j].M != b.g[0].M || b.g[j].N != b.g[0].N) splittable = false;
+    if (t_ordered) splittable = false;
     auto choose_ksplit = [&](int grid, int want) {
         if (!splittable) return 1;
         const int ktiles = count_ktiles(b.g[0]);

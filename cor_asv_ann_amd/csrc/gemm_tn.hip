@@ -28,6 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TBM = 128, TBN = 128, TBK = 16;
 constexpr int T_TILE = TBK * 128;                       // floats of one operand tile in LDS ([k][128])
 
+template <bool PART>        // PART: the ordered form's epilogue (partials stored per K share, launch_gemm_tn_ordered)
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
     __shared__ __attribute__((aligned(16))) float smem[2 * 2 * T_TILE];     // 32 KB: two buffers x (A tile, B tile)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -211,7 +212,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
             float t = 0.f;
 #pragma unroll
             for (int q = 0; q < 8; ++q) t += smem[q * 128 + tid];
-            atomicAdd(g.colsum + m0 + tid, t);
+            if (PART) g.colpart[(long long)zidx * g.Mstore + m0 + tid] = t;
+            else atomicAdd(g.colsum + m0 + tid, t);
         }
     }
 #pragma unroll
@@ -222,6 +224,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (m < g.Mstore) {
+                    if (PART) { g.part[((long long)zidx * g.Mstore + m) * g.N + n] = acc[c][r]; continue; }
                     float* dst = g.C + (long long)m * g.ldc + n;
                     if (nsplit > 1) atomicAdd(dst, acc[c][r]);
                     else *dst = g.accumulate ? (*dst + acc[c][r]) : acc[c][r];
@@ -245,7 +248,63 @@ void launch_gemm_tn(const TnArgs& g, hipStream_t stream) {
     }
     TnArgs gg = g;
     gg.nsplit = ks;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles * ks), dim3(256), 0, stream, gg);
+    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(tiles * ks), dim3(256), 0, stream, gg);
+}
+
+// ---- ordered form ----
+// C[m][n] (+)= part[0][m][n] + part[1][m][n] + ... in share order; colsum[m] += colpart[0][m] + colpart[1][m] + ...
+__global__ void tn_reduce_kernel(const float* __restrict__ part, const float* __restrict__ colpart, int nz, int Mstore, int N,
+                                 float* __restrict__ C, long long ldc, int accumulate, float* __restrict__ colsum) {
+    const long long mn = (long long)Mstore * N;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < mn; i += (long long)gridDim.x * blockDim.x) {
+        float s = part[i];
+        for (int z = 1; z < nz; ++z) s += part[(long long)z * mn + i];
+        float* dst = C + (i / N) * ldc + i % N;
+        *dst = accumulate ? *dst + s : s;
+    }
+    if (colsum && blockIdx.x == 0)
+        for (int m = threadIdx.x; m < Mstore; m += blockDim.x) {
+            float s = colpart[m];
+            for (int z = 1; z < nz; ++z) s += colpart[(long long)z * Mstore + m];
+            colsum[m] += s;
+        }
+}
+
+bool gemm_tn_split_shares(const TnArgs& g, int& ks);      // gemm_tn_split.hip: the ordered form's shares on 256x256 split tiles
+
+// K shares of the ordered form: a function of the shape only (not of the device's CU count), and the shares that hold k-tiles at all
+static void tn_ordered_plan(const TnArgs& g, bool& split, int& ks, int& nz) {
+    split = gemm_split_bf16() && gemm_tn_split_shares(g, ks);
+    int ktiles;
+    if (split) ktiles = g.K / 16;
+    else {
+        const int tiles = ((g.M + TBM - 1) / TBM) * ((g.N + TBN - 1) / TBN);
+        ktiles = (g.K + TBK - 1) / TBK;
+        ks = (512 + tiles - 1) / tiles;
+        if (ks > ktiles / 64) ks = ktiles / 64;
+        if (ks < 1) ks = 1;
+    }
+    const int per = (ktiles + ks - 1) / ks;
+    nz = per > 0 ? (ktiles + per - 1) / per : 1;
+}
+size_t gemm_tn_ordered_floats(const TnArgs& g) {
+    bool split; int ks, nz;
+    tn_ordered_plan(g, split, ks, nz);
+    return (size_t)nz * g.Mstore * ((size_t)g.N + 1);
+}
+void launch_gemm_tn_split_part(const TnArgs& g, hipStream_t stream);        // gemm_tn_split.hip
+
+void launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream) {
+    bool split; int ks, nz;
+    tn_ordered_plan(g, split, ks, nz);
+    TnArgs gg = g;
+    gg.nsplit = ks;
+    gg.part = ws; gg.colpart = ws + (size_t)nz * g.Mstore * g.N;
+    if (split) launch_gemm_tn_split_part(gg, stream);
+    else hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(((g.M + TBM - 1) / TBM) * ((g.N + TBN - 1) / TBN) * ks), dim3(256), 0, stream, gg);
+    const long long mn = (long long)g.Mstore * g.N;
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)std::min<long long>((mn + 255) / 256, 2048)), dim3(256), 0, stream,
+                       gg.part, gg.colpart, nz, g.Mstore, g.N, g.C, g.ldc, g.accumulate, g.colsum);
 }
 
 }  // namespace casv

@@ -33,6 +33,7 @@ constexpr int TS_PLANE = 256 * 32;                 // bytes: one bf16 plane of a
 constexpr int TS_BUF = 6 * TS_PLANE;               // A planes 0..2, B planes 0..2
 constexpr int TS_LDS = 2 * TS_BUF;                 // 96 KB
 
+template <bool PART>        // PART: the ordered form's epilogue (gemm_tn.hip, launch_gemm_tn_ordered)
 __global__ __launch_bounds__(512, 1) void gemm_tn_split256_kernel(const TnArgs g) {
     extern __shared__ __attribute__((aligned(16))) char ts_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -144,7 +145,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_split256_kernel(const TnArgs g
         float* red = reinterpret_cast<float*>(ts_smem);
         red[kc * 256 + r0] = cs0; red[kc * 256 + 128 + r0] = cs1;
         __syncthreads();
-        if (tid < 256 && m0 + tid < g.Mstore) atomicAdd(g.colsum + m0 + tid, (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]));
+        if (tid < 256 && m0 + tid < g.Mstore) {
+            const float t = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
+            if (PART) g.colpart[(long long)zidx * g.Mstore + m0 + tid] = t;
+            else atomicAdd(g.colsum + m0 + tid, t);
+        }
     }
     // ---- epilogue: C += acc (atomics where K is shared out) ----
 #pragma unroll
@@ -156,6 +161,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_split256_kernel(const TnArgs g
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (m < g.Mstore) {
+                    if (PART) { g.part[((long long)zidx * g.Mstore + m) * g.N + n] = acc[rb][c][r]; continue; }
                     float* dst = g.C + (long long)m * g.ldc + n;
                     if (nsplit > 1) atomicAdd(dst, acc[rb][c][r]);
                     else *dst = g.accumulate ? (*dst + acc[rb][c][r]) : acc[rb][c][r];
@@ -185,13 +191,37 @@ bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     TnArgs gg = g;
     gg.nsplit = ks;
-    hipLaunchKernelGGL(gemm_tn_split256_kernel, dim3(tiles * ks), dim3(512), TS_LDS, stream, gg);
+    hipLaunchKernelGGL(gemm_tn_split256_kernel<false>, dim3(tiles * ks), dim3(512), TS_LDS, stream, gg);
     return true;
+}
+
+// The ordered form (launch_gemm_tn_ordered): the shares as above for a chip of 256 CUs whatever the device has, so that the
+// partition -- and with it every bit of the result -- follows from the shape alone.  false: no split form for the shape.
+bool gemm_tn_split_shares(const TnArgs& g, int& ks) {
+    static const bool off = [] { const char* e = getenv("CASV_TN_SPLIT"); return e && e[0] == '0'; }();
+    if (off) return false;
+    if (g.M <= 0 || g.N <= 0 || g.M % TS_BM || g.N % TS_BN || g.K < 64 * TS_BK || g.K % TS_BK) return false;
+    if (g.Mstore <= 0 || g.Mstore > g.M) return false;
+    const int tiles = (g.M / TS_BM) * (g.N / TS_BN), ktiles = g.K / TS_BK;
+    ks = 256 / tiles;
+    if (ks > ktiles / 64) ks = ktiles / 64;
+    if (ks < 1) ks = 1;
+    return tiles * ks >= 128;
+}
+void launch_gemm_tn_split_part(const TnArgs& g, hipStream_t stream) {
+    static bool attr_set[64] = {false};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS);
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_split256_kernel<true>, dim3((g.M / TS_BM) * (g.N / TS_BN) * g.nsplit), dim3(512), TS_LDS, stream, g);
 }
 
 }  // namespace casv

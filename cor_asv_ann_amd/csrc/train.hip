@@ -49,6 +49,11 @@ struct TrainState {
     std::vector<DevBuf> XD;                // deep_bidirectional_encoder: layer n's input = the cross sum of O[n-1] (seq2seq.py:246-259)
     DevBuf loss, normsq;
     DevBuf dcalt;                          // second dL/dc buffers of the fused backward steps (two layers)
+    // "deterministic" option: the ordered K-major contractions' partial sums, the workgroups' loss / norm parts, the per-character
+    // segments of the embedding gradient (encoder, decoder input) and their host images
+    int tn_ws_rc = 0;                      // the ordered contractions' workspace could not be had this step (its error, reported by the step)
+    DevBuf tn_ws, sum_parts, seg_enc_off, seg_enc_pos, seg_dec_off, seg_dec_pos;
+    std::vector<int> h_seg_enc_off, h_seg_enc_pos, h_seg_dec_off, h_seg_dec_pos;
     DevBuf rec_cnt; int rec_launches = 0, rec_checked = 0, rec_skip = 0, rec_penalty = 0;   // persistent recurrences: counters per launch, back-off
     const unsigned* rec_abort[16] = {nullptr};    // ... and where each launch leaves its "gave up" word
     // The attention cell's backward recurrence as TWO launches side by side (train_persist_topb.hip, split_a): the second stream and
@@ -125,7 +130,8 @@ int casv_train_release(casv_model* m) {
     DevBuf* bufs[] = {&ts->ETp, &ts->WaN, &ts->UaN, &ts->e_idx, &ts->e_val, &ts->d_in, &ts->d_out, &ts->d_w, &ts->m_enc, &ts->m_dec,
         &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn, &ts->prev,
         &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->HP, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
-        &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt};
+        &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
+        &ts->seg_dec_pos};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : ts->O) b.release();
     for (auto& b : ts->DO) b.release();
@@ -238,7 +244,7 @@ static void run_plain(casv_model* m, GemmArgs& g) {
         fprintf(stderr, "plain gemm M=%d N=%d K=%d accumulate=%d\n", g.M, g.N, g.Ktot, g.accumulate);
     }
 #endif
-    if (m->vendor_gemm && g.nseg == 1 && !g.a[0].rows && !g.step_ptr && g.M >= 4096 && g.a[0].width == g.Ktot && g.a[0].koff == 0) {
+    if (m->vendor_gemm && !m->deterministic && g.nseg == 1 && !g.a[0].rows && !g.step_ptr && g.M >= 4096 && g.a[0].width == g.Ktot && g.a[0].koff == 0) {
         hipEvent_t ev{};
         m->prof_begin(PC_GEMM, 2.0 * g.M * (double)g.N * g.Ktot, 4.0 * ((double)g.M * g.Ktot + (double)g.N * g.Ktot + (double)g.M * g.N), ev);
         const bool done = vendor_gemm_nt(g.a[0].base, g.a[0].ld, g.M, g.Ktot, g.Bt, g.N, g.bias, g.out.base, g.out.ld, g.accumulate, m->stream);
@@ -257,7 +263,15 @@ static void run_gemm_tn(casv_model* m, const float* A, long long lda, int M, int
     hipEvent_t ev{};
     m->prof_begin(PC_GEMM, 2.0 * Mstore * (double)N * (double)K, 4.0 * ((double)K * (M + N) + (double)Mstore * N), ev);
     // (the step's arithmetic, engine.h ENTRY_TRAIN: the big weight gradients on bf16x3-split operands where the shape has that form)
-    if (!(gemm_split_bf16() && launch_gemm_tn_split(g, m->stream))) launch_gemm_tn(g, m->stream);
+    if (m->deterministic) {             // K shares from the shape alone, their partials added in share order (gemm_tn.hip)
+        const size_t bytes = gemm_tn_ordered_floats(g) * sizeof(float);
+        TrainState* ts = m->train;
+        if (bytes > ts->tn_ws.cap) {
+            (void)hipStreamSynchronize(m->stream);
+            if (int rc = ts->tn_ws.ensure(bytes)) { if (!ts->tn_ws_rc) ts->tn_ws_rc = rc; m->prof_end(PC_GEMM, ev); return; }
+        }
+        launch_gemm_tn_ordered(g, ts->tn_ws.as<float>(), m->stream);
+    } else if (!(gemm_split_bf16() && launch_gemm_tn_split(g, m->stream))) launch_gemm_tn(g, m->stream);
     m->prof_end(PC_GEMM, ev);
 }
 
@@ -383,7 +397,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
         maxlen = std::max(maxlen, a[j].l->len);
     }
     bool persistent = false;
-    if (m->persist_mode != 0 && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
         RecBwdArgs ra{};
         ra.njobs = count; ra.B = B; ra.W = W;
         bool plain = true;
@@ -408,7 +422,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
         }
     }
     if (persistent) {
-    } else if (m->fused_backward) {
+    } else if (m->fused_backward && !m->deterministic) {
         // one launch per step for both layers: the cells' backward inside the data GEMM (gemm_bwd.hip); dL/dc ping-pongs
         float* dcb[2][2];
         int done[2] = {0, 0};
@@ -463,7 +477,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
     const int W = m->W, B = ts->B;
     int maxlen = 0;
     for (int j = 0; j < count; ++j) maxlen = std::max(maxlen, a[j].l->len);
-    if (m->persist_mode != 0 && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
         RecArgs ra{};
         ra.njobs = count; ra.B = B; ra.W = W;
         for (int j = 0; j < count; ++j) {
@@ -513,6 +527,11 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     ts->B = B; ts->T = T; ts->U = U; ts->A = A;
     m->encoded = false;                    // the final-state buffers are shared with the inference session
     const bool training = mode != 0;
+    // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent
+    // recurrence, hence no give-up fallback; no fused backward step), no split-K in the launcher, the K-major contractions'
+    // shares added in order, the workgroups' loss / norm parts added by one ordered pass, the embedding gradient per character
+    const bool det = m->deterministic, fused = m->fused_backward && !det;
+    OrderedScope ordered(det);
 
     // ---- buffers ----
 #define ENS(buf, bytes) if (int rc_ = (buf).ensure(bytes)) return rc_;
@@ -538,6 +557,10 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         else { ENS(l.Hown, rows * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = W; }
     }
     ENS(ts->rec_cnt, 16 * train_recurrence_bwd_counter_bytes(B)) ENS(ts->dcalt, (size_t)2 * B * W * 4)
+    if (det) {
+        ENS(ts->sum_parts, (size_t)std::max(MULTI_MAX * 64, (W + 63) / 64 + V) * 8)
+        ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
+    }
     const bool residual = m->cfg.residual_connections != 0, bridged = m->cfg.bridge_dense != 0;
     if (bridged) { ENS(ts->hbr, (size_t)D * B * W * 4) ENS(ts->cbr, (size_t)D * B * W * 4) ENS(ts->brtmp, (size_t)B * W * 4) }
     if (residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
@@ -551,6 +574,29 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipMemcpyAsync(ts->d_in.p, dec_in, UB * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_out.p, dec_out, UB * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_w.p, weights, UB * 4, hipMemcpyHostToDevice, st));
+    double* parts = det ? ts->sum_parts.as<double>() : nullptr;
+    if (det) {
+        // per-character segments of the index arrays, positions in (t, b, k) order within a character (counting sort on the host)
+        auto segments = [&](const int32_t* idx, int L, int A_, std::vector<int>& off, std::vector<int>& pos) {
+            off.assign(V + 2, 0);
+            for (long long q = 0; q < (long long)B * L * A_; ++q) if (idx[q] >= 0 && idx[q] < V) ++off[idx[q] + 2];
+            for (int v = 0; v < V; ++v) off[v + 2] += off[v + 1];
+            pos.resize(std::max<size_t>(1, off[V + 1]));
+            for (int t = 0; t < L; ++t)
+                for (int b = 0; b < B; ++b)
+                    for (int k = 0; k < A_; ++k) {
+                        const long long q = ((long long)b * L + t) * A_ + k;
+                        if (idx[q] >= 0 && idx[q] < V) pos[off[idx[q] + 1]++] = (int)q;
+                    }
+            off.pop_back();             // off[v] = first position of character v, off[V] = count
+        };
+        segments(enc_idx, T, A, ts->h_seg_enc_off, ts->h_seg_enc_pos);
+        segments(dec_in, U, 1, ts->h_seg_dec_off, ts->h_seg_dec_pos);
+        HIPCHK(hipMemcpyAsync(ts->seg_enc_off.p, ts->h_seg_enc_off.data(), (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ts->seg_enc_pos.p, ts->h_seg_enc_pos.data(), ts->h_seg_enc_pos.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ts->seg_dec_off.p, ts->h_seg_dec_off.data(), (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ts->seg_dec_pos.p, ts->h_seg_dec_pos.data(), ts->h_seg_dec_pos.size() * 4, hipMemcpyHostToDevice, st));
+    }
     // masks: enc = 2W + (D-1)*W floats, dec = (D-1)*W floats, cell = B*(W+C)
     const float* menc = nullptr; const float* mdec = nullptr; const float* mcell = nullptr;
     if (mask_enc) { HIPCHK(hipMemcpyAsync(ts->m_enc.p, mask_enc, (size_t)(deep ? 2 * D : D + 1) * W * 4, hipMemcpyHostToDevice, st)); menc = ts->m_enc.as<float>(); }
@@ -564,7 +610,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipMemsetAsync(ts->loss.p, 0, 16, st));
     HIPCHK(hipMemsetAsync(ts->normsq.p, 0, 16, st));
     HIPCHK(hipMemsetAsync(ts->rec_cnt.p, 0, 16 * train_recurrence_bwd_counter_bytes(B), st));
-    ts->rec_launches = ts->rec_checked = 0; ts->split_launch = -1;
+    ts->rec_launches = ts->rec_checked = 0; ts->split_launch = -1; ts->tn_ws_rc = 0;
     for (auto& l : ts->layers) l.drec_cleared = false;
     if (ts->rec_skip > 0) --ts->rec_skip;
     if (training) for (auto& t : ts->tens) HIPCHK(hipMemsetAsync(t.g.p, 0, t.n * 4, st));
@@ -687,7 +733,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     att.apos = nullptr; att.amax1 = nullptr; att.nrows = nullptr;
     att.u_line = W; att.u_time = (long long)B * W; att.enc_line = C; att.enc_time = (long long)B * C;
     bool top_persistent = false;
-    if (m->persist_mode != 0 && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
         // ONE launch for the whole recurrence of the cell (train_persist_top.hip)
         TopRecArgs ra{};
         ra.Wr = ts->W_(top.iwr); ra.WaT = ts->W_(ts->iWaT); ra.bUW = ts->W_(ts->ibUW); ra.Z = top.Z.as<float>();
@@ -729,7 +775,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     }
     { GemmArgs g = plain_gemm(proj_in, proj_ld, (int)UB, W, ts->W_(ts->iE), V, nullptr, ts->logits.as<float>(), Vp); run_plain(m, g); }
     launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, inv_count, ts->loss.as<double>(),
-                      training ? 1 : 0, st);
+                      training ? 1 : 0, st, parts);
     // Did every persistent recurrence so far run to its end?  (A launch gives up when its workgroups wait too long for each
     // other -- a GPU shared with another process: handoff.h.)  Nothing has been updated yet: start over with per-step launches,
     // and keep to them for the next 16, 32, ... steps.  Asked after the forward pass and again in front of the update.
@@ -791,7 +837,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         HIPCHK(hipMemsetAsync(dc, 0, (size_t)B * W * 4, st));
         const int kr = C + W;
         bool topb_persistent = false;
-        if (m->persist_mode != 0 && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+        if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
             // ONE launch for the whole backward recurrence of the cell (train_persist_topb.hip)
             TopBwdArgs ra{};
             ra.WrT = top.wrT.as<float>(); ra.WaN = ts->WaN.as<float>(); ra.dG = ts->dG.as<float>();
@@ -875,7 +921,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
             p.c_prev = t > 0 ? top.Cs.as<float>() + (long long)(t - 1) * B * W : c0t; p.ld_cprev = W;
             p.dc = dc; p.dz = top.Z.as<float>() + (long long)t * B * 4 * W; p.rows = B; p.W = W;
             float* drec = top.dRec.as<float>() + (long long)t * B * kr;
-            if (m->fused_backward) {
+            if (fused) {
                 BwdStepBatch fb{};
                 fb.count = 1;
                 BwdStepJob& q = fb.j[0];
@@ -898,14 +944,14 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
             ab.enc = enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
             ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>(); ab.dwq = ts->DWQ.as<float>() + (long long)t * B * W;
             ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
-            launch_attention_bwd(ab, st);
+            launch_attention_bwd(ab, st, det);
             GemmArgs g = plain_gemm(ab.dwq, W, B, W, ts->WaN.as<float>(), W, nullptr, ts->dhatt.as<float>() + (long long)t * B * W, W);
             g.out_zeroed = 1;
             run_gemm(m, EPI_PLAIN, g);
         }
-        if (!topb_persistent && m->fused_backward && (U & 1)) HIPCHK(hipMemcpyAsync(dc, ts->dcalt.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));   // dL/dc0 of the cell
-        launch_colsum(ts->dvaP.as<float>(), B, W, W, ts->G_(ts->iva), st);
-        launch_colsum(ts->dbvP.as<float>(), B, 1, 1, ts->G_(ts->ibv), st);
+        if (!topb_persistent && fused && (U & 1)) HIPCHK(hipMemcpyAsync(dc, ts->dcalt.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));   // dL/dc0 of the cell
+        launch_colsum(ts->dvaP.as<float>(), B, W, W, ts->G_(ts->iva), st, det);
+        launch_colsum(ts->dbvP.as<float>(), B, 1, 1, ts->G_(ts->ibv), st, det);
         // dL/dh0 of the cell = recurrent part of step 0 + the query path of step 0
         launch_mul_mask(top.dRec.as<float>() + C, kr, nullptr, dfin_h(D), W, B, W, st);
         launch_axpy(dfin_h(D), ts->dhatt.as<float>(), (long long)B * W, st);       // slot of step 0
@@ -998,7 +1044,8 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         dy_cur ^= 1; dy = dy_bufs[dy_cur];
         dO = do_bufs[do_out]; ld_dO = le.kx; do_out ^= 1;
     }
-    launch_embed_scatter(ts->G_(ts->iE), ts->d_in.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
+    if (det) launch_embed_segments(ts->G_(ts->iE), ts->seg_dec_off.as<int>(), ts->seg_dec_pos.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
+    else launch_embed_scatter(ts->G_(ts->iE), ts->d_in.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
 
     // ---- encoder layer 1: forward direction takes columns [0,W) of dO1, backward direction [W,2W) ----
     {
@@ -1009,7 +1056,9 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
              ts->X0.as<float>(), W, ts->dX0.as<float>(), W, 1}};
         if (int rc = layers_backward(m, pair, 2)) return rc;
     }
-    launch_embed_scatter(ts->G_(ts->iE), ts->e_idx.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr, ts->dX0.as<float>(), W, B, T, A, V, W, st);
+    if (det) launch_embed_segments(ts->G_(ts->iE), ts->seg_enc_off.as<int>(), ts->seg_enc_pos.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr,
+                                   ts->dX0.as<float>(), W, B, T, A, V, W, st);
+    else launch_embed_scatter(ts->G_(ts->iE), ts->e_idx.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr, ts->dX0.as<float>(), W, B, T, A, V, W, st);
 
     {
         bool any = false;
@@ -1017,8 +1066,12 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         if (any) return casv_train_step(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, dec_out, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out);
         if (ts->rec_launches) ts->rec_penalty = 0;
     }
+    if (ts->tn_ws_rc) {                    // (a weight gradient was not computed: no update, the step fails with the allocation's error)
+        (void)hipStreamSynchronize(st);
+        return ts->tn_ws_rc;
+    }
     // ---- regulariser, clip, update ----
-    launch_reg(ts->W_(ts->iE), ts->G_(ts->iE), V, W, ts->loss.as<double>(), 1, st);
+    launch_reg(ts->W_(ts->iE), ts->G_(ts->iE), V, W, ts->loss.as<double>(), 1, st, parts);
     // (norm and update over all parameter tensors as one launch each; lists of MULTI_MAX tensors at a time)
     auto over_tensors = [&](int max_blocks, auto&& launch) {
         MultiTensor mt{};
@@ -1030,7 +1083,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         launch(mt);
     };
     // (few workgroups per tensor: every one of them ends in an atomic add on the ONE sum -- ~12 ns each, one after the other)
-    over_tensors(64, [&](const MultiTensor& mt) { launch_sumsq_multi(mt, ts->normsq.as<double>(), st); });
+    over_tensors(64, [&](const MultiTensor& mt) { launch_sumsq_multi(mt, ts->normsq.as<double>(), st, parts); });
     if (mode == 1) {
         ts->step += 1;
         const double b1 = ts->ap.beta1, b2 = ts->ap.beta2;
@@ -1050,14 +1103,15 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     return CASV_OK;
 }
 
-// Keras-layout view of the master weights (which = 0) or of the last gradients (which = 1).
+// Keras-layout view of the master weights (which = 0), of the last gradients (which = 1) or of Adam's m (2) / v (3).
+static DevBuf& which_buf(TTensor& t, int which) { return which == 0 ? t.w : which == 1 ? t.g : which == 2 ? t.m : t.v; }
 static int keras_view(casv_model* m, int which, std::map<std::string, std::vector<float>>& out) {
     TrainState* ts = m->train;
     const int W = m->W, C = m->C, D = m->D;
     HIPCHK(hipStreamSynchronize(m->stream));
     auto fetch = [&](int i, std::vector<float>& v) -> int {
         v.resize(ts->tens[i].n);
-        HIPCHK(hipMemcpy(v.data(), which ? ts->tens[i].g.p : ts->tens[i].w.p, v.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(v.data(), which_buf(ts->tens[i], which).p, v.size() * 4, hipMemcpyDeviceToHost));
         return 0;
     };
     if (int rc = fetch(ts->iE, out["E"])) return rc;
@@ -1101,6 +1155,143 @@ extern "C" int casv_train_get_gradient(casv_model* m, const char* name, float* o
     if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
     if ((size_t)capacity < it->second.size()) return fail(CASV_ERR_ARG, "buffer too small");
     memcpy(out, it->second.data(), it->second.size() * 4);
+    return CASV_OK;
+}
+
+// ---- optimizer state (resumable training) ----
+// The packed tensors (Wx / Wr / bias, transposed attention and bridge kernels) that hold a Keras tensor's values, or -1.
+static void keras_parts(TrainState* ts, const std::string& name, std::vector<int>& idx) {
+    idx.clear();
+    auto ends = [&](const std::string& suf) { return name.size() > suf.size() && name.compare(name.size() - suf.size(), suf.size(), suf) == 0; };
+    if (name == "E") { idx.push_back(ts->iE); return; }
+    if (name == "att_U") { idx.push_back(ts->iUT); return; }
+    if (name == "att_Wa") { idx.push_back(ts->iWaT); return; }
+    if (name == "att_bUW") { idx.push_back(ts->ibUW); return; }
+    if (name == "att_va") { idx.push_back(ts->iva); return; }
+    if (name == "att_bv") { idx.push_back(ts->ibv); return; }
+    for (auto& l : ts->layers)
+        if ((ends("_K") || ends("_R") || ends("_b")) && name.compare(0, name.size() - 2, l.name) == 0 && name.size() - 2 == l.name.size()) {
+            idx = {l.iwx, l.iwr, l.ib}; return;
+        }
+    for (size_t i = 0; i < ts->bridge.size(); ++i) {
+        const std::string b = "bridge" + std::to_string(i / 2 + 1) + (i % 2 ? "_c" : "_h");
+        if (name == b + "_K") { idx.push_back(ts->bridge[i].ikt); return; }
+        if (name == b + "_b") { idx.push_back(ts->bridge[i].ib); return; }
+    }
+}
+
+static int state_check(casv_model* m, const char* name, int which, std::vector<int>& parts) {
+    if (!m || !name) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
+    if (which != 0 && which != 1) return fail(CASV_ERR_ARG, "which must be 0 (Adam m) or 1 (Adam v)");
+    keras_parts(m->train, name, parts);
+    if (parts.empty()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
+    if (m->train->tens[parts[0]].frozen) return fail(CASV_ERR_STATE, "tensor '%s' is frozen: it has no optimizer state", name);
+    return 0;
+}
+
+// Keras-layout values of ONE tensor from buffer `which` (as keras_view) -- only the packed tensors that hold it are copied: an LSTM
+// tensor comes with its layer's other two (K / R / b pack into Wx, Wr and the bias together), everything else alone.
+static int keras_tensor(casv_model* m, int which, const std::string& n, const std::vector<int>& parts,
+                        std::map<std::string, std::vector<float>>& out) {
+    TrainState* ts = m->train;
+    const int W = m->W, C = m->C;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    auto fetch = [&](int i, std::vector<float>& v) -> int {
+        v.resize(ts->tens[i].n);
+        HIPCHK(hipMemcpy(v.data(), which_buf(ts->tens[i], which).p, v.size() * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if (parts.size() == 3) {
+        const std::string pre = n.substr(0, n.size() - 2);
+        for (auto& l : ts->layers)
+            if (l.name == pre) {
+                std::vector<float> wx, wr, b;
+                if (int rc = fetch(l.iwx, wx)) return rc;
+                if (int rc = fetch(l.iwr, wr)) return rc;
+                if (int rc = fetch(l.ib, b)) return rc;
+                unpack_train_lstm(W, l.kx, l.kr - W, wx, wr, b, out[pre + "_K"], out[pre + "_R"], out[pre + "_b"]);
+                return 0;
+            }
+        return fail(CASV_ERR_ARG, "unknown tensor '%s'", n.c_str());
+    }
+    std::vector<float> v;
+    if (int rc = fetch(parts[0], v)) return rc;
+    std::vector<float>& o = out[n];
+    o = v;
+    if (n == "att_U") {
+        for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) o[(size_t)c * W + j] = v[(size_t)j * C + c];
+    } else if (n == "att_Wa" || (n.compare(0, 6, "bridge") == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_K") == 0)) {
+        for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) o[(size_t)k * W + j] = v[(size_t)j * W + k];
+    }
+    return 0;
+}
+
+extern "C" int casv_train_get_state(casv_model* m, const char* name, int32_t which, float* out, int64_t capacity) {
+    std::vector<int> parts;
+    if (int rc = state_check(m, name, which, parts)) return rc;
+    if (!out) return fail(CASV_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(m->device));
+    std::map<std::string, std::vector<float>> view;
+    if (int rc = keras_tensor(m, 2 + which, name, parts, view)) return rc;
+    auto it = view.find(name);
+    if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
+    if ((size_t)capacity < it->second.size()) return fail(CASV_ERR_ARG, "buffer too small");
+    memcpy(out, it->second.data(), it->second.size() * 4);
+    return CASV_OK;
+}
+
+extern "C" int casv_train_set_state(casv_model* m, const char* name, int32_t which, const float* data, int64_t count) {
+    std::vector<int> parts;
+    if (int rc = state_check(m, name, which, parts)) return rc;
+    if (!data) return fail(CASV_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(m->device));
+    TrainState* ts = m->train;
+    const int W = m->W, C = m->C;
+    std::map<std::string, std::vector<float>> view;
+    if (int rc = keras_tensor(m, 2 + which, name, parts, view)) return rc;
+    auto it = view.find(name);
+    if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
+    if ((size_t)count != it->second.size()) return fail(CASV_ERR_ARG, "tensor '%s' has %zu values, got %lld", name, it->second.size(), (long long)count);
+    it->second.assign(data, data + count);
+    auto put = [&](int i, const std::vector<float>& v) -> int {
+        HIPCHK(hipMemcpy(which_buf(ts->tens[i], 2 + which).p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    };
+    const std::string n = name;
+    if (parts.size() == 3) {            // an LSTM layer: K / R / b pack into Wx, Wr and the bias together
+        const std::string pre = n.substr(0, n.size() - 2);
+        for (auto& l : ts->layers)
+            if (l.name == pre) {
+                std::vector<float> wx, wr, bias;
+                pack_train_lstm(W, l.kx, l.kr - W, view[pre + "_K"], view[pre + "_R"], view[pre + "_b"], wx, wr, bias);
+                if (int rc = put(l.iwx, wx)) return rc;
+                if (int rc = put(l.iwr, wr)) return rc;
+                return put(l.ib, bias);
+            }
+        return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
+    }
+    std::vector<float> v = it->second;
+    if (n == "att_U") {
+        for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) v[(size_t)j * C + c] = it->second[(size_t)c * W + j];
+    } else if (n == "att_Wa" || (n.compare(0, 6, "bridge") == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_K") == 0)) {
+        for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) v[(size_t)j * W + k] = it->second[(size_t)k * W + j];
+    }
+    return put(parts[0], v);
+}
+
+extern "C" int casv_train_get_step(casv_model* m, int64_t* step) {
+    if (!m || !step) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
+    *step = m->train->step;
+    return CASV_OK;
+}
+
+extern "C" int casv_train_set_step(casv_model* m, int64_t step) {
+    if (!m) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
+    if (step < 0) return fail(CASV_ERR_ARG, "step must be >= 0");
+    m->train->step = (long)step;
     return CASV_OK;
 }
 

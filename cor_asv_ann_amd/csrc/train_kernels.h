@@ -9,6 +9,9 @@ void launch_transpose(const float* src, int rows, int cols, long long ld_src, fl
 void launch_embed_tm(const float* E, const int* idx, const float* val, float* out, int B, int T, int A, int V, int W, hipStream_t st);
 void launch_embed_scatter(float* dE, const int* idx, const float* val, const float* dX, long long ld_dx, int B, int T, int A,
                           int V, int W, hipStream_t st);
+// the same sums in a fixed order: per-character segments of the index array (train.hip builds them on the host from the batch)
+void launch_embed_segments(float* dE, const int* seg_off, const int* seg_pos, const float* val, const float* dX, long long ld_dx,
+                           int B, int T, int A, int V, int W, hipStream_t st);
 void launch_mul_mask(const float* in, long long ld_in, const float* mask, float* out, long long ld_out, long long rows, int F, hipStream_t st);
 // residual_connections (seq2seq.py:284-291,359-360): out[r][f] = (a[r][f] + b[r][f]) * mask[f] (mask nullptr: times one)
 void launch_add_mul_mask(const float* a, long long lda, const float* b, long long ldb, const float* mask, float* out, long long ld_out,
@@ -17,8 +20,9 @@ void launch_add_mul_mask(const float* a, long long lda, const float* b, long lon
 void launch_tanh_bwd(float* dy, const float* y, long long n, hipStream_t st);
 void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, long long ld_mask, float* out, long long ld_out,
                         long long rows, int B, int F, hipStream_t st);
+// parts (ordered form, "deterministic" train step): [min(ceil(B*U/4), 2048)] doubles of workspace, or nullptr
 void launch_softmax_ce(float* logits, const int* target, const float* weight, int B, int U, int V, int Vp, float inv_count,
-                       double* loss, int want_grad, hipStream_t st);
+                       double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
 
 // The forward recurrence of up to two independent plain LSTM layers over all their time steps as ONE launch (train_persist.hip).
 struct RecJob {
@@ -104,7 +108,7 @@ struct AttnBwdArgs {
     int B, T, W, C;
     float* ds_out;                                           // deferred form (attn_bwd.h): dL/dscore row of this step, [B][16]
 };
-void launch_attention_bwd(const AttnBwdArgs& p, hipStream_t st);
+void launch_attention_bwd(const AttnBwdArgs& p, hipStream_t st, bool ordered = false);
 // The deferred sums of the persistent attention-cell backward: d_enc += sum_t a_t (x) dctx_t, du += sum_t dpre_t, per sample in LDS
 // (T <= ATTN_DEFER_MAX_T positions).  dctx_t = dRec[t][b][0:C] (row stride ld_drec) x the sample's input mask.
 constexpr int ATTN_DEFER_MAX_T = 288;
@@ -148,15 +152,15 @@ bool train_attention_cell_bwd_rows_fit(const TopBwdArgs& ra);
 void launch_train_attention_cell_bwd_rows(const TopBwdArgs& ra, int grid, hipStream_t stream);
 
 void launch_axpy(float* y, const float* x, long long n, hipStream_t st);
-void launch_colsum(const float* in, long long rows, int cols, long long ld, float* out, hipStream_t st);
-void launch_reg(const float* E, float* dE, int V, int W, double* loss, int want_grad, hipStream_t st);
+void launch_colsum(const float* in, long long rows, int cols, long long ld, float* out, hipStream_t st, bool ordered = false);
+void launch_reg(const float* E, float* dE, int V, int W, double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
 void launch_sumsq(const float* g, long long n, double* acc, hipStream_t st);
 // ... over a list of tensors in ONE launch each (the train step has 30-odd parameter tensors: one launch per tensor is mostly
 // launch boundaries).  first_block[k] .. first_block[k + 1] are tensor k's workgroups of the launch.
 constexpr int MULTI_MAX = 48;
 struct MultiTensor { float* w[MULTI_MAX]; float* g[MULTI_MAX]; float* m[MULTI_MAX]; float* v[MULTI_MAX]; long long n[MULTI_MAX]; int first_block[MULTI_MAX + 1]; int count; };
 bool multi_add(MultiTensor& mt, float* w, float* g, float* m, float* v, long long n, int max_blocks);      // false: the list is full
-void launch_sumsq_multi(const MultiTensor& mt, double* acc, hipStream_t st);
+void launch_sumsq_multi(const MultiTensor& mt, double* acc, hipStream_t st, double* parts = nullptr);
 void launch_adam_multi(const MultiTensor& mt, const double* normsq, float clipnorm, float lr_t, float b1, float b2, float eps, hipStream_t st);
 void launch_adam(float* w, const float* g, float* m, float* v, long long n, const double* normsq, float clipnorm, float lr_t,
                  float b1, float b2, float eps, hipStream_t st);

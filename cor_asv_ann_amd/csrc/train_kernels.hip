@@ -69,6 +69,41 @@ void launch_embed_scatter(float* dE, const int* idx, const float* val, const flo
     hipLaunchKernelGGL(embed_scatter_kernel, dim3(B * T), dim3(128), 0, st, dE, idx, val, dX, ld_dx, B, T, A, V, W);
 }
 
+// ---- ordered sums (the train step's "deterministic" option) ----
+// *acc += parts[0] + parts[1] + ... + parts[n-1]: one workgroup, strided partial sums and a fixed tree -- the same order every run
+__global__ __launch_bounds__(256) void ordered_sum_kernel(const double* __restrict__ parts, int n, double* __restrict__ acc) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += parts[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) *acc += red[0];
+}
+static void ordered_sum(const double* parts, int n, double* acc, hipStream_t st) {
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, st, parts, n, acc);
+}
+
+// dE[v][w] += sum over the rows that use character v, in row order, of val * dX[row][w]: the embedding gradient as per-character
+// segments (seg_off [V+1], seg_pos = positions (b*T + t)*A + k of the index array, sorted by character, within one by (t, b, k))
+__global__ void embed_segments_kernel(float* __restrict__ dE, const int* __restrict__ seg_off, const int* __restrict__ seg_pos,
+                                      const float* __restrict__ val, const float* __restrict__ dX, long long ld_dx, int B, int T, int A, int W) {
+    const int v = blockIdx.x, p0 = seg_off[v], p1 = seg_off[v + 1];
+    if (p0 == p1) return;
+    for (int w = threadIdx.x; w < W; w += blockDim.x) {
+        float s = 0.f;
+        for (int q = p0; q < p1; ++q) {
+            const int pos = seg_pos[q], bt = pos / A, b = bt / T, t = bt % T;
+            s += (val ? val[pos] : 1.0f) * dX[((long long)t * B + b) * ld_dx + w];
+        }
+        dE[(long long)v * W + w] += s;
+    }
+}
+void launch_embed_segments(float* dE, const int* seg_off, const int* seg_pos, const float* val, const float* dX, long long ld_dx,
+                           int B, int T, int A, int V, int W, hipStream_t st) {
+    hipLaunchKernelGGL(embed_segments_kernel, dim3(V), dim3(128), 0, st, dE, seg_off, seg_pos, val, dX, ld_dx, B, T, A, W);
+}
+
 // ---- out[r][f] = in[r][f] * mask[f] (+ add[r][f]) : time-constant dropout masks (seq2seq.py:298,367) ----
 __global__ void mul_mask_kernel(const float* __restrict__ in, long long ld_in, const float* __restrict__ mask,
                                 float* __restrict__ out, long long ld_out, long long rows, int F) {
@@ -127,6 +162,7 @@ void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, lon
 // workgroup first (float64) and reach the accumulator as ONE atomic per workgroup: 52 224 adds to a single address -- one per
 // row -- were 0.63 ms of the step (profiles/r02_train_kernel_stats.csv: softmax_ce_kernel), every one serialised behind the
 // others at the memory side.
+template <bool ORDERED>        // ORDERED: the workgroup's sum goes to parts[blockIdx.x] (ordered_sum adds them)
 __global__ __launch_bounds__(256) void softmax_ce_kernel(float* __restrict__ logits, const int* __restrict__ target,
                                                          const float* __restrict__ weight, long long rows, int B, int U, int V,
                                                          int Vp, float inv_count, double* __restrict__ loss, int want_grad) {
@@ -164,14 +200,21 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(float* __restrict__ log
     __syncthreads();
     if (threadIdx.x == 0) {
         const double s4 = part[0] + part[1] + part[2] + part[3];
-        if (s4 != 0.0) atomicAdd(loss, s4);
+        if (ORDERED) loss[blockIdx.x] = s4;
+        else if (s4 != 0.0) atomicAdd(loss, s4);
     }
 }
 void launch_softmax_ce(float* logits, const int* target, const float* weight, int B, int U, int V, int Vp, float inv_count,
-                       double* loss, int want_grad, hipStream_t st) {
+                       double* loss, int want_grad, hipStream_t st, double* parts) {
     const long long rows = (long long)B * U;
     const long long wgs = std::min<long long>((rows + 3) / 4, 2048);
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, weight, rows, B, U, V,
+    if (parts) {
+        hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, weight, rows, B, U, V,
+                           Vp, inv_count, parts, want_grad);
+        ordered_sum(parts, (int)wgs, loss, st);
+        return;
+    }
+    hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, weight, rows, B, U, V,
                        Vp, inv_count, loss, want_grad);
 }
 
@@ -218,10 +261,11 @@ void launch_lstm_bwd(const LstmBwdArgs& p, hipStream_t st) {
 // One workgroup per sample.  Everything that is read is independent of what is written, so the loads batch; the
 // read-modify-writes of d_enc / du go out as fire-and-forget float atomics (distinct addresses: no contention).
 // dva / dbv are kept as per-sample partial sums across the steps and reduced once after the loop.
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttnBwdArgs p) {
     __shared__ float s_dx[2048];
     __shared__ float s_da[16], s_ds[16], s_av[16];
-    attention_bwd_sample<false>(p, blockIdx.x, true, threadIdx.x, 256, s_dx, s_da, s_ds, s_av);
+    attention_bwd_sample<false, 0, ORDERED>(p, blockIdx.x, true, threadIdx.x, 256, s_dx, s_da, s_ds, s_av);
 }
 // ---- the deferred sums of the attention backward (attn_bwd.h, DEFER): one wave per (sample, 64 columns), its share of the
 // sample's [T][64] sums in LDS, one pass over the steps (loads of four steps in flight together) ----
@@ -300,8 +344,9 @@ void launch_attention_deferred(const AttnDeferArgs& p, hipStream_t st) {
     if (p.what & 2) hipLaunchKernelGGL(attention_deferred_u_kernel, dim3(p.W / 64, p.B), dim3(64), (size_t)p.T * 64 * 4, st, p);
 }
 
-void launch_attention_bwd(const AttnBwdArgs& p, hipStream_t st) {
-    hipLaunchKernelGGL(attention_bwd_kernel, dim3(p.B), dim3(256), 0, st, p);
+void launch_attention_bwd(const AttnBwdArgs& p, hipStream_t st, bool ordered) {
+    if (ordered) hipLaunchKernelGGL(attention_bwd_kernel<true>, dim3(p.B), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(attention_bwd_kernel<false>, dim3(p.B), dim3(256), 0, st, p);
 }
 
 __global__ void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, long long n) {
@@ -325,7 +370,16 @@ __global__ void colsum_kernel(const float* __restrict__ in, long long rows, int 
     __syncthreads();
     if (rl == 0 && c < cols) atomicAdd(out + c, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
-void launch_colsum(const float* in, long long rows, int cols, long long ld, float* out, hipStream_t st) {
+// ... one thread per column, the rows in order
+__global__ void colsum_ordered_kernel(const float* __restrict__ in, long long rows, int cols, long long ld, float* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    float s = 0.f;
+    for (long long r = 0; r < rows; ++r) s += in[r * ld + c];
+    out[c] += s;
+}
+void launch_colsum(const float* in, long long rows, int cols, long long ld, float* out, hipStream_t st, bool ordered) {
+    if (ordered) { hipLaunchKernelGGL(colsum_ordered_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, in, rows, cols, ld, out); return; }
     const int rpb = 512;
     hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64, (unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, in, rows, cols, ld, out, rpb);
 }
@@ -335,6 +389,7 @@ void launch_colsum(const float* in, long long rows, int cols, long long ld, floa
 // Two small grids instead of one workgroup walking the whole table (0.54 ms of the step): columns in blocks of 64 (four row
 // groups per block meet in LDS), rows one wave each.  The gradient is added in place: every contribution to dE of this step
 // has been queued on the same stream before.
+template <bool ORDERED>        // ORDERED: loss = parts, one value per workgroup (cols) / row (rows), added by ordered_sum
 __global__ __launch_bounds__(256) void reg_cols_kernel(const float* __restrict__ E, float* __restrict__ dE, int V, int W,
                                                        double* __restrict__ loss, int want_grad) {
     __shared__ float part[4][64];
@@ -352,9 +407,10 @@ __global__ __launch_bounds__(256) void reg_cols_kernel(const float* __restrict__
     }
     if (g == 0) {
         sq = wsum(sq);
-        if (c == 0) atomicAdd(loss, (double)sq);
+        if (c == 0) { if (ORDERED) loss[blockIdx.x] = (double)sq; else atomicAdd(loss, (double)sq); }
     }
 }
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void reg_rows_kernel(const float* __restrict__ E, float* __restrict__ dE, int V, int W,
                                                        double* __restrict__ loss, int want_grad) {
     const int lane = threadIdx.x & 63, v = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -367,11 +423,21 @@ __global__ __launch_bounds__(256) void reg_rows_kernel(const float* __restrict__
         const float k = -0.04f * (1.0f - n);
         for (int w = lane; w < W; w += 64) dE[(long long)v * W + w] += k * row[w];
     }
-    if (lane == 0) atomicAdd(loss, (double)(0.01f * (1.0f - n) * (1.0f - n)));
+    if (lane == 0) {
+        if (ORDERED) loss[v] = (double)(0.01f * (1.0f - n) * (1.0f - n));
+        else atomicAdd(loss, (double)(0.01f * (1.0f - n) * (1.0f - n)));
+    }
 }
-void launch_reg(const float* E, float* dE, int V, int W, double* loss, int want_grad, hipStream_t st) {
-    hipLaunchKernelGGL(reg_cols_kernel, dim3((W + 63) / 64), dim3(256), 0, st, E, dE, V, W, loss, want_grad);
-    hipLaunchKernelGGL(reg_rows_kernel, dim3((V + 3) / 4), dim3(256), 0, st, E, dE, V, W, loss, want_grad);
+void launch_reg(const float* E, float* dE, int V, int W, double* loss, int want_grad, hipStream_t st, double* parts) {
+    if (parts) {            // parts [(W + 63) / 64 + V]
+        const int nc = (W + 63) / 64;
+        hipLaunchKernelGGL(reg_cols_kernel<true>, dim3(nc), dim3(256), 0, st, E, dE, V, W, parts, want_grad);
+        hipLaunchKernelGGL(reg_rows_kernel<true>, dim3((V + 3) / 4), dim3(256), 0, st, E, dE, V, W, parts + nc, want_grad);
+        ordered_sum(parts, nc + V, loss, st);
+        return;
+    }
+    hipLaunchKernelGGL(reg_cols_kernel<false>, dim3((W + 63) / 64), dim3(256), 0, st, E, dE, V, W, loss, want_grad);
+    hipLaunchKernelGGL(reg_rows_kernel<false>, dim3((V + 3) / 4), dim3(256), 0, st, E, dE, V, W, loss, want_grad);
 }
 
 // ---- global gradient norm and Adam (Keras Adam(clipnorm)) ----
@@ -422,6 +488,7 @@ __device__ __forceinline__ int multi_find(const MultiTensor& mt, const int block
     while (k + 1 < mt.count && block >= mt.first_block[k + 1]) ++k;
     return k;
 }
+template <bool ORDERED>        // ORDERED: acc = parts, one value per workgroup (added by ordered_sum)
 __global__ void sumsq_multi_kernel(const MultiTensor mt, double* __restrict__ acc) {
     __shared__ double red[256];
     const int k = multi_find(mt, blockIdx.x);
@@ -434,11 +501,16 @@ __global__ void sumsq_multi_kernel(const MultiTensor mt, double* __restrict__ ac
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) atomicAdd(acc, red[0]);
+    if (threadIdx.x == 0) { if (ORDERED) acc[blockIdx.x] = red[0]; else atomicAdd(acc, red[0]); }
 }
-void launch_sumsq_multi(const MultiTensor& mt, double* acc, hipStream_t st) {
+void launch_sumsq_multi(const MultiTensor& mt, double* acc, hipStream_t st, double* parts) {
     if (mt.count < 1) return;
-    hipLaunchKernelGGL(sumsq_multi_kernel, dim3((unsigned)mt.first_block[mt.count]), dim3(256), 0, st, mt, acc);
+    if (parts) {            // parts [first_block[count]] (<= MULTI_MAX * the caller's max_blocks)
+        hipLaunchKernelGGL(sumsq_multi_kernel<true>, dim3((unsigned)mt.first_block[mt.count]), dim3(256), 0, st, mt, parts);
+        ordered_sum(parts, mt.first_block[mt.count], acc, st);
+        return;
+    }
+    hipLaunchKernelGGL(sumsq_multi_kernel<false>, dim3((unsigned)mt.first_block[mt.count]), dim3(256), 0, st, mt, acc);
 }
 __global__ void adam_multi_kernel(const MultiTensor mt, const double* __restrict__ normsq, float clipnorm, float lr_t, float b1, float b2,
                                   float eps) {

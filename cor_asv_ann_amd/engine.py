@@ -300,6 +300,7 @@ class HipEngine(object):
     def train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-7, clipnorm=5.0, frozen=()):
         p = nv.AdamParams(lr, beta1, beta2, epsilon, clipnorm)
         csv = ','.join(frozen).encode() if frozen else None
+        self._frozen = tuple(frozen)
         nv.check(self.lib.casv_train_begin(self.handle, byref(p), csv))
 
     def train_step(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1):
@@ -336,6 +337,29 @@ class HipEngine(object):
             nv.check(self.lib.casv_train_get_gradient(self.handle, name.encode(), nv.ptr(a), a.size))
             out[name] = self._strip_weight(name, a)
         return out
+
+    def train_state(self):
+        """Adam's state of the session in Keras layout: ({name: m}, {name: v}, step); frozen tensors have none."""
+        ms, vs = {}, {}
+        frozen = tuple(getattr(self, '_frozen', ()))
+        for name, shape in self.pshapes.items():
+            if any(name.startswith(p) for p in frozen):
+                continue
+            for which, out in ((0, ms), (1, vs)):
+                a = np.empty(shape, np.float32)
+                nv.check(self.lib.casv_train_get_state(self.handle, name.encode(), which, nv.ptr(a), a.size))
+                out[name] = self._strip_weight(name, a)
+        step = c_int64()
+        nv.check(self.lib.casv_train_get_step(self.handle, byref(step)))
+        return ms, vs, step.value
+
+    def set_train_state(self, m, v, step):
+        """Set Adam's moments ({name: array} in Keras layout, as train_state returns them) and step count into the session."""
+        for which, src in ((0, m), (1, v)):
+            for name, a in src.items():
+                a = nv.carray(self._pad_weight(name, nv.carray(a, np.float32)), np.float32)
+                nv.check(self.lib.casv_train_set_state(self.handle, name.encode(), which, nv.ptr(a), a.size))
+        nv.check(self.lib.casv_train_set_step(self.handle, int(step)))
 
     def train_weights(self):
         nv.check(self.lib.casv_train_sync_weights(self.handle))

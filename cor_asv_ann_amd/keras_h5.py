@@ -15,7 +15,23 @@ seq2seq.py:1172): the names themselves only address the datasets.  Layers traine
 carry the cuDNN weight format (bias of 8W); `_from_cudnn` restates keras' `_convert_rnn_weights`.
 
 Tensor names on this side are those of `engine.weight_shapes`.
+
+Optional training state (this package only; `write_model(..., state=...)`, read by `read_training_state`): a group beside the
+layers that is not named in `layer_names`, so that keras' `load_weights` and this package's loaders never look at it:
+
+    /training_state/format                      int64 scalar (1)
+    /training_state/{epoch,step,wait,best_epoch}  int64 scalars: completed epochs, Adam's step count, EarlyStopping patience
+                                                counter and the epoch of the best val_loss (0: none yet)
+    /training_state/best_val_loss               float64 scalar (inf: none yet)
+    /training_state/adam                        float64[5]: lr, beta1, beta2, epsilon, clipnorm
+    /training_state/frozen                      bytes: the frozen tensor-name prefixes, comma-separated
+    /training_state/rng                         bytes: JSON of the numpy bit generator's state
+    /training_state/split_rand                  float64[lines]: the validation split (absent: validation files were given)
+    /training_state/history_{loss,val_loss}     float64[epochs]
+    /training_state/m/<tensor>, .../v/<tensor>  float32: Adam's moments of every trained tensor (names as in the layers)
+    /training_state/best/<tensor>               float32: the best epoch's weights (EarlyStopping(restore_best_weights))
 """
+import json
 from collections import OrderedDict
 
 import numpy as np
@@ -198,8 +214,9 @@ def read_model(filename, logger=None):
     return read_config(filename), layers_to_tensors(read_layers(filename), logger)
 
 
-def write_model(filename, config, weights):
-    """Write `weights` ({tensor name: array}, all tensors of the model) and `config` in the reference's layout."""
+def write_model(filename, config, weights, state=None):
+    """Write `weights` ({tensor name: array}, all tensors of the model) and `config` in the reference's layout;
+    `state` (a dict as read_training_state returns it, or None): the optional training-state group as well."""
     depth = int(config['depth'])
     bridge = bool(np.asarray(config.get('bridge_dense', False)).item()) if 'bridge_dense' in config else False
     deep = bool(np.asarray(config.get('deep_bidirectional_encoder', False)).item()) if 'deep_bidirectional_encoder' in config else False
@@ -218,4 +235,61 @@ def write_model(filename, config, weights):
             w.create_dataset(lname + '/' + kname, a)
     for key, value in config.items():
         w.create_dataset('config/' + key, np.asarray(value))
+    if state is not None:
+        _write_state(w, state)
     w.save(filename)
+
+
+STATE = 'training_state'
+
+
+def _write_state(w, st):
+    g = STATE + '/'
+    w.create_group(STATE)
+    w.create_dataset(g + 'format', np.asarray(1, np.int64))
+    for key in ('epoch', 'step', 'wait', 'best_epoch'):
+        w.create_dataset(g + key, np.asarray(int(st[key]), np.int64))
+    w.create_dataset(g + 'best_val_loss', np.asarray(float(st['best_val_loss']), np.float64))
+    w.create_dataset(g + 'adam', np.asarray(st['adam'], np.float64).reshape(5))
+    w.create_dataset(g + 'frozen', np.bytes_(','.join(st['frozen']).encode('utf-8') or b','))
+    w.create_dataset(g + 'rng', np.bytes_(json.dumps(st['rng']).encode('utf-8')))
+    if st.get('split_rand') is not None:
+        w.create_dataset(g + 'split_rand', np.asarray(st['split_rand'], np.float64))
+    hist = st.get('history') or []
+    if hist:
+        w.create_dataset(g + 'history_loss', np.asarray([h['loss'] for h in hist], np.float64))
+        w.create_dataset(g + 'history_val_loss', np.asarray([h['val_loss'] for h in hist], np.float64))
+    for sub in ('m', 'v', 'best'):
+        tensors = st.get(sub) or {}
+        w.create_group(g + sub)
+        for name, a in tensors.items():
+            w.create_dataset(g + sub + '/' + name, np.asarray(a, np.float32))
+
+
+@_guard
+def read_training_state(filename):
+    """The training-state group of a checkpoint as a dict (the keys write_model's `state` takes), or None if it has none."""
+    with hdf5.File(filename) as f:
+        if STATE not in f:
+            return None
+        g = f[STATE]
+        fmt = int(np.asarray(g['format'].read()))
+        if fmt != 1:
+            raise hdf5.H5Error('training state of "%s" has format %d, this package reads format 1' % (filename, fmt))
+        text = lambda key: bytes(np.asarray(g[key].read()).reshape(-1)[0]).decode('utf-8')
+        st = {key: int(np.asarray(g[key].read())) for key in ('epoch', 'step', 'wait', 'best_epoch')}
+        st['best_val_loss'] = float(np.asarray(g['best_val_loss'].read()))
+        st['adam'] = [float(x) for x in np.asarray(g['adam'].read(), np.float64).reshape(5)]
+        st['frozen'] = [p for p in text('frozen').split(',') if p]
+        st['rng'] = json.loads(text('rng'))
+        st['split_rand'] = np.asarray(g['split_rand'].read(), np.float64) if 'split_rand' in g else None
+        st['history'] = []
+        if 'history_loss' in g:
+            st['history'] = [{'loss': float(a), 'val_loss': float(b)} for a, b in
+                             zip(np.asarray(g['history_loss'].read()).reshape(-1), np.asarray(g['history_val_loss'].read()).reshape(-1))]
+        for sub in ('m', 'v', 'best'):
+            st[sub] = OrderedDict()
+            if sub in g:
+                for name in g[sub].keys():
+                    st[sub][name] = np.asarray(g[sub][name].read(), np.float32)
+        return st

@@ -95,6 +95,12 @@ class Sequence2Sequence(object):
         self.frozen_prefixes = []
         self._dirty = True
         self._rng = np.random.default_rng()
+        # reproducible training: `seed` (int) seeds the generator configure() and train() draw from (None: an
+        # unseeded one, as before); `deterministic` runs the train step with every sum in a fixed order (casv_set_option
+        # "deterministic"); `checkpoint_training_state` makes the per-epoch checkpoints carry what train(resume=...) needs
+        self.seed = None
+        self.deterministic = False
+        self.checkpoint_training_state = False
 
     def __repr__(self):
         return (__name__ + " (width: %d)" % self.width + " (depth: %d)" % self.depth +
@@ -119,6 +125,8 @@ class Sequence2Sequence(object):
         if self.engine is not None:
             self.engine.close()
             self.engine = None
+        if self.seed is not None:
+            self._rng = np.random.default_rng(int(self.seed))
         self._weights = self._initial_weights()
         self._dirty = True      # the device copy is created / refreshed at the first compute call
         self.status = 1
@@ -992,9 +1000,12 @@ class Sequence2Sequence(object):
             for k in names:
                 self.logger.info('%s %-7s %.3f±%.3f', what, labels[k].strip() + ':', counts[k].mean, math.sqrt(counts[k].varia))
 
-    def train(self, filenames, val_filenames=None):
+    def train(self, filenames, val_filenames=None, resume=None):
+        """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
+        from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
+        restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint)."""
         from .training import train_files
-        return train_files(self, filenames, val_filenames)
+        return train_files(self, filenames, val_filenames, resume=resume)
 
 
 class _EncoderModel(object):

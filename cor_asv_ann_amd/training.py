@@ -139,19 +139,59 @@ def dropout_masks(s2s, B, rng):
             'cell': keep((B, W + C))}
 
 
-def train_files(s2s, filenames, val_filenames=None):
+ADAM = (1e-3, 0.9, 0.999, 1e-7, 5.0)        # Adam(clipnorm=5) with Keras defaults (seq2seq.py:496), HipEngine.train_begin's
+
+
+def resume_state(s2s, filename):
+    """The training state of checkpoint `filename`, checked against the model: width, depth, mapping, topology flags and frozen
+    set must be those of `s2s`.  Raises ValueError with the first difference."""
+    state = keras_h5.read_training_state(filename)
+    if state is None:
+        raise ValueError('cannot resume from "%s": it holds weights only (write checkpoints with checkpoint_training_state = True)'
+                         % filename)
+    config = keras_h5.read_config(filename)
+    mine = s2s._config_dict()
+    for key, value in mine.items():
+        if key not in config:
+            raise ValueError('cannot resume from "%s": its config has no "%s"' % (filename, key))
+        theirs = np.asarray(config[key])
+        if theirs.shape != np.asarray(value).shape or not np.array_equal(theirs, np.asarray(value)):
+            raise ValueError('cannot resume from "%s": %s differs (file %s, model %s)' % (filename, key, theirs.tolist(),
+                                                                                          np.asarray(value).tolist()))
+    if sorted(state['frozen']) != sorted(s2s.frozen_prefixes):
+        raise ValueError('cannot resume from "%s": frozen layers differ (file %s, model %s)' % (filename, state['frozen'],
+                                                                                                list(s2s.frozen_prefixes)))
+    return state
+
+
+def train_files(s2s, filenames, val_filenames=None, resume=None):
     num_lines = s2s.map_files(filenames)
     s2s.logger.info('Training on "%d" files with %d lines', len(filenames), num_lines)
     if val_filenames:
         num_lines = s2s.map_files(val_filenames)
         s2s.logger.info('Validating on "%d" files with %d lines', len(val_filenames), num_lines)
         split_rand = None
+    state = resume_state(s2s, resume) if resume else None        # (after map_files: the mapping is part of what must match)
+    if val_filenames:
+        if state is not None and state['split_rand'] is not None:
+            raise ValueError('cannot resume from "%s": it was trained without validation files' % resume)
     else:
         s2s.logger.info('Validating on random 20% lines from those files')
-        split_rand = s2s._rng.uniform(0, 1, (num_lines,))
+        split_rand = s2s._rng.uniform(0, 1, (num_lines,)) if state is None else state['split_rand']
+        if split_rand is None or len(split_rand) != num_lines:
+            raise ValueError('cannot resume from "%s": it was trained with %s' % (
+                resume, 'validation files' if split_rand is None else 'a split of %d lines, these files have %d' % (len(split_rand), num_lines)))
+    if state is not None:
+        _, layers = s2s._read_container(resume)          # the checkpoint's weights ...
+        s2s._assign_layers(layers, keras_h5.layer_tensors(s2s.depth, s2s.bridge_dense, s2s.deep_bidirectional_encoder), skip_mismatch=False)
+        s2s._rng.bit_generator.state = state['rng']      # ... and the generator as the next epoch found it
     rng = s2s._rng
     engine = s2s._require_engine()
-    engine.train_begin(frozen=tuple(s2s.frozen_prefixes))
+    engine.set_option('deterministic', 1 if s2s.deterministic else 0)
+    adam = tuple(state['adam']) if state is not None else ADAM
+    engine.train_begin(*adam, frozen=tuple(s2s.frozen_prefixes))
+    if state is not None:
+        engine.set_train_state(state['m'], state['v'], state['step'])
     stop = {'flag': False}
     old_handler = None
     try:
@@ -159,11 +199,21 @@ def train_files(s2s, filenames, val_filenames=None):
     except ValueError:
         pass                                           # not in the main thread
     history = []
-    best, best_weights, wait = np.inf, None, 0
+    best, best_weights, wait, best_epoch, first = np.inf, None, 0, 0, 0
+    if state is not None:
+        history = list(state['history'])
+        best, wait, best_epoch, first = state['best_val_loss'], state['wait'], state['best_epoch'], state['epoch']
+        if best_epoch:
+            if set(state['best']) != set(engine.pshapes):
+                raise ValueError('cannot resume from "%s": the best epoch\'s weights are missing' % resume)
+            best_weights = {k: np.array(v) for k, v in state['best'].items()}
+        if wait >= 3:                                  # the run ended there (EarlyStopping): nothing left to train
+            s2s.logger.info('Epoch %05d: early stopping (at the checkpoint resumed from)', first)
+            first = s2s.epochs
     try:
-        for epoch in range(s2s.epochs):
+        for epoch in range(first, s2s.epochs):
             total, nb = 0.0, 0
-            nan = False
+            nan = cut = False
             # the next batches are vectorised by a worker thread while the device runs this one (kt:133-145)
             for idx, val, dec_in, dec_out, w, masks in prefetch(train_batches(s2s, filenames, split_rand, rng)):
                 loss, _ = engine.train_step(idx, val, dec_in, dec_out, w, masks, mode=1)
@@ -173,6 +223,7 @@ def train_files(s2s, filenames, val_filenames=None):
                     break
                 total += loss; nb += 1
                 if stop['flag']:
+                    cut = True                         # (the epoch is incomplete: see the checkpoint below)
                     break
             vtotal, vn = 0.0, 0
             if not nan:
@@ -185,15 +236,23 @@ def train_files(s2s, filenames, val_filenames=None):
             if nan or not np.isfinite(val_loss):
                 break
             weights = engine.train_weights()
-            # ModelCheckpoint("model.ckpt.weights-{epoch:02d}-{val_loss:.2f}.h5", save_weights_only=True), seq2seq.py:621-622
-            keras_h5.write_model('model.ckpt.weights-%02d-%.2f.h5' % (epoch + 1, val_loss), s2s._config_dict(), weights)
             if val_loss < best:
-                best, best_weights, wait = val_loss, weights, 0
+                best, best_weights, wait, best_epoch = val_loss, weights, 0, epoch + 1
             else:
                 wait += 1
-                if wait >= 3:                          # EarlyStopping(patience=3, restore_best_weights)
-                    s2s.logger.info('Epoch %05d: early stopping', epoch + 1)
-                    break
+            # ModelCheckpoint("model.ckpt.weights-{epoch:02d}-{val_loss:.2f}.h5", save_weights_only=True), seq2seq.py:621-622 -- with
+            # checkpoint_training_state, plus everything the next epoch starts from (keras_h5: the training-state group) -- only
+            # after a whole epoch: a run stopped inside one resumes from the checkpoint before and trains the epoch again
+            ckpt_state = None
+            if s2s.checkpoint_training_state and not cut:
+                m, v, step = engine.train_state()
+                ckpt_state = {'epoch': epoch + 1, 'step': step, 'wait': wait, 'best_epoch': best_epoch, 'best_val_loss': best,
+                              'adam': adam, 'frozen': list(s2s.frozen_prefixes), 'rng': rng.bit_generator.state,
+                              'split_rand': split_rand, 'history': history, 'm': m, 'v': v, 'best': best_weights or {}}
+            keras_h5.write_model('model.ckpt.weights-%02d-%.2f.h5' % (epoch + 1, val_loss), s2s._config_dict(), weights, ckpt_state)
+            if wait >= 3:                              # EarlyStopping(patience=3, restore_best_weights)
+                s2s.logger.info('Epoch %05d: early stopping', epoch + 1)
+                break
             if stop['flag']:
                 break
     finally:

@@ -177,6 +177,15 @@ int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U
                     double* loss, double* grad_norm);
 /* Gradient of the last step for one tensor, in Keras layout (parity tests). */
 int casv_train_get_gradient(casv_model* m, const char* name, float* out, int64_t capacity);
+/* Adam's optimizer state of one trained tensor in Keras layout, like casv_train_get_gradient: which = 0 the first moment m,
+ * 1 the second moment v.  Valid inside a session, between steps.  A frozen tensor has no state (CASV_ERR_STATE).
+ * With casv_train_get_step / casv_train_set_step (the step count of Adam's bias correction) this is everything a session
+ * carries from one step to the next: a fresh session given the weights, these moments and the step continues the old one
+ * (bit for bit with the "deterministic" option of casv_set_option). */
+int casv_train_get_state(casv_model* m, const char* name, int32_t which, float* out, int64_t capacity);
+int casv_train_set_state(casv_model* m, const char* name, int32_t which, const float* data, int64_t count);
+int casv_train_get_step(casv_model* m, int64_t* step);
+int casv_train_set_step(casv_model* m, int64_t step);
 /* Make casv_get_weight see the current training weights (ModelCheckpoint, EarlyStopping restore; seq2seq.py:619-622). */
 int casv_train_sync_weights(casv_model* m);
 /* End the session: the trained weights replace the handle's weights and are repacked for inference
@@ -245,6 +254,14 @@ int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int32_t N, int3
  * without handing on: the give-up path, the step is redone with per-step launches.  Not available otherwise.);
  * "fused_backward" = 1 (default): a backward time step without a persistent form is ONE launch (cell backward inside the data
  * GEMM), 0: two;
+ * "deterministic" = 0 (default) / 1: casv_train_step's results (loss, grad_norm, gradients, weights, Adam's moments; modes 0, 1
+ * and 2) become a function of its inputs alone -- weights, Adam state and step count, batch arrays, masks, Adam parameters and
+ * frozen set -- on a given device model and build: not of the run's timing, other work on the GPU, the device's CU count or the
+ * "persistent" / "fused_backward" / CASV_ATTN_DEFER choices.  Every sum runs in a fixed order and no kernel of the step adds floats
+ * atomically: the recurrences take their per-step launches, no launch splits K over workgroups except the K-major weight
+ * gradients, whose shares follow from the shape and are added in share order; loss, regulariser and norm are per-workgroup
+ * partial sums added by one ordered pass; the embedding gradient is summed per character in row order.  Slower than the default
+ * step (profiles/);
  * "vendor_gemm" = 0 (default): every contraction runs in this library's own kernels; 1 = calibration: the train step's plain
  * whole-sequence contractions (input projections, their data gradients) go through hipBLASLt where it can be loaded at run time
  * (bench.py reports that time beside the own-kernel figure; inference never uses it);
