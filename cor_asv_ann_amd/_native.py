@@ -51,6 +51,7 @@ SIGNATURES = {
     'casv_set_encoder_outputs': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'casv_get_encoder_outputs': (c_int, [c_void_p, c_void_p, c_void_p]),
     'casv_decoder_step': (c_int, [c_void_p, c_int32] + [c_void_p] * 7),
+    'casv_decoder_step_lm': (c_int, [c_void_p, c_int32] + [c_void_p] * 8),
     'casv_decode_greedy': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'casv_decode_beam': (c_int, [c_void_p, POINTER(BeamParams), c_int32] + [c_void_p] * 8),
     'casv_train_begin': (c_int, [c_void_p, POINTER(AdamParams), c_char_p]),

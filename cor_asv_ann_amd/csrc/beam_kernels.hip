@@ -10,6 +10,7 @@
 // Order of nodes = (pro_cost descending, creation order ascending): `insort_left` + `pop()` take,
 // among equal pro_cost, the node inserted first.
 #include "common.h"
+#include "row_kernels.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -80,11 +81,44 @@ void beam_prof_dump(int steps) {
 #define BPROF(slot)
 #endif
 
+// lm_predict: the statistics of the LM row of expansion row r -- the max (NaN if a logit is NaN) and the
+// sum of softmax_kernel, in its order: the LM probability of index v is then expf(x[v] - m) / sum, its cost -logf of that.  Any NaN
+// probability makes the sum NaN and with it the whole row, so the NaN skip of s2s:1503-1505 drops a row's children all together.
+struct LmStats { float m, sum; };
+template <int VPL>
+__device__ __forceinline__ LmStats lm_stats(const BeamState& s, const int r, const int lane) {
+    const int V = s.V, Vp = (V + 31) & ~31;
+    const float* x = s.lm_logits + (long long)r * Vp;
+    float xv[VPL];
+    float m = -INFINITY, nn = 0.0f;
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+        const int v = lane + 64 * k;
+        xv[k] = v < V ? x[v] : 0.0f;
+        if (v < V) { m = fmaxf(m, xv[k]); nn += (xv[k] != xv[k]) ? 1.0f : 0.0f; }
+    }
+    m = wave_butterfly(m, [](float a, float b) { return fmaxf(a, b); });
+    if (wave_butterfly(nn, [](float a, float b) { return a + b; }) > 0.0f) m = __builtin_nanf("");
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) if (lane + 64 * k < V) sum += expf(xv[k] - m);
+    sum = wave_butterfly(sum, [](float a, float b) { return a + b; });
+    return LmStats{m, sum};
+}
+__device__ __forceinline__ float lm_prob(const BeamState& s, const int r, const int v, const LmStats& st) {
+    return expf(s.lm_logits[(long long)r * ((s.V + 31) & ~31) + v] - st.m) / st.sum;
+}
+// ... and whether the row is NaN: its context (row_kernels.h, lm_context_nan: the window of this step, the parent's query) or a logit
+__device__ __forceinline__ bool lm_row_nan(const BeamState& s, const int r, const int step, const LmStats& st, const int lane) {
+    const int win = s.lm_win[(long long)(step + 1) * s.R + r];
+    return lm_context_nan(s.lm_q + (long long)s.prev[r] * s.W, s.lm_va, s.lm_bv, s.W, win < 0 ? 0 : win >> 16, lane) || st.sum != st.sum;
+}
+
 // Phase A1 for expansion row i of `line` (one wave): the row's softmax (when the step hands over logits), the rejection
 // candidate (seq2seq.py:1457-1470) written over its score, the beam width from the relative threshold (:1472-1480), the
 // ranks of index 0 and of the rejection index => number of children.  The row's final scores stay in `vals`
 // (lane + 64 k; -inf beyond V) and in the score store.
-template <int VPL>
+template <int VPL, bool LM>
 __device__ __forceinline__ RowRec expand_row_scores(const BeamState& s, const BeamParams& p, const int line, const int i, const int step,
                                                     const int lane, float (&vals)[VPL]) {
     const int N = p.N, V = s.V, Vp = (V + 31) & ~31, T = s.T, R = s.R;
@@ -181,6 +215,7 @@ __device__ __forceinline__ RowRec expand_row_scores(const BeamState& s, const Be
     const int rejlate = (rej > 0 && rankr > beampos) ? 1 : 0;  // `if rej_idx:` is false for 0 (s2s:1498)
     count += rejlate;
     if (anynan) count = 0;
+    if constexpr (LM) if (lm_row_nan(s, r, step, lm_stats<VPL>(s, r, lane), lane)) count = 0;
     return RowRec{count, beampos, rej, srcpos, anynan ? 1 : 0, rejlate};
 }
 
@@ -228,7 +263,7 @@ __device__ __forceinline__ int select_children(const float (&vals)[VPL], const i
 // (beam_expand_kernel), and leaves per row a record and the list of its children; the per-line kernel (SPLIT) then only numbers
 // the children, writes their node records (one thread per child), sorts, merges and pops.  With one workgroup per line doing
 // all of it, a page of 40 lines x 256 hypotheses kept 40 CUs busy for 0.45 ms per step, most of it walking rows.
-template <int VPL>
+template <int VPL, bool LM>
 __global__ __launch_bounds__(512) void beam_expand_kernel(const BeamState s, const BeamParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = blockIdx.x * 8 + wave;
@@ -238,12 +273,15 @@ __global__ __launch_bounds__(512) void beam_expand_kernel(const BeamState s, con
     if (s.line_done[line] || i >= s.nact[line] || step + 1 >= s.S) return;
     const int CMAX = (p.width_in < s.V ? p.width_in : s.V) + 1;
     float vals[VPL];
-    RowRec rc = expand_row_scores<VPL>(s, p, line, i, step, lane, vals);
+    RowRec rc = expand_row_scores<VPL, LM>(s, p, line, i, step, lane, vals);
     int rej_k = -1;
     if (rc.count > 0) {
         short* ci = s.cand_idx + (long long)r * CMAX;
         float* cv = s.cand_val + (long long)r * CMAX;
+        LmStats lm{};
+        if constexpr (LM) lm = lm_stats<VPL>(s, r, lane);
         select_children<VPL>(vals, s.V, rc.beampos, rc.rejlate, rc.rej, lane, [&](const int k, const int bi, const float bv, const bool isrej) {
+            if constexpr (LM) { const float lp = lm_prob(s, r, bi, lm); if (lane == 0) s.cand_lm[(long long)r * CMAX + k] = lp; }
             if (lane == 0) { ci[k] = (short)bi; cv[k] = bv; }
             if (isrej) rej_k = k;
         });
@@ -253,9 +291,9 @@ __global__ __launch_bounds__(512) void beam_expand_kernel(const BeamState s, con
 }
 
 // VPL = vocabulary entries per lane (V <= 64 * VPL); NWV = waves per workgroup (one wave expands one hypothesis row);
-// SPLIT: phase A has run as beam_expand_kernel
-template <int VPL, int NWV, bool SPLIT>
-__global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <= 4 && NWV <= 8 ? 8 : (NWV > 8 ? 4 : 1), 8))) void beam_step_kernel(const BeamState s, const BeamParams p) {
+// SPLIT: phase A has run as beam_expand_kernel; LM: lm_predict (children's costs from the LM row, BeamState.lm_logits)
+template <int VPL, int NWV, bool SPLIT, bool LM>
+__global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <= 4 && NWV <= 8 ? (LM ? 6 : 8) : (NWV > 8 ? 4 : 1), 8))) void beam_step_kernel(const BeamState s, const BeamParams p) {
     constexpr int NT = 64 * NWV;
     // dynamic LDS: [sort_cap new keys (f64)] [q_stage old keys (f64)] [pop_cap head keys (f64)] [sort_cap new ids] [q_stage old ids]
     // [7 x (N+1) row records] [pop_cap head ids] [pop_cap head characters]
@@ -300,7 +338,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <=
     if (!SPLIT) {
         for (int i = wave; i < nact; i += NWV) {
             float vals[VPL];
-            const RowRec rc = expand_row_scores<VPL>(s, p, line, i, step, lane, vals);
+            const RowRec rc = expand_row_scores<VPL, LM>(s, p, line, i, step, lane, vals);
             if (lane == 0) {
                 r_count[i] = rc.count; r_beampos[i] = rc.beampos; r_rej[i] = rc.rej; r_srcpos[i] = rc.srcpos;
                 r_nan[i] = rc.nan; r_rejlate[i] = rc.rejlate;
@@ -333,11 +371,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <=
 
     BPROF(1);
     // ---------------- A2: iterative selection, node records, keys ----------------
-    auto new_node = [&](const int i, const int k, const int bi, const float bv, const bool isrej, const int node, const int plen,
-                        const double pcum, const double pos, const int is1, const long long exp) {
+    // cp: the probability the child's cost is taken from -- its score bv, or with lm_predict the LM's probability (s2s:1487-1490)
+    auto new_node = [&](const int i, const int k, const int bi, const float bv, const float cp, const bool isrej, const int node,
+                        const int plen, const double pcum, const double pos, const int is1, const long long exp) {
         const int slot = r_off[i] + k;
         const int id = id0 + slot;
-        const float cost = -logf(bv);
+        const float cost = -logf(cp);
         const double cum = pcum + (double)cost;
         const int len = plen + 1;
         const long long g = nbase + id;
@@ -366,8 +405,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <=
             float vals[VPL];
 #pragma unroll
             for (int k = 0; k < VPL; ++k) { const int v = lane + 64 * k; vals[k] = v < V ? sc[v] : -INFINITY; }
+            LmStats lm{};
+            if constexpr (LM) lm = lm_stats<VPL>(s, r, lane);
             select_children<VPL>(vals, V, r_beampos[i], r_rejlate[i], r_rej[i], lane, [&](const int k, const int bi, const float bv, const bool isrej) {
-                if (lane == 0) new_node(i, k, bi, bv, isrej, node, plen, pcum, pos, is1, exp);
+                float cp = bv;
+                if constexpr (LM) cp = lm_prob(s, r, bi, lm);
+                if (lane == 0) new_node(i, k, bi, bv, cp, isrej, node, plen, pcum, pos, is1, exp);
             });
         }
     } else {
@@ -379,7 +422,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(VPL <=
             const int r = line * N + i;
             const long long exp = (long long)(step + 1) * R + r;
             const int node = s.beam_node[r];
-            new_node(i, k, (int)s.cand_idx[(long long)r * CMAX + k], s.cand_val[(long long)r * CMAX + k], k == r_rej[i], node,
+            const float bv = s.cand_val[(long long)r * CMAX + k];
+            new_node(i, k, (int)s.cand_idx[(long long)r * CMAX + k], bv, LM ? s.cand_lm[(long long)r * CMAX + k] : bv, k == r_rej[i], node,
                      s.n_len[nbase + node], s.n_cum[nbase + node], s.apos[r], s.amax1[r], exp);
         }
     }
@@ -670,9 +714,14 @@ void launch_beam_step(const BeamState& s, const BeamParams& p, hipStream_t strea
     const bool huge = p.N >= 64;
     // sixteen waves per line and phase A as a grid of its own (beam_expand_kernel) when the host has given it buffers
     const bool split = huge && s.rowrec != nullptr;
-#define CASV_BEAM_LAUNCH(VPL_, NWV_) hipLaunchKernelGGL((beam_step_kernel<VPL_, NWV_, false>), dim3(s.B), dim3(64 * NWV_), lds, stream, s, pp)
-#define CASV_BEAM_SPLIT(VPL_) do { hipLaunchKernelGGL((beam_expand_kernel<VPL_>), dim3((s.R + 7) / 8), dim3(512), 0, stream, s, pp); \
-                                   hipLaunchKernelGGL((beam_step_kernel<VPL_, 16, true>), dim3(s.B), dim3(1024), lds, stream, s, pp); \
+    // lm_predict: the same launches of the LM instantiations (the default path launches exactly the kernels it did without the option)
+    const bool lm = s.lm_logits != nullptr;
+#define CASV_BEAM_LAUNCH(VPL_, NWV_) do { if (lm) hipLaunchKernelGGL((beam_step_kernel<VPL_, NWV_, false, true>), dim3(s.B), dim3(64 * NWV_), lds, stream, s, pp); \
+                                          else hipLaunchKernelGGL((beam_step_kernel<VPL_, NWV_, false, false>), dim3(s.B), dim3(64 * NWV_), lds, stream, s, pp); } while (0)
+#define CASV_BEAM_SPLIT(VPL_) do { if (lm) { hipLaunchKernelGGL((beam_expand_kernel<VPL_, true>), dim3((s.R + 7) / 8), dim3(512), 0, stream, s, pp); \
+                                             hipLaunchKernelGGL((beam_step_kernel<VPL_, 16, true, true>), dim3(s.B), dim3(1024), lds, stream, s, pp); } \
+                                   else { hipLaunchKernelGGL((beam_expand_kernel<VPL_, false>), dim3((s.R + 7) / 8), dim3(512), 0, stream, s, pp); \
+                                          hipLaunchKernelGGL((beam_step_kernel<VPL_, 16, true, false>), dim3(s.B), dim3(1024), lds, stream, s, pp); } \
                                    hipLaunchKernelGGL(beam_inputs_kernel, dim3((s.R + 7) / 8), dim3(512), 0, stream, s, pp); } while (0)
     if (vpl <= 4) { if (split) CASV_BEAM_SPLIT(4); else if (huge) CASV_BEAM_LAUNCH(4, 16); else if (wide) CASV_BEAM_LAUNCH(4, 8); else CASV_BEAM_LAUNCH(4, 4); }
     else if (vpl <= 8) { if (split) CASV_BEAM_SPLIT(8); else if (huge) CASV_BEAM_LAUNCH(8, 16); else if (wide) CASV_BEAM_LAUNCH(8, 8); else CASV_BEAM_LAUNCH(8, 4); }

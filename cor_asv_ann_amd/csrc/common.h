@@ -252,6 +252,17 @@ struct SoftmaxArgs {
     int nact_group;
 };
 void launch_softmax(const SoftmaxArgs& a, hipStream_t stream);
+// lm_predict's probabilities for casv_decoder_step_lm: softmax_kernel's arithmetic on the LM logits; rows whose LM context is NaN
+// (row_kernels.h, lm_context_nan: the window `win` of the step, -1 = empty, and the query wq of the row) are NaN
+struct LmSoftmaxArgs {
+    const float* logits;    // [R][Vp]
+    float* probs;           // [R][Vp]
+    const float* wq;        // [R][W]
+    const float* va; const float* bv;
+    const int* win;         // [R]
+    int R, V, W;
+};
+void launch_lm_softmax(const LmSoftmaxArgs& a, hipStream_t stream);
 
 void launch_embed_sparse(const float* E, const int* idx, const float* val, float* x0,
                          int rows, int A, int V, int W, hipStream_t stream);
@@ -341,6 +352,12 @@ struct BeamState {
     // wide beams (N >= 64): phase A as its own grid -- per row its record and the list of its children in creation order
     RowRec* rowrec;             // [R] or nullptr (then the per-line kernel does phase A itself)
     short* cand_idx; float* cand_val;   // [R][min(beam_width_in, V) + 1]
+    // lm_predict (lm_logits == nullptr: off): a child's cost is -log of the LM's probability of its index.
+    // lm_logits [R][Vp] of this step; the NaN rule of the LM's context (row_kernels.h, lm_context_nan) reads the query store
+    // [(S+1)*R][W] at the parent expansion prev[r], v_a, b_v and the window store [(S+1)*R]; wide beams: cand_lm [R][CMAX] = the
+    // LM probability of every child beam_expand_kernel chose
+    const float* lm_logits; const float* lm_q; const float* lm_va; const float* lm_bv; const int* lm_win; int W;
+    float* cand_lm;
 };
 void launch_beam_init(const BeamState& s, const BeamParams& p, hipStream_t stream);
 void launch_beam_step(const BeamState& s, const BeamParams& p, hipStream_t stream);

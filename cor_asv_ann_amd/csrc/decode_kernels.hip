@@ -80,6 +80,31 @@ void launch_softmax(const SoftmaxArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(softmax_kernel, dim3((a.R + 3) / 4), dim3(256), 0, stream, a);
 }
 
+// lm_predict's probabilities of casv_decoder_step_lm (s2s:470-473): the sums of softmax_kernel; a row whose LM context is NaN is NaN
+__global__ __launch_bounds__(256) void lm_softmax_kernel(const LmSoftmaxArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= a.R) return;
+    const int V = a.V, Vp = (V + 31) & ~31;
+    const float* x = a.logits + (long long)r * Vp;
+    float* p = a.probs + (long long)r * Vp;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+    float anynan = 0.0f;
+    for (int v = lane; v < V; v += 64) anynan += (x[v] != x[v]) ? 1.0f : 0.0f;
+    m = wave_max(m);
+    if (wave_sum(anynan) > 0.0f) m = __builtin_nanf("");
+    float sum = 0.0f;
+    for (int v = lane; v < V; v += 64) sum += expf(x[v] - m);
+    sum = wave_sum(sum);
+    const int win = a.win[r];
+    const bool cnan = lm_context_nan(a.wq + (long long)r * a.W, a.va, a.bv, a.W, win < 0 ? 0 : win >> 16, lane);
+    for (int v = lane; v < Vp; v += 64) p[v] = v < V ? (cnan ? __builtin_nanf("") : expf(x[v] - m) / sum) : 0.0f;
+}
+void launch_lm_softmax(const LmSoftmaxArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lm_softmax_kernel, dim3((a.R + 3) / 4), dim3(256), 0, stream, a);
+}
+
 // ---------------------------------------------------------------------------------------------
 // char_input_projection on the encoder side (seq2seq.py:243-244) for sparse input rows:
 // x0[row] = sum_a val[row][a] * E[idx[row][a]]   (one-hot: a single exact row copy)

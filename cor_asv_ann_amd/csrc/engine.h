@@ -127,6 +127,9 @@ struct casv_model {
     DevBuf st_a, st_p, ctx, wq, logits, prev, pin, apos, amax1, d_step, d_line, d_nan;
     DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (engine.hip, launch_step)
     DevBuf o_idx, o_prob, o_align, st_win, sp_lo, sp_w;
+    // lm_predict: per-step scratch of the LM output -- h of the LM cell [R][W] (its c [R][W] is written and
+    // never read), LM logits [R][Vp], casv_decoder_step_lm's probabilities [R][Vp]; wide beams: the LM probability of every child
+    DevBuf lm_h, lm_c, lm_logits, lm_probs, b_candlm;
     // what the last decode call left on the device (casv_get_alignments_sparse): 0 nothing, 1 greedy, 2 beam
     int last_decode = 0, last_S = 0, last_rows = 0, last_mode = 0; unsigned long long last_signature = 0;
     BeamState last_beam{}; BeamParams last_beam_params{};
@@ -144,6 +147,7 @@ struct casv_model {
     bool vendor_gemm = false;                             // calibration only: the train step's plain whole-sequence contractions through hipBLASLt (vendor_gemm.hip)
     bool fused_backward = true;                           // train step: cell backward fused into the step's data GEMM (gemm_bwd.hip)
     bool deterministic = false;                           // train step: every sum in a fixed order ("Reproducible training")
+    bool lm_predict = false;                              // beam decode: children's costs from the decoder's context-free LM (option "lm_predict")
     const int* skip_nact = nullptr;                       // beam decode: live rows per line, handed to the step's kernels when
     int skip_group = 0;                                   // skipping can pay (wide beams, or a line has finished); rows per line
     // the captured step graph of the last decode configuration (option "graph"): kept across calls, rebuilt when the

@@ -82,7 +82,8 @@ extern "C" void casv_model_destroy(casv_model* m) {
         &m->b_cum, &m->b_len, &m->b_exp, &m->b_k, &m->b_rejpos, &m->b_pos, &m->b_is1, &m->b_count, &m->b_created,
         &m->b_gkey, &m->b_gid, &m->b_qkey, &m->b_qid, &m->b_qn, &m->b_fkey, &m->b_fid, &m->b_fn, &m->b_ftotal, &m->b_beamnode, &m->b_nact,
         &m->b_done, &m->b_steps, &m->b_active, &m->bo_idx, &m->bo_prob, &m->bo_len, &m->bo_score,
-        &m->bo_rej, &m->bo_align, &m->bo_found, &m->bo_nsteps, &m->b_rowrec, &m->b_candidx, &m->b_candval};
+        &m->bo_rej, &m->bo_align, &m->bo_found, &m->bo_nsteps, &m->b_rowrec, &m->b_candidx, &m->b_candval,
+        &m->lm_h, &m->lm_c, &m->lm_logits, &m->lm_probs, &m->b_candlm};
     for (DevBuf* b : bufs) b->release();
     for (auto& l : m->enc) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
     for (LstmW* l : {&m->enc_fw, &m->enc_bw}) { l->pw.release(); l->pbias.release(); }
@@ -719,8 +720,13 @@ static int init_root(casv_model* m, int rows_per_line, SmallOps ops = SmallOps{}
 
 // One decoder_model step on R rows (seq2seq.py:416-480).  beam=true reads the input rows from `pin`,
 // otherwise from the previous slot of the score store (the fed-back softmax, seq2seq.py:1252).
+// lm=true (lm_predict, seq2seq.py:464-470) also computes the LM output: the top cell once more on the decoder's
+// own top-layer input and states with a zero context -- a second job of the top cell's launch that contracts the same packed weights
+// over the x and h segments only (the context rows are skipped: 0 . K_ctx) and leaves h in m->lm_h -- and its tied projection, a
+// job of the output projection's launch, into m->lm_logits.  Rows whose LM context would be NaN are marked by whoever reads the
+// logits (the beam step kernel; lm_softmax_kernel).  lm=false launches exactly what the step launched without the option.
 static void launch_step(casv_model* m, bool beam, int mode, const int* line, int rows_per_line,
-                        int* o_idx, float* o_prob, const int* step_ptr, int step_imm, bool softmax = true) {
+                        int* o_idx, float* o_prob, const int* step_ptr, int step_imm, bool softmax = true, bool lm = false) {
     const int W = m->W, V = m->V, Vp = m->Vp, C = m->C, T = m->T, D = m->D, R = m->R;
     const long long RW = (long long)R * W;
     // previous-step rows of the state stores: the beam gathers its parents' expansions through `prev`; without a beam
@@ -806,7 +812,19 @@ static void launch_step(casv_model* m, bool beam, int mode, const int* line, int
         g.nact = live; g.nact_group = m->skip_group;
     }
     for (int n = 2; n < D; ++n) { GemmArgs g = lower(n); run_gemm(m, EPI_LSTM, g); }
-    run_gemm(m, EPI_LSTM, gtop);
+    if (lm) {   // the LM cell beside the top cell: [x | 0] and the same h, c; its c goes to a scratch nothing reads
+        GemmBatch b{};
+        b.g[0] = gtop;
+        GemmArgs& g = b.g[1];
+        g = gtop;
+        g.nseg = 2;
+        g.a[1] = hseg(m->st_h[D].as<float>(), xwidth(D) + C);
+        g.a[2] = Seg{};
+        g.out = mkslot(m->lm_h.as<float>(), W);
+        g.c_out = mkslot(m->lm_c.as<float>(), W);
+        b.count = 2;
+        run_gemm_batch(m, EPI_LSTM, b);
+    } else run_gemm(m, EPI_LSTM, gtop);
     {   // tied output projection (seq2seq.py:379)
         GemmArgs g{};
         g.nseg = 1; g.a[0] = mkseg(m->st_h[D].as<float>(), W, W, 0, nullptr, RW, 1, 1);
@@ -814,9 +832,14 @@ static void launch_step(casv_model* m, bool beam, int mode, const int* line, int
         g.out = mkslot(m->logits.as<float>(), Vp);
         g.step_ptr = step_ptr; g.step_imm = step_imm;
         g.nact = live; g.nact_group = m->skip_group;
-        if (query_ahead) {
+        GemmArgs gl = g;                    // the LM's projection (seq2seq.py:468-469): the same tied weights on h of the LM cell
+        gl.a[0] = mkseg(m->lm_h.as<float>(), W, W, 0);
+        gl.out = mkslot(m->lm_logits.as<float>(), Vp);
+        if (query_ahead || lm) {
             GemmBatch b{};
-            b.g[0] = g; b.g[1] = gq; b.count = 2;
+            b.g[b.count++] = g;
+            if (query_ahead) b.g[b.count++] = gq;
+            if (lm) b.g[b.count++] = gl;
             run_gemm_batch(m, EPI_PLAIN, b);
         } else run_gemm(m, EPI_PLAIN, g);
     }
@@ -833,9 +856,9 @@ static void launch_step(casv_model* m, bool beam, int mode, const int* line, int
     }
 }
 
-extern "C" int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line, const float* p_in,
-                                 const float* states_in, const float* a_in, float* probs, float* states_out,
-                                 float* a_out) {
+// casv_decoder_step and (lm_probs != nullptr) casv_decoder_step_lm
+static int decoder_step(casv_model* m, int32_t R, const int32_t* line, const float* p_in, const float* states_in, const float* a_in,
+                        float* probs, float* states_out, float* a_out, float* lm_probs) {
     if (!m || !line || !p_in || !states_in || !a_in) return fail(CASV_ERR_ARG, "null argument");
     if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
     if (R < 1) return fail(CASV_ERR_ARG, "R must be positive");
@@ -857,7 +880,20 @@ extern "C" int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line, 
         HIPCHK(hipMemcpyAsync(m->st_c[n].p, states_in + (size_t)(2 * n - 1) * R * W, (size_t)R * W * 4, hipMemcpyHostToDevice, m->stream));
     }
     HIPCHK(hipMemcpyAsync(m->st_a.p, a_in, (size_t)R * T * 4, hipMemcpyHostToDevice, m->stream));
-    launch_step(m, false, -1, m->d_line.as<int>(), 1, nullptr, nullptr, nullptr, 0);
+    const bool lm = lm_probs != nullptr;
+    if (lm) {
+        if (int rc = m->lm_h.ensure((size_t)R * W * 4)) return rc;
+        if (int rc = m->lm_c.ensure((size_t)R * W * 4)) return rc;
+        if (int rc = m->lm_logits.ensure((size_t)R * Vp * 4)) return rc;
+        if (int rc = m->lm_probs.ensure((size_t)R * Vp * 4)) return rc;
+    }
+    launch_step(m, false, -1, m->d_line.as<int>(), 1, nullptr, nullptr, nullptr, 0, true, lm);
+    if (lm) {       // the step's query (m->wq) and window (slot 1 of the window store) give the LM's NaN rows
+        LmSoftmaxArgs a{};
+        a.logits = m->lm_logits.as<float>(); a.probs = m->lm_probs.as<float>(); a.wq = m->wq.as<float>();
+        a.va = m->va.as<float>(); a.bv = m->bv.as<float>(); a.win = m->st_win.as<int>() + R; a.R = R; a.V = V; a.W = W;
+        launch_lm_softmax(a, m->stream);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream));
     if (probs) HIPCHK(hipMemcpy2D(probs, (size_t)V * 4, m->st_p.as<float>() + (size_t)R * Vp, (size_t)Vp * 4, (size_t)V * 4, R, hipMemcpyDeviceToHost));
@@ -867,7 +903,21 @@ extern "C" int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line, 
             HIPCHK(hipMemcpy(states_out + (size_t)(2 * n - 1) * R * W, m->st_c[n].as<float>() + (size_t)R * W, (size_t)R * W * 4, hipMemcpyDeviceToHost));
         }
     if (a_out) HIPCHK(hipMemcpy(a_out, m->st_a.as<float>() + (size_t)R * T, (size_t)R * T * 4, hipMemcpyDeviceToHost));
+    if (lm) HIPCHK(hipMemcpy2D(lm_probs, (size_t)V * 4, m->lm_probs.as<float>(), (size_t)Vp * 4, (size_t)V * 4, R, hipMemcpyDeviceToHost));
     return CASV_OK;
+}
+
+extern "C" int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line, const float* p_in,
+                                 const float* states_in, const float* a_in, float* probs, float* states_out,
+                                 float* a_out) {
+    return decoder_step(m, R, line, p_in, states_in, a_in, probs, states_out, a_out, nullptr);
+}
+
+extern "C" int casv_decoder_step_lm(casv_model* m, int32_t R, const int32_t* line, const float* p_in,
+                                    const float* states_in, const float* a_in, float* probs, float* states_out,
+                                    float* a_out, float* lm_probs) {
+    if (!lm_probs) return fail(CASV_ERR_ARG, "null argument");
+    return decoder_step(m, R, line, p_in, states_in, a_in, probs, states_out, a_out, lm_probs);
 }
 
 // Runs iterations of `body(step_ptr, step_imm)` (which launches one step).  Eagerly the host passes the step number as
@@ -1171,6 +1221,11 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     ENS(m->b_steps, (size_t)B * 4) ENS(m->b_active, 16)
     ENS(m->b_gkey, (size_t)2 * B * s.g_cap * 8) ENS(m->b_gid, (size_t)2 * B * s.g_cap * 4)
     if (N >= 64) { ENS(m->b_rowrec, (size_t)R * sizeof(RowRec)) ENS(m->b_candidx, (size_t)R * CM * 2) ENS(m->b_candval, (size_t)R * CM * 4) }
+    const bool lm = m->lm_predict;          // (read at every call)
+    if (lm) {
+        ENS(m->lm_h, (size_t)R * m->W * 4) ENS(m->lm_c, (size_t)R * m->W * 4) ENS(m->lm_logits, (size_t)R * m->Vp * 4)
+        if (N >= 64) ENS(m->b_candlm, (size_t)R * CM * 4)
+    }
     const size_t OR = (size_t)B * MR;
     ENS(m->bo_idx, OR * S * 4) ENS(m->bo_prob, OR * S * 4) ENS(m->bo_len, OR * 4) ENS(m->bo_score, OR * 8) ENS(m->bo_rej, OR * S * 4)
     ENS(m->bo_found, (size_t)B * 4) ENS(m->bo_nsteps, (size_t)B * 4)
@@ -1189,6 +1244,10 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     s.apos = m->apos.as<double>(); s.amax1 = m->amax1.as<int>(); s.src_rej = m->d_srcrej.as<int>();
     s.step_ptr = m->d_step.as<int>();
     if (N >= 64) { s.rowrec = m->b_rowrec.as<RowRec>(); s.cand_idx = m->b_candidx.as<short>(); s.cand_val = m->b_candval.as<float>(); }
+    if (lm) {
+        s.lm_q = m->st_q.as<float>(); s.lm_va = m->va.as<float>(); s.lm_bv = m->bv.as<float>(); s.lm_win = m->st_win.as<int>(); s.W = m->W;
+        if (N >= 64) s.cand_lm = m->b_candlm.as<float>();
+    }
     BeamParams p{};
     p.N = N; p.width_in = bp->beam_width_in; p.width_out = bp->beam_width_out; p.max_results = MR;
     p.threshold_in = bp->beam_threshold_in; p.rejection = bp->rejection_threshold; p.cost0 = bp->cost0; p.eos = m->eos;
@@ -1199,11 +1258,12 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     m->skip_nact = (N >= 128 && !m->use_graph) ? m->b_nact.as<int>() : nullptr; m->skip_group = N;
     launch_beam_init(s, p, m->stream);
     auto body = [&](const int* step_ptr, int step_imm) {
-        launch_step(m, true, -1, nullptr, N, nullptr, nullptr, step_ptr, step_imm, false);
+        launch_step(m, true, -1, nullptr, N, nullptr, nullptr, step_ptr, step_imm, false, lm);
         hipEvent_t ev{};
-        m->prof_begin(PC_BEAM, 0.0, 4.0 * R * (2.0 * m->Vp), ev);
+        m->prof_begin(PC_BEAM, 0.0, 4.0 * R * ((lm ? 3.0 : 2.0) * m->Vp), ev);
         BeamState sb = s;
         sb.step_ptr = step_ptr; sb.step_imm = step_imm; sb.logits = m->logits.as<float>();
+        if (lm) sb.lm_logits = m->lm_logits.as<float>();
         launch_beam_step(sb, p, m->stream);
         m->prof_end(PC_BEAM, ev);
     };
@@ -1213,8 +1273,8 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     const int chunk = 16;
     int done_steps = 0;
     char key[256];
-    snprintf(key, sizeof key, "beam/%d/%d/%d/%d/%d/%d/%d/%.17g/%.17g/%.17g/%d", B, T, S, N, p.width_in, p.width_out, MR, p.threshold_in,
-             p.rejection, p.cost0, p.eos);
+    snprintf(key, sizeof key, "beam/%d/%d/%d/%d/%d/%d/%d/%.17g/%.17g/%.17g/%d%s", B, T, S, N, p.width_in, p.width_out, MR, p.threshold_in,
+             p.rejection, p.cost0, p.eos, lm ? "/lm" : "");
     StepRunner runner(m, key);
     if (!m->pin_active) {
         HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_active), 2 * sizeof(int), hipHostMallocDefault));
@@ -1515,6 +1575,10 @@ extern "C" int casv_set_option(casv_model* m, const char* key, int64_t value) {
     if (!strcmp(key, "deterministic")) {        // train step: bits a function of its inputs alone (train.hip)
         if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "deterministic must be 0 or 1");
         m->deterministic = value != 0; return CASV_OK;
+    }
+    if (!strcmp(key, "lm_predict")) {           // beam decode: children's costs from the LM output
+        if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "lm_predict must be 0 or 1");
+        m->lm_predict = value != 0; return CASV_OK;
     }
     if (!strcmp(key, "vendor_gemm")) { m->vendor_gemm = value != 0; return CASV_OK; }
     if (!strcmp(key, "skinny") || !strcmp(key, "tile")) {   // process-wide: tile shape of the GEMM launches (results identical)

@@ -210,6 +210,26 @@ __device__ __forceinline__ void att_context(const AttnArgs& a, const int r, cons
     }
 }
 
+// The LM output of lm_predict (seq2seq.py:464-470): the top cell's attention with zero constants (enc_out = u = 0).  Every position
+// of the window then has the one energy e = exp(tanh(wq) . v_a + b_v) -- the sum of att_energy_sums with u = 0, in its order -- and
+// the context sum_s (e / sum e) * 0 is exactly 0, unless the window is empty (cnt <= 0) or e is 0 or not finite: then it is NaN
+// (0/0, inf/inf), and so is the whole LM row.  wq = the row's attention query (h_D . W_a + b_UW).
+__device__ __forceinline__ bool lm_context_nan(const float* wq, const float* va, const float* bv, const int W, const int cnt,
+                                               const int lane) {
+    const float4* wq4 = reinterpret_cast<const float4*>(wq);
+    const float4* va4 = reinterpret_cast<const float4*>(va);
+    float e = 0.0f;
+    for (int j = lane; j < (W >> 2); j += 64) {
+        const float4 q = wq4[j], v = va4[j];
+        e += fast_tanh(q.x + 0.0f) * v.x;
+        e += fast_tanh(q.y + 0.0f) * v.y;
+        e += fast_tanh(q.z + 0.0f) * v.z;
+        e += fast_tanh(q.w + 0.0f) * v.w;
+    }
+    const float x = expf(wave_sum(e) + bv[0]);
+    return cnt <= 0 || !(x > 0.0f) || x == INFINITY;
+}
+
 template <bool HANDOFF, int WB = MAXWIN>
 __device__ __forceinline__ void attention_row(const AttnArgs& a, const int r, const int step, const int lane) {
     const int ln = a.line ? a.line[r] : r / a.rows_per_line;

@@ -263,6 +263,22 @@ class HipEngine(object):
         st_out = self._stripw(st_out)
         return probs, [st_out[i] for i in range(2 * self.depth)] + [a_out]
 
+    def decoder_step_lm(self, line, p_in, states, a_in):
+        """decoder_step plus the LM output of lm_predict (casv_decoder_step_lm): (probs, lm_probs, new states)."""
+        line = nv.carray(line, np.int32)
+        R = line.shape[0]
+        p_in = nv.carray(p_in, np.float32)
+        st = nv.carray(self._padw(np.stack(states[:2 * self.depth])), np.float32)
+        a_in = nv.carray(a_in, np.float32)
+        probs = np.empty((R, self.voc_size), np.float32)
+        lm_probs = np.empty((R, self.voc_size), np.float32)
+        st_out = np.empty_like(st)
+        a_out = np.empty((R, self.T), np.float32)
+        nv.check(self.lib.casv_decoder_step_lm(self.handle, R, nv.ptr(line), nv.ptr(p_in), nv.ptr(st), nv.ptr(a_in),
+                                               nv.ptr(probs), nv.ptr(st_out), nv.ptr(a_out), nv.ptr(lm_probs)))
+        st_out = self._stripw(st_out)
+        return probs, lm_probs, [st_out[i] for i in range(2 * self.depth)] + [a_out]
+
     # -- decode loops --------------------------------------------------------------------------
     def decode_greedy(self, mode=0, steps=None, want_align=False):
         S = int(steps or 2 * self.T)

@@ -119,7 +119,9 @@ class Sequence2Sequence(object):
         for flag in _UNSUPPORTED:
             if getattr(self, flag):
                 raise NotImplementedError('%s is not implemented in the MI355X hot path (only the default '
-                                          'topology of the published models is)' % flag)
+                                          'topology of the published models is)%s' % (
+                                              flag, '; set lm_predict after configure() / load_config(): it is read at '
+                                              'every beam decode' if flag == 'lm_predict' else ''))
         self.logger.info('using HIP/gfx950 implementation to compile %s model of depth %d width %d size %d '
                          'with attention', 'stateless', self.depth, self.width, self.voc_size)
         if self.engine is not None:
@@ -449,6 +451,9 @@ class Sequence2Sequence(object):
         self._eos = self.mapping[0].get('\n', 1)
         self.engine.set_option('eos', self._eos)
         self.engine.set_option('arithmetic', {'auto': -1, 'fp32': 0, 'split': 2}[self.arithmetic])
+        # lm_predict (seq2seq.py:145-149, 1487-1490): a decode-time switch of the beam search, read at every call like
+        # rejection_threshold (the greedy decodes do not look at it)
+        self.engine.set_option('lm_predict', int(bool(self.lm_predict)))
         return self.engine
 
     def _codepoint_table(self):
@@ -577,7 +582,7 @@ class Sequence2Sequence(object):
     @property
     def decoder_model(self):
         """Stand-in for the Keras `decoder_model` (seq2seq.py:470-473): `.predict_on_batch([p, enc_out] + states)` ->
-        [scores (R,1,V)] + new states."""
+        [scores (R,1,V)] + new states; with lm_predict [scores, lm_scores (R,1,V)] + new states."""
         return _DecoderModel(self)
 
     def decode_sequence_greedy(self, source_seq=None, encoder_outputs=None):
@@ -735,6 +740,8 @@ class Sequence2Sequence(object):
         # plus the trie: up to min(beam_width_in, V) + 1 child records of 60 bytes per expansion
         children = min(self.beam_width_in, self.voc_size) + 1
         per_line = 2 * T * self.batch_size * (((2 * self.depth + 1) * self.width + self.voc_size + 32 + T) * 4 + 60 * children)
+        if self.lm_predict:     # the LM's per-step scratch: h and c of its cell, its logits, the LM probability of every child
+            per_line += self.batch_size * ((2 * self.width + self.voc_size + 32 + children) * 4)
         budget = float(os.environ.get('CASV_BEAM_MEMORY_GB', '96')) * 2 ** 30
         chunk = int(max(1, min(B, budget // max(per_line, 1))))
         out = []
@@ -1040,6 +1047,9 @@ class _DecoderModel(object):
         zero = [np.zeros((Ba, s2s.width), np.float32)] * (2 * d)
         eng.set_encoder_outputs(attended, zero)
         line = np.arange(R, dtype=np.int32) if Ba == R else np.zeros(R, np.int32)
+        if s2s.lm_predict:          # (seq2seq.py:464-473: the LM output follows the decoder's)
+            probs, lm_probs, new = eng.decoder_step_lm(line, p_in.reshape(R, -1), states[:2 * d], states[2 * d])
+            return [probs[:, None, :], lm_probs[:, None, :]] + new
         probs, new = eng.decoder_step(line, p_in.reshape(R, -1), states[:2 * d], states[2 * d])
         return [probs[:, None, :]] + new
 

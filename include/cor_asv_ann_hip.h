@@ -48,7 +48,9 @@ typedef enum {
  * 2k+1 of [fw | bw] both replaced by their sum -- and hands on its backward final state; the attended width is then 2 * width for
  * every depth (att_U (2W,W), top decoder kernel (3W,4W)).  The train step adds the training graph's decoder sums (layers >= 2 and
  * the projection's input) -- which the reference's inference decoder does not have (seq2seq.py:421-436), restated as it is.
- * lm_loss/lm_predict and stateful must be 0 (both published models use the default topology, wrapper/ocrd-tool.json:61-74). */
+ * lm (lm_loss / lm_predict set at model build) and stateful must be 0 (both published models use the default topology,
+ * wrapper/ocrd-tool.json:61-74).  The LM output of lm_predict needs no other weights: it is a decode-time switch of the handle,
+ * casv_set_option(m, "lm_predict", 1), read by casv_decode_beam, and casv_decoder_step_lm computes it for one step. */
 typedef struct {
     int32_t depth;          /* seq2seq.py:117 */
     int32_t width;          /* seq2seq.py:115; must be a multiple of 32 (any other width: pad with dead units, as
@@ -115,6 +117,15 @@ int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line,
                       const float* p_in, const float* states_in, const float* a_in,
                       float* probs, float* states_out, float* a_out);
 
+/* decoder_model.predict_on_batch with lm_predict (seq2seq.py:464-473): casv_decoder_step (same arguments, same results bit for bit)
+ * plus lm_probs (R,V) = the decoder's context-free language model -- the top cell once more on the same input and states with zero
+ * attention constants (enc_out = u = 0: a zero context, or NaN where the window is empty or the energy exp(tanh(q).v_a + b_v) is 0
+ * or infinite: the whole row is NaN then), its states discarded, through the tied projection and softmax.  Always computed,
+ * whatever the "lm_predict" option says; arithmetic 0 like casv_decoder_step. */
+int casv_decoder_step_lm(casv_model* m, int32_t R, const int32_t* line,
+                         const float* p_in, const float* states_in, const float* a_in,
+                         float* probs, float* states_out, float* a_out, float* lm_probs);
+
 /* decode_batch_greedy (seq2seq.py:1215-1286; mode 0: argmax without index 0, S = 2T steps for
  * all lines) and decode_sequence_greedy for every line at once (seq2seq.py:1288-1354; mode 1:
  * argmax over all V with the index-0 NaN write-back, a line's steps after its '\n' are not
@@ -129,7 +140,12 @@ int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S,
  * (seq2seq.py:1543), out_rej ((B*max_results), S) = source position if that step was a
  * rejection candidate (one-hot alignment row, seq2seq.py:1495) else -1, out_align
  * ((B*max_results), S, T) or NULL.  n_found (B) = finished hypotheses per line (0 = the
- * generator would raise StopIteration, seq2seq.py:826); n_steps (B) = search iterations run. */
+ * generator would raise StopIteration, seq2seq.py:826); n_steps (B) = search iterations run.
+ * With the option "lm_predict" = 1 (casv_set_option, read at every call) a child's cost -- and so cum_cost, the queue order, the
+ * stopping test and out_score -- is -log of the LM's probability of its character (casv_decoder_step_lm), and a child whose LM
+ * probability is NaN is dropped (seq2seq.py:1487-1490, 1503-1505); out_prob, the rejection candidates, the beam width, the order of
+ * the children and the fed-back scores stay the decoder's.  Needs batch_size * ((2 * width + V) * 4 + 4 * (beam_width_in + 1)) more
+ * bytes per line (per-step scratch of the LM). */
 int casv_decode_beam(casv_model* m, const casv_beam_params* p, int32_t S,
                      int32_t* out_idx, float* out_prob, int32_t* out_len, double* out_score,
                      int32_t* out_rej, float* out_align, int32_t* n_found, int32_t* n_steps);
@@ -262,6 +278,9 @@ int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int32_t N, int3
  * gradients, whose shares follow from the shape and are added in share order; loss, regulariser and norm are per-workgroup
  * partial sums added by one ordered pass; the embedding gradient is summed per character in row order.  Slower than the default
  * step (profiles/);
+ * "lm_predict" = 0 (default) / 1: casv_decode_beam rates its children by the decoder's context-free LM (seq2seq.py:145-149, 1487-1490;
+ * see casv_decode_beam); the LM jobs take the search's arithmetic, so a line's bits are a function of (weights, line, entry point,
+ * lm_predict).  The greedy decodes never use it;
  * "vendor_gemm" = 0 (default): every contraction runs in this library's own kernels; 1 = calibration: the train step's plain
  * whole-sequence contractions (input projections, their data gradients) go through hipBLASLt where it can be loaded at run time
  * (bench.py reports that time beside the own-kernel figure; inference never uses it);
