@@ -163,12 +163,17 @@ struct TnArgs {
     float* part;         // ordered form (launch_gemm_tn_ordered): K share z stores its partial tile at part[z][Mstore][N] ...
     float* colpart;      // ... and its column sums at colpart[z][Mstore]; a second pass adds the shares in z order
 };
-void launch_gemm_tn(const TnArgs& g, hipStream_t stream);
-bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream);      // the same contraction on bf16x3-split operands (gemm_tn_split.hip); false: no such form for the shape
+int launch_gemm_tn(const TnArgs& g, hipStream_t stream);           // returns the K shares launched
+// the same contraction on bf16x3-split operands (gemm_tn_split.hip); false: no such form for the shape.  *shares: K shares launched
+bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream, int* shares = nullptr);
 // The same contraction with its sums in a fixed order (the train step's "deterministic" option): K shares chosen from the shape alone,
 // each share's partial stored, then added in share order -- no float atomics.  Needs gemm_tn_ordered_floats(g) floats at `ws`.
+struct TnLaunch { int split, shares, nonempty; };   // which kernel ran (1: gemm_tn_split.hip), K shares launched, shares holding k-tiles
 size_t gemm_tn_ordered_floats(const TnArgs& g);
-void launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream);
+TnLaunch launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream);
+// The weight-gradient launch as the train step makes it: the ordered form when `ordered_ws` is given, else under the calling thread's
+// arithmetic the split kernel where the shape has that form, else the fp32-input kernel.
+TnLaunch launch_gemm_tn_any(const TnArgs& g, float* ordered_ws, hipStream_t stream);
 void launch_gemm(int epi, const GemmArgs& g, hipStream_t stream);
 void launch_gemm_batch(int epi, const GemmBatch& b, hipStream_t stream);
 void launch_gemm_skinny(int epi, const GemmBatch& b, int ksplit, int rows, hipStream_t stream);

@@ -157,6 +157,7 @@ struct casv_model {
     DevBuf rec; int rec_rows = 0, rec_S = 0;              // result records of this rank's lines, packed on the device (casv_records_*)
     int* pin_active = nullptr; hipEvent_t ev_active[2] = {nullptr, nullptr};   // beam decode: unfinished-line count, read one chunk behind
     int stat_beam[3] = {0, 0, 0};                         // last beam decode: most new hypotheses of one line in one step; rows stepped
+    int stat_tn[3] = {0, 0, 0};                           // last casv_debug_contract_tn: split kernel (0/1), K shares launched, shares holding k-tiles
                                                           // and distinct parent expansions among them (N <= 16 only)
     Prof prof;
 

@@ -1417,6 +1417,10 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!m || !key || !value) return fail(CASV_ERR_ARG, "null argument");
     if (!strcmp(key, "beam_max_new_keys")) { *value = m->stat_beam[0]; return CASV_OK; }
     if (!strcmp(key, "beam_sort_capacity")) { *value = 4096; return CASV_OK; }
+    if (!strcmp(key, "cus")) { *value = m->ncu; return CASV_OK; }
+    if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
+    if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
+    if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }
     return fail(CASV_ERR_ARG, "unknown statistic '%s'", key);
 }
 
@@ -1549,6 +1553,56 @@ extern "C" int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int3
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(C_, C.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
+}
+
+// Test support: ONE weight-gradient contraction C[m][n] (+)= sum_k A[k][m] * B[k][n] (m < Mstore) through the train step's own
+// dispatch (launch_gemm_tn_any, under the train step's arithmetic), on operands copied in with their strides.  Rows Mstore..M-1 of C
+// and colsum get a guard pattern on the device: a launch that stores there is an error.
+extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, int32_t Mstore, int32_t N, int32_t K,
+                                      const float* A_, int64_t lda, const float* B_, int64_t ldb, float* C_, int64_t ldc,
+                                      float* colsum_) {
+    if (!m || !A_ || !B_ || !C_ || ((flags & 2) && !colsum_)) return fail(CASV_ERR_ARG, "null argument");
+    if (flags & ~7) return fail(CASV_ERR_ARG, "flags: 1 accumulate, 2 colsum, 4 ordered form");
+    if (M < 4 || N < 4 || K < 1 || M % 4 || N % 4 || Mstore < 1 || Mstore > M)
+        return fail(CASV_ERR_ARG, "M and N positive multiples of 4, 1 <= Mstore <= M, K positive");
+    if (lda < M || ldb < N || ldc < N || lda % 4 || ldb % 4) return fail(CASV_ERR_ARG, "lda >= M, ldb >= N (multiples of 4), ldc >= N");
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));
+    const size_t na = (size_t)(K - 1) * lda + M, nb = (size_t)(K - 1) * ldb + N;
+    const size_t nc = (size_t)(Mstore - 1) * ldc + N, nc_all = (size_t)M * ldc + N;      // (guard: every row of M and one more)
+    DevBuf A, B, C, cs, ws;
+    DebugBuffers release_on_exit{{&A, &B, &C, &cs, &ws}, nullptr, m->stream};
+    if (int rc = A.ensure(na * 4)) return rc;
+    if (int rc = B.ensure(nb * 4)) return rc;
+    if (int rc = C.ensure(nc_all * 4)) return rc;
+    if (int rc = cs.ensure((size_t)(M + 1) * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(A.p, A_, na * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(B.p, B_, nb * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemsetAsync(C.p, 0xff, nc_all * 4, m->stream));
+    HIPCHK(hipMemcpyAsync(C.p, C_, nc * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemsetAsync(cs.p, 0xff, (size_t)(M + 1) * 4, m->stream));
+    if (flags & 2) HIPCHK(hipMemcpyAsync(cs.p, colsum_, (size_t)Mstore * 4, hipMemcpyHostToDevice, m->stream));
+    TnArgs t{};
+    t.A = A.as<float>(); t.lda = lda; t.B = B.as<float>(); t.ldb = ldb; t.C = C.as<float>(); t.ldc = ldc;
+    t.M = M; t.Mstore = Mstore; t.N = N; t.K = K; t.accumulate = flags & 1; t.out_zeroed = 0;
+    t.colsum = (flags & 2) ? cs.as<float>() : nullptr;
+    float* wsp = nullptr;
+    if (flags & 4) {
+        if (int rc = ws.ensure(gemm_tn_ordered_floats(t) * 4)) return rc;
+        wsp = ws.as<float>();
+    }
+    const TnLaunch r = launch_gemm_tn_any(t, wsp, m->stream);
+    HIPCHK(hipGetLastError());
+    m->stat_tn[0] = r.split; m->stat_tn[1] = r.shares; m->stat_tn[2] = r.nonempty;
+    std::vector<uint32_t> guard(nc_all - nc), cguard((size_t)(M + 1 - Mstore));
+    HIPCHK(hipMemcpyAsync(C_, C.p, nc * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(guard.data(), C.as<float>() + nc, guard.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    if (flags & 2) HIPCHK(hipMemcpyAsync(colsum_, cs.p, (size_t)Mstore * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(cguard.data(), cs.as<float>() + Mstore, cguard.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (uint32_t v : guard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past row Mstore - 1 of C");
+    for (uint32_t v : cguard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past colsum[Mstore - 1]");
     return CASV_OK;
 }
 

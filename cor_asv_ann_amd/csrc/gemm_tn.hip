@@ -26,7 +26,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CASV_TN_XCD_ORDER 1         // 0: tile index fastest (the order of rounds 3-4; A/B builds)
 #endif
 constexpr int TBM = 128, TBN = 128, TBK = 16;
-constexpr int T_TILE = TBK * 128;                       // floats of one operand tile in LDS ([k][128])
+constexpr int T_TILE = TBK * 128;
+constexpr int TS_BK_SPLIT = 16;                        // k-tile of gemm_tn_split.hip                       // floats of one operand tile in LDS ([k][128])
 
 template <bool PART>        // PART: the ordered form's epilogue (partials stored per K share, launch_gemm_tn_ordered)
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
 }
 
 // `accumulate` = 0 with a split K needs a cleared C: the caller says so (out_zeroed) or gets a memset here.
-void launch_gemm_tn(const TnArgs& g, hipStream_t stream) {
+int launch_gemm_tn(const TnArgs& g, hipStream_t stream) {
     const int nbm = (g.M + TBM - 1) / TBM, nbn = (g.N + TBN - 1) / TBN;
     const int tiles = nbm * nbn, ktiles = (g.K + TBK - 1) / TBK;
     // fill the chip (512 workgroup slots), keep >= 64 k-tiles per workgroup so that the atomic epilogue stays a small part
@@ -249,6 +250,7 @@ void launch_gemm_tn(const TnArgs& g, hipStream_t stream) {
     TnArgs gg = g;
     gg.nsplit = ks;
     hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(tiles * ks), dim3(256), 0, stream, gg);
+    return ks;
 }
 
 // ---- ordered form ----
@@ -294,7 +296,7 @@ size_t gemm_tn_ordered_floats(const TnArgs& g) {
 }
 void launch_gemm_tn_split_part(const TnArgs& g, hipStream_t stream);        // gemm_tn_split.hip
 
-void launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream) {
+TnLaunch launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream) {
     bool split; int ks, nz;
     tn_ordered_plan(g, split, ks, nz);
     TnArgs gg = g;
@@ -305,6 +307,21 @@ void launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream) {
     const long long mn = (long long)g.Mstore * g.N;
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)std::min<long long>((mn + 255) / 256, 2048)), dim3(256), 0, stream,
                        gg.part, gg.colpart, nz, g.Mstore, g.N, g.C, g.ldc, g.accumulate, g.colsum);
+    return TnLaunch{split ? 1 : 0, ks, nz};
+}
+
+// K shares of a split-K launch that hold k-tiles at all (the last share may be partly filled)
+static int tn_nonempty_shares(int ktiles, int ks) {
+    const int per = (ktiles + ks - 1) / ks;
+    return per > 0 ? (ktiles + per - 1) / per : 1;
+}
+
+TnLaunch launch_gemm_tn_any(const TnArgs& g, float* ordered_ws, hipStream_t stream) {
+    if (ordered_ws) return launch_gemm_tn_ordered(g, ordered_ws, stream);
+    int ks = 0;
+    if (gemm_split_bf16() && launch_gemm_tn_split(g, stream, &ks)) return TnLaunch{1, ks, tn_nonempty_shares(g.K / TS_BK_SPLIT, ks)};
+    ks = launch_gemm_tn(g, stream);
+    return TnLaunch{0, ks, tn_nonempty_shares((g.K + TBK - 1) / TBK, ks)};
 }
 
 }  // namespace casv

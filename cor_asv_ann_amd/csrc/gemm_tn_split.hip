@@ -171,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_split256_kernel(const TnArgs g
 }
 
 // true: launched.  false: the shape has no 256x256 split form (the caller takes the fp32-input kernel).
-bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream) {
+bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream, int* shares) {
     static const bool off = [] { const char* e = getenv("CASV_TN_SPLIT"); return e && e[0] == '0'; }();
     if (off) return false;
     if (g.M <= 0 || g.N <= 0 || g.M % TS_BM || g.N % TS_BN || g.K < 64 * TS_BK || g.K % TS_BK) return false;
@@ -197,6 +197,7 @@ bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream) {
     TnArgs gg = g;
     gg.nsplit = ks;
     hipLaunchKernelGGL(gemm_tn_split256_kernel<false>, dim3(tiles * ks), dim3(512), TS_LDS, stream, gg);
+    if (shares) *shares = ks;
     return true;
 }
 

@@ -270,8 +270,8 @@ static void run_gemm_tn(casv_model* m, const float* A, long long lda, int M, int
             (void)hipStreamSynchronize(m->stream);
             if (int rc = ts->tn_ws.ensure(bytes)) { if (!ts->tn_ws_rc) ts->tn_ws_rc = rc; m->prof_end(PC_GEMM, ev); return; }
         }
-        launch_gemm_tn_ordered(g, ts->tn_ws.as<float>(), m->stream);
-    } else if (!(gemm_split_bf16() && launch_gemm_tn_split(g, m->stream))) launch_gemm_tn(g, m->stream);
+        (void)launch_gemm_tn_any(g, ts->tn_ws.as<float>(), m->stream);
+    } else (void)launch_gemm_tn_any(g, nullptr, m->stream);
     m->prof_end(PC_GEMM, ev);
 }
 

@@ -416,6 +416,24 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_contract(self.handle, flags, M, N, K, nv.ptr(A), nv.ptr(Bt), nv.ptr(bias), nv.ptr(C)))
         return C
 
+    def debug_contract_tn(self, A, B, C, Mstore=None, colsum=None, accumulate=False, ordered=False):
+        """Test support (casv_debug_contract_tn): C[:Mstore] (+)= A^T . B through the train step's weight-gradient dispatch, in
+        place; colsum[:Mstore] += A.sum(0) when given.  A (K, M) and B (K, N) may be column windows of wider float32 arrays (row
+        stride = lda / ldb), C (Mstore, N) one of a wider array too.  Returns the launch's (split, shares, nonempty_shares)."""
+        def window(a, name):
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 2 and a.strides[1] == 4, name
+            return a.strides[0] // 4
+        (K, M), N = A.shape, B.shape[1]
+        Mstore = M if Mstore is None else int(Mstore)
+        assert B.shape[0] == K and C.shape == (Mstore, N)
+        lda, ldb, ldc = window(A, 'A'), window(B, 'B'), window(C, 'C')
+        flags = (1 if accumulate else 0) | (2 if colsum is not None else 0) | (4 if ordered else 0)
+        if colsum is not None:
+            assert colsum.dtype == np.float32 and colsum.shape == (Mstore,) and colsum.flags.c_contiguous
+        nv.check(self.lib.casv_debug_contract_tn(self.handle, flags, M, Mstore, N, K, nv.ptr(A), lda, nv.ptr(B), ldb, nv.ptr(C), ldc,
+                                                 nv.ptr(colsum)))
+        return self.stat('tn_split'), self.stat('tn_shares'), self.stat('tn_nonempty_shares')
+
     def alignments_sparse(self, rows, steps, K=None):
         """Window form of the last decode call's soft alignments: (lo int32 (rows, S), w float32 (rows, S, K))."""
         K = int(K or 2 * self.window_width + 1)

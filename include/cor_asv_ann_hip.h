@@ -261,6 +261,15 @@ int casv_debug_gemm(casv_model* m, int32_t lstm, int32_t M, int32_t N, int32_t K
  * multiples of 256).  tests/test_gpu_gemm.py compares the result with a float64 product. */
 int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int32_t N, int32_t K, const float* A, const float* Bt,
                         const float* bias, float* C);
+/* Test support: ONE weight-gradient contraction as the train step launches it (csrc/gemm_tn.hip, launch_gemm_tn_any, under the train
+ * step's arithmetic): C[m][n] (+)= sum_k A[k][m] * B[k][n] for m < Mstore <= M, A [K][lda], B [K][ldb], C [Mstore][ldc] (row-major,
+ * copied in and out with their strides; lda, ldb, M, N multiples of 4).  flags: 1 = accumulate into the caller's C (else C =);
+ * 2 = colsum[m] += sum_k A[k][m] (in/out, Mstore entries); 4 = the ordered form of the "deterministic" option (K shares from the
+ * shape, partials added in share order).  casv_get_stat then reports "tn_split" (1: the bf16x3-split kernel ran), "tn_shares" (K
+ * shares launched) and "tn_nonempty_shares" (shares that hold k-tiles).  A store past row Mstore - 1 is reported as an error.
+ * tests/test_gpu_gemm_tn.py compares every form with a float64 product. */
+int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, int32_t Mstore, int32_t N, int32_t K, const float* A, int64_t lda,
+                           const float* B, int64_t ldb, float* C, int64_t ldc, float* colsum);
 /* Options: "graph" = replay the decode step through a captured hipGraph (1) or launch kernels eagerly (0);
  * "persistent" = greedy decoding through the persistent decoder (all steps in ONE launch, workgroups hand rows to each
  * other through memory: small batches, where a step is too short for a launch per kernel): -1 by batch size (default:
