@@ -70,6 +70,7 @@ SIGNATURES = {
     'casv_debug_contract': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'casv_debug_contract_tn': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                        c_void_p, c_int64, c_void_p]),
+    'casv_debug_activation': (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     'casv_set_option': (c_int, [c_void_p, c_char_p, c_int64]),
     'casv_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_comm_unique_id': (c_int, [c_void_p]),

@@ -5,7 +5,9 @@
 
 namespace casv {
 
-// tanh on the transcendental units (v_exp_f32 + v_rcp_f32): |error| <= ~2e-7 absolute.  The energies
+// tanh on the transcendental units (v_exp_f32 + v_rcp_f32): |error| <= 1.06e-7 absolute for tanh and sigmoid alike, measured on an
+// MI355X against float64 over every 64th float32 with |x| <= 30 plus the branch switch and saturation ranges
+// (profiles/r09_activation_error.txt; tests/test_gpu_activations.py holds it to 2e-7).  The energies
 // need 11*W tanh per decoder row; libm's tanhf made this kernel VALU-bound at 5x the time.
 // Value of lane (id ^ MASK) of a fully active 64-lane wave, without the LDS crossbar round trip of ds_bpermute (what
 // __shfl_xor compiles to): DPP for partners inside a row of 16 lanes, the gfx950 row-swap instructions across rows.  Same
@@ -275,6 +277,9 @@ void launch_advance_step(int* step_ptr, hipStream_t stream);
 // elementwise helpers of the optional topologies (seq2seq.py:284-301): dst[i] += src[i]; dst[i] = tanh(src[i]) (n floats, 16-byte aligned)
 void launch_add_inplace(float* dst, const float* src, long long n, hipStream_t stream);
 void launch_tanh(const float* src, float* dst, long long n, hipStream_t stream);
+// test support (casv_debug_activation): which 0 = fast_tanh, 1 = fast_sigmoid on n floats; 2 = lstm_cell on n rows of 5 floats
+// (z_i, z_f, z_g, z_o, c_prev) -> n rows of 2 (c, h)
+void launch_debug_activation(int which, const float* in, float* out, long long n, hipStream_t stream);
 // deep_bidirectional_encoder's "cross sum" (seq2seq.py:246-259, as computed): dst[2k] = dst[2k+1] = src[2k] + src[2k+1] (n floats, n even)
 void launch_cross_sum(const float* src, float* dst, long long n, hipStream_t stream);
 // Source of the result records of one decode call (pack_records_kernel): row j * row_mul of idx / prob [rows][S];

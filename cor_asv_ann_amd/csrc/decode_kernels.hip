@@ -285,6 +285,24 @@ void launch_tanh(const float* src, float* dst, long long n, hipStream_t stream) 
     if (n > 0) hipLaunchKernelGGL(tanh_kernel, dim3(blocks), dim3(256), 0, stream, src, dst, n);
 }
 
+// Test support (casv_debug_activation): the activations of common.h as the kernels inline them, one element per thread.
+// which 0: out[i] = fast_tanh(in[i]); 1: fast_sigmoid(in[i]); 2: lstm_cell(in[5i .. 5i+4]) -> out[2i] = c, out[2i+1] = h.
+__global__ void debug_activation_kernel(const int which, const float* __restrict__ in, float* __restrict__ out, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (which == 0) out[i] = fast_tanh(in[i]);
+        else if (which == 1) out[i] = fast_sigmoid(in[i]);
+        else {
+            const float* z = in + 5 * i;
+            const LstmCellOut r = lstm_cell(z[0], z[1], z[2], z[3], z[4]);
+            out[2 * i] = r.c; out[2 * i + 1] = r.h;
+        }
+    }
+}
+void launch_debug_activation(int which, const float* in, float* out, long long n, hipStream_t stream) {
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
+    if (n > 0) hipLaunchKernelGGL(debug_activation_kernel, dim3(blocks), dim3(256), 0, stream, which, in, out, n);
+}
+
 __global__ void cross_sum_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
         const float2 v = reinterpret_cast<const float2*>(src)[i];

@@ -706,7 +706,11 @@ static int ensure_session(casv_model* m, int R, int S) {
 // scatter of its own costs ~5 us of an otherwise idle GPU each: 13 of them in front of every batch of configs[1]).
 static int init_root(casv_model* m, int rows_per_line, SmallOps ops = SmallOps{}) {
     const int W = m->W, Vp = m->Vp, T = m->T, D = m->D, R = m->R, B = m->B;
-    bool ok = ops.fill(m->st_a.p, (size_t)R * T * 4);
+    // The operations of one launch run in no order among themselves: the initial alignment must not be both cleared and copied
+    // by it.  One row per line: the copy covers the whole slot.  Several: the clear goes ahead as a launch of its own.
+    bool ok = true;
+    if (!m->has_a0) ok = ops.fill(m->st_a.p, (size_t)R * T * 4);
+    else if (rows_per_line != 1 || R != B) HIPCHK(hipMemsetAsync(m->st_a.p, 0, (size_t)R * T * 4, m->stream));
     if (m->has_a0) ok = ok && ops.rows(m->a0.as<float>(), T, m->st_a.as<float>(), T, B, T, rows_per_line);
     ok = ok && ops.fill(m->st_p.p, (size_t)R * Vp * 4) && ops.fill(m->logits.p, (size_t)R * Vp * 4);
     for (int n = 1; n <= D; ++n) {
@@ -1603,6 +1607,25 @@ extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, i
     HIPCHK(hipStreamSynchronize(m->stream));
     for (uint32_t v : guard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past row Mstore - 1 of C");
     for (uint32_t v : cguard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past colsum[Mstore - 1]");
+    return CASV_OK;
+}
+
+extern "C" int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* in_, float* out_) {
+    if (!m || (n > 0 && (!in_ || !out_))) return fail(CASV_ERR_ARG, "null argument");
+    if (which < 0 || which > 2) return fail(CASV_ERR_ARG, "which: 0 tanh, 1 sigmoid, 2 lstm_cell");
+    if (n < 0 || n > (1LL << 28)) return fail(CASV_ERR_ARG, "n must be in [0, 2^28]");
+    if (n == 0) return CASV_OK;
+    HIPCHK(hipSetDevice(m->device));
+    const size_t nin = (size_t)n * (which == 2 ? 5 : 1), nout = (size_t)n * (which == 2 ? 2 : 1);
+    DevBuf in, out;
+    DebugBuffers release_on_exit{{&in, &out}, nullptr, m->stream};
+    if (int rc = in.ensure(nin * 4)) return rc;
+    if (int rc = out.ensure(nout * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(in.p, in_, nin * 4, hipMemcpyHostToDevice, m->stream));
+    launch_debug_activation(which, in.as<float>(), out.as<float>(), n, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_, out.p, nout * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
     return CASV_OK;
 }
 

@@ -434,6 +434,17 @@ class HipEngine(object):
                                                  nv.ptr(colsum)))
         return self.stat('tn_split'), self.stat('tn_shares'), self.stat('tn_nonempty_shares')
 
+    def debug_activation(self, which, x):
+        """Test support (casv_debug_activation): which 'tanh' / 'sigmoid' on x (float32, any shape), or 'lstm_cell' on x (n, 5) =
+        (z_i, z_f, z_g, z_o, c_prev) rows -> (n, 2) = (c, h), through the inline functions of csrc/common.h."""
+        w = {'tanh': 0, 'sigmoid': 1, 'lstm_cell': 2}[which]
+        x = nv.carray(x, np.float32)
+        n = x.shape[0] if w == 2 else x.size
+        assert w != 2 or x.shape == (n, 5)
+        out = np.empty((n, 2) if w == 2 else x.shape, np.float32)
+        nv.check(self.lib.casv_debug_activation(self.handle, w, n, nv.ptr(x), nv.ptr(out)))
+        return out
+
     def alignments_sparse(self, rows, steps, K=None):
         """Window form of the last decode call's soft alignments: (lo int32 (rows, S), w float32 (rows, S, K))."""
         K = int(K or 2 * self.window_width + 1)

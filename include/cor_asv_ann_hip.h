@@ -270,6 +270,10 @@ int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int32_t N, int3
  * tests/test_gpu_gemm_tn.py compares every form with a float64 product. */
 int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, int32_t Mstore, int32_t N, int32_t K, const float* A, int64_t lda,
                            const float* B, int64_t ldb, float* C, int64_t ldc, float* colsum);
+/* Test support: the activation functions every kernel inlines (csrc/common.h: fast_tanh, fast_sigmoid, lstm_cell), on n inputs.
+ * which = 0: out[i] = tanh(in[i]); 1: out[i] = sigmoid(in[i]); 2: the LSTM cell on in[5i .. 5i+4] = (z_i, z_f, z_g, z_o, c_prev)
+ * -> out[2i] = c, out[2i+1] = h.  tests/test_gpu_activations.py compares them with float64. */
+int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* in, float* out);
 /* Options: "graph" = replay the decode step through a captured hipGraph (1) or launch kernels eagerly (0);
  * "persistent" = greedy decoding through the persistent decoder (all steps in ONE launch, workgroups hand rows to each
  * other through memory: small batches, where a step is too short for a launch per kernel): -1 by batch size (default:

@@ -94,32 +94,36 @@ def encode(cfg, w, x):
     return [out] + states + [a0]
 
 
-def attention(cfg, w, h, a_prev, enc_out, u):
+def attention(cfg, w, h, a_prev, enc_out, u, window_dtype=None):
     """DenseAnnotationAttention.attention_call (attention.py:526-575), dense over all T then
     masked by the window around t' = sum_s a_prev[s]*s + 1.
 
     Spec decision: t' is accumulated in float64 and rounded once to the working
-    dtype, so it does not depend on a summation order."""
+    dtype, so it does not depend on a summation order.  window_dtype: round t' to this dtype and
+    decide the window in it instead (float32: the spec's window rule in a float64 run; the rest
+    stays in the working dtype)."""
     dt = h.dtype
+    wd = dt if window_dtype is None else np.dtype(window_dtype)
     T = enc_out.shape[1]
     wq = h @ w['att_Wa'] + w['att_bUW']                                   # att:539
     e = np.exp(np.tanh(wq[:, None, :] + u) @ w['att_va'] + w['att_bv'][0])   # att:540, (R,T)
     steps = np.arange(T)
-    tprime = (a_prev.astype(np.float64) @ steps.astype(np.float64) + 1.0).astype(dt)   # att:553
-    dist = np.abs(tprime[:, None] - steps[None, :].astype(dt))
-    mask = dist <= dt.type(cfg.window)             # K.relu(max=5, threshold=5) == 0, att:562-567
+    tprime = (a_prev.astype(np.float64) @ steps.astype(np.float64) + 1.0).astype(wd)   # att:553
+    dist = np.abs(tprime[:, None] - steps[None, :].astype(wd))
+    mask = dist <= wd.type(cfg.window)             # K.relu(max=5, threshold=5) == 0, att:562-567
     e = e * mask.astype(dt)
     a = e / e.sum(axis=1, keepdims=True)          # att:571 (0/0 -> NaN if window is off the line)
     ctx = (a[:, :, None] * enc_out).sum(axis=1)   # att:572
     return ctx.astype(dt), a.astype(dt)
 
 
-def decoder_step(cfg, w, p_in, enc_out, states, u=None):
+def decoder_step(cfg, w, p_in, enc_out, states, u=None, window_dtype=None):
     """decoder_model.predict_on_batch for one character (seq2seq.py:416-480).
 
     p_in (R,V): zeros at step 0, otherwise the fed-back distribution.  enc_out (R or 1,T,C).
     states = [h1,c1,...,hd,cd,a].  u = enc_out.U_a; the reference recomputes it inside every
     step (seq2seq.py:459-460) -- pass u=None to do the same.
+    window_dtype: see `attention`.
     Returns (probs (R,V), new_states).
 
     residual_connections: the reference's INFERENCE decoder has none (seq2seq.py:421-436 builds `decoder_model` layer by layer
@@ -137,7 +141,7 @@ def decoder_step(cfg, w, p_in, enc_out, states, u=None):
         if u is None:
             u = enc_out @ w['att_U']                   # attention_dense, s2s:313,460
         hd, cd, a_prev = states[2 * d - 2], states[2 * d - 1], states[2 * d]
-        ctx, a = attention(cfg, w, hd, a_prev, enc_out, u)
+        ctx, a = attention(cfg, w, hd, a_prev, enc_out, u, window_dtype)
         x = np.concatenate([y, ctx], axis=1)           # input_mode="concatenate", att:341-342
         h, c = lstm_step(x, hd, cd, w['dec%d_K' % d], w['dec%d_R' % d], w['dec%d_b' % d])
         new_states += [h, c, a]

@@ -76,10 +76,12 @@ def lstm_backward(cache, dH, dh_fin=None, dc_fin=None):
     return dX, dK, dR, db, dh, dc
 
 
-def forward_backward(cfg, w, enc_in, dec_in, dec_out, weights, masks=None, want_grads=True):
-    """Returns (loss, grads dict with the keys of `w`, aux)."""
+def forward_backward(cfg, w, enc_in, dec_in, dec_out, weights, masks=None, want_grads=True, window_dtype=None):
+    """Returns (loss, grads dict with the keys of `w`, aux).  window_dtype: the dtype t' is rounded to and the attention window
+    decided in (oracle.model.attention); default the working dtype."""
     d, W, V, C = cfg.depth, cfg.width, cfg.voc_size, cfg.ctx_width
     dt = w['E'].dtype
+    wd = dt if window_dtype is None else np.dtype(window_dtype)
     E = w['E']
     B, T, _ = enc_in.shape
     U = dec_in.shape[1]
@@ -148,8 +150,8 @@ def forward_backward(cfg, w, enc_in, dec_in, dec_out, weights, masks=None, want_
         wq = h @ Wa + bUW
         th = np.tanh(wq[:, None, :] + u)                     # (B,T,W)
         e = np.exp(th @ va + bv)
-        tprime = (a.astype(np.float64) @ steps + 1.0).astype(dt)
-        mask = (np.abs(tprime[:, None] - steps[None, :].astype(dt)) <= dt.type(cfg.window)).astype(dt)
+        tprime = (a.astype(np.float64) @ steps + 1.0).astype(wd)
+        mask = (np.abs(tprime[:, None] - steps[None, :].astype(wd)) <= wd.type(cfg.window)).astype(dt)
         e = e * mask
         a = e / e.sum(axis=1, keepdims=True)
         ctx = (a[:, :, None] * enc_out).sum(axis=1)

@@ -1,7 +1,8 @@
 """The train step's loss, norm and gradients against a float64 run of the oracle, in units of the fp32 oracle's own rounding noise
 (tests/test_gpu_grad_noise.py, tests/test_grad_noise_bounds.py, profiles/gradient_noise.py).
 
-For a case, o64 = oracle.train.forward_backward on float64 weights, inputs and masks; o32 = the same in float32.  Per gradient
+For a case, o64 = oracle.train.forward_backward on float64 weights, inputs and masks, the attention window decided by the spec's
+fp32 rule (window_dtype); o32 = the same in float32.  Per gradient
 tensor, noise_rms = rms(o32 - o64) and noise_max = max|o32 - o64|; the device must stay within C_RMS x noise_rms (rms) and
 C_MAX x noise_max (max), or 2^-24 x max|o64| where that is larger; the loss and the norm likewise with |o32 - o64|."""
 import numpy as np
@@ -87,7 +88,8 @@ def oracle(cfg, w, inputs, dtype, frozen=()):
     enc_in, dec_in, dec_out, wts, masks = inputs
     cast = lambda a: np.asarray(a, dtype)
     m = None if masks is None else {'enc': [cast(x) for x in masks['enc']], 'dec': [cast(x) for x in masks['dec']], 'cell': cast(masks['cell'])}
-    loss, grads, _ = forward_backward(cfg, {k: cast(v) for k, v in w.items()}, cast(enc_in), cast(dec_in), cast(dec_out), cast(wts), m)
+    loss, grads, _ = forward_backward(cfg, {k: cast(v) for k, v in w.items()}, cast(enc_in), cast(dec_in), cast(dec_out), cast(wts), m,
+                                      window_dtype=np.float32)
     grads = {k: np.asarray(g, np.float64) for k, g in grads.items() if not (frozen and k.startswith(tuple(frozen)))}
     norm = float(np.sqrt(sum((g ** 2).sum() for g in grads.values())))
     return float(loss), norm, grads

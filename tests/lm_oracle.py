@@ -15,15 +15,15 @@ from oracle.decode import Node
 from oracle.model import decoder_step
 
 
-def lm_step(m, p_in, enc_out, states):
+def lm_step(m, p_in, enc_out, states, window_dtype=None):
     """LM probabilities (R,V) of one decoder_model call: oracle.model.decoder_step with enc_out AND u set to zeros
     (`constants=[attention_zero, attention_zero]`, s2s:466-470).  The lower layers are the decoder's own; the attention has one
     energy at every position of the window, so the context is exactly 0 -- or NaN where the window is empty or the energy is 0 or
-    infinite.  The LM cell's states are discarded."""
+    infinite.  The LM cell's states are discarded.  window_dtype: oracle.model.attention."""
     dt = m.weights['E'].dtype
     z = np.zeros(np.asarray(enc_out).shape, dt)
     u = np.zeros(z.shape[:2] + (m.cfg.width,), dt)
-    p, _ = decoder_step(m.cfg, m.weights, p_in, z, states, u=u)
+    p, _ = decoder_step(m.cfg, m.weights, p_in, z, states, u=u, window_dtype=window_dtype)
     return p
 
 

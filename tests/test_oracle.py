@@ -131,6 +131,40 @@ def test_attention_window_edges():
     assert a[0, 29] == 1.0 and np.count_nonzero(a) == 1
 
 
+def test_window_dtype_keeps_fp32_bits_and_gives_float64_the_fp32_window():
+    """window_dtype: a float32 run is the same bit for bit with window_dtype=float32; a float64 run with it decides the window by the
+    spec's fp32 rule.  Constructed row: t' = 11 + 2^-30 rounds to 11 in fp32, so s = 6 (|t' - s| = 5) is inside; the plain float64
+    window leaves it out (5 + 2^-30 > 5)."""
+    from oracle.train import forward_backward
+    cfg = ModelConfig(depth=2, width=32, voc_size=16)
+    w32 = make_weights(cfg, emb_scale=4.0)
+    w64 = {k: v.astype(np.float64) for k, v in w32.items()}
+    T, R = 20, 4
+    rng = np.random.default_rng(2)
+    enc = rng.normal(size=(R, T, cfg.ctx_width)).astype(np.float32)
+    a_prev = rng.random((R, T)).astype(np.float32)
+    a_prev /= a_prev.sum(axis=1, keepdims=True)
+    a_prev[0] = 0; a_prev[0, 10] = 1; a_prev[0, 1] = 2.0 ** -30
+    states = [rng.normal(size=(R, 32)).astype(np.float32) for _ in range(4)] + [a_prev]
+    p_in = rng.dirichlet(np.ones(16), R).astype(np.float32)
+    p0, s0 = decoder_step(cfg, w32, p_in, enc, states)
+    p1, s1 = decoder_step(cfg, w32, p_in, enc, states, window_dtype=np.float32)
+    assert p0.tobytes() == p1.tobytes() and all(a.tobytes() == b.tobytes() for a, b in zip(s0, s1))
+    up = lambda xs: [np.asarray(x, np.float64) for x in xs]
+    _, s64 = decoder_step(cfg, w64, p_in.astype(np.float64), enc.astype(np.float64), up(states))
+    _, s64w = decoder_step(cfg, w64, p_in.astype(np.float64), enc.astype(np.float64), up(states), window_dtype=np.float32)
+    sup = lambda a: np.nonzero(a[0])[0].tolist()
+    assert sup(s0[-1]) == sup(s64w[-1]) == list(range(6, 17))
+    assert sup(s64[-1]) == list(range(7, 17))
+    # the train oracle: the same in float32 bit for bit
+    src, _ = make_lines(3, 8, 1, voc_size=16)
+    tgt, _ = make_lines(3, 8, 2, voc_size=16)
+    enc_in, dec_in, dec_out, wts = vectorize_lines(OracleModel(cfg, w32), src, tgt)
+    l0, g0, _ = forward_backward(cfg, w32, enc_in, dec_in, dec_out, wts)
+    l1, g1, _ = forward_backward(cfg, w32, enc_in, dec_in, dec_out, wts, window_dtype=np.float32)
+    assert np.float32(l0).tobytes() == np.float32(l1).tobytes() and all(g0[k].tobytes() == g1[k].tobytes() for k in g0)
+
+
 def test_vectorize_lines_layouts():
     cfg = ModelConfig(depth=1, width=32, voc_size=8)
     c_i = {'': 0, '\n': 1, 'a': 2, 'b': 3, 'c': 4, 'd': 5, 'e': 6, 'f': 7}
