@@ -425,6 +425,20 @@ size_t persist_enc_counter_bytes(int B, int D);
 int persist_encode_blocks_per_cu(size_t lds_bytes);
 int persist_decode_blocks_per_cu(size_t lds_bytes);
 int launch_persist_encode(const PersistEncArgs& pa, int grid, hipStream_t stream);
+// persistent encoder in the split arithmetic (persist_split.hip): the same buffers; rows in blocks of 32, units in groups of 32;
+// PersistLayer.w = the per-step launches' weights [4W][Kt] (gate-interleaved rows, K in natural order), .bias = theirs [4W]
+struct PersistSplitEncArgs {
+    int B, T, D, W;
+    PersistLayer l1[2];            // forward, backward
+    PersistLayer ln[7];            // layers 2..D
+    const float* x0; float* H1; float* Hn[7]; float* cfin;
+    unsigned* counters;            // persist_split_enc_counter_bytes(); zeroed ahead of the launch
+    int inject;                    // test support: workgroup 0 leaves without handing on (the launch gives up and is redone per step)
+};
+size_t persist_split_enc_counter_bytes(int B, int D);
+int persist_split_encode_blocks_per_cu();          // workgroups per CU the runtime admits (capped at 2; 0: none)
+int persist_split_enc_max_tiles();                 // tiles of one phase a workgroup may own
+int launch_persist_split_encode(const PersistSplitEncArgs& pa, int grid, hipStream_t stream);
 size_t persist_counter_bytes(int R, int D);
 size_t persist_lds_bytes(const PersistArgs& pa);
 int launch_persist_decode(const PersistArgs& pa, hipStream_t stream);   // -1: the staged rows do not fit the LDS

@@ -105,7 +105,8 @@ struct casv_model {
     char* pin_in = nullptr; size_t pin_in_cap = 0;        // pinned staging of casv_encode's inputs (reused behind ev_inputs)
     char* pin_out = nullptr; size_t pin_out_cap = 0;      // pinned staging of the greedy decode's results
     size_t pin_limit = (size_t)64 << 20;                  // larger inputs / results bypass the pinned staging (option "pin_limit_mb")
-    int persist_mode = -1;                                // -1 by size, 0 never, 1 always (greedy decode of small batches)
+    int persist_mode = -1;                                // -1 by size, 0 never, 1 always (the persistent small-batch kernels: encoder passes, greedy decode)
+    bool persist_fault_split = false;                     // test support (option "persistent" = 3): the split persistent encoder gives up (persist_split.hip)
     int persist_skip = 0, persist_penalty = 0; bool persist_told = false;   // back-off after a persistent launch gave up waiting
     int ncu = 0;
     LstmW enc_fw, enc_bw;
@@ -157,6 +158,7 @@ struct casv_model {
     DevBuf rec; int rec_rows = 0, rec_S = 0;              // result records of this rank's lines, packed on the device (casv_records_*)
     int* pin_active = nullptr; hipEvent_t ev_active[2] = {nullptr, nullptr};   // beam decode: unfinished-line count, read one chunk behind
     int stat_beam[3] = {0, 0, 0};                         // last beam decode: most new hypotheses of one line in one step; rows stepped
+    int stat_enc_persistent = 0;                          // the encoder pass behind the last entry point ran as ONE persistent launch and was not redone
     int stat_tn[3] = {0, 0, 0};                           // last casv_debug_contract_tn: split kernel (0/1), K shares launched, shares holding k-tiles
                                                           // and distinct parent expansions among them (N <= 16 only)
     Prof prof;

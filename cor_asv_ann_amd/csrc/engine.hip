@@ -297,12 +297,24 @@ static void persist_note_abort(casv_model* m, const char* what) {
 }
 // workgroups per CU for the staged rows of `lda` floats, as the runtime admits them for the loaded kernel
 static int persist_enc_lds(const casv_model* m) { return 16 * ((m->D >= 2 ? 3 * m->W : 2 * m->W) + 4) * 4; }
+// Rows up to which the split-arithmetic persistent encoder (persist_split.hip) is the default form of a pass (option "persistent" = -1):
+// the largest batch of profiles/split_persist_encoder_timing.json at which its median lies below the per-step launches' by more than the
+// spread of the repetitions.
+constexpr int SPLIT_PERSIST_DEFAULT_ROWS = 256;
 static bool persist_enc_applies(const casv_model* m, int B) {
     if (m->persist_mode == 0 || m->ncu < 64 || m->D > 8) return false;
-    if (m->enc_arith > 0) return false;                    // (the persistent kernels are fp32-input kernels)
     if (m->cfg.residual_connections && m->D >= 3) return false;   // (the layers' sums of seq2seq.py:284-291 have no persistent form)
     if (m->cfg.deep_bidirectional_encoder && m->D >= 2) return false;
     const int W = m->W, D = m->D;
+    if (m->enc_arith > 0) {         // split arithmetic: persist_split.hip -- tiles of 32 rows x 32 units, a fixed LDS size
+        const int per_cu = persist_split_encode_blocks_per_cu();
+        if (per_cu < 1) return false;
+        const int ntile = ((B + 31) / 32) * (W / 32), grid = std::min(std::max(2, D - 1) * ntile, per_cu * m->ncu);
+        const int maxt = persist_split_enc_max_tiles();
+        if ((2 * ntile + grid - 1) / grid > maxt || ((D - 1) * ntile + grid - 1) / grid > maxt) return false;
+        if (m->persist_mode == 1) return B <= 4096;
+        return B <= SPLIT_PERSIST_DEFAULT_ROWS;
+    }
     const int per_cu = persist_encode_blocks_per_cu((size_t)persist_enc_lds(m));            // 0: the staged rows do not fit the LDS
     if (per_cu < 1) return false;
     const int ntile = ((B + 15) / 16) * (W / 16), grid = std::min(std::max(2, D - 1) * ntile, per_cu * m->ncu);
@@ -362,7 +374,33 @@ static int run_encoder(casv_model* m, bool try_persistent) {
     // Small batches: the whole encoder in one launch of the persistent encoder (persist.hip; same values bit for bit)
     const bool persistent = try_persistent && persist_enc_applies(m, B) && !persist_backed_off(m);
     unsigned* enc_abort_word = nullptr;
-    if (persistent) {
+    if (persistent && m->enc_arith > 0) {
+        // split arithmetic: persist_split.hip on the per-step launches' own weights (same bits as those launches)
+        std::lock_guard<std::mutex> lock(g_persist_mutex);
+        const size_t cbytes = persist_split_enc_counter_bytes(B, D);
+        if (int rc = m->p_enc_counters.ensure(cbytes)) return rc;
+        HIPCHK(hipMemsetAsync(m->p_enc_counters.p, 0, cbytes, m->stream));
+        PersistSplitEncArgs pa{};
+        pa.B = B; pa.T = T; pa.D = D; pa.W = W;
+        pa.l1[0] = PersistLayer{m->enc_fw.wt.as<float>(), m->enc_fw.bias.as<float>(), 2 * W};
+        pa.l1[1] = PersistLayer{m->enc_bw.wt.as<float>(), m->enc_bw.bias.as<float>(), 2 * W};
+        for (int n = 2; n <= D; ++n) {
+            pa.ln[n - 2] = PersistLayer{m->enc[n].wt.as<float>(), m->enc[n].bias.as<float>(), m->enc[n].kin + W};
+            pa.Hn[n - 2] = lout[n];
+        }
+        pa.x0 = x0; pa.H1 = H1; pa.cfin = cfin; pa.counters = m->p_enc_counters.as<unsigned>();
+        pa.inject = m->persist_fault_split ? 1 : 0;
+        const int nrb = (B + 31) / 32, ntile = nrb * (W / 32);
+        const int grid = std::min(std::max(2, D - 1) * ntile, std::max(persist_split_encode_blocks_per_cu(), 1) * m->ncu);   // all workgroups resident at once
+        hipEvent_t pev{};
+        m->prof_begin(PC_PERSIST, 2.0 * BT * 4.0 * W * (2.0 * 2 * W + (D >= 2 ? 3.0 * W : 0.0) + (D >= 3 ? (D - 2) * 2.0 * W : 0.0)), 0.0, pev);
+        persist_order_before(m);
+        if (launch_persist_split_encode(pa, grid, m->stream)) return fail(CASV_ERR_ARG, "persistent split encoder: no launch form for this shape");
+        persist_order_after(m);
+        m->prof_end(PC_PERSIST, pev);
+        HIPCHK(hipGetLastError());
+        enc_abort_word = m->p_enc_counters.as<unsigned>() + (size_t)nrb * (D + 1) * 32;
+    } else if (persistent) {
         std::lock_guard<std::mutex> lock(g_persist_mutex);
         const size_t cbytes = persist_enc_counter_bytes(B, D);
         if (int rc = m->p_enc_counters.ensure(cbytes)) return rc;
@@ -489,6 +527,7 @@ static int run_encoder(casv_model* m, bool try_persistent) {
         if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
     }
     m->enc_check_pending = persistent;
+    m->stat_enc_persistent = persistent ? 1 : 0;
     if (m->cfg.bridge_dense) {      // bridge_dense (seq2seq.py:299-301): the final states through Dense(width, tanh) on their way to the decoder
         const size_t BW = (size_t)B * W;
         if (int rc = m->br_tmp.ensure(BW * 4)) return rc;
@@ -533,15 +572,16 @@ static int settle_encoder(casv_model* m, const unsigned* flag = nullptr) {
     m->enc_check_pending = false;
     if (!aborted) { if (!flag) m->persist_penalty = 0; return 0; }      // (with `flag` the caller has a second launch to account for before the back-off is reset)
     persist_note_abort(m, "encoder");
-    if (int rc = run_encoder(m, false)) return rc;
+    if (int rc = run_encoder(m, false)) return rc;      // (also takes the statistic "encoder_persistent" back)
     return 1;
 }
 
 // The encoder outputs in the arithmetic of the entry point that is about to consume them (engine.h, arithmetic_of): computed at the
 // first such call after casv_encode / casv_set_encoder_outputs, kept for further calls of the same arithmetic, redone for the other.
 static int ensure_encoded(casv_model* m, int want) {
-    if (m->enc_arith == want) return 0;
+    if (m->enc_arith == want) { m->stat_enc_persistent = 0; return 0; }     // (an encoding that is reused)
     m->enc_check_pending = false;
+    m->stat_enc_persistent = 0;
     m->enc_arith = want;                // (run_encoder reads it; taken back on every failure: the outputs on the device are then nobody's)
     if (!m->enc_explicit) {
         if (int rc = run_encoder(m, true)) { m->enc_arith = -1; return rc; }
@@ -1196,7 +1236,7 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
         return fail(CASV_ERR_ARG, "search too large: S * batch_size * (beam_width_in + 1) nodes per line overflow int32 (decode fewer lines or steps per call)");
     HIPCHK(hipSetDevice(m->device));
     if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_SEARCH))) return rc;
-    if (int rc = settle_encoder(m); rc < 0) return rc;
+    // (a persistent encoder launch's give-up word is looked at below, where this call first waits for the device anyway)
     SplitScope arithmetic(arithmetic_of(m, ENTRY_SEARCH));         // the search: bf16x3-split operands by default (engine.h)
     const int B = m->B, T = m->T, R = B * N, MR = bp->max_results;
     m->last_decode = 0;         // until this call has succeeded there is nothing to take alignments from
@@ -1281,9 +1321,21 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
              p.rejection, p.cost0, p.eos, lm ? "/lm" : "");
     StepRunner runner(m, key);
     if (!m->pin_active) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_active), 2 * sizeof(int), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_active), 3 * sizeof(int), hipHostMallocDefault));      // ([2]: the encoder's give-up word)
         for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&m->ev_active[k], hipEventDisableTiming));
     }
+    // The persistent encoder's give-up word travels with the first count.  A pass that gave up is redone per step (settle_encoder)
+    // and the search starts over on its outputs: nothing decoded from the abandoned pass is trusted.
+    const bool enc_pending = m->enc_check_pending;
+    if (enc_pending) HIPCHK(hipMemcpyAsync(&m->pin_active[2], m->d_flags.p, 4, hipMemcpyDeviceToHost, m->stream));
+    bool enc_settled = !enc_pending;
+    auto settle_now = [&](int& redone) {          // behind a wait that covers the copy above
+        const unsigned flag = (unsigned)m->pin_active[2];
+        redone = settle_encoder(m, &flag);
+        if (redone == 0) m->persist_penalty = 0;
+        enc_settled = true;
+        return redone < 0 ? redone : 0;
+    };
     int pending = -1;                       // slot whose copy is in flight
     int slot = 0;
     while (done_steps < S) {
@@ -1294,6 +1346,11 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
         HIPCHK(hipEventRecord(m->ev_active[slot], m->stream));
         if (pending >= 0) {                 // the chunk before this one
             HIPCHK(hipEventSynchronize(m->ev_active[pending]));
+            if (!enc_settled) {
+                int redone = 0;
+                if (int rc = settle_now(redone)) return rc;
+                if (redone) { m->skip_nact = nullptr; m->skip_group = 0; return casv_decode_beam(m, bp, S, out_idx, out_prob, out_len, out_score, out_rej, out_align, n_found, n_steps); }
+            }
             const int active = m->pin_active[pending];
             if (active <= 0) break;
             if (active < B && !m->use_graph) m->skip_nact = m->b_nact.as<int>();
@@ -1328,6 +1385,11 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     if (n_steps) HIPCHK(hipMemcpyAsync(n_steps, o.n_steps, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(m->stat_beam, m->b_active.as<int>() + 1, 12, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
+    if (!enc_settled) {                     // (a search of at most two chunks: no count was waited for)
+        int redone = 0;
+        if (int rc = settle_now(redone)) return rc;
+        if (redone) return casv_decode_beam(m, bp, S, out_idx, out_prob, out_len, out_score, out_rej, out_align, n_found, n_steps);
+    }
     if (m->prof.on) m->prof.collect();
     m->last_decode = 2; m->last_S = S; m->last_rows = (int)OR; m->last_beam = s; m->last_beam_params = p;
     m->last_signature = decode_buffers_signature(m);
@@ -1422,6 +1484,7 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "beam_max_new_keys")) { *value = m->stat_beam[0]; return CASV_OK; }
     if (!strcmp(key, "beam_sort_capacity")) { *value = 4096; return CASV_OK; }
     if (!strcmp(key, "cus")) { *value = m->ncu; return CASV_OK; }
+    if (!strcmp(key, "encoder_persistent")) { *value = m->stat_enc_persistent; return CASV_OK; }
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }
@@ -1637,8 +1700,10 @@ extern "C" int casv_set_option(casv_model* m, const char* key, int64_t value) {
         // after their bounded wait and the step falls back to per-step launches -- a test of that path)
         // The fault injection is not part of the production interface: only a process started with CASV_FAULT_INJECTION=1 gets it.
         static const bool fault_ok = [] { const char* e = getenv("CASV_FAULT_INJECTION"); return e && e[0] == '1'; }();
-        if (value < -1 || value > (fault_ok ? 2 : 1)) return fail(CASV_ERR_ARG, "persistent must be -1 (by batch size), 0 (per-step kernels) or 1 (always)");
-        m->persist_mode = (int)value; return CASV_OK;
+        // (3: as 1, and one workgroup of the split persistent encoder leaves without handing on -- the same test of the encoder's give-up path)
+        if (value < -1 || value > (fault_ok ? 3 : 1)) return fail(CASV_ERR_ARG, "persistent must be -1 (by batch size), 0 (per-step kernels) or 1 (always)");
+        m->persist_fault_split = value == 3;
+        m->persist_mode = value == 3 ? 1 : (int)value; return CASV_OK;
     }
     if (!strcmp(key, "eos")) {
         if (value < 0 || value >= m->V) return fail(CASV_ERR_ARG, "eos index %lld outside the vocabulary", (long long)value);

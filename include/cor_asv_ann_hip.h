@@ -280,7 +280,13 @@ int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* 
  * up to 512 lines), 0 never, 1 always -- the results are the same bit for bit; the same option governs the train step's
  * recurrences (every pair of plain layers walks its sequence in ONE launch forward and ONE backward unless 0).  (A process started
  * with CASV_FAULT_INJECTION=1 -- the test suite -- also accepts 2 = as -1, and one workgroup of the first forward recurrence leaves
- * without handing on: the give-up path, the step is redone with per-step launches.  Not available otherwise.);
+ * without handing on: the give-up path, the step is redone with per-step launches; and 3 = as 1, and one workgroup of the split
+ * arithmetic's persistent encoder does the same: the pass is redone with per-step launches.  Not available otherwise.)
+ * The option also governs the ENCODER pass of small batches, in either arithmetic: all layers and time steps in ONE launch
+ * (csrc/persist.hip for arithmetic 0; csrc/persist_split.hip for 1 / 2, i.e. for the pass behind casv_decode_beam by default) --
+ * -1: up to 512 lines in arithmetic 0, up to 256 lines in arithmetic 1 / 2 (where it measured faster than the per-step launches,
+ * profiles/split_persist_encoder_timing.json), 0 never, 1 wherever the kernel fits; not for residual_connections at depth >= 3 or
+ * deep_bidirectional_encoder.  Same bits as the per-step launches of the same arithmetic (tests/test_gpu_split_persistent.py);
  * "fused_backward" = 1 (default): a backward time step without a persistent form is ONE launch (cell backward inside the data
  * GEMM), 0: two;
  * "deterministic" = 0 (default) / 1: casv_train_step's results (loss, grad_norm, gradients, weights, Adam's moments; modes 0, 1
@@ -315,13 +321,17 @@ int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* 
  * per step: the GEMM-bound bulk of the path); casv_encode / casv_set_encoder_outputs, casv_decode_greedy, casv_decoder_step and
  * casv_train_step take 0.  The choice never looks at the batch: a line's bits are a function of (weights, line, entry point) --
  * not of the batch it is decoded in, the tile shape, the launch form (persistent or per step) or the GPU of a sharded job
- * (tests/test_gpu_arithmetic.py).  With 1 / 2 the persistent small-batch kernels (fp32-input kernels) are not used.
+ * (tests/test_gpu_arithmetic.py).  With 1 / 2 the encoder pass of a small batch has a persistent form of its own (option
+ * "persistent"; csrc/persist_split.hip: the same instruction, product and tile order as the per-step launches, the same bits); the
+ * persistent greedy DECODER exists in arithmetic 0 only, so under 1 / 2 the greedy decodes step kernel by kernel.
  * "split_bf16" (process-wide; default -1 = none; also CASV_SPLIT_BF16 = 0 / 1 / 2 in the environment when the library is loaded):
  * override of every handle's "arithmetic" for all launches of the decode path (tests, A/B measurements). */
 int casv_set_option(casv_model* m, const char* key, int64_t value);
 /* Statistics of the last call (tests): "beam_max_new_keys" = most child hypotheses one line created in one search
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
- * sorted in runs and merged by rank). */
+ * sorted in runs and merged by rank); "encoder_persistent" = 1 if the encoder pass behind the last entry point ran as ONE
+ * persistent launch and was not redone per step, else 0 (0 also where the entry point reused an encoding it found);
+ * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn. */
 int casv_get_stat(casv_model* m, const char* key, int64_t* value);
 int casv_synchronize(casv_model* m);
 
