@@ -424,6 +424,7 @@ size_t persist_enc_counter_bytes(int B, int D);
 // workgroups per CU the runtime admits for the persistent kernels at a given dynamic-LDS size (capped at 2; 0: none)
 int persist_encode_blocks_per_cu(size_t lds_bytes);
 int persist_decode_blocks_per_cu(size_t lds_bytes);
+int persist_enc_max_tiles();                       // tiles of one phase a workgroup of the encoder may own
 int launch_persist_encode(const PersistEncArgs& pa, int grid, hipStream_t stream);
 // persistent encoder in the split arithmetic (persist_split.hip): the same buffers; rows in blocks of 32, units in groups of 32;
 // PersistLayer.w = the per-step launches' weights [4W][Kt] (gate-interleaved rows, K in natural order), .bias = theirs [4W]

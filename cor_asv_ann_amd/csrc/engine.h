@@ -5,6 +5,7 @@
 // the handle; callers pass plain host pointers.
 #pragma once
 #include "common.h"
+#include "persist_host.h"
 #include "../../include/cor_asv_ann_hip.h"
 
 #include <cstdio>
@@ -101,13 +102,13 @@ struct casv_model {
     DevBuf WaP, EP;                                       // query / output projection in the persistent decoder's K order
     DevBuf p_ctx, p_wq, p_logits, p_counters;             // persistent decoder: slot-indexed hand-off buffers, counters
     DevBuf p_enc_counters, d_flags;                       // persistent encoder's counters; [0] its give-up word set aside, [1] the decoder's, [2] the NaN flag
-    bool enc_check_pending = false;                       // the persistent encoder's give-up word has not been looked at yet (engine.hip, settle_encoder)
+    bool enc_check_pending = false;                       // the persistent encoder's give-up word has not been looked at yet (encoder.hip, settle_encoder)
     char* pin_in = nullptr; size_t pin_in_cap = 0;        // pinned staging of casv_encode's inputs (reused behind ev_inputs)
     char* pin_out = nullptr; size_t pin_out_cap = 0;      // pinned staging of the greedy decode's results
     size_t pin_limit = (size_t)64 << 20;                  // larger inputs / results bypass the pinned staging (option "pin_limit_mb")
     int persist_mode = -1;                                // -1 by size, 0 never, 1 always (the persistent small-batch kernels: encoder passes, greedy decode)
     bool persist_fault_split = false;                     // test support (option "persistent" = 3): the split persistent encoder gives up (persist_split.hip)
-    int persist_skip = 0, persist_penalty = 0; bool persist_told = false;   // back-off after a persistent launch gave up waiting
+    PersistBackoff persist_backoff;                       // after a persistent launch gave up waiting (persist_host.h)
     int ncu = 0;
     LstmW enc_fw, enc_bw;
     std::vector<LstmW> enc_dfw, enc_dbw;                  // deep_bidirectional_encoder: the two directions of layer n >= 2 at index n
@@ -183,7 +184,7 @@ struct casv_model {
 //   ENTRY_SEARCH  casv_decode_beam (R = lines x hypotheses rows per step, the GEMM-bound bulk of the path): bf16x3-split operands on
 //                 the bf16 matrix instruction (2) -- its decoder steps AND the encoder pass whose outputs it consumes (casv_encode only
 //                 stages the input; the encoder runs for the first entry point that needs its outputs, in that entry point's
-//                 arithmetic, and again if a later one needs the other: engine.hip, ensure_encoded);
+//                 arithmetic, and again if a later one needs the other: encoder.hip, ensure_encoded);
 //   ENTRY_CHAIN   the greedy decodes, the explicit decoder step, casv_get_encoder_outputs: the fp32-input instruction's k-ordered
 //                 chain (0) -- the arithmetic the persistent small-batch kernels are built on;
 //   ENTRY_TRAIN   casv_train_step: 2 -- the whole-sequence contractions that have a split form (input projections of all time
@@ -239,6 +240,14 @@ inline void run_gemm(casv_model* m, int epi, GemmArgs& g) {
     run_gemm_batch(m, epi, b);
 }
 
+
+// encoder.hip, for the entry points that consume the encoder outputs (engine.hip):
+// The encoder outputs in the arithmetic `want` of the entry point that is about to consume them (arithmetic_of): computed at the first
+// such call after casv_encode / casv_set_encoder_outputs, kept for further calls of the same arithmetic, redone for the other.
+int ensure_encoded(casv_model* m, int want);
+// A persistent encoder launch's give-up word, where the host has to wait for the device anyway (`flag`: the word, if the caller has
+// brought it to the host already).  1: the pass had given up and was redone per step, 0: nothing to do, < 0: error.
+int settle_encoder(casv_model* m, const unsigned* flag = nullptr);
 
 int casv_train_release(casv_model* m);
 extern "C" int casv_comm_destroy(casv_model* m);

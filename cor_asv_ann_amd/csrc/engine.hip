@@ -1,7 +1,6 @@
-// Host side of the C ABI (include/cor_asv_ann_hip.h): weight repacking, the encoder (seq2seq.py:237-314),
-// the decoder step (seq2seq.py:416-480) and the greedy / beam decode loops (seq2seq.py:1215-1544).
+// Host side of the C ABI (include/cor_asv_ann_hip.h): weight repacking, the decoder step (seq2seq.py:416-480) and the greedy /
+// beam decode loops (seq2seq.py:1215-1544).  The encoder pass (seq2seq.py:237-314) is encoder.hip.
 #include "engine.h"
-#include <mutex>
 
 static std::map<std::string, size_t> expected_shapes(const casv_config& c) {
     const size_t W = c.width, V = c.voc_size, D = c.depth, C = ((D == 1 || c.deep_bidirectional_encoder) ? 2 * W : W);
@@ -254,456 +253,6 @@ extern "C" int casv_commit_weights(casv_model* m) {
                 if (int rc = upload(s ? m->br_cb[n] : m->br_hb[n], m->host[b + "_b"])) return rc;
             }
     m->committed = true;
-    return CASV_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Persistent launches (persist.hip) are serialised inside the process: two of them together can want more workgroup slots
-// than the chip has, and workgroups that spin on peers which are not resident never make room for them.  (Across processes
-// the bounded spins catch that case: the launch aborts and the caller falls back to the per-step kernels.)  On the host the
-// mutex orders the ENQUEUEING of such launches (round 5: no call waits for its kernel inside it any more) ...
-static std::mutex g_persist_mutex;
-// ... and on the DEVICE: a persistent launch of any handle starts behind the previous one of the process on the same device (an
-// event wait on the launching handle's stream -- the host does not wait).  Call both with g_persist_mutex held.
-static hipEvent_t g_persist_event[64];
-static bool g_persist_event_made[64] = {false}, g_persist_event_set[64] = {false};
-static void persist_order_before(casv_model* m) {
-    const int d = m->device;
-    if (d >= 0 && d < 64 && g_persist_event_set[d]) (void)hipStreamWaitEvent(m->stream, g_persist_event[d], 0);
-}
-static void persist_order_after(casv_model* m) {
-    const int d = m->device;
-    if (d < 0 || d >= 64) return;
-    if (!g_persist_event_made[d]) {
-        if (hipEventCreateWithFlags(&g_persist_event[d], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return; }
-        g_persist_event_made[d] = true;
-    }
-    if (hipEventRecord(g_persist_event[d], m->stream) == hipSuccess) g_persist_event_set[d] = true;
-}
-// A persistent launch that gave up waiting (its workgroups were not all resident: the GPU is shared with another process's
-// persistent kernel, or partitioned) costs one bounded wait.  The handle then leaves the persistent path alone for a number
-// of calls that doubles with every further abort, instead of paying that wait on every call.
-static bool persist_backed_off(casv_model* m) {
-    if (m->persist_skip > 0) { --m->persist_skip; return true; }
-    return false;
-}
-static void persist_note_abort(casv_model* m, const char* what) {
-    m->persist_penalty = std::min(m->persist_penalty ? 2 * m->persist_penalty : 16, 1 << 16);
-    m->persist_skip = m->persist_penalty;
-    if (!m->persist_told) {
-        fprintf(stderr, "cor_asv_ann_hip: persistent %s gave up waiting (GPU shared with another persistent kernel?); using the per-step kernels for the next %d calls\n", what, m->persist_skip);
-        m->persist_told = true;
-    }
-}
-// workgroups per CU for the staged rows of `lda` floats, as the runtime admits them for the loaded kernel
-static int persist_enc_lds(const casv_model* m) { return 16 * ((m->D >= 2 ? 3 * m->W : 2 * m->W) + 4) * 4; }
-// Rows up to which the split-arithmetic persistent encoder (persist_split.hip) is the default form of a pass (option "persistent" = -1):
-// the largest batch of profiles/split_persist_encoder_timing.json at which its median lies below the per-step launches' by more than the
-// spread of the repetitions.
-constexpr int SPLIT_PERSIST_DEFAULT_ROWS = 256;
-static bool persist_enc_applies(const casv_model* m, int B) {
-    if (m->persist_mode == 0 || m->ncu < 64 || m->D > 8) return false;
-    if (m->cfg.residual_connections && m->D >= 3) return false;   // (the layers' sums of seq2seq.py:284-291 have no persistent form)
-    if (m->cfg.deep_bidirectional_encoder && m->D >= 2) return false;
-    const int W = m->W, D = m->D;
-    if (m->enc_arith > 0) {         // split arithmetic: persist_split.hip -- tiles of 32 rows x 32 units, a fixed LDS size
-        const int per_cu = persist_split_encode_blocks_per_cu();
-        if (per_cu < 1) return false;
-        const int ntile = ((B + 31) / 32) * (W / 32), grid = std::min(std::max(2, D - 1) * ntile, per_cu * m->ncu);
-        const int maxt = persist_split_enc_max_tiles();
-        if ((2 * ntile + grid - 1) / grid > maxt || ((D - 1) * ntile + grid - 1) / grid > maxt) return false;
-        if (m->persist_mode == 1) return B <= 4096;
-        return B <= SPLIT_PERSIST_DEFAULT_ROWS;
-    }
-    const int per_cu = persist_encode_blocks_per_cu((size_t)persist_enc_lds(m));            // 0: the staged rows do not fit the LDS
-    if (per_cu < 1) return false;
-    const int ntile = ((B + 15) / 16) * (W / 16), grid = std::min(std::max(2, D - 1) * ntile, per_cu * m->ncu);
-    if ((2 * ntile + grid - 1) / grid > 8 || ((D - 1) * ntile + grid - 1) / grid > 8) return false;   // tiles per workgroup (PENC_MAXT)
-    if (m->persist_mode == 1) return B <= 4096;
-    return B <= 512 && (2 * ntile + grid - 1) / grid <= 2 && ((D - 1) * ntile + grid - 1) / grid <= 2;
-}
-
-// The encoder (seq2seq.py:237-314) on the inputs that lie in d_idx / d_val: embedding, BiLSTM layer, stacked layers, final states,
-// u = attention_dense(enc_out).  Small batches: the whole recurrence as ONE launch of the persistent encoder (persist.hip; same
-// values bit for bit) -- whose give-up word is NOT waited for here: it is copied aside (d_flags[0]) and looked at where the host
-// waits for the device anyway (settle_encoder: the end of the greedy decode, or the first other consumer of the outputs); a launch
-// that gave up is redone with the per-step kernels then.  (Waiting here cost every batch of configs[1] a host round trip with the
-// GPU idle between its encoder and its decoder's set-up.)
-static int run_encoder(casv_model* m, bool try_persistent) {
-    SplitScope arithmetic(m->enc_arith < 0 ? 0 : m->enc_arith);   // (set by ensure_encoded; its own scope: settle_encoder redoes an encoder from inside any entry point)
-    const int B = m->B, T = m->T, A = m->A;
-    const int W = m->W, C = m->C, D = m->D;
-    const size_t BT = (size_t)B * T;
-    hipEvent_t ev{};
-    m->prof_begin(PC_EMBED, 2.0 * BT * A * W, 4.0 * BT * W * (A + 1), ev);
-    launch_embed_sparse(m->E.as<float>(), m->d_idx.as<int>(), m->d_val.as<float>(), m->x0.as<float>(), (int)BT, A,
-                        m->V, W, m->stream);
-    m->prof_end(PC_EMBED, ev);
-
-    float* x0 = m->x0.as<float>(); float* H1 = m->H1.as<float>();
-    float* cfin = m->cfin.as<float>();
-    // layer 1 (seq2seq.py:272-281): the forward step at time t and the backward step at time T-1-t are
-    // independent -> one launch of two jobs
-    // one direction of a bidirectional layer at step t (layer 1; with deep_bidirectional_encoder every layer n): inputs x [B][T][kin],
-    // outputs into its half of H [B][T][2W], cell state of the backward direction in cfin slot n - 1 (the forward one's in a scratch slot)
-    auto bidir_job = [&](const LstmW& w, int n, int dir, int t, const float* x, int kin, float* H) {
-        GemmArgs g{};
-        const int mul = dir == 0 ? 1 : -1;
-        const int addx = dir == 0 ? 0 : T - 1, addh = dir == 0 ? -1 : T;
-        g.nseg = 2;
-        g.a[0] = mkseg(x, T * kin, kin, 0, nullptr, kin, mul, addx);
-        g.a[1] = mkseg(H + dir * W, T * 2 * W, W, kin, nullptr, 2 * W, mul, addh, 1);
-        g.Bt = w.wt.as<float>(); g.bias = w.bias.as<float>();
-        g.M = B; g.N = 4 * W; g.Ktot = kin + W;
-        g.out = mkslot(H + dir * W, T * 2 * W, 2 * W, mul, addx);
-        float* cb = cfin + (size_t)(dir == 0 ? D : n - 1) * B * W;
-        g.c_in = mkseg(cb, W, W, 0, nullptr, 0, 0, 0, 1);
-        g.c_out = mkslot(cb, W);
-        g.step_imm = t; g.step_ptr = nullptr;
-        return g;
-    };
-    auto layer1_job = [&](int dir, int t) { return bidir_job(dir == 0 ? m->enc_fw : m->enc_bw, 1, dir, t, x0, W, H1); };
-    std::vector<float*> lout(D + 1, nullptr);
-    lout[1] = H1;
-    for (int n = 2; n <= D; ++n) lout[n] = (n % 2 == 0) ? m->Ha.as<float>() : m->Hb.as<float>();
-    if (D >= 4) {   // layers alternate between two buffers only when they run strictly one after another
-        if (int rc = m->Hc.ensure((size_t)(D - 1) * BT * W * 4)) return rc;
-        for (int n = 2; n <= D; ++n) lout[n] = m->Hc.as<float>() + (size_t)(n - 2) * BT * W;
-    }
-    if (int rc = m->d_flags.ensure(64)) return rc;
-    // Small batches: the whole encoder in one launch of the persistent encoder (persist.hip; same values bit for bit)
-    const bool persistent = try_persistent && persist_enc_applies(m, B) && !persist_backed_off(m);
-    unsigned* enc_abort_word = nullptr;
-    if (persistent && m->enc_arith > 0) {
-        // split arithmetic: persist_split.hip on the per-step launches' own weights (same bits as those launches)
-        std::lock_guard<std::mutex> lock(g_persist_mutex);
-        const size_t cbytes = persist_split_enc_counter_bytes(B, D);
-        if (int rc = m->p_enc_counters.ensure(cbytes)) return rc;
-        HIPCHK(hipMemsetAsync(m->p_enc_counters.p, 0, cbytes, m->stream));
-        PersistSplitEncArgs pa{};
-        pa.B = B; pa.T = T; pa.D = D; pa.W = W;
-        pa.l1[0] = PersistLayer{m->enc_fw.wt.as<float>(), m->enc_fw.bias.as<float>(), 2 * W};
-        pa.l1[1] = PersistLayer{m->enc_bw.wt.as<float>(), m->enc_bw.bias.as<float>(), 2 * W};
-        for (int n = 2; n <= D; ++n) {
-            pa.ln[n - 2] = PersistLayer{m->enc[n].wt.as<float>(), m->enc[n].bias.as<float>(), m->enc[n].kin + W};
-            pa.Hn[n - 2] = lout[n];
-        }
-        pa.x0 = x0; pa.H1 = H1; pa.cfin = cfin; pa.counters = m->p_enc_counters.as<unsigned>();
-        pa.inject = m->persist_fault_split ? 1 : 0;
-        const int nrb = (B + 31) / 32, ntile = nrb * (W / 32);
-        const int grid = std::min(std::max(2, D - 1) * ntile, std::max(persist_split_encode_blocks_per_cu(), 1) * m->ncu);   // all workgroups resident at once
-        hipEvent_t pev{};
-        m->prof_begin(PC_PERSIST, 2.0 * BT * 4.0 * W * (2.0 * 2 * W + (D >= 2 ? 3.0 * W : 0.0) + (D >= 3 ? (D - 2) * 2.0 * W : 0.0)), 0.0, pev);
-        persist_order_before(m);
-        if (launch_persist_split_encode(pa, grid, m->stream)) return fail(CASV_ERR_ARG, "persistent split encoder: no launch form for this shape");
-        persist_order_after(m);
-        m->prof_end(PC_PERSIST, pev);
-        HIPCHK(hipGetLastError());
-        enc_abort_word = m->p_enc_counters.as<unsigned>() + (size_t)nrb * (D + 1) * 32;
-    } else if (persistent) {
-        std::lock_guard<std::mutex> lock(g_persist_mutex);
-        const size_t cbytes = persist_enc_counter_bytes(B, D);
-        if (int rc = m->p_enc_counters.ensure(cbytes)) return rc;
-        HIPCHK(hipMemsetAsync(m->p_enc_counters.p, 0, cbytes, m->stream));
-        PersistEncArgs pa{};
-        pa.B = B; pa.T = T; pa.D = D; pa.W = W; pa.lda = (D >= 2 ? 3 * W : 2 * W) + 4;
-        pa.l1[0] = PersistLayer{m->enc_fw.pw.as<float>(), m->enc_fw.pbias.as<float>(), 2 * W};
-        pa.l1[1] = PersistLayer{m->enc_bw.pw.as<float>(), m->enc_bw.pbias.as<float>(), 2 * W};
-        for (int n = 2; n <= D; ++n) {
-            pa.ln[n - 2] = PersistLayer{m->enc[n].pw.as<float>(), m->enc[n].pbias.as<float>(), m->enc[n].kin + W};
-            pa.Hn[n - 2] = lout[n];
-        }
-        pa.x0 = x0; pa.H1 = H1; pa.cfin = cfin; pa.counters = m->p_enc_counters.as<unsigned>();
-        const int nrb = (B + 15) / 16, ntile = nrb * (W / 16);
-        const int per_cu = persist_encode_blocks_per_cu((size_t)16 * pa.lda * 4);                      // all workgroups resident at once
-        const int grid = std::min(std::max(2, D - 1) * ntile, std::max(per_cu, 1) * m->ncu);
-#ifdef CASV_PERSIST_PROF
-        static DevBuf eprof;
-        if (int rc = eprof.ensure(32 * 8)) return rc;
-        HIPCHK(hipMemsetAsync(eprof.p, 0, 32 * 8, m->stream));
-        pa.prof = eprof.as<unsigned long long>();
-#endif
-        hipEvent_t pev{};
-        m->prof_begin(PC_PERSIST, 2.0 * BT * 4.0 * W * (2.0 * 2 * W + (D >= 2 ? 3.0 * W : 0.0) + (D >= 3 ? (D - 2) * 2.0 * W : 0.0)), 0.0, pev);
-        persist_order_before(m);
-        if (launch_persist_encode(pa, grid, m->stream)) return fail(CASV_ERR_ARG, "persistent encoder: rows do not fit the LDS");
-        persist_order_after(m);
-        m->prof_end(PC_PERSIST, pev);
-        HIPCHK(hipGetLastError());
-        enc_abort_word = m->p_enc_counters.as<unsigned>() + (size_t)nrb * (D + 1) * 32;
-#ifdef CASV_PERSIST_PROF
-        {
-            unsigned long long h[32];
-            HIPCHK(hipMemcpy(h, eprof.p, sizeof h, hipMemcpyDeviceToHost));
-            fprintf(stderr, "persist enc prof (workgroup 0) us/step: phase A wait %.2f stage %.2f kloop %.2f cell %.2f publish %.2f | phase B %.2f %.2f %.2f %.2f %.2f | totals A %.1f us, B %.1f us\n",
-                    h[0] * 0.01 / T, h[1] * 0.01 / T, h[2] * 0.01 / T, h[3] * 0.01 / T, h[4] * 0.01 / T,
-                    h[8] * 0.01 / T, h[9] * 0.01 / T, h[10] * 0.01 / T, h[11] * 0.01 / T, h[12] * 0.01 / T, h[16] * 0.01, h[17] * 0.01);
-        }
-#endif
-    }
-    if (!persistent) {
-    for (int t = 0; t < T; ++t) {
-        GemmBatch b{};
-        b.g[0] = layer1_job(0, t); b.g[1] = layer1_job(1, t); b.count = 2;
-        run_gemm_batch(m, EPI_LSTM, b);
-    }
-    }
-    // layers 2..D (seq2seq.py:283): cell (n, t) needs (n-1, t) and (n, t-1); the cells of one
-    // anti-diagonal k = t + (n-2) are independent -> one launch per diagonal (<= GEMM_MAX_JOBS cells,
-    // deeper stacks are cut into groups of GEMM_MAX_JOBS layers)
-    auto layer_job = [&](int n, int t) {
-        GemmArgs g{};
-        const int win = n == 2 ? 2 * W : W;
-        g.nseg = 2;
-        g.a[0] = mkseg(lout[n - 1], T * win, win, 0, nullptr, win, 1, 0);
-        g.a[1] = mkseg(lout[n], T * W, W, win, nullptr, W, 1, -1, 1);
-        g.Bt = m->enc[n].wt.as<float>(); g.bias = m->enc[n].bias.as<float>();
-        g.M = B; g.N = 4 * W; g.Ktot = win + W;
-        g.out = mkslot(lout[n], T * W, W, 1, 0);
-        float* cb = cfin + (size_t)(n - 1) * B * W;
-        g.c_in = mkseg(cb, W, W, 0, nullptr, 0, 0, 0, 1);
-        g.c_out = mkslot(cb, W);
-        g.step_imm = t;
-        return g;
-    };
-    // deep_bidirectional_encoder (seq2seq.py:246-281): every layer n >= 2 is bidirectional too, reads the "cross sum" of the layer below
-    // (each pair of neighbouring features of [fw | bw] replaced by its sum) and hands on its BACKWARD final state -- layer after
-    // layer (a backward direction ends where the next layer starts), two jobs per launch; the outputs alternate between two buffers
-    const bool deep = m->cfg.deep_bidirectional_encoder && D >= 2;
-    float* deep_out = H1;
-    if (deep) {
-        if (int rc = m->Hc.ensure((size_t)2 * BT * 2 * W * 4)) return rc;
-        float* bufA = m->Hc.as<float>(); float* xs = bufA + (size_t)BT * 2 * W;
-        float* prev = H1;
-        {   // (layer 1's backward final h now: its buffer takes layer 3's outputs)
-            SmallOps ops{};
-            ops.rows(H1 + W, (long long)T * 2 * W, m->hfin.as<float>(), W, B, W, 1);
-            if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-        }
-        for (int n = 2; n <= D; ++n) {
-            float* H = prev == H1 ? bufA : H1;
-            launch_cross_sum(prev, xs, (long long)BT * 2 * W, m->stream);
-            for (int t = 0; t < T; ++t) {
-                GemmBatch b{};
-                b.g[0] = bidir_job(m->enc_dfw[n], n, 0, t, xs, 2 * W, H); b.g[1] = bidir_job(m->enc_dbw[n], n, 1, t, xs, 2 * W, H); b.count = 2;
-                run_gemm_batch(m, EPI_LSTM, b);
-            }
-            SmallOps ops{};         // backward final h of layer n = its output at time 0
-            ops.rows(H + W, (long long)T * 2 * W, m->hfin.as<float>() + (size_t)(n - 1) * B * W, W, B, W, 1);
-            if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-            prev = H;
-        }
-        deep_out = prev;
-    }
-    // residual_connections (seq2seq.py:284-291): from layer 3 on a layer's output sequence is its LSTM output plus its input sequence
-    // -- no wavefront across such layers: they run one after the other, the sum is taken in place over the whole sequence once a
-    // layer has finished (its final h -- the LSTM's own -- set aside first)
-    const bool residual = m->cfg.residual_connections && D >= 3 && !deep;       // (the sums live in the unidirectional branch, seq2seq.py:282-291)
-    for (int n = 2; n <= D && residual && !persistent; ++n) {
-        for (int t = 0; t < T; ++t) { GemmArgs g = layer_job(n, t); run_gemm(m, EPI_LSTM, g); }
-        SmallOps ops{};
-        ops.rows(lout[n] + (size_t)(T - 1) * W, (long long)T * W, m->hfin.as<float>() + (size_t)(n - 1) * B * W, W, B, W, 1);
-        if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-        if (n >= 3) launch_add_inplace(lout[n], lout[n - 1], (long long)BT * W, m->stream);
-    }
-    for (int n0 = 2; n0 <= D && !persistent && !residual && !deep; n0 += GEMM_MAX_JOBS) {
-        const int n1 = std::min(D, n0 + GEMM_MAX_JOBS - 1);
-        for (int k = 0; k < T + (n1 - n0); ++k) {
-            GemmBatch b{};
-            for (int n = n0; n <= n1; ++n) {
-                const int t = k - (n - n0);
-                if (t >= 0 && t < T) b.g[b.count++] = layer_job(n, t);
-            }
-            run_gemm_batch(m, EPI_LSTM, b);
-        }
-    }
-    {   // final hidden states, and the persistent launch's give-up word set aside, in one launch:
-        // backward final h of layer 1 = its output at time 0 (seq2seq.py:280); layers n >= 2: the output at the last position
-        SmallOps ops{};
-        if (!deep) ops.rows(H1 + W, (long long)T * 2 * W, m->hfin.as<float>(), W, B, W, 1);
-        for (int n = 2; n <= D && !residual && !deep; ++n)
-            ops.rows(lout[n] + (size_t)(T - 1) * W, (long long)T * W, m->hfin.as<float>() + (size_t)(n - 1) * B * W, W, B, W, 1);
-        if (enc_abort_word) ops.rows(reinterpret_cast<const float*>(enc_abort_word), 1, m->d_flags.as<float>(), 1, 1, 1, 1);
-        if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-    }
-    m->enc_check_pending = persistent;
-    m->stat_enc_persistent = persistent ? 1 : 0;
-    if (m->cfg.bridge_dense) {      // bridge_dense (seq2seq.py:299-301): the final states through Dense(width, tanh) on their way to the decoder
-        const size_t BW = (size_t)B * W;
-        if (int rc = m->br_tmp.ensure(BW * 4)) return rc;
-        for (int n = 1; n <= D; ++n)
-            for (int s = 0; s < 2; ++s) {
-                float* st = (s ? m->cfin.as<float>() : m->hfin.as<float>()) + (size_t)(n - 1) * BW;
-                GemmArgs g{};
-                g.nseg = 1; g.a[0] = mkseg(st, W, W, 0);
-                g.Bt = (s ? m->br_cT[n] : m->br_hT[n]).as<float>(); g.bias = (s ? m->br_cb[n] : m->br_hb[n]).as<float>();
-                g.M = B; g.N = W; g.Ktot = W;
-                g.out = mkslot(m->br_tmp.as<float>(), W);
-                run_gemm(m, EPI_PLAIN, g);
-                launch_tanh(m->br_tmp.as<float>(), st, (long long)BW, m->stream);
-            }
-    }
-    float* outb = lout[D];
-    m->enc_out = D == 1 ? H1 : deep ? deep_out : outb;
-    // u = attention_dense(enc_out) once per line (seq2seq.py:313; the reference redoes it every step)
-    {
-        GemmArgs g{};
-        g.nseg = 1; g.a[0] = mkseg(m->enc_out, C, C, 0);
-        g.Bt = m->UT.as<float>(); g.bias = nullptr; g.M = (int)BT; g.N = W; g.Ktot = C;
-        g.out = mkslot(m->u.as<float>(), W);
-        run_gemm(m, EPI_PLAIN, g);
-    }
-    HIPCHK(hipGetLastError());
-    return CASV_OK;
-}
-
-// The persistent encoder's give-up word, where the host has to wait for the device anyway.  `have_flag`: the caller has already
-// brought d_flags[0] to the host (value in *flag) behind a synchronisation of its own; otherwise this function does both.
-// A launch that gave up (its workgroups were not all resident: another process's persistent kernel on this GPU) is redone with the
-// per-step kernels -- same values.  Returns 1 if the encoder was redone (whatever was decoded from its outputs must be redone too).
-static int settle_encoder(casv_model* m, const unsigned* flag = nullptr) {
-    if (!m->enc_check_pending) return 0;
-    unsigned aborted = 0;
-    if (flag) aborted = *flag;
-    else {
-        HIPCHK(hipMemcpyAsync(&aborted, m->d_flags.p, 4, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    }
-    m->enc_check_pending = false;
-    if (!aborted) { if (!flag) m->persist_penalty = 0; return 0; }      // (with `flag` the caller has a second launch to account for before the back-off is reset)
-    persist_note_abort(m, "encoder");
-    if (int rc = run_encoder(m, false)) return rc;      // (also takes the statistic "encoder_persistent" back)
-    return 1;
-}
-
-// The encoder outputs in the arithmetic of the entry point that is about to consume them (engine.h, arithmetic_of): computed at the
-// first such call after casv_encode / casv_set_encoder_outputs, kept for further calls of the same arithmetic, redone for the other.
-static int ensure_encoded(casv_model* m, int want) {
-    if (m->enc_arith == want) { m->stat_enc_persistent = 0; return 0; }     // (an encoding that is reused)
-    m->enc_check_pending = false;
-    m->stat_enc_persistent = 0;
-    m->enc_arith = want;                // (run_encoder reads it; taken back on every failure: the outputs on the device are then nobody's)
-    if (!m->enc_explicit) {
-        if (int rc = run_encoder(m, true)) { m->enc_arith = -1; return rc; }
-        return 0;
-    }
-    // u = attention_dense(enc_out) on outputs that were handed in (seq2seq.py:313,459-460)
-    SplitScope arithmetic(want);
-    GemmArgs g{};
-    g.nseg = 1; g.a[0] = mkseg(m->enc_out, m->C, m->C, 0);
-    g.Bt = m->UT.as<float>(); g.bias = nullptr; g.M = m->B * m->T; g.N = m->W; g.Ktot = m->C;
-    g.out = mkslot(m->u.as<float>(), m->W);
-    run_gemm(m, EPI_PLAIN, g);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) { m->enc_arith = -1; return fail(CASV_ERR_HIP, "attention_dense launch failed: %s", hipGetErrorString(e)); }
-    return 0;
-}
-
-extern "C" int casv_encode(casv_model* m, int32_t B, int32_t T, int32_t A, const int32_t* idx, const float* val,
-                           const int32_t* src_rej) {
-    if (!m || !idx || !val) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->committed) return fail(CASV_ERR_STATE, "weights not committed");
-    if (B < 1 || T < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape B=%d T=%d A=%d", B, T, A);
-    if (T > CASV_MAX_T) return fail(CASV_ERR_ARG, "line length %d exceeds the supported maximum of %d", T, CASV_MAX_T);
-    HIPCHK(hipSetDevice(m->device));
-    const int W = m->W, D = m->D;
-    const size_t BT = (size_t)B * T;
-    if (int rc = m->d_idx.ensure(BT * A * 4)) return rc;
-    if (int rc = m->d_val.ensure(BT * A * 4)) return rc;
-    if (int rc = m->d_srcrej.ensure(BT * 4)) return rc;
-    if (int rc = m->x0.ensure(BT * W * 4)) return rc;
-    if (int rc = m->H1.ensure(BT * 2 * W * 4)) return rc;
-    if (D == 2 || D == 3) { if (int rc = m->Ha.ensure(BT * W * 4)) return rc; }
-    if (D == 3) { if (int rc = m->Hb.ensure(BT * W * 4)) return rc; }
-    if (int rc = m->cfin.ensure((size_t)(D + 1) * B * W * 4)) return rc;     // slot D: forward c of layer 1 (unused later)
-    if (int rc = m->hfin.ensure((size_t)D * B * W * 4)) return rc;
-    if (int rc = m->u.ensure(BT * W * 4)) return rc;
-    // The caller owns idx / val / src_rej and may release them as soon as this function returns (the encoder itself runs
-    // asynchronously).  They are copied into a pinned staging buffer of the handle first: the device copies then need no wait --
-    // the function returns while they are still queued (waiting for pageable copies cost every batch of configs[1] ~40 us of idle
-    // GPU) -- and the staging buffer is reused only once its previous copies have gone (ev_inputs).
-    const size_t nin = BT * A * 4, nrej = BT * 4, need = 2 * nin + nrej;
-    if (need > m->pin_limit) {
-        // (very large inputs: no pinned copy of that size -- straight from the caller's buffers, and wait until they have been read)
-        HIPCHK(hipMemcpyAsync(m->d_idx.p, idx, nin, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(m->d_val.p, val, nin, hipMemcpyHostToDevice, m->stream));
-        if (src_rej) HIPCHK(hipMemcpyAsync(m->d_srcrej.p, src_rej, nrej, hipMemcpyHostToDevice, m->stream));
-        else HIPCHK(hipMemsetAsync(m->d_srcrej.p, 0xff, nrej, m->stream));
-        HIPCHK(hipEventRecord(m->ev_inputs, m->stream));
-        HIPCHK(hipEventSynchronize(m->ev_inputs));
-    } else {
-    if (m->pin_in_cap < need) {
-        if (m->pin_in) { HIPCHK(hipStreamSynchronize(m->stream)); (void)hipHostFree(m->pin_in); m->pin_in = nullptr; m->pin_in_cap = 0; }
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_in), need, hipHostMallocDefault));
-        m->pin_in_cap = need;
-    } else HIPCHK(hipEventSynchronize(m->ev_inputs));
-    memcpy(m->pin_in, idx, nin); memcpy(m->pin_in + nin, val, nin);
-    if (src_rej) memcpy(m->pin_in + 2 * nin, src_rej, nrej);
-    HIPCHK(hipMemcpyAsync(m->d_idx.p, m->pin_in, nin, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_val.p, m->pin_in + nin, nin, hipMemcpyHostToDevice, m->stream));
-    if (src_rej) HIPCHK(hipMemcpyAsync(m->d_srcrej.p, m->pin_in + 2 * nin, nrej, hipMemcpyHostToDevice, m->stream));
-    else HIPCHK(hipMemsetAsync(m->d_srcrej.p, 0xff, nrej, m->stream));
-    HIPCHK(hipEventRecord(m->ev_inputs, m->stream));
-    }
-    m->B = B; m->T = T; m->A = A;
-    m->last_decode = 0; m->has_a0 = false;
-    m->enc_check_pending = false;
-    // The encoder itself runs for the first entry point that needs its outputs, in that entry point's arithmetic (ensure_encoded):
-    // what a search returns for a line must not depend on whether somebody looked at the encoder outputs or decoded greedily before.
-    m->enc_arith = -1; m->enc_explicit = false;
-    m->encoded = true;
-    return CASV_OK;
-}
-
-extern "C" int casv_set_encoder_outputs(casv_model* m, int32_t B, int32_t T, const float* enc_out, const float* states,
-                                        const float* a0, const int32_t* src_rej) {
-    if (!m || !enc_out || !states) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->committed) return fail(CASV_ERR_STATE, "weights not committed");
-    if (B < 1 || T < 1) return fail(CASV_ERR_ARG, "bad shape B=%d T=%d", B, T);
-    if (T > CASV_MAX_T) return fail(CASV_ERR_ARG, "line length %d exceeds the supported maximum of %d", T, CASV_MAX_T);
-    HIPCHK(hipSetDevice(m->device));
-    const int W = m->W, C = m->C, D = m->D;
-    const size_t BT = (size_t)B * T, BW = (size_t)B * W;
-    if (int rc = m->Hc.ensure(std::max((size_t)(D - 1), (size_t)1) * BT * std::max(W, C) * 4)) return rc;
-    if (int rc = m->d_srcrej.ensure(BT * 4)) return rc;
-    if (int rc = m->cfin.ensure((size_t)(D + 1) * BW * 4)) return rc;
-    if (int rc = m->hfin.ensure((size_t)D * BW * 4)) return rc;
-    if (int rc = m->u.ensure(BT * W * 4)) return rc;
-    m->enc_out = m->Hc.as<float>();
-    HIPCHK(hipMemcpyAsync(m->enc_out, enc_out, BT * C * 4, hipMemcpyHostToDevice, m->stream));
-    for (int n = 0; n < D; ++n) {
-        HIPCHK(hipMemcpyAsync(m->hfin.as<float>() + n * BW, states + (size_t)(2 * n) * BW, BW * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(m->cfin.as<float>() + n * BW, states + (size_t)(2 * n + 1) * BW, BW * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    if (src_rej) HIPCHK(hipMemcpyAsync(m->d_srcrej.p, src_rej, BT * 4, hipMemcpyHostToDevice, m->stream));
-    else HIPCHK(hipMemsetAsync(m->d_srcrej.p, 0xff, BT * 4, m->stream));
-    m->has_a0 = a0 != nullptr;
-    if (a0) {
-        if (int rc = m->a0.ensure(BT * 4)) return rc;
-        HIPCHK(hipMemcpyAsync(m->a0.p, a0, BT * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    HIPCHK(hipEventRecord(m->ev_inputs, m->stream));
-    HIPCHK(hipEventSynchronize(m->ev_inputs));
-    m->B = B; m->T = T; m->A = 1;
-    m->last_decode = 0; m->enc_check_pending = false;
-    m->enc_arith = -1; m->enc_explicit = true;         // u = attention_dense(enc_out) follows in the consumer's arithmetic (ensure_encoded)
-    m->encoded = true;
-    return CASV_OK;
-}
-
-extern "C" int casv_get_encoder_outputs(casv_model* m, float* enc_out, float* states) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->encoded) return fail(CASV_ERR_STATE, "nothing encoded");
-    HIPCHK(hipSetDevice(m->device));
-    if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_CHAIN))) return rc;
-    if (int rc = settle_encoder(m); rc < 0) return rc;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    const size_t BW = (size_t)m->B * m->W;
-    if (enc_out) HIPCHK(hipMemcpy(enc_out, m->enc_out, (size_t)m->B * m->T * m->C * 4, hipMemcpyDeviceToHost));
-    if (states)
-        for (int n = 0; n < m->D; ++n) {
-            HIPCHK(hipMemcpy(states + (2 * n) * BW, m->hfin.as<float>() + n * BW, BW * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(states + (2 * n + 1) * BW, m->cfin.as<float>() + n * BW, BW * 4, hipMemcpyDeviceToHost));
-        }
     return CASV_OK;
 }
 
@@ -1009,7 +558,6 @@ struct StepRunner {
     }
 };
 
-// (declared ahead of casv_encode, which uses them too)
 // All S greedy steps in ONE launch of the persistent decoder (persist.hip): small batches, where the per-step kernels are
 // bound by launch and memory latency.  Same results bit for bit (tested), same state / alignment / window stores.
 static bool persist_applies(const casv_model* m, int B) {
@@ -1082,9 +630,9 @@ static int decode_greedy_persistent(casv_model* m, int mode, int S) {
         const double by = 4.0 * R * (4.0 * D * W + 11.0 * (W + C) + 2.0 * m->V + 2.0 * T);
         m->prof_begin(PC_PERSIST, fl * S, by * S, pev);
     }
-    persist_order_before(m);
+    persist_order_before(m->device, m->stream);
     if (launch_persist_decode(pa, m->stream)) return fail(CASV_ERR_ARG, "persistent decoder: rows of %d floats do not fit the LDS", kmax);
-    persist_order_after(m);
+    persist_order_after(m->device, m->stream);
     m->prof_end(PC_PERSIST, pev);
     HIPCHK(hipGetLastError());
 #ifdef CASV_PERSIST_PROF
@@ -1119,7 +667,7 @@ static int decode_greedy_persistent(casv_model* m, int mode, int S) {
     // the launch's give-up word, set aside beside the encoder's (the caller brings both to the host with the results)
     {
         SmallOps ops{};
-        ops.rows(reinterpret_cast<const float*>(m->p_counters.as<unsigned>() + (size_t)nrb * (D + 3) * 32), 1, m->d_flags.as<float>() + 1, 1, 1, 1, 1);
+        ops.rows(reinterpret_cast<const float*>(persist_give_up_word(m->p_counters.as<unsigned>(), persist_counter_bytes(R, D))), 1, m->d_flags.as<float>() + 1, 1, 1, 1, 1);
         if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
     }
     return 0;
@@ -1150,7 +698,7 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
         m->pin_out_cap = want;
     }
     unsigned* const pin_flags = reinterpret_cast<unsigned*>(staged ? m->pin_out + 2 * nres : m->pin_out);
-    bool persistent = persist_applies(m, B) && !persist_backed_off(m);
+    bool persistent = persist_applies(m, B) && !persist_backed_off(m->persist_backoff);
     auto begin = [&](bool with_counters) -> int {        // the set-up of a run, as one launch
         SmallOps ops{};
         ops.fill(m->o_idx.p, nres); ops.fill(m->o_prob.p, nres);
@@ -1186,10 +734,10 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
         const int redone = settle_encoder(m, &flags[0]);
         if (redone < 0) return redone;
         const bool dec_aborted = persistent && flags[1] != 0;
-        if (dec_aborted) { persist_note_abort(m, "decoder"); persistent = false; }
+        if (dec_aborted) { persist_note_abort(m->persist_backoff, "decoder"); persistent = false; }
         // the back-off is reset only by an attempt in which NO persistent launch gave up (an encoder that keeps losing residency
         // must not restart its penalty at 16 because the decoder behind it happened to run through)
-        if (!redone && !dec_aborted && (persistent || enc_was_persistent)) m->persist_penalty = 0;
+        if (!redone && !dec_aborted && (persistent || enc_was_persistent)) m->persist_backoff.penalty = 0;
         if (!redone && !dec_aborted) break;
         if (attempt >= 2) return fail(CASV_ERR_STATE, "persistent launches keep giving up");
     }
@@ -1332,7 +880,7 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     auto settle_now = [&](int& redone) {          // behind a wait that covers the copy above
         const unsigned flag = (unsigned)m->pin_active[2];
         redone = settle_encoder(m, &flag);
-        if (redone == 0) m->persist_penalty = 0;
+        if (redone == 0) m->persist_backoff.penalty = 0;
         enc_settled = true;
         return redone < 0 ? redone : 0;
     };

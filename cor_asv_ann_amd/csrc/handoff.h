@@ -7,7 +7,7 @@ namespace casv {
 
 // A wait gives up after this many ticks of the 100 MHz wall clock (50 ms: a whole decode takes milliseconds; a hand-off
 // microseconds).  Lost residency -- a compiler that changed the register count, a partitioned or shared GPU -- then costs
-// one such wait per call, after which the host stops choosing the persistent path for a while (engine.hip).
+// one such wait per call, after which the host stops choosing the persistent path for a while (persist_host.h).
 constexpr unsigned long long PERSIST_WAIT_TICKS = 5ull * 1000ull * 1000ull;
 
 __device__ __forceinline__ unsigned ld_agent(const unsigned* p) {

@@ -34,10 +34,8 @@
 #include "common.h"
 #include "row_kernels.h"
 #include "handoff.h"
+#include "persist_host.h"
 #include <math.h>
-#include <map>
-#include <mutex>
-#include <utility>
 
 namespace casv {
 
@@ -657,34 +655,12 @@ __global__ __launch_bounds__(256, 2) void persist_encode_kernel(const PersistEnc
 #endif
 }
 
-// Workgroups of `kernel` (256 threads, `lds` bytes of dynamic LDS) that one CU holds at once, as the runtime reports it for
-// the code object that is actually loaded -- asked once per (device, LDS size).  0 = the query failed: no persistent launch.
-template <class K>
-static int blocks_per_cu(K kernel, size_t lds) {
-    static std::mutex mu;
-    static std::map<std::pair<int, size_t>, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find({dev, lds});
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) n = 0;
-    else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kernel), 256, lds) != hipSuccess) n = 0;
-    // The query counts registers and LDS; the workgroup's static LDS (gate exchange, flags: ~4.3 KB) is part of the kernel's
-    // own figure.  Never plan for more than the two workgroups per CU the launch bounds promise.
-    n = n > 2 ? 2 : (n < 0 ? 0 : n);
-    cache[{dev, lds}] = n;
-    return n;
-}
-int persist_encode_blocks_per_cu(size_t lds) { return lds > 150 * 1024 ? 0 : blocks_per_cu(persist_encode_kernel, lds); }
-int persist_decode_blocks_per_cu(size_t lds) { return lds > 150 * 1024 ? 0 : blocks_per_cu(persist_decode_kernel, lds); }
+// (no launch form above 150 KB of staged rows)
+int persist_encode_blocks_per_cu(size_t lds) { return lds > 150 * 1024 ? 0 : persist_blocks_per_cu(persist_encode_kernel, lds, 2); }
+int persist_decode_blocks_per_cu(size_t lds) { return lds > 150 * 1024 ? 0 : persist_blocks_per_cu(persist_decode_kernel, lds, 2); }
+int persist_enc_max_tiles() { return PENC_MAXT; }
 
-size_t persist_enc_counter_bytes(int B, int D) {
-    const size_t nrb = (B + 15) / 16;
-    return (nrb * (D + 1) * 32 + 32) * sizeof(unsigned);
-}
+size_t persist_enc_counter_bytes(int B, int D) { return persist_counters_bytes((size_t)((B + 15) / 16) * (D + 1)); }
 
 int launch_persist_encode(const PersistEncArgs& pa, int grid, hipStream_t stream) {
     const size_t lds = (size_t)16 * pa.lda * sizeof(float);
@@ -697,10 +673,7 @@ int launch_persist_encode(const PersistEncArgs& pa, int grid, hipStream_t stream
     return 0;
 }
 
-size_t persist_counter_bytes(int R, int D) {
-    const size_t nrb = (R + 15) / 16;
-    return (nrb * (D + 3) * 32 + 32) * sizeof(unsigned);
-}
+size_t persist_counter_bytes(int R, int D) { return persist_counters_bytes((size_t)((R + 15) / 16) * (D + 3)); }
 
 size_t persist_lds_bytes(const PersistArgs& pa) { return (size_t)16 * pa.lda * sizeof(float); }
 

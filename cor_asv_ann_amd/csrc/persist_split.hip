@@ -23,9 +23,7 @@
 #include "common.h"
 #include "row_kernels.h"
 #include "handoff.h"
-#include <map>
-#include <mutex>
-#include <utility>
+#include "persist_host.h"
 
 namespace casv {
 
@@ -251,29 +249,10 @@ __global__ __launch_bounds__(256, 2) void persist_split_encode_kernel(const Pers
     }
 }
 
-// Workgroups of the kernel that one CU holds at once, as the runtime reports it for the loaded code object (asked once per device;
-// capped at the two the launch bounds promise).  0: the query failed -- no persistent launch.
-int persist_split_encode_blocks_per_cu() {
-    static std::mutex mu;
-    static std::map<int, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(dev);
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(persist_split_encode_kernel), 256, PS_LDS_BYTES) != hipSuccess) n = 0;
-    n = n > 2 ? 2 : (n < 0 ? 0 : n);
-    cache[dev] = n;
-    return n;
-}
-
+int persist_split_encode_blocks_per_cu() { return persist_blocks_per_cu(persist_split_encode_kernel, PS_LDS_BYTES, 2); }
 int persist_split_enc_max_tiles() { return PS_MAXT; }
 
-size_t persist_split_enc_counter_bytes(int B, int D) {
-    const size_t nrb = (B + 31) / 32;
-    return (nrb * (D + 1) * 32 + 32) * sizeof(unsigned);
-}
+size_t persist_split_enc_counter_bytes(int B, int D) { return persist_counters_bytes((size_t)((B + 31) / 32) * (D + 1)); }
 
 int launch_persist_split_encode(const PersistSplitEncArgs& pa, int grid, hipStream_t stream) {
     if (grid < 1 || pa.W % 32 || pa.D < 1 || pa.D > 8) return -1;

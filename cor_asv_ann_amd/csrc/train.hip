@@ -417,7 +417,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
             m->prof_begin(PC_PERSIST, flops, 0.0, ev);
             launch_train_recurrence_bwd(ra, grid, m->stream);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = ra.counters + (cb / sizeof(unsigned) - 32);
+            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, cb);
             persistent = true;
         }
     }
@@ -495,7 +495,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
             m->prof_begin(PC_PERSIST, flops, 0.0, ev);
             launch_train_recurrence(ra, grid, m->stream);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = ra.counters + (train_recurrence_counter_bytes(B) / sizeof(unsigned) - 32);
+            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_recurrence_counter_bytes(B));
             if (masked) *masked = true;
             for (int j = 0; j < count; ++j) a[j].l->drec_cleared = a[j].l->kr == W;
             return 0;
@@ -746,7 +746,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
             m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
             launch_train_attention_cell(ra, grid, st);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = ra.counters + (train_attention_cell_counter_bytes(B) / sizeof(unsigned) - 32);
+            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_attention_cell_counter_bytes(B));
             top_persistent = true;
         }
     }
@@ -904,7 +904,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
                     launch_attention_deferred(da, st);
                 }
                 m->prof_end(PC_PERSIST, ev);
-                ts->rec_abort[ts->rec_launches++] = ra.counters + (train_attention_cell_bwd_counter_bytes(B) / sizeof(unsigned) - 32);
+                ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_attention_cell_bwd_counter_bytes(B));
                 topb_persistent = true;
             }
         }

@@ -16,9 +16,8 @@
 // the same MFMA sequence, and its cell epilogue.  Results are therefore those of the per-step launches bit for bit (tested).
 #include "common.h"
 #include "handoff.h"
+#include "persist_host.h"
 #include "train_kernels.h"
-#include <map>
-#include <mutex>
 
 namespace casv {
 
@@ -200,30 +199,13 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
     }
 }
 
-template <class K>
-static int rec_blocks_per_cu(K kernel) {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    const void* f = reinterpret_cast<const void*>(kernel);
-    auto it = cache.find({dev, f});
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess) n = 0;
-    n = n > 2 ? 2 : (n < 0 ? 0 : n);
-    cache[{dev, f}] = n;
-    return n;
-}
-
-size_t train_recurrence_counter_bytes(int B) { return ((size_t)2 * ((B + RBM - 1) / RBM) * 32 + 32) * sizeof(unsigned); }
+size_t train_recurrence_counter_bytes(int B) { return persist_counters_bytes((size_t)2 * ((B + RBM - 1) / RBM)); }
 
 // Workgroups of the launch if this shape has a persistent form on a device of `ncu` CUs whose every workgroup is resident at
 // once, else 0 (the caller runs the per-step launches).
 template <int NT> static int rec_grid(const RecArgs& ra, int ncu) {
     const int grid = ra.njobs * ((ra.B + RBM - 1) / RBM) * NT;
-    return grid <= rec_blocks_per_cu(train_recurrence_kernel<NT>) * ncu ? grid : 0;
+    return grid <= persist_blocks_per_cu(train_recurrence_kernel<NT>, 0, 2) * ncu ? grid : 0;
 }
 #define CASV_REC_WIDTHS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 int train_recurrence_grid(const RecArgs& ra, int ncu) {

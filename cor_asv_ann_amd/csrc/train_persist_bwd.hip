@@ -16,10 +16,9 @@
 // Weight panels: slot s = (column tile, K share) of every row block and both layers sits on XCD s % 8, whose L2 holds them.
 #include "common.h"
 #include "handoff.h"
+#include "persist_host.h"
 #include "train_kernels.h"
 #include <math.h>
-#include <map>
-#include <mutex>
 
 namespace casv {
 
@@ -232,28 +231,11 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_bwd_kernel(const RecB
     if (row_ok) *reinterpret_cast<f32x4*>(job.dc_out + (long long)mrow * W + u0) = dc;
 }
 
-template <class K>
-static int recb_blocks_per_cu(K kernel) {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    const void* f = reinterpret_cast<const void*>(kernel);
-    auto it = cache.find({dev, f});
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess) n = 0;
-    n = n > 2 ? 2 : (n < 0 ? 0 : n);
-    cache[{dev, f}] = n;
-    return n;
-}
-
-size_t train_recurrence_bwd_counter_bytes(int B) { return ((size_t)2 * ((B + QBM - 1) / QBM) * 8 * 32 + 32) * sizeof(unsigned); }
+size_t train_recurrence_bwd_counter_bytes(int B) { return persist_counters_bytes((size_t)2 * ((B + QBM - 1) / QBM) * 8); }
 
 template <int NT> static int recb_grid(const RecBwdArgs& ra, int ncu) {
     const int grid = ra.njobs * ((ra.B + QBM - 1) / QBM) * NT;
-    return grid <= recb_blocks_per_cu(train_recurrence_bwd_kernel<NT>) * ncu ? grid : 0;
+    return grid <= persist_blocks_per_cu(train_recurrence_bwd_kernel<NT>, 0, 2) * ncu ? grid : 0;
 }
 // Workgroups of the launch, or 0: no persistent form for this shape on this device (whole column tiles of 128 units only)
 int train_recurrence_bwd_grid(const RecBwdArgs& ra, int ncu) {

@@ -15,10 +15,9 @@
 // (per-step: two split-K shares), so the results agree with the per-step path to fp32 rounding, not bit for bit.
 #include "common.h"
 #include "handoff.h"
+#include "persist_host.h"
 #include "row_kernels.h"
 #include "train_kernels.h"
-#include <map>
-#include <mutex>
 
 namespace casv {
 
@@ -363,28 +362,12 @@ __global__ __launch_bounds__(256, 1) void train_attention_cell_kernel(const TopR
 #undef CASV_LOAD_BH
 }
 
-template <class K>
-static int top_blocks_per_cu(K kernel) {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    const void* f = reinterpret_cast<const void*>(kernel);
-    auto it = cache.find({dev, f});
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess) n = 0;
-    n = n > 1 ? 1 : (n < 0 ? 0 : n);          // planned for one workgroup per CU (its two idle waves in part A leave room)
-    cache[{dev, f}] = n;
-    return n;
-}
-
-size_t train_attention_cell_counter_bytes(int B) { return ((size_t)((B + TBM - 1) / TBM) * 3 * 32 + 32) * sizeof(unsigned); }
+size_t train_attention_cell_counter_bytes(int B) { return persist_counters_bytes((size_t)((B + TBM - 1) / TBM) * 3); }
 
 template <int NT> static int top_grid(const TopRecArgs& ra, int ncu) {
     const int grid = ((ra.B + TBM - 1) / TBM) * NT;
-    return grid <= top_blocks_per_cu(train_attention_cell_kernel<NT>) * ncu ? grid : 0;
+    // (planned for one workgroup per CU: its two idle waves in part A leave room)
+    return grid <= persist_blocks_per_cu(train_attention_cell_kernel<NT>, 0, 1) * ncu ? grid : 0;
 }
 // Workgroups of the launch, or 0: no persistent form for this shape on this device (context as wide as the layer, i.e. depth >= 2;
 // widths whose unit groups divide the 32 rows of a row block)

@@ -13,12 +13,11 @@
 // Five counters per row block (dZ quarters, ctx tiles, h column tiles, dwq rows, dhatt columns).
 #include "common.h"
 #include "handoff.h"
+#include "persist_host.h"
 #include "row_kernels.h"
 #include "train_kernels.h"
 #include "attn_bwd.h"
 #include <math.h>
-#include <map>
-#include <mutex>
 
 namespace casv {
 
@@ -503,28 +502,11 @@ __global__ __launch_bounds__(256, 3) void train_attention_cell_bwd_rows_kernel(c
     }
 }
 
-template <class K>
-static int topb_blocks_per_cu(K kernel) {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(mu);
-    const void* f = reinterpret_cast<const void*>(kernel);
-    auto it = cache.find({dev, f});
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess) n = 0;
-    n = n > 1 ? 1 : (n < 0 ? 0 : n);
-    cache[{dev, f}] = n;
-    return n;
-}
-
-size_t train_attention_cell_bwd_counter_bytes(int B) { return ((size_t)((B + VBM - 1) / VBM) * 12 * 32 + 32) * sizeof(unsigned); }
+size_t train_attention_cell_bwd_counter_bytes(int B) { return persist_counters_bytes((size_t)((B + VBM - 1) / VBM) * 12); }
 
 template <int NT> static int topb_grid(const TopBwdArgs& ra, int ncu) {
     const int grid = ((ra.B + VBM - 1) / VBM) * NT;
-    return grid <= topb_blocks_per_cu(train_attention_cell_bwd_kernel<NT>) * ncu ? grid : 0;
+    return grid <= persist_blocks_per_cu(train_attention_cell_bwd_kernel<NT>, 0, 1) * ncu ? grid : 0;
 }
 // Workgroups of the launch, or 0: no persistent form for this shape on this device (context as wide as the layer; whole column
 // tiles of 128 units; unit groups that divide the 32 rows of a row block)
