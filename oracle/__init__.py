@@ -53,6 +53,9 @@ global-norm clip then Adam            ``Optimizer.get_gradients``: ``norm = sqrt
                                       ``clip_norm(g, clipnorm, norm)`` = ``g * c / norm`` where
                                       ``norm >= c``; ``Adam.get_updates``: ``lr_t = lr * sqrt(1 - b2^t) /
                                       (1 - b1^t)``, ``p -= lr_t * m / (sqrt(v) + epsilon)``, epsilon 1e-7
+Adam's hyper-parameters are float32    ``Adam.__init__``: ``K.variable(lr)``, ``K.variable(beta_1)``, ... of     ``train.adam_step``
+constants                             floatx float32, ``clipnorm`` against the float32 norm: ``1 - beta_2``
+                                      is ``1 - fl32(0.999)`` = 0.00100004673, not 0.001
 ``predict_on_batch`` broadcasts a     no batch-size check between inputs in ``Model.predict_on_batch``         ``decode.decode_sequence_beam``
 (1, T, C) attended input              (seq2seq.py:1428-1429 relies on it)
 candidate order of equal scores       ``np.argsort`` (quicksort, unstable) at seq2seq.py:1473: ties have no    ``decode`` module docstring

@@ -276,10 +276,14 @@ def forward_backward(cfg, w, enc_in, dec_in, dec_out, weights, masks=None, want_
 
 
 def adam_step(w, grads, state, lr=1e-3, beta1=0.9, beta2=0.999, eps=EPS, clipnorm=5.0, frozen=()):
-    """Keras Adam with global-norm clipping; `state` = {'t': int, 'm': {...}, 'v': {...}}."""
+    """Keras Adam with global-norm clipping; `state` = {'t': int, 'm': {...}, 'v': {...}}.
+    The hyper-parameters and the norm the clip decision reads enter as their float32 values: they are float32 variables in Keras
+    (and float32 fields of casv_adam_params), so 1 - beta2 is 1 - fl32(0.999), not 0.001."""
+    lr, beta1, beta2, eps, clipnorm = (float(np.float32(x)) for x in (lr, beta1, beta2, eps, clipnorm))
     names = [k for k in w if not any(k.startswith(p) for p in frozen)]
     norm = np.sqrt(sum(float((grads[k].astype(np.float64) ** 2).sum()) for k in names))
-    scale = clipnorm / norm if norm >= clipnorm else 1.0
+    norm32 = float(np.float32(norm))
+    scale = clipnorm / norm32 if (clipnorm > 0 and norm32 >= clipnorm) else 1.0
     state['t'] += 1
     t = state['t']
     lr_t = lr * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)

@@ -138,14 +138,16 @@ def test_adam_clipnorm_known_answer():
     norm = adam_step(w, g, st)
     assert abs(norm - 13.0) < 1e-12
     gs = 3.0 * 5 / 13
-    lr_t = 1e-3 * np.sqrt(1 - 0.999) / (1 - 0.9)
-    m, v = 0.1 * gs, 0.001 * gs * gs
-    assert abs(w['a'][0] - (1.0 - lr_t * m / (np.sqrt(v) + 1e-7))) < 1e-15
+    # (the hyper-parameters are float32 variables in Keras: their float32 values enter)
+    lr, b1, b2, eps = (float(np.float32(x)) for x in (1e-3, 0.9, 0.999, 1e-7))
+    lr_t = lr * np.sqrt(1 - b2) / (1 - b1)
+    m, v = (1 - b1) * gs, (1 - b2) * gs * gs
+    assert abs(w['a'][0] - (1.0 - lr_t * m / (np.sqrt(v) + eps))) < 1e-15
     # below the threshold gradients pass unchanged
     w2 = {'a': np.array([1.0])}
     st2 = {'t': 0, 'm': {}, 'v': {}}
     adam_step(w2, {'a': np.array([0.5])}, st2)
-    assert abs(st2['m']['a'][0] - 0.05) < 1e-15
+    assert abs(st2['m']['a'][0] - (1 - b1) * 0.5) < 1e-15
 
 
 def test_training_reduces_loss():
