@@ -1033,6 +1033,8 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "beam_sort_capacity")) { *value = 4096; return CASV_OK; }
     if (!strcmp(key, "cus")) { *value = m->ncu; return CASV_OK; }
     if (!strcmp(key, "encoder_persistent")) { *value = m->stat_enc_persistent; return CASV_OK; }
+    if (!strcmp(key, "train_persistent_launches")) { *value = m->stat_train_launches; return CASV_OK; }
+    if (!strcmp(key, "train_give_ups")) { *value = m->stat_train_give_ups; return CASV_OK; }
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }

@@ -796,6 +796,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         }
         ts->rec_checked = ts->rec_launches;
         if (any) {
+            ++m->stat_train_give_ups;           // (statistic "train_give_ups": the caller redoes the step)
             ts->rec_penalty = ts->rec_penalty ? std::min(2 * ts->rec_penalty, 1 << 20) : 16;
             ts->rec_skip = ts->rec_penalty + 1;
             fprintf(stderr, "cor_asv_ann_hip: a persistent recurrence of the train step gave up waiting (is the GPU shared?); "
@@ -812,6 +813,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         HIPCHK(hipMemcpyAsync(loss_out, ts->loss.p, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (norm_out) *norm_out = 0.0;
+        m->stat_train_launches = ts->rec_launches;
         return CASV_OK;
     }
 
@@ -1100,6 +1102,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipStreamSynchronize(st));
     if (norm_out) *norm_out = sqrt(nsq);
     if (m->prof.on) m->prof.collect();
+    m->stat_train_launches = ts->rec_launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
     return CASV_OK;
 }
 

@@ -331,7 +331,10 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
  * sorted in runs and merged by rank); "encoder_persistent" = 1 if the encoder pass behind the last entry point ran as ONE
  * persistent launch and was not redone per step, else 0 (0 also where the entry point reused an encoding it found);
- * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn. */
+ * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
+ * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
+ * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
+ * give-up on this handle so far. */
 int casv_get_stat(casv_model* m, const char* key, int64_t* value);
 int casv_synchronize(casv_model* m);
 

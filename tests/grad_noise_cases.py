@@ -50,8 +50,12 @@ MID = ('mid_d2_w256_b512', 2, 256, 40, 512, 63, 4.0, True, {}, 1, ())
 ALL = CASES + [MID]
 
 
-def build(case, seed=4):
-    """cfg, float32 weights, oracle inputs (enc_in, dec_in, dec_out, wts, masks) and the device batch of a case."""
+def build(case, seed=4, source=None):
+    """cfg, float32 weights, oracle inputs (enc_in, dec_in, dec_out, wts, masks) and the device batch of a case.
+    source: None -- every source line has the targets' L characters and the end character; S -- the source lines have S characters
+    and the end character (the targets keep L: the two lengths are separate), and about a third of them are shorter, the
+    shortest of one character (where S = 1: the end character alone): the positions behind a line's end are zero rows for the oracle (the reference
+    runs its LSTMs over them unmasked) and index -1 for the device."""
     name, d, W, V, B, L, es, with_masks, flags, A, frozen = case
     cfg = ModelConfig(depth=d, width=W, voc_size=V, **flags)
     w = make_weights(cfg, emb_scale=es)
@@ -60,10 +64,18 @@ def build(case, seed=4):
         if k.endswith('_b') or k in ('att_bUW', 'att_bv'):
             w[k] = (w[k] + rng.normal(size=w[k].shape) * 0.2).astype(np.float32)
     om = OracleModel(cfg, w)
-    src, sidx = make_lines(B, L, 1, voc_size=V)
+    src, sidx = make_lines(B, L if source is None else source, 1, voc_size=V)
     tgt, _ = make_lines(B, L, 2, voc_size=V)
-    tgt[1] = tgt[1][:L // 2] + '\n'                         # ragged targets: padded steps have weight 0
+    if B > 1:
+        tgt[1] = tgt[1][:L // 2] + '\n'                     # ragged targets: padded steps have weight 0
+    if source is not None:      # ragged sources, drawn apart from the jitter and the masks below (which stay what they are without)
+        cut = np.random.default_rng(seed + 1)
+        short = [b for b in range(1, B) if b % 3 == 2 or (B == 2 and b == 1)]
+        for i, b in enumerate(short):
+            src[b] = src[b][:min(1, source - 1) if i == 0 or source < 3 else int(cut.integers(1, source))] + '\n'
     enc_in, dec_in, dec_out, wts = vectorize_lines(om, src, tgt)
+    if source is not None:
+        sidx = _idx(enc_in)
     val = None
     if A > 1:                   # confusion network: two alternatives per position, 0.75 / 0.25
         alt = np.where(sidx >= 0, np.roll(sidx, 1, axis=1), -1)
@@ -110,8 +122,8 @@ def ratios(got, o32, o64):
     return out
 
 
-def device(case, w, batch, path, deterministic):
-    """(loss, norm, grads) of one mode-2 train step on the device."""
+def device(case, w, batch, path, deterministic, probe=None):
+    """(loss, norm, grads) of one mode-2 train step on the device.  probe(eng): called behind the step, inside its session."""
     from cor_asv_ann_amd.engine import HipEngine
     name, d, W, V, B, L, es, with_masks, flags, A, frozen = case
     eng = HipEngine(d, W, V, **flags)
@@ -123,6 +135,8 @@ def device(case, w, batch, path, deterministic):
         eng.train_begin(frozen=frozen)
         loss, norm = eng.train_step(*batch, mode=2)
         grads = {k: g for k, g in eng.train_gradients().items() if not (frozen and k.startswith(tuple(frozen)))}
+        if probe is not None:
+            probe(eng)
         eng.train_end()
         return float(loss), float(norm), grads
     finally:
