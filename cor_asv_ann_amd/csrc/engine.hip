@@ -995,7 +995,10 @@ extern "C" int casv_records_append(casv_model* m, int32_t row_offset) {
     RecordSrc r{};
     r.B = B; r.S = m->last_S; r.T = m->T; r.A = m->A; r.eos = m->eos;
     r.src_idx = m->d_idx.as<int>(); r.src_val = m->d_val.as<float>();
-    if (!r.src_idx || m->A < 1) return fail(CASV_ERR_STATE, "the lines of the last decode were not encoded by casv_encode");
+    // (casv_set_encoder_outputs leaves d_idx / d_val alone: they would still hold the batch of an earlier casv_encode, read with
+    // this batch's B and T -- wrong padding decisions and fallback characters, beyond the allocation if this batch is larger)
+    if (!r.src_idx || m->A < 1 || m->enc_explicit)
+        return fail(CASV_ERR_STATE, "records need the input lines: the last decode's encoder outputs were handed in (casv_set_encoder_outputs), not computed by casv_encode");
     if (m->last_decode == 2) {
         r.idx = m->bo_idx.as<int>(); r.prob = m->bo_prob.as<float>(); r.len = m->bo_len.as<int>(); r.score = m->bo_score.as<double>();
         r.row_mul = m->last_rows / B;                   // max_results rows per line, best first

@@ -229,7 +229,9 @@ int casv_comm_destroy(casv_model* m);
  * device; casv_records_append: the best result of every line of the LAST casv_decode_beam (max_results rows per line: the
  * first) or casv_decode_greedy (mode 0) call goes to records [row_offset, row_offset + B) -- a line without a finished
  * hypothesis gets what correct_lines falls back to (its input characters, probability 1, score 0; seq2seq.py:826-836), an
- * empty padding line an empty record; casv_records_read: the buffer to the host; casv_records_device_ptr: its device address
+ * empty padding line an empty record.  The padding decision and the fallback read the input lines on the device, so the batch
+ * must have gone through casv_encode: after casv_set_encoder_outputs casv_records_append returns CASV_ERR_STATE.  A greedy
+ * record's score is the sum of -log((double)p) in double over the line, divided by its length; casv_records_read: the buffer to the host; casv_records_device_ptr: its device address
  * (after the handle's stream has drained) for a host program that runs the collective itself (torch.distributed);
  * casv_comm_all_gather_records: RCCL all-gather of every rank's buffer, result (world * rows records, rank order) to the host. */
 int casv_records_reset(casv_model* m, int32_t rows, int32_t S);
