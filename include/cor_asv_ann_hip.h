@@ -130,7 +130,10 @@ int casv_decoder_step_lm(casv_model* m, int32_t R, const int32_t* line,
  * all lines) and decode_sequence_greedy for every line at once (seq2seq.py:1288-1354; mode 1:
  * argmax over all V with the index-0 NaN write-back, a line's steps after its '\n' are not
  * reported).  out_idx/out_prob (B,S); out_len (B) = reported steps per line (mode 0: S);
- * out_align (B,S,T) or NULL. */
+ * out_align (B,S,T) or NULL.
+ * A row whose candidates are all NaN: mode 0 reports index 1 with a NaN probability at that step and returns CASV_OK (the other
+ * rows are untouched); mode 1 reports the same, ends the line there and returns CASV_ERR_NAN if that is before the line's '\n'
+ * (the outputs are filled either way). */
 int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S,
                        int32_t* out_idx, float* out_prob, int32_t* out_len, float* out_align);
 
