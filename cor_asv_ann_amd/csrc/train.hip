@@ -9,6 +9,17 @@
 // data GEMM through the recurrent part; input gradients and all weight gradients are big GEMMs over
 // the whole sequence (operands transposed by a bandwidth-bound kernel).  Adam and the global-norm clip
 // run on these packed tensors; Keras layouts exist only at set/get time.
+//
+// casv_train_step fills the step's view (Step) and makes at most two attempts (train_attempt); an attempt is these phases, in order:
+//   1 plan_buffers     every buffer large enough for the step's shapes, the layers' output places
+//   2 stage_inputs     batch, masks, segments on the device; sums, counters, gradients cleared; the per-step state reset
+//   3 forward_layers   encoder stack beside the decoder layers below the cell; final states, bridges, u
+//   4 forward_cell     attention cell
+//   5 loss_head        projection, softmax cross-entropy (training: dL/dlogits)        -- give-up check; mode 0 ends here
+//   6 backward_cell    tied projection, attention cell, the cell's and the attention's parameters
+//   7 backward_layers  decoder / encoder pairs downwards, embedding                    -- give-up check
+//   8 update           regulariser, norm, clipped Adam, results
+// persist_slot is the one place that decides whether a recurrence goes persistent; persist_launched the one that counts it.
 #include "engine.h"
 #include "train_kernels.h"
 
@@ -29,6 +40,8 @@ struct TLayer {
 
 }  // namespace
 
+constexpr int REC_LAUNCH_CAP = 16;         // persistent launches of one train step: the slots of rec_cnt, the words of rec_abort
+
 struct TrainState {
     casv_adam_params ap{};
     long step = 0;
@@ -44,7 +57,7 @@ struct TrainState {
     DevBuf hbr, cbr, brtmp, Ytop;          // [D][B][W] bridged final states; scratch [B][W]; residual_connections: top output + its input [U*B][W]
     int B = 0, T = 0, U = 0, A = 0;
     DevBuf e_idx, e_val, d_in, d_out, d_w, m_enc, m_dec, m_cell;
-    DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, prev, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, HP, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
+    DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
     std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])
     std::vector<DevBuf> XD;                // deep_bidirectional_encoder: layer n's input = the cross sum of O[n-1] (seq2seq.py:246-259)
     DevBuf loss, normsq;
@@ -55,7 +68,7 @@ struct TrainState {
     DevBuf tn_ws, sum_parts, seg_enc_off, seg_enc_pos, seg_dec_off, seg_dec_pos;
     std::vector<int> h_seg_enc_off, h_seg_enc_pos, h_seg_dec_off, h_seg_dec_pos;
     DevBuf rec_cnt; int rec_launches = 0, rec_checked = 0, rec_skip = 0, rec_penalty = 0;   // persistent recurrences: counters per launch, back-off
-    const unsigned* rec_abort[16] = {nullptr};    // ... and where each launch leaves its "gave up" word
+    const unsigned* rec_abort[REC_LAUNCH_CAP] = {nullptr};    // ... and where each launch leaves its "gave up" word
     // The attention cell's backward recurrence as TWO launches side by side (train_persist_topb.hip, split_a): the second stream and
     // the events that tie it into the step; split_off: a step gave up with the two launches in flight -- one launch from then on.
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool split_off = false; int split_launch = -1;
@@ -63,6 +76,27 @@ struct TrainState {
     float* W_(int i) { return tens[i].w.as<float>(); }
     float* G_(int i) { return tens[i].g.as<float>(); }
 };
+
+// The one place that decides whether a recurrence of the step goes persistent: the hand-off counters of the step's next persistent
+// launch, or nullptr -- the option is off, the step is deterministic, the back-off holds (rec_skip), the step has had its
+// REC_LAUNCH_CAP launches or the device is too small.  (The caller still asks its own kind's *_grid whether the shape has a form.)
+// Every launch takes one slot of rec_cnt, and the slots are of one size whatever the kind of launch: the largest of the four
+// kinds' counters (the backward recurrence's: 16 per 32-row block against 12, 3 and 2).  The give-up word sits inside the
+// slot at the END OF THE KIND'S OWN counters (persist_host.h), which is why persist_launched takes that kind's size.
+static size_t persist_slot_bytes(int B) {
+    return std::max(std::max(train_recurrence_counter_bytes(B), train_recurrence_bwd_counter_bytes(B)),
+                    std::max(train_attention_cell_counter_bytes(B), train_attention_cell_bwd_counter_bytes(B)));
+}
+static unsigned* persist_slot(casv_model* m, TrainState* ts) {
+    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < REC_LAUNCH_CAP && m->ncu >= 64) {
+        return reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + persist_slot_bytes(ts->B) * ts->rec_launches);
+    }
+    return nullptr;
+}
+// ... and the launch into that slot has been issued: where it leaves its "gave up" word, for recurrences_gave_up
+static void persist_launched(TrainState* ts, unsigned* slot, size_t counter_bytes) {
+    ts->rec_abort[ts->rec_launches++] = persist_give_up_word(slot, counter_bytes);
+}
 
 static int gate_row(int W, int u, int g) { return (u / 32) * 128 + g * 32 + (u % 32); }
 
@@ -128,8 +162,8 @@ int casv_train_release(casv_model* m) {
     for (auto& b : ts->bridge) b.kn.release();
     for (DevBuf* b : {&ts->hbr, &ts->cbr, &ts->brtmp, &ts->Ytop}) b->release();
     DevBuf* bufs[] = {&ts->ETp, &ts->WaN, &ts->UaN, &ts->e_idx, &ts->e_val, &ts->d_in, &ts->d_out, &ts->d_w, &ts->m_enc, &ts->m_dec,
-        &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn, &ts->prev,
-        &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->HP, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
+        &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn,
+        &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
         &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
         &ts->seg_dec_pos};
     for (DevBuf* b : bufs) b->release();
@@ -397,7 +431,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
         maxlen = std::max(maxlen, a[j].l->len);
     }
     bool persistent = false;
-    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (unsigned* slot = persist_slot(m, ts)) {
         RecBwdArgs ra{};
         ra.njobs = count; ra.B = B; ra.W = W;
         bool plain = true;
@@ -407,8 +441,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
             ra.job[j] = RecBwdJob{l.wrT.as<float>(), a[j].dOut, a[j].ld_out, a[j].mask, a[j].dh_fin, a[j].dc_fin, l.Gt.as<float>(), l.Cs.as<float>(), a[j].c0,
                                   l.Z.as<float>(), l.dRec.as<float>(), a[j].dc, l.len, l.reverse ? 1 : 0};
         }
-        const size_t cb = train_recurrence_bwd_counter_bytes(B);
-        ra.counters = reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + cb * ts->rec_launches);
+        ra.counters = slot;
         const int grid = plain ? train_recurrence_bwd_grid(ra, m->ncu) : 0;
         if (grid) {
             hipEvent_t ev{};
@@ -417,7 +450,7 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
             m->prof_begin(PC_PERSIST, flops, 0.0, ev);
             launch_train_recurrence_bwd(ra, grid, m->stream);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, cb);
+            persist_launched(ts, slot, train_recurrence_bwd_counter_bytes(B));
             persistent = true;
         }
     }
@@ -477,7 +510,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
     const int W = m->W, B = ts->B;
     int maxlen = 0;
     for (int j = 0; j < count; ++j) maxlen = std::max(maxlen, a[j].l->len);
-    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (unsigned* slot = persist_slot(m, ts)) {
         RecArgs ra{};
         ra.njobs = count; ra.B = B; ra.W = W;
         for (int j = 0; j < count; ++j) {
@@ -485,8 +518,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
             ra.job[j] = RecJob{ts->W_(l.iwr), l.Z.as<float>(), l.hs, l.hs_ld, l.Cs.as<float>(), l.Gt.as<float>(), a[j].h0, a[j].c0, l.len,
                                l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr};
         }
-        const size_t cb = train_recurrence_bwd_counter_bytes(B);        // (one slot size for both kinds of launch)
-        ra.counters = reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + cb * ts->rec_launches);
+        ra.counters = slot;
         ra.fault = m->persist_mode == 2;       // (test of the give-up path)
         if (const int grid = train_recurrence_grid(ra, m->ncu)) {
             hipEvent_t ev{};
@@ -495,7 +527,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
             m->prof_begin(PC_PERSIST, flops, 0.0, ev);
             launch_train_recurrence(ra, grid, m->stream);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_recurrence_counter_bytes(B));
+            persist_launched(ts, slot, train_recurrence_counter_bytes(B));
             if (masked) *masked = true;
             for (int j = 0; j < count; ++j) a[j].l->drec_cleared = a[j].l->kr == W;
             return 0;
@@ -510,37 +542,56 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
     return 0;
 }
 
-extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
-                               const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
-                               const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
-                               double* loss_out, double* norm_out) {
-    if (!m || !enc_idx || !dec_in || !dec_out || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
-    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
-    if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
-    HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
-    TrainState* ts = m->train;
-    hipStream_t st = m->stream;
-    const int W = m->W, V = m->V, Vp = m->Vp, C = m->C, D = m->D;
-    const long long TB = (long long)T * B, UB = (long long)U * B;
-    ts->B = B; ts->T = T; ts->U = U; ts->A = A;
-    m->encoded = false;                    // the final-state buffers are shared with the inference session
-    const bool training = mode != 0;
+// One attempt's view of the step: what the caller passed, the model's shapes, the step's flags, and what one phase leaves for the
+// next.  casv_train_step fills the first three groups once; every attempt starts from a copy and its phases fill in the rest.
+struct Step {
+    casv_model* m; TrainState* ts; hipStream_t st;
+    int mode, B, T, U, A;
+    const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
+    const float* mask_enc; const float* mask_dec; const float* mask_cell;
+    int W, V, Vp, C, D;
+    long long TB, UB;
     // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent
     // recurrence, hence no give-up fallback; no fused backward step), no split-K in the launcher, the K-major contractions'
     // shares added in order, the workgroups' loss / norm parts added by one ordered pass, the embedding gradient per character
-    const bool det = m->deterministic, fused = m->fused_backward && !det;
-    OrderedScope ordered(det);
+    bool training, det, fused, deep, residual, bridged;
+    // plan_buffers: the encoder's final states [n-1][B][W], the decoder's initial states (the bridged ones with bridge_dense), the
+    // gradients w.r.t. the final states [n-1][0|1][B][W], the ordered sums' parts (deterministic only)
+    float* hfin; float* cfin; const float* h0base; const float* c0base; float* dfin; double* parts;
+    // stage_inputs: the dropout masks on the device (nullptr: none) -- enc = 2W + (D-1)*W floats (deep: D * 2W), dec = (D-1)*W floats,
+    // cell = B*(W+C) -- and 1 / the number of weighted targets
+    const float* menc; const float* mdec; const float* mcell; float inv_count;
+    // forward_layers: the cell's input sequence (decoder layer D - 1's masked outputs, Y0 when D == 1) and the attended sequence O[D]
+    const float* y; const float* enc_out;
+    // loss_head: the projection's input
+    const float* proj_in; long long proj_ld;
 
-    // ---- buffers ----
+    const float* menc_n(int n) const { return menc ? menc + (n == 1 ? 0 : deep ? (n - 1) * 2 * W : 2 * W + (n - 2) * W) : nullptr; }   // layer n (1-based)
+    const float* mdec_n(int n) const { return mdec ? mdec + (n - 1) * W : nullptr; }
+    TLayer& enc_layer(int n) const { return ts->layers[n]; }            // n >= 2 -> index n (not with a deep bidirectional encoder)
+    TLayer& enc_dir(int n, int dir) const { return ts->layers[2 * (n - 1) + dir]; }      // deep: layer n = 1..D, direction 0 fw / 1 bw
+    TLayer& dec_layer(int n) const { return ts->layers[(deep ? 2 * D - 1 : D) + n]; }    // n = 1..D
+    TLayer& top() const { return dec_layer(D); }                        // the attention cell
+    const float* dec_h0(int n) const { return h0base + (size_t)(n - 1) * B * W; }        // decoder layer n starts from encoder layer n's final state
+    const float* dec_c0(int n) const { return c0base + (size_t)(n - 1) * B * W; }
+    float* dfin_h(int n) const { return dfin + (size_t)(2 * (n - 1)) * B * W; }
+    float* dfin_c(int n) const { return dfin + (size_t)(2 * (n - 1) + 1) * B * W; }
+    bool res_top() const { return residual && D >= 2; }                 // the projection reads the cell's outputs PLUS its input sequence
+};
+
+// Phase 1 leaves every buffer of the session at least as large as this step's shapes ask, every layer's len / hs / hs_ld, and the
+// view's pointers into the state buffers (read behind the calls that may have moved them).
+static int plan_buffers(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts;
+    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
+    const long long TB = s.TB, UB = s.UB;
+    const bool deep = s.deep;
 #define ENS(buf, bytes) if (int rc_ = (buf).ensure(bytes)) return rc_;
     ENS(ts->e_idx, TB * A * 4) ENS(ts->e_val, TB * A * 4) ENS(ts->d_in, UB * 4) ENS(ts->d_out, UB * 4) ENS(ts->d_w, UB * 4)
-    const bool deep = m->cfg.deep_bidirectional_encoder != 0 && D >= 2;
     ENS(ts->m_enc, (size_t)std::max(D + 1, 2 * D) * W * 4) ENS(ts->m_dec, (size_t)D * W * 4) ENS(ts->m_cell, (size_t)B * (W + C) * 4)
     ENS(ts->X0, TB * W * 4) ENS(ts->H1, TB * 2 * W * 4) ENS(ts->u, TB * W * 4) ENS(ts->Y0, UB * W * 4) ENS(ts->Ym, UB * W * 4)
     ENS(ts->WQ, UB * W * 4) ENS(ts->Ast, (size_t)(U + 1) * B * T * 4) ENS(ts->WIN, UB * 4)
-    ENS(ts->RecIn, UB * (C + W) * 4) ENS(ts->prev, (size_t)B * 4) ENS(ts->logits, UB * Vp * 4)
+    ENS(ts->RecIn, UB * (C + W) * 4) ENS(ts->logits, UB * Vp * 4)
     ENS(ts->dG, UB * W * 4) ENS(ts->d_enc, TB * C * 4) ENS(ts->du, TB * W * 4) ENS(ts->DWQ, UB * W * 4) ENS(ts->DSrows, UB * 16 * 4) ENS(ts->dhatt, UB * W * 4)
     ENS(ts->dfin, (size_t)2 * D * B * W * 4) ENS(ts->dcbuf, (size_t)B * W * 4)
     ENS(ts->dX0, TB * W * 4) ENS(ts->dXtop, UB * W * 4) ENS(ts->dXl, TB * 2 * W * 4) ENS(ts->dYl, UB * W * 4) ENS(ts->dOin, TB * 2 * W * 4)
@@ -556,103 +607,117 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         else if (deep && enc) { l.hs = (&l - 1)->hs + W; l.hs_ld = 2 * W; }        // (a backward direction: the second half of its forward partner's rows)
         else { ENS(l.Hown, rows * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = W; }
     }
-    ENS(ts->rec_cnt, 16 * train_recurrence_bwd_counter_bytes(B)) ENS(ts->dcalt, (size_t)2 * B * W * 4)
-    if (det) {
+    ENS(ts->rec_cnt, REC_LAUNCH_CAP * persist_slot_bytes(B)) ENS(ts->dcalt, (size_t)2 * B * W * 4)
+    if (s.det) {
         ENS(ts->sum_parts, (size_t)std::max(MULTI_MAX * 64, (W + 63) / 64 + V) * 8)
         ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
     }
-    const bool residual = m->cfg.residual_connections != 0, bridged = m->cfg.bridge_dense != 0;
-    if (bridged) { ENS(ts->hbr, (size_t)D * B * W * 4) ENS(ts->cbr, (size_t)D * B * W * 4) ENS(ts->brtmp, (size_t)B * W * 4) }
-    if (residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
+    if (s.bridged) { ENS(ts->hbr, (size_t)D * B * W * 4) ENS(ts->cbr, (size_t)D * B * W * 4) ENS(ts->brtmp, (size_t)B * W * 4) }
+    if (s.residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
     for (int n = 1; n <= D; ++n) ENS(ts->O[n], TB * ((n == 1 || deep) ? 2 * W : W) * 4)
     for (int n = 2; n <= D && deep; ++n) ENS(ts->XD[n], TB * 2 * W * 4)
     for (int n = 1; n < D; ++n) ENS(ts->DO[n], UB * W * 4)
+    ENS(m->hfin, (size_t)D * B * W * 4) ENS(m->cfin, (size_t)(D + 1) * B * W * 4)       // (shared with the inference session)
 #undef ENS
-    // ---- inputs ----
-    HIPCHK(hipMemcpyAsync(ts->e_idx.p, enc_idx, TB * A * 4, hipMemcpyHostToDevice, st));
-    if (enc_val) HIPCHK(hipMemcpyAsync(ts->e_val.p, enc_val, TB * A * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ts->d_in.p, dec_in, UB * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ts->d_out.p, dec_out, UB * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ts->d_w.p, weights, UB * 4, hipMemcpyHostToDevice, st));
-    double* parts = det ? ts->sum_parts.as<double>() : nullptr;
-    if (det) {
-        // per-character segments of the index arrays, positions in (t, b, k) order within a character (counting sort on the host)
-        auto segments = [&](const int32_t* idx, int L, int A_, std::vector<int>& off, std::vector<int>& pos) {
-            off.assign(V + 2, 0);
-            for (long long q = 0; q < (long long)B * L * A_; ++q) if (idx[q] >= 0 && idx[q] < V) ++off[idx[q] + 2];
-            for (int v = 0; v < V; ++v) off[v + 2] += off[v + 1];
-            pos.resize(std::max<size_t>(1, off[V + 1]));
-            for (int t = 0; t < L; ++t)
-                for (int b = 0; b < B; ++b)
-                    for (int k = 0; k < A_; ++k) {
-                        const long long q = ((long long)b * L + t) * A_ + k;
-                        if (idx[q] >= 0 && idx[q] < V) pos[off[idx[q] + 1]++] = (int)q;
-                    }
-            off.pop_back();             // off[v] = first position of character v, off[V] = count
-        };
-        segments(enc_idx, T, A, ts->h_seg_enc_off, ts->h_seg_enc_pos);
-        segments(dec_in, U, 1, ts->h_seg_dec_off, ts->h_seg_dec_pos);
+    s.hfin = m->hfin.as<float>(); s.cfin = m->cfin.as<float>();
+    // bridge_dense (seq2seq.py:299-301): the decoder starts from tanh(state . K + b) of every encoder layer's final h and c
+    s.h0base = s.bridged ? ts->hbr.as<float>() : s.hfin; s.c0base = s.bridged ? ts->cbr.as<float>() : s.cfin;
+    s.dfin = ts->dfin.as<float>();
+    s.parts = s.det ? ts->sum_parts.as<double>() : nullptr;
+    return 0;
+}
+
+// per-character segments of an index array [B][L][A_], positions in (t, b, k) order within a character (counting sort on the host)
+static void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::vector<int>& off, std::vector<int>& pos) {
+    off.assign(V + 2, 0);
+    for (long long q = 0; q < (long long)B * L * A_; ++q) if (idx[q] >= 0 && idx[q] < V) ++off[idx[q] + 2];
+    for (int v = 0; v < V; ++v) off[v + 2] += off[v + 1];
+    pos.resize(std::max<size_t>(1, off[V + 1]));
+    for (int t = 0; t < L; ++t)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < A_; ++k) {
+                const long long q = ((long long)b * L + t) * A_ + k;
+                if (idx[q] >= 0 && idx[q] < V) pos[off[idx[q] + 1]++] = (int)q;
+            }
+    off.pop_back();             // off[v] = first position of character v, off[V] = count
+}
+
+// Phase 2 leaves the batch, the masks and (deterministic) the characters' segments on the device, the step's sums, hand-off counters
+// and (training) gradients cleared, and the session's per-step state reset.
+static int stage_inputs(Step& s) {
+    TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;
+    const long long TB = s.TB, UB = s.UB;
+    HIPCHK(hipMemcpyAsync(ts->e_idx.p, s.enc_idx, TB * A * 4, hipMemcpyHostToDevice, st));
+    if (s.enc_val) HIPCHK(hipMemcpyAsync(ts->e_val.p, s.enc_val, TB * A * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ts->d_in.p, s.dec_in, UB * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ts->d_out.p, s.dec_out, UB * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ts->d_w.p, s.weights, UB * 4, hipMemcpyHostToDevice, st));
+    if (s.det) {
+        char_segments(s.enc_idx, B, T, A, V, ts->h_seg_enc_off, ts->h_seg_enc_pos);
+        char_segments(s.dec_in, B, U, 1, V, ts->h_seg_dec_off, ts->h_seg_dec_pos);
         HIPCHK(hipMemcpyAsync(ts->seg_enc_off.p, ts->h_seg_enc_off.data(), (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ts->seg_enc_pos.p, ts->h_seg_enc_pos.data(), ts->h_seg_enc_pos.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ts->seg_dec_off.p, ts->h_seg_dec_off.data(), (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ts->seg_dec_pos.p, ts->h_seg_dec_pos.data(), ts->h_seg_dec_pos.size() * 4, hipMemcpyHostToDevice, st));
     }
-    // masks: enc = 2W + (D-1)*W floats, dec = (D-1)*W floats, cell = B*(W+C)
-    const float* menc = nullptr; const float* mdec = nullptr; const float* mcell = nullptr;
-    if (mask_enc) { HIPCHK(hipMemcpyAsync(ts->m_enc.p, mask_enc, (size_t)(deep ? 2 * D : D + 1) * W * 4, hipMemcpyHostToDevice, st)); menc = ts->m_enc.as<float>(); }
-    if (mask_dec && D > 1) { HIPCHK(hipMemcpyAsync(ts->m_dec.p, mask_dec, (size_t)(D - 1) * W * 4, hipMemcpyHostToDevice, st)); mdec = ts->m_dec.as<float>(); }
-    if (mask_cell) { HIPCHK(hipMemcpyAsync(ts->m_cell.p, mask_cell, (size_t)B * (W + C) * 4, hipMemcpyHostToDevice, st)); mcell = ts->m_cell.as<float>(); }
-    auto menc_n = [&](int n) { return menc ? menc + (n == 1 ? 0 : deep ? (n - 1) * 2 * W : 2 * W + (n - 2) * W) : nullptr; };   // layer n (1-based)
-    auto mdec_n = [&](int n) { return mdec ? mdec + (n - 1) * W : nullptr; };
+    s.menc = s.mdec = s.mcell = nullptr;
+    if (s.mask_enc) { HIPCHK(hipMemcpyAsync(ts->m_enc.p, s.mask_enc, (size_t)(s.deep ? 2 * D : D + 1) * W * 4, hipMemcpyHostToDevice, st)); s.menc = ts->m_enc.as<float>(); }
+    if (s.mask_dec && D > 1) { HIPCHK(hipMemcpyAsync(ts->m_dec.p, s.mask_dec, (size_t)(D - 1) * W * 4, hipMemcpyHostToDevice, st)); s.mdec = ts->m_dec.as<float>(); }
+    if (s.mask_cell) { HIPCHK(hipMemcpyAsync(ts->m_cell.p, s.mask_cell, (size_t)B * (W + C) * 4, hipMemcpyHostToDevice, st)); s.mcell = ts->m_cell.as<float>(); }
     long cnt = 0;
-    for (long long i = 0; i < UB; ++i) cnt += weights[i] != 0.f;
-    const float inv_count = 1.0f / (float)std::max(cnt, 1L);
+    for (long long i = 0; i < UB; ++i) cnt += s.weights[i] != 0.f;
+    s.inv_count = 1.0f / (float)std::max(cnt, 1L);
     HIPCHK(hipMemsetAsync(ts->loss.p, 0, 16, st));
     HIPCHK(hipMemsetAsync(ts->normsq.p, 0, 16, st));
-    HIPCHK(hipMemsetAsync(ts->rec_cnt.p, 0, 16 * train_recurrence_bwd_counter_bytes(B), st));
+    HIPCHK(hipMemsetAsync(ts->rec_cnt.p, 0, REC_LAUNCH_CAP * persist_slot_bytes(B), st));
     ts->rec_launches = ts->rec_checked = 0; ts->split_launch = -1; ts->tn_ws_rc = 0;
     for (auto& l : ts->layers) l.drec_cleared = false;
     if (ts->rec_skip > 0) --ts->rec_skip;
-    if (training) for (auto& t : ts->tens) HIPCHK(hipMemsetAsync(t.g.p, 0, t.n * 4, st));
+    if (s.training) for (auto& t : ts->tens) HIPCHK(hipMemsetAsync(t.g.p, 0, t.n * 4, st));
+    return 0;
+}
 
+// bridge_dense forward of encoder layer n (1-based): hfin / cfin slot n - 1 -> hbr / cbr slot n - 1
+static void bridge_forward(Step& s, int n) {
+    if (!s.bridged) return;
+    casv_model* m = s.m; TrainState* ts = s.ts;
+    const int B = s.B, W = s.W;
+    for (int s_ = 0; s_ < 2; ++s_) {
+        const TrainState::Bridge& br = ts->bridge[2 * (n - 1) + s_];
+        const float* src = (s_ ? s.cfin : s.hfin) + (size_t)(n - 1) * B * W;
+        float* dst = (s_ ? ts->cbr.as<float>() : ts->hbr.as<float>()) + (size_t)(n - 1) * B * W;
+        GemmArgs g = plain_gemm(src, W, B, W, ts->W_(br.ikt), W, ts->W_(br.ib), ts->brtmp.as<float>(), W);
+        g.ksplit = 0; g.kgroups = 0;            // (one k-ordered chain per element, no atomics into an uncleared buffer)
+        run_gemm(m, EPI_PLAIN, g);
+        launch_tanh(ts->brtmp.as<float>(), dst, (long long)B * W, s.st);
+    }
+}
+
+// Phase 3 leaves every encoder layer's and every decoder layer's below the cell outputs, cell states and gates, the masked outputs
+// O[n] / DO[n], the final states (and the bridged ones), the cell's input sequence s.y, the attended sequence s.enc_out and its
+// projection u.
+static int forward_layers(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;
+    const long long TB = s.TB, UB = s.UB;
+    const bool deep = s.deep, residual = s.residual;
+    float* hfin = s.hfin; float* cfin = s.cfin;
     TLayer* Lfw = &ts->layers[0]; TLayer* Lbw = &ts->layers[1];
-    auto enc_layer = [&](int n) -> TLayer& { return ts->layers[n]; };            // n >= 2 -> index n (not with a deep bidirectional encoder)
-    auto enc_dir = [&](int n, int dir) -> TLayer& { return ts->layers[2 * (n - 1) + dir]; };      // deep: layer n = 1..D, direction 0 fw / 1 bw
-    auto dec_layer = [&](int n) -> TLayer& { return ts->layers[(deep ? 2 * D - 1 : D) + n]; };    // n = 1..D
-    float* hfin = m->hfin.as<float>(); float* cfin = m->cfin.as<float>();
-    if (int rc = m->hfin.ensure((size_t)D * B * W * 4)) return rc;
-    if (int rc = m->cfin.ensure((size_t)(D + 1) * B * W * 4)) return rc;
-    hfin = m->hfin.as<float>(); cfin = m->cfin.as<float>();
-
-    // ================= forward: encoder =================
-    launch_embed_tm(ts->W_(ts->iE), ts->e_idx.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr, ts->X0.as<float>(), B, T, A, V, W, st);
+    launch_embed_tm(ts->W_(ts->iE), ts->e_idx.as<int>(), s.enc_val ? ts->e_val.as<float>() : nullptr, ts->X0.as<float>(), B, T, A, V, W, st);
     layer_input_gemm(m, *Lfw, ts->X0.as<float>(), W);
     layer_input_gemm(m, *Lbw, ts->X0.as<float>(), W);
     bool masked1 = false;
     {
-        const LayerFwd f[2] = {{Lfw, nullptr, nullptr, ts->O[1].as<float>(), 2 * W, menc_n(1)},
-                               {Lbw, nullptr, nullptr, ts->O[1].as<float>() + W, 2 * W, menc_n(1) ? menc_n(1) + W : nullptr}};
+        const LayerFwd f[2] = {{Lfw, nullptr, nullptr, ts->O[1].as<float>(), 2 * W, s.menc_n(1)},
+                               {Lbw, nullptr, nullptr, ts->O[1].as<float>() + W, 2 * W, s.menc_n(1) ? s.menc_n(1) + W : nullptr}};
         if (int rc = layers_forward(m, f, 2, &masked1)) return rc;
     }
     // final states handed to the decoder: layer 1 = backward direction after t = 0 (seq2seq.py:280)
     HIPCHK(hipMemcpy2DAsync(hfin, (size_t)W * 4, Lbw->hs, (size_t)2 * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(cfin, Lbw->Cs.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-    // bridge_dense (seq2seq.py:299-301): the decoder starts from tanh(state . K + b) of every encoder layer's final h and c
-    const float* h0base = bridged ? ts->hbr.as<float>() : hfin; const float* c0base = bridged ? ts->cbr.as<float>() : cfin;
-    auto bridge_forward = [&](int n) {              // encoder layer n (1-based): hfin / cfin slot n - 1 -> hbr / cbr slot n - 1
-        if (!bridged) return;
-        for (int s_ = 0; s_ < 2; ++s_) {
-            const TrainState::Bridge& br = ts->bridge[2 * (n - 1) + s_];
-            const float* src = (s_ ? cfin : hfin) + (size_t)(n - 1) * B * W;
-            float* dst = (s_ ? ts->cbr.as<float>() : ts->hbr.as<float>()) + (size_t)(n - 1) * B * W;
-            GemmArgs g = plain_gemm(src, W, B, W, ts->W_(br.ikt), W, ts->W_(br.ib), ts->brtmp.as<float>(), W);
-            g.ksplit = 0; g.kgroups = 0;            // (one k-ordered chain per element, no atomics into an uncleared buffer)
-            run_gemm(m, EPI_PLAIN, g);
-            launch_tanh(ts->brtmp.as<float>(), dst, (long long)B * W, st);
-        }
-    };
-    bridge_forward(1);
-    if (!masked1) launch_mul_mask(ts->H1.as<float>(), 2 * W, menc_n(1), ts->O[1].as<float>(), 2 * W, TB, 2 * W, st);
+    bridge_forward(s, 1);
+    if (!masked1) launch_mul_mask(ts->H1.as<float>(), 2 * W, s.menc_n(1), ts->O[1].as<float>(), 2 * W, TB, 2 * W, st);
     launch_embed_tm(ts->W_(ts->iE), ts->d_in.as<int>(), nullptr, ts->Y0.as<float>(), B, U, 1, V, W, st);
     // Encoder layer n and decoder layer n-1 depend only on encoder layer n-1 / decoder layer n-2, so the two
     // recurrences advance in lockstep, one launch per step for both.
@@ -660,93 +725,99 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     // deep_bidirectional_encoder (seq2seq.py:246-281): every encoder layer n >= 2 is a BiLSTM on the cross sum of the (dropped-out) layer
     // below; its two directions are the pair of a launch, the decoder layer n - 1 walks alone
     for (int n = 2; n <= D && deep; ++n) {
-        TLayer& lf = enc_dir(n, 0); TLayer& lb = enc_dir(n, 1); TLayer& ld = dec_layer(n - 1);
+        TLayer& lf = s.enc_dir(n, 0); TLayer& lb = s.enc_dir(n, 1); TLayer& ld = s.dec_layer(n - 1);
         launch_cross_sum(ts->O[n - 1].as<float>(), ts->XD[n].as<float>(), TB * 2 * W, st);
         layer_input_gemm(m, lf, ts->XD[n].as<float>(), 2 * W);
         layer_input_gemm(m, lb, ts->XD[n].as<float>(), 2 * W);
         layer_input_gemm(m, ld, y, W);
         bool maskede = false, maskedd = false;
         {
-            const LayerFwd f[2] = {{&lf, nullptr, nullptr, ts->O[n].as<float>(), 2 * W, menc_n(n)},
-                                   {&lb, nullptr, nullptr, ts->O[n].as<float>() + W, 2 * W, menc_n(n) ? menc_n(n) + W : nullptr}};
+            const LayerFwd f[2] = {{&lf, nullptr, nullptr, ts->O[n].as<float>(), 2 * W, s.menc_n(n)},
+                                   {&lb, nullptr, nullptr, ts->O[n].as<float>() + W, 2 * W, s.menc_n(n) ? s.menc_n(n) + W : nullptr}};
             if (int rc = layers_forward(m, f, 2, &maskede)) return rc;
         }
         HIPCHK(hipMemcpy2DAsync(hfin + (size_t)(n - 1) * B * W, (size_t)W * 4, lb.hs, (size_t)2 * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * B * W, lb.Cs.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-        bridge_forward(n);
-        if (!maskede) launch_mul_mask(lf.hs, 2 * W, menc_n(n), ts->O[n].as<float>(), 2 * W, TB, 2 * W, st);
-        const float* h0 = h0base + (size_t)(n - 2) * B * W; const float* c0 = c0base + (size_t)(n - 2) * B * W;
+        bridge_forward(s, n);
+        if (!maskede) launch_mul_mask(lf.hs, 2 * W, s.menc_n(n), ts->O[n].as<float>(), 2 * W, TB, 2 * W, st);
         const bool res_n = residual && n >= 3;
         {
-            const LayerFwd f[1] = {{&ld, h0, c0, res_n ? nullptr : ts->DO[n - 1].as<float>(), W, mdec_n(n - 1)}};
+            const LayerFwd f[1] = {{&ld, s.dec_h0(n - 1), s.dec_c0(n - 1), res_n ? nullptr : ts->DO[n - 1].as<float>(), W, s.mdec_n(n - 1)}};
             if (int rc = layers_forward(m, f, 1, &maskedd)) return rc;
         }
-        if (res_n) launch_add_mul_mask(ld.hs, W, y, W, mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
-        else if (!maskedd) launch_mul_mask(ld.hs, W, mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
+        if (res_n) launch_add_mul_mask(ld.hs, W, y, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
+        else if (!maskedd) launch_mul_mask(ld.hs, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
         y = ts->DO[n - 1].as<float>();
     }
     for (int n = 2; n <= D && !deep; ++n) {
-        TLayer& le = enc_layer(n);
-        TLayer& ld = dec_layer(n - 1);
+        TLayer& le = s.enc_layer(n);
+        TLayer& ld = s.dec_layer(n - 1);
         layer_input_gemm(m, le, ts->O[n - 1].as<float>(), le.kx);
         layer_input_gemm(m, ld, y, W);
-        const float* h0 = h0base + (size_t)(n - 2) * B * W; const float* c0 = c0base + (size_t)(n - 2) * B * W;
         // residual_connections: encoder layer n >= 3 / decoder layer n - 1 >= 2 hand on LSTM output + input sequence (seq2seq.py:284-291,
         // 359-360) -- the sum and the next layer's dropout mask in one pass behind the recurrences (which then write no masked copy)
         const bool res_n = residual && n >= 3;
         bool maskedn = false;
         {
-            const LayerFwd f[2] = {{&le, nullptr, nullptr, res_n ? nullptr : ts->O[n].as<float>(), W, menc_n(n)},
-                                   {&ld, h0, c0, res_n ? nullptr : ts->DO[n - 1].as<float>(), W, mdec_n(n - 1)}};
+            const LayerFwd f[2] = {{&le, nullptr, nullptr, res_n ? nullptr : ts->O[n].as<float>(), W, s.menc_n(n)},
+                                   {&ld, s.dec_h0(n - 1), s.dec_c0(n - 1), res_n ? nullptr : ts->DO[n - 1].as<float>(), W, s.mdec_n(n - 1)}};
             if (int rc = layers_forward(m, f, 2, &maskedn)) return rc;
         }
         HIPCHK(hipMemcpyAsync(hfin + (size_t)(n - 1) * B * W, le.hs + (long long)(T - 1) * B * W, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * B * W, le.Cs.as<float>() + (long long)(T - 1) * B * W, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-        bridge_forward(n);
+        bridge_forward(s, n);
         if (res_n) {
-            launch_add_mul_mask(le.hs, W, ts->O[n - 1].as<float>(), W, menc_n(n), ts->O[n].as<float>(), W, TB, W, st);
-            launch_add_mul_mask(ld.hs, W, y, W, mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
+            launch_add_mul_mask(le.hs, W, ts->O[n - 1].as<float>(), W, s.menc_n(n), ts->O[n].as<float>(), W, TB, W, st);
+            launch_add_mul_mask(ld.hs, W, y, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
         } else if (!maskedn) {
-            launch_mul_mask(le.hs, W, menc_n(n), ts->O[n].as<float>(), W, TB, W, st);
-            launch_mul_mask(ld.hs, W, mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
+            launch_mul_mask(le.hs, W, s.menc_n(n), ts->O[n].as<float>(), W, TB, W, st);
+            launch_mul_mask(ld.hs, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
         }
         y = ts->DO[n - 1].as<float>();
     }
-    const float* enc_out = ts->O[D].as<float>();
-    { GemmArgs g = plain_gemm(enc_out, C, (int)TB, C, ts->W_(ts->iUT), W, nullptr, ts->u.as<float>(), W); run_plain(m, g); }
+    s.y = y;
+    s.enc_out = ts->O[D].as<float>();
+    { GemmArgs g = plain_gemm(s.enc_out, C, (int)TB, C, ts->W_(ts->iUT), W, nullptr, ts->u.as<float>(), W); run_plain(m, g); }
+    return 0;
+}
 
-    // ================= forward: attention cell =================
-    TLayer& top = dec_layer(D);
-    launch_mul_rowmask(y, W, mcell, W + C, ts->Ym.as<float>(), W, UB, B, W, st);
+// Phase 4 leaves the attention cell's outputs, cell states and gates, its input rows RecIn, the queries WQ, the attention rows Ast
+// and the windows WIN of every step.
+static int forward_cell(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, W = s.W, C = s.C, D = s.D;
+    const long long UB = s.UB;
+    const float* mcell = s.mcell;
+    TLayer& top = s.top();
+    launch_mul_rowmask(s.y, W, mcell, W + C, ts->Ym.as<float>(), W, UB, B, W, st);
     layer_input_gemm(m, top, ts->Ym.as<float>(), W);
-    const float* h0t = h0base + (size_t)(D - 1) * B * W; const float* c0t = c0base + (size_t)(D - 1) * B * W;
+    const float* h0t = s.dec_h0(D); const float* c0t = s.dec_c0(D);
     HIPCHK(hipMemsetAsync(ts->Ast.p, 0, (size_t)B * T * 4, st));
     // The cell's input rows [ctx * mask | h(t-1)] (LSTMCell(dropout) masks the cell input [y | ctx] per sample, seq2seq.py:345; the y
     // part is masked where it is precomputed) are filled where their parts are produced: the attention rows write the masked
     // context straight into them, the cell of the step before stores its h a second time.
     HIPCHK(hipMemcpy2DAsync(ts->RecIn.as<float>() + C, (size_t)(C + W) * 4, h0t, (size_t)W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
     AttnArgs att{};         // what every step's attention rows share
-    att.u = ts->u.as<float>(); att.enc = enc_out; att.va = ts->W_(ts->iva); att.bv = ts->W_(ts->ibv);
+    att.u = ts->u.as<float>(); att.enc = s.enc_out; att.va = ts->W_(ts->iva); att.bv = ts->W_(ts->ibv);
     att.a_base = ts->Ast.as<float>(); att.prev = nullptr; att.line = nullptr; att.rows_per_line = 1;
     att.ctx_ld = C + W; att.ctx_mask = mcell ? mcell + W : nullptr; att.ctx_mask_ld = W + C;
     att.R = B; att.T = T; att.W = W; att.C = C; att.window = m->cfg.window_width;
     att.apos = nullptr; att.amax1 = nullptr; att.nrows = nullptr;
     att.u_line = W; att.u_time = (long long)B * W; att.enc_line = C; att.enc_time = (long long)B * C;
     bool top_persistent = false;
-    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
+    if (unsigned* slot = persist_slot(m, ts)) {
         // ONE launch for the whole recurrence of the cell (train_persist_top.hip)
         TopRecArgs ra{};
         ra.Wr = ts->W_(top.iwr); ra.WaT = ts->W_(ts->iWaT); ra.bUW = ts->W_(ts->ibUW); ra.Z = top.Z.as<float>();
         ra.RecIn = ts->RecIn.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.hs = top.hs; ra.Cs = top.Cs.as<float>(); ra.Gt = top.Gt.as<float>();
         ra.c0 = c0t; ra.WIN = ts->WIN.as<int>(); ra.att = att; ra.B = B; ra.U = U; ra.W = W; ra.C = C;
-        const size_t cb = train_recurrence_bwd_counter_bytes(B);
-        ra.counters = reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + cb * ts->rec_launches);
+        ra.counters = slot;
         if (const int grid = top.hs_ld == W ? train_attention_cell_grid(ra, m->ncu) : 0) {
             hipEvent_t ev{};
             m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
             launch_train_attention_cell(ra, grid, st);
             m->prof_end(PC_PERSIST, ev);
-            ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_attention_cell_counter_bytes(B));
+            persist_launched(ts, slot, train_attention_cell_counter_bytes(B));
             top_persistent = true;
         }
     }
@@ -765,63 +836,213 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         if (t + 1 < U) g.out2 = mkslot(rec + (long long)B * (C + W) + C, C + W);
         run_gemm(m, EPI_LSTM, g);
     }
-    // ================= loss =================
-    // (residual_connections: the projection reads the cell's outputs PLUS the cell's input sequence, seq2seq.py:359-360 at the top layer)
-    const bool res_top = residual && D >= 2;
-    const float* proj_in = top.hs; long long proj_ld = W;
-    if (res_top) {
-        launch_add_mul_mask(top.hs, top.hs_ld, y, W, nullptr, ts->Ytop.as<float>(), W, UB, W, st);
-        proj_in = ts->Ytop.as<float>();
-    }
-    { GemmArgs g = plain_gemm(proj_in, proj_ld, (int)UB, W, ts->W_(ts->iE), V, nullptr, ts->logits.as<float>(), Vp); run_plain(m, g); }
-    launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, inv_count, ts->loss.as<double>(),
-                      training ? 1 : 0, st, parts);
-    // Did every persistent recurrence so far run to its end?  (A launch gives up when its workgroups wait too long for each
-    // other -- a GPU shared with another process: handoff.h.)  Nothing has been updated yet: start over with per-step launches,
-    // and keep to them for the next 16, 32, ... steps.  Asked after the forward pass and again in front of the update.
-    auto recurrences_gave_up = [&](bool& any) -> int {
-        any = false;
-        if (ts->rec_launches == ts->rec_checked) return 0;
-        unsigned gave_up[16] = {0};
-        for (int i = ts->rec_checked; i < ts->rec_launches; ++i)
-            HIPCHK(hipMemcpyAsync(&gave_up[i], ts->rec_abort[i], 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = ts->rec_checked; i < ts->rec_launches; ++i) {
-            any |= gave_up[i] != 0;
-            if (gave_up[i] && i == ts->split_launch && !ts->split_off) {        // (the two launches were not resident together: one launch from now on)
-                ts->split_off = true;
-                fprintf(stderr, "cor_asv_ann_hip: the two launches of the attention cell's backward were not resident together (serialised "
-                                "dispatch, or the GPU is shared): ONE launch from now on\n");
-            }
-        }
-        ts->rec_checked = ts->rec_launches;
-        if (any) {
-            ++m->stat_train_give_ups;           // (statistic "train_give_ups": the caller redoes the step)
-            ts->rec_penalty = ts->rec_penalty ? std::min(2 * ts->rec_penalty, 1 << 20) : 16;
-            ts->rec_skip = ts->rec_penalty + 1;
-            fprintf(stderr, "cor_asv_ann_hip: a persistent recurrence of the train step gave up waiting (is the GPU shared?); "
-                            "per-step launches for the next %d steps\n", ts->rec_penalty);
-        }
-        return 0;
-    };
-    {
-        bool any = false;
-        if (int rc = recurrences_gave_up(any)) return rc;
-        if (any) return casv_train_step(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, dec_out, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out);
-    }
-    if (!training) {                       // K.in_train_phase: the regulariser counts only in the train phase
-        HIPCHK(hipMemcpyAsync(loss_out, ts->loss.p, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (norm_out) *norm_out = 0.0;
-        m->stat_train_launches = ts->rec_launches;
-        return CASV_OK;
-    }
+    return 0;
+}
 
-    // ================= backward =================
+// Phase 5 leaves the projection's input s.proj_in, the step's cross-entropy in ts->loss and (training) dL/dlogits in place of the logits.
+static int loss_head(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, U = s.U, W = s.W, V = s.V, Vp = s.Vp;
+    const long long UB = s.UB;
+    TLayer& top = s.top();
+    // (residual_connections: the projection reads the cell's outputs PLUS the cell's input sequence, seq2seq.py:359-360 at the top layer)
+    s.proj_in = top.hs; s.proj_ld = W;
+    if (s.res_top()) {
+        launch_add_mul_mask(top.hs, top.hs_ld, s.y, W, nullptr, ts->Ytop.as<float>(), W, UB, W, st);
+        s.proj_in = ts->Ytop.as<float>();
+    }
+    { GemmArgs g = plain_gemm(s.proj_in, s.proj_ld, (int)UB, W, ts->W_(ts->iE), V, nullptr, ts->logits.as<float>(), Vp); run_plain(m, g); }
+    launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, s.inv_count, ts->loss.as<double>(),
+                      s.training ? 1 : 0, st, s.parts);
+    return 0;
+}
+
+// Did every persistent recurrence so far run to its end?  (A launch gives up when its workgroups wait too long for each
+// other -- a GPU shared with another process: handoff.h.)  Nothing has been updated yet: the caller starts over with per-step
+// launches, and keeps to them for the next 16, 32, ... steps.  Asked after the forward pass and again in front of the update.
+static int recurrences_gave_up(casv_model* m, bool& any) {
+    TrainState* ts = m->train; hipStream_t st = m->stream;
+    any = false;
+    if (ts->rec_launches == ts->rec_checked) return 0;
+    unsigned gave_up[REC_LAUNCH_CAP] = {0};
+    for (int i = ts->rec_checked; i < ts->rec_launches; ++i)
+        HIPCHK(hipMemcpyAsync(&gave_up[i], ts->rec_abort[i], 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = ts->rec_checked; i < ts->rec_launches; ++i) {
+        any |= gave_up[i] != 0;
+        if (gave_up[i] && i == ts->split_launch && !ts->split_off) {        // (the two launches were not resident together: one launch from now on)
+            ts->split_off = true;
+            fprintf(stderr, "cor_asv_ann_hip: the two launches of the attention cell's backward were not resident together (serialised "
+                            "dispatch, or the GPU is shared): ONE launch from now on\n");
+        }
+    }
+    ts->rec_checked = ts->rec_launches;
+    if (any) {
+        ++m->stat_train_give_ups;           // (statistic "train_give_ups": the caller redoes the step)
+        ts->rec_penalty = ts->rec_penalty ? std::min(2 * ts->rec_penalty, 1 << 20) : 16;
+        ts->rec_skip = ts->rec_penalty + 1;
+        fprintf(stderr, "cor_asv_ann_hip: a persistent recurrence of the train step gave up waiting (is the GPU shared?); "
+                        "per-step launches for the next %d steps\n", ts->rec_penalty);
+    }
+    return 0;
+}
+
+// CASV_ATTN_DEFER, read once: d_enc / du summed behind the cell's backward recurrence instead of by float atomics inside it
+// (attn_bwd.h, DEFER; the recurrence has forms 0, 1 and 3 only)
+static int attn_defer_option() {
+    static const int opt = [] { const char* e = getenv("CASV_ATTN_DEFER"); const int v = e ? atoi(e) : 1; return v == 3 ? 3 : v == 0 ? 0 : 1; }();
+    return opt;
+}
+
+// CASV_TOPB_SPLIT, read once: the attention backward of the samples as a launch of its own on a second stream, resident beside the
+// big one: it then runs under the h tiles instead of behind them (CASV_TOPB_SPLIT=0: one launch).
+// Two launches that hand rows to each other must be resident TOGETHER: where the runtime serialises kernel dispatch
+// (rocprofv3 --pmc sets ROCPROF_COUNTERS; AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING) the side launch would never see
+// the main one's counters -- one launch there, said once on stderr (profiles taken that way describe that form).
+static bool read_cell_bwd_split_option() {
+    const char* e = getenv("CASV_TOPB_SPLIT");
+    if (e && e[0] == '0') return false;
+    auto on = [](const char* name) { const char* v = getenv(name); return v && v[0] && !(v[0] == '0' && !v[1]); };
+    const char* why = getenv("ROCPROF_COUNTERS") ? "ROCPROF_COUNTERS (counter collection)" : on("AMD_SERIALIZE_KERNEL") ? "AMD_SERIALIZE_KERNEL" :
+                      on("HIP_LAUNCH_BLOCKING") ? "HIP_LAUNCH_BLOCKING" : nullptr;
+    if (why && !(e && e[0] == '1')) {       // (CASV_TOPB_SPLIT=1 insists)
+        fprintf(stderr, "cor_asv_ann_hip: kernel dispatch is serialised (%s): the attention cell's backward runs as ONE launch "
+                        "(the two-launch form needs both resident together)\n", why);
+        return false;
+    }
+    return true;
+}
+static bool cell_bwd_split_option() {
+    static const bool opt = read_cell_bwd_split_option();
+    return opt;
+}
+
+// The cell's backward recurrence as ONE launch (train_persist_topb.hip; two side by side in the split form) where the step may
+// take a persistent launch and the shape has one; *done says whether it did.  dc: dL/dc, cleared; dL/dc0 at the end.
+static int cell_backward_persistent(Step& s, float* dc, bool* done) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, W = s.W, C = s.C;
+    const int kr = C + W;
+    TLayer& top = s.top();
+    *done = false;
+    unsigned* slot = persist_slot(m, ts);
+    if (!slot) return 0;
+    TopBwdArgs ra{};
+    ra.WrT = top.wrT.as<float>(); ra.WaN = ts->WaN.as<float>(); ra.dG = ts->dG.as<float>();
+    ra.Gt = top.Gt.as<float>(); ra.Cs = top.Cs.as<float>(); ra.c0 = s.dec_c0(s.D); ra.dZ = top.Z.as<float>(); ra.dRec = top.dRec.as<float>();
+    ra.dhatt = ts->dhatt.as<float>(); ra.DWQ = ts->DWQ.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.Ast = ts->Ast.as<float>();
+    ra.WIN = ts->WIN.as<int>(); ra.dc_out = dc; ra.B = B; ra.U = U; ra.W = W; ra.C = C;
+    AttnBwdArgs& ab = ra.ab;
+    ab.mcell = s.mcell; ab.ld_mcell = W + C; ab.mc_off = W; ab.va = ts->W_(ts->iva);
+    ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
+    ab.enc = s.enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
+    ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>();
+    ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
+    ra.counters = slot;
+    const int defer_opt = attn_defer_option();
+    const int defer = (T <= ATTN_DEFER_MAX_T && W % 64 == 0 && C % 64 == 0) ? defer_opt : 0;
+    ra.DS = defer ? ts->DSrows.as<float>() : nullptr; ra.defer = defer;
+    const int grid = train_attention_cell_bwd_grid(ra, m->ncu);
+    if (!grid) return 0;
+    hipEvent_t ev{};
+    m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
+    const bool split_opt = cell_bwd_split_option();
+    ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;
+    if (ra.split_a && !ts->side) {          // (no second stream to be had: one launch, as before)
+        if (hipStreamCreateWithFlags(&ts->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ts->side = nullptr; }
+        else if (hipEventCreateWithFlags(&ts->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                 hipEventCreateWithFlags(&ts->ev_join, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamDestroy(ts->side); ts->side = nullptr;
+        }
+        if (!ts->side) { ts->split_off = true; ra.split_a = 0; }
+    }
+    if (ra.split_a) {
+        HIPCHK(hipEventRecord(ts->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(ts->side, ts->ev_fork, 0));
+        launch_train_attention_cell_bwd_rows(ra, grid, ts->side);
+        HIPCHK(hipEventRecord(ts->ev_join, ts->side));
+        ts->split_launch = ts->rec_launches;
+    }
+    launch_train_attention_cell_bwd(ra, grid, st);
+    if (ra.split_a) HIPCHK(hipStreamWaitEvent(st, ts->ev_join, 0));
+    if (defer) {
+        AttnDeferArgs da{};
+        da.dRec = ra.dRec; da.ld_drec = kr; da.mcell = s.mcell; da.ld_mcell = W + C; da.mc_off = W;
+        da.Ast = ra.Ast; da.WIN = ra.WIN; da.DS = ra.DS; da.WQ = ra.WQ; da.va = ab.va; da.u = ab.u;
+        da.d_enc = ab.d_enc; da.du = ab.du; da.B = B; da.U = U; da.T = T; da.W = W; da.C = C; da.what = defer;
+        launch_attention_deferred(da, st);
+    }
+    m->prof_end(PC_PERSIST, ev);
+    persist_launched(ts, slot, train_attention_cell_bwd_counter_bytes(B));
+    *done = true;
+    return 0;
+}
+
+// ... and as three launches per time step (two with the fused backward step): cell backward + data GEMM, attention backward, query GEMM
+static int cell_backward_steps(Step& s, float* dc) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, W = s.W, C = s.C;
+    const int kr = C + W;
+    TLayer& top = s.top();
+    const float* c0t = s.dec_c0(s.D);
+    HIPCHK(hipMemsetAsync(ts->dhatt.p, 0, s.UB * W * 4, st));     // (split-K outputs of the per-step GEMMs; the persistent kernel stores them)
+    for (int t = U - 1; t >= 0; --t) {
+        LstmBwdArgs p{};
+        p.a = ts->dG.as<float>() + (long long)t * B * W; p.lda = W;
+        if (t < U - 1) {
+            p.b = top.dRec.as<float>() + (long long)(t + 1) * B * kr + C; p.ldb = kr;
+            p.c = ts->dhatt.as<float>() + (long long)(t + 1) * B * W; p.ldc = W;
+        }
+        p.gates = top.Gt.as<float>() + (long long)t * B * 4 * W;
+        p.cell = top.Cs.as<float>() + (long long)t * B * W;
+        p.c_prev = t > 0 ? top.Cs.as<float>() + (long long)(t - 1) * B * W : c0t; p.ld_cprev = W;
+        p.dc = dc; p.dz = top.Z.as<float>() + (long long)t * B * 4 * W; p.rows = B; p.W = W;
+        float* drec = top.dRec.as<float>() + (long long)t * B * kr;
+        if (s.fused) {
+            BwdStepBatch fb{};
+            fb.count = 1;
+            BwdStepJob& q = fb.j[0];
+            q.p = p;
+            q.dc_in = ((U - 1 - t) & 1) ? ts->dcalt.as<float>() : dc; q.p.dc = ((U - 1 - t) & 1) ? dc : ts->dcalt.as<float>();
+            q.Bt = top.wrT.as<float>(); q.out = drec; q.ld_out = kr; q.N = kr;
+            hipEvent_t ev{};
+            m->prof_begin(PC_GEMM, 2.0 * B * (double)kr * 4.0 * W, 4.0 * ((double)B * 4 * W + (double)kr * 4 * W + (double)B * kr), ev);
+            launch_lstm_bwd_gemm(fb, st);
+            m->prof_end(PC_GEMM, ev);
+        } else {
+            launch_lstm_bwd(p, st);
+            GemmArgs g = plain_gemm(p.dz, 4 * W, B, 4 * W, top.wrT.as<float>(), kr, nullptr, drec, kr); g.out_zeroed = 1; run_gemm(m, EPI_PLAIN, g);
+        }
+        AttnBwdArgs ab{};
+        ab.dxh = drec; ab.ld_dxh = kr; ab.ctx_off = 0; ab.mcell = s.mcell; ab.ld_mcell = W + C; ab.mc_off = W;
+        ab.a = ts->Ast.as<float>() + (long long)(t + 1) * B * T; ab.win = ts->WIN.as<int>() + (long long)t * B;
+        ab.wq = ts->WQ.as<float>() + (long long)t * B * W; ab.va = ts->W_(ts->iva);
+        ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
+        ab.enc = s.enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
+        ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>(); ab.dwq = ts->DWQ.as<float>() + (long long)t * B * W;
+        ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
+        launch_attention_bwd(ab, st, s.det);
+        GemmArgs g = plain_gemm(ab.dwq, W, B, W, ts->WaN.as<float>(), W, nullptr, ts->dhatt.as<float>() + (long long)t * B * W, W);
+        g.out_zeroed = 1;
+        run_gemm(m, EPI_PLAIN, g);
+    }
+    if (s.fused && (U & 1)) HIPCHK(hipMemcpyAsync(dc, ts->dcalt.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));   // dL/dc0 of the cell
+    return 0;
+}
+
+// Phase 6 leaves the tied projection's gradient, dL/d(cell input sequence) in dXtop, dL/d(attended sequence) in d_enc, the
+// gradients of the cell's and the attention's parameters, and dL/dh0, dL/dc0 of the cell in dfin_h(D), dfin_c(D).
+static int backward_cell(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
+    const long long TB = s.TB, UB = s.UB;
+    const int kr = C + W;
+    TLayer& top = s.top();
     float* dlog = ts->logits.as<float>();
     // tied projection: dE += dlogits^T . G ; dG = dlogits . E
     {
-        run_gemm_tn(m, dlog, Vp, Vp, V, proj_in, proj_ld, W, UB, ts->G_(ts->iE), W);      // (the padding columns of dlogits are zero)
+        run_gemm_tn(m, dlog, Vp, Vp, V, s.proj_in, s.proj_ld, W, UB, ts->G_(ts->iE), W);      // (the padding columns of dlogits are zero)
         GemmArgs g2 = plain_gemm(dlog, Vp, (int)UB, Vp, ts->ETp.as<float>(), W, nullptr, ts->dG.as<float>(), W);
         run_plain(m, g2);
     }
@@ -830,168 +1051,63 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipMemsetAsync(ts->dvaP.p, 0, (size_t)B * W * 4, st));
     for (auto& l : ts->layers) if (!l.drec_cleared) HIPCHK(hipMemsetAsync(l.dRec.p, 0, (size_t)l.len * B * l.kr * 4, st));
     HIPCHK(hipMemsetAsync(ts->dbvP.p, 0, (size_t)B * 4, st));
-    float* dfin = ts->dfin.as<float>();          // [n-1][0|1][B][W]
-    auto dfin_h = [&](int n) { return dfin + (size_t)(2 * (n - 1)) * B * W; };
-    auto dfin_c = [&](int n) { return dfin + (size_t)(2 * (n - 1) + 1) * B * W; };
-    // ---- attention cell (top decoder layer) ----
-    {
-        float* dc = dfin_c(D);
-        HIPCHK(hipMemsetAsync(dc, 0, (size_t)B * W * 4, st));
-        const int kr = C + W;
-        bool topb_persistent = false;
-        if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < 16 && m->ncu >= 64) {
-            // ONE launch for the whole backward recurrence of the cell (train_persist_topb.hip)
-            TopBwdArgs ra{};
-            ra.WrT = top.wrT.as<float>(); ra.WaN = ts->WaN.as<float>(); ra.dG = ts->dG.as<float>();
-            ra.Gt = top.Gt.as<float>(); ra.Cs = top.Cs.as<float>(); ra.c0 = c0t; ra.dZ = top.Z.as<float>(); ra.dRec = top.dRec.as<float>();
-            ra.dhatt = ts->dhatt.as<float>(); ra.DWQ = ts->DWQ.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.Ast = ts->Ast.as<float>();
-            ra.WIN = ts->WIN.as<int>(); ra.dc_out = dc; ra.B = B; ra.U = U; ra.W = W; ra.C = C;
-            AttnBwdArgs& ab = ra.ab;
-            ab.mcell = mcell; ab.ld_mcell = W + C; ab.mc_off = W; ab.va = ts->W_(ts->iva);
-            ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
-            ab.enc = enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
-            ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>();
-            ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
-            const size_t cb = train_recurrence_bwd_counter_bytes(B);
-            ra.counters = reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + cb * ts->rec_launches);
-            // d_enc / du summed behind the recurrence instead of by float atomics inside it (attn_bwd.h, DEFER)
-            static const int defer_opt = [] { const char* e = getenv("CASV_ATTN_DEFER"); const int v = e ? atoi(e) : 1; return v == 3 ? 3 : v == 0 ? 0 : 1; }();       // (the recurrence has forms 0, 1 and 3 only)
-            const int defer = (T <= ATTN_DEFER_MAX_T && W % 64 == 0 && C % 64 == 0) ? defer_opt : 0;
-            ra.DS = defer ? ts->DSrows.as<float>() : nullptr; ra.defer = defer;
-            if (const int grid = train_attention_cell_bwd_grid(ra, m->ncu)) {
-                hipEvent_t ev{};
-                m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
-                // the attention backward of the samples as a launch of its own on a second stream, resident beside the big one: it
-                // then runs under the h tiles instead of behind them (CASV_TOPB_SPLIT=0: one launch)
-                // Two launches that hand rows to each other must be resident TOGETHER: where the runtime serialises kernel dispatch
-                // (rocprofv3 --pmc sets ROCPROF_COUNTERS; AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING) the side launch would never see
-                // the main one's counters -- one launch there, said once on stderr (profiles taken that way describe that form).
-                static const bool split_opt = [] {
-                    const char* e = getenv("CASV_TOPB_SPLIT");
-                    if (e && e[0] == '0') return false;
-                    auto on = [](const char* name) { const char* v = getenv(name); return v && v[0] && !(v[0] == '0' && !v[1]); };
-                    const char* why = getenv("ROCPROF_COUNTERS") ? "ROCPROF_COUNTERS (counter collection)" : on("AMD_SERIALIZE_KERNEL") ? "AMD_SERIALIZE_KERNEL" :
-                                      on("HIP_LAUNCH_BLOCKING") ? "HIP_LAUNCH_BLOCKING" : nullptr;
-                    if (why && !(e && e[0] == '1')) {       // (CASV_TOPB_SPLIT=1 insists)
-                        fprintf(stderr, "cor_asv_ann_hip: kernel dispatch is serialised (%s): the attention cell's backward runs as ONE launch "
-                                        "(the two-launch form needs both resident together)\n", why);
-                        return false;
-                    }
-                    return true;
-                }();
-                ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;
-                if (ra.split_a && !ts->side) {          // (no second stream to be had: one launch, as before)
-                    if (hipStreamCreateWithFlags(&ts->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ts->side = nullptr; }
-                    else if (hipEventCreateWithFlags(&ts->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                             hipEventCreateWithFlags(&ts->ev_join, hipEventDisableTiming) != hipSuccess) {
-                        (void)hipGetLastError();
-                        (void)hipStreamDestroy(ts->side); ts->side = nullptr;
-                    }
-                    if (!ts->side) { ts->split_off = true; ra.split_a = 0; }
-                }
-                if (ra.split_a) {
-                    HIPCHK(hipEventRecord(ts->ev_fork, st));
-                    HIPCHK(hipStreamWaitEvent(ts->side, ts->ev_fork, 0));
-                    launch_train_attention_cell_bwd_rows(ra, grid, ts->side);
-                    HIPCHK(hipEventRecord(ts->ev_join, ts->side));
-                    ts->split_launch = ts->rec_launches;
-                }
-                launch_train_attention_cell_bwd(ra, grid, st);
-                if (ra.split_a) HIPCHK(hipStreamWaitEvent(st, ts->ev_join, 0));
-                if (defer) {
-                    AttnDeferArgs da{};
-                    da.dRec = ra.dRec; da.ld_drec = kr; da.mcell = mcell; da.ld_mcell = W + C; da.mc_off = W;
-                    da.Ast = ra.Ast; da.WIN = ra.WIN; da.DS = ra.DS; da.WQ = ra.WQ; da.va = ab.va; da.u = ab.u;
-                    da.d_enc = ab.d_enc; da.du = ab.du; da.B = B; da.U = U; da.T = T; da.W = W; da.C = C; da.what = defer;
-                    launch_attention_deferred(da, st);
-                }
-                m->prof_end(PC_PERSIST, ev);
-                ts->rec_abort[ts->rec_launches++] = persist_give_up_word(ra.counters, train_attention_cell_bwd_counter_bytes(B));
-                topb_persistent = true;
-            }
-        }
-        if (!topb_persistent) HIPCHK(hipMemsetAsync(ts->dhatt.p, 0, UB * W * 4, st));     // (split-K outputs of the per-step GEMMs; the persistent kernel stores them)
-        for (int t = U - 1; t >= 0 && !topb_persistent; --t) {
-            LstmBwdArgs p{};
-            p.a = ts->dG.as<float>() + (long long)t * B * W; p.lda = W;
-            if (t < U - 1) {
-                p.b = top.dRec.as<float>() + (long long)(t + 1) * B * kr + C; p.ldb = kr;
-                p.c = ts->dhatt.as<float>() + (long long)(t + 1) * B * W; p.ldc = W;
-            }
-            p.gates = top.Gt.as<float>() + (long long)t * B * 4 * W;
-            p.cell = top.Cs.as<float>() + (long long)t * B * W;
-            p.c_prev = t > 0 ? top.Cs.as<float>() + (long long)(t - 1) * B * W : c0t; p.ld_cprev = W;
-            p.dc = dc; p.dz = top.Z.as<float>() + (long long)t * B * 4 * W; p.rows = B; p.W = W;
-            float* drec = top.dRec.as<float>() + (long long)t * B * kr;
-            if (fused) {
-                BwdStepBatch fb{};
-                fb.count = 1;
-                BwdStepJob& q = fb.j[0];
-                q.p = p;
-                q.dc_in = ((U - 1 - t) & 1) ? ts->dcalt.as<float>() : dc; q.p.dc = ((U - 1 - t) & 1) ? dc : ts->dcalt.as<float>();
-                q.Bt = top.wrT.as<float>(); q.out = drec; q.ld_out = kr; q.N = kr;
-                hipEvent_t ev{};
-                m->prof_begin(PC_GEMM, 2.0 * B * (double)kr * 4.0 * W, 4.0 * ((double)B * 4 * W + (double)kr * 4 * W + (double)B * kr), ev);
-                launch_lstm_bwd_gemm(fb, st);
-                m->prof_end(PC_GEMM, ev);
-            } else {
-                launch_lstm_bwd(p, st);
-                GemmArgs g = plain_gemm(p.dz, 4 * W, B, 4 * W, top.wrT.as<float>(), kr, nullptr, drec, kr); g.out_zeroed = 1; run_gemm(m, EPI_PLAIN, g);
-            }
-            AttnBwdArgs ab{};
-            ab.dxh = drec; ab.ld_dxh = kr; ab.ctx_off = 0; ab.mcell = mcell; ab.ld_mcell = W + C; ab.mc_off = W;
-            ab.a = ts->Ast.as<float>() + (long long)(t + 1) * B * T; ab.win = ts->WIN.as<int>() + (long long)t * B;
-            ab.wq = ts->WQ.as<float>() + (long long)t * B * W; ab.va = ts->W_(ts->iva);
-            ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
-            ab.enc = enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
-            ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>(); ab.dwq = ts->DWQ.as<float>() + (long long)t * B * W;
-            ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
-            launch_attention_bwd(ab, st, det);
-            GemmArgs g = plain_gemm(ab.dwq, W, B, W, ts->WaN.as<float>(), W, nullptr, ts->dhatt.as<float>() + (long long)t * B * W, W);
-            g.out_zeroed = 1;
-            run_gemm(m, EPI_PLAIN, g);
-        }
-        if (!topb_persistent && fused && (U & 1)) HIPCHK(hipMemcpyAsync(dc, ts->dcalt.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));   // dL/dc0 of the cell
-        launch_colsum(ts->dvaP.as<float>(), B, W, W, ts->G_(ts->iva), st, det);
-        launch_colsum(ts->dbvP.as<float>(), B, 1, 1, ts->G_(ts->ibv), st, det);
-        // dL/dh0 of the cell = recurrent part of step 0 + the query path of step 0
-        launch_mul_mask(top.dRec.as<float>() + C, kr, nullptr, dfin_h(D), W, B, W, st);
-        launch_axpy(dfin_h(D), ts->dhatt.as<float>(), (long long)B * W, st);       // slot of step 0
-        // y-part gradient for all steps, weight grads
-        GemmArgs g = plain_gemm(top.Z.as<float>(), 4 * W, (int)UB, 4 * W, top.wxT.as<float>(), W, nullptr, ts->dXtop.as<float>(), W);
-        run_plain(m, g);
-        launch_mul_rowmask(ts->dXtop.as<float>(), W, mcell, W + C, ts->dXtop.as<float>(), W, UB, B, W, st);
-        if (res_top) launch_axpy(ts->dXtop.as<float>(), ts->dG.as<float>(), UB * W, st);       // the sum's other branch: dL/d(cell input sequence) += dL/d(projection input)
-        if (int rc = layer_weight_grads(m, top, ts->Ym.as<float>(), W, ts->RecIn.as<float>(), kr)) return rc;
-        // attention parameters: dWaT = DWQ^T . Hprev ; dbUW = colsum(DWQ) ; u path
-        if (!ts->tens[ts->iWaT].frozen) {
-            // the h_prev of every step are columns C.. of the cell's recurrent-side inputs
-            run_gemm_tn(m, ts->DWQ.as<float>(), W, W, W, ts->RecIn.as<float>() + C, kr, W, UB, ts->G_(ts->iWaT), W, ts->G_(ts->ibUW));
-        }
-        {
-            run_gemm_tn(m, ts->du.as<float>(), W, W, W, enc_out, C, C, TB, ts->G_(ts->iUT), C);
-            GemmArgs gd = plain_gemm(ts->du.as<float>(), W, (int)TB, W, ts->UaN.as<float>(), C, nullptr, ts->d_enc.as<float>(), C, 1);
-            run_plain(m, gd);
-        }
+    float* dc = s.dfin_c(D);
+    HIPCHK(hipMemsetAsync(dc, 0, (size_t)B * W * 4, st));
+    bool topb_persistent = false;
+    if (int rc = cell_backward_persistent(s, dc, &topb_persistent)) return rc;
+    if (!topb_persistent) if (int rc = cell_backward_steps(s, dc)) return rc;
+    launch_colsum(ts->dvaP.as<float>(), B, W, W, ts->G_(ts->iva), st, s.det);
+    launch_colsum(ts->dbvP.as<float>(), B, 1, 1, ts->G_(ts->ibv), st, s.det);
+    // dL/dh0 of the cell = recurrent part of step 0 + the query path of step 0
+    launch_mul_mask(top.dRec.as<float>() + C, kr, nullptr, s.dfin_h(D), W, B, W, st);
+    launch_axpy(s.dfin_h(D), ts->dhatt.as<float>(), (long long)B * W, st);       // slot of step 0
+    // y-part gradient for all steps, weight grads
+    GemmArgs g = plain_gemm(top.Z.as<float>(), 4 * W, (int)UB, 4 * W, top.wxT.as<float>(), W, nullptr, ts->dXtop.as<float>(), W);
+    run_plain(m, g);
+    launch_mul_rowmask(ts->dXtop.as<float>(), W, s.mcell, W + C, ts->dXtop.as<float>(), W, UB, B, W, st);
+    if (s.res_top()) launch_axpy(ts->dXtop.as<float>(), ts->dG.as<float>(), UB * W, st);       // the sum's other branch: dL/d(cell input sequence) += dL/d(projection input)
+    if (int rc = layer_weight_grads(m, top, ts->Ym.as<float>(), W, ts->RecIn.as<float>(), kr)) return rc;
+    // attention parameters: dWaT = DWQ^T . Hprev ; dbUW = colsum(DWQ) ; u path
+    if (!ts->tens[ts->iWaT].frozen) {
+        // the h_prev of every step are columns C.. of the cell's recurrent-side inputs
+        run_gemm_tn(m, ts->DWQ.as<float>(), W, W, W, ts->RecIn.as<float>() + C, kr, W, UB, ts->G_(ts->iWaT), W, ts->G_(ts->ibUW));
     }
-    // bridge_dense backward: dfin_h(n) / dfin_c(n) arrive as gradients w.r.t. the BRIDGED states; through tanh' and the Dense layer
-    // they become the gradients w.r.t. encoder layer n's own final states (in place), and leave the Dense layers' gradients
-    auto bridge_backward = [&](int n) {
-        if (!bridged) return;
-        for (int s_ = 0; s_ < 2; ++s_) {
-            const TrainState::Bridge& br = ts->bridge[2 * (n - 1) + s_];
-            float* d = s_ ? dfin_c(n) : dfin_h(n);
-            const float* raw = (s_ ? cfin : hfin) + (size_t)(n - 1) * B * W;
-            const float* post = (s_ ? ts->cbr.as<float>() : ts->hbr.as<float>()) + (size_t)(n - 1) * B * W;
-            launch_tanh_bwd(d, post, (long long)B * W, st);
-            if (!ts->tens[br.ikt].frozen) run_gemm_tn(m, d, W, W, W, raw, W, W, B, ts->G_(br.ikt), W, ts->G_(br.ib));
-            GemmArgs g = plain_gemm(d, W, B, W, br.kn.as<float>(), W, nullptr, ts->brtmp.as<float>(), W);
-            g.ksplit = 0; g.kgroups = 0;
-            run_gemm(m, EPI_PLAIN, g);
-            (void)hipMemcpyAsync(d, ts->brtmp.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st);
-        }
-    };
-    bridge_backward(D);
+    {
+        run_gemm_tn(m, ts->du.as<float>(), W, W, W, s.enc_out, C, C, TB, ts->G_(ts->iUT), C);
+        GemmArgs gd = plain_gemm(ts->du.as<float>(), W, (int)TB, W, ts->UaN.as<float>(), C, nullptr, ts->d_enc.as<float>(), C, 1);
+        run_plain(m, gd);
+    }
+    return 0;
+}
+
+// bridge_dense backward of encoder layer n: dfin_h(n) / dfin_c(n) arrive as gradients w.r.t. the BRIDGED states; through tanh' and the
+// Dense layer they become the gradients w.r.t. the layer's own final states (in place), and leave the Dense layers' gradients
+static void bridge_backward(Step& s, int n) {
+    if (!s.bridged) return;
+    casv_model* m = s.m; TrainState* ts = s.ts;
+    const int B = s.B, W = s.W;
+    for (int s_ = 0; s_ < 2; ++s_) {
+        const TrainState::Bridge& br = ts->bridge[2 * (n - 1) + s_];
+        float* d = s_ ? s.dfin_c(n) : s.dfin_h(n);
+        const float* raw = (s_ ? s.cfin : s.hfin) + (size_t)(n - 1) * B * W;
+        const float* post = (s_ ? ts->cbr.as<float>() : ts->hbr.as<float>()) + (size_t)(n - 1) * B * W;
+        launch_tanh_bwd(d, post, (long long)B * W, s.st);
+        if (!ts->tens[br.ikt].frozen) run_gemm_tn(m, d, W, W, W, raw, W, W, B, ts->G_(br.ikt), W, ts->G_(br.ib));
+        GemmArgs g = plain_gemm(d, W, B, W, br.kn.as<float>(), W, nullptr, ts->brtmp.as<float>(), W);
+        g.ksplit = 0; g.kgroups = 0;
+        run_gemm(m, EPI_PLAIN, g);
+        (void)hipMemcpyAsync(d, ts->brtmp.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, s.st);
+    }
+}
+
+// Phase 7 leaves the gradients of every layer below the cell, of the bridges and of the embedding (decoder inputs, encoder inputs).
+static int backward_layers(Step& s) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;
+    const long long TB = s.TB, UB = s.UB;
+    const bool deep = s.deep, residual = s.residual;
+    TLayer* Lfw = &ts->layers[0]; TLayer* Lbw = &ts->layers[1];
+    bridge_backward(s, D);
     // ---- decoder layer n with encoder layer n+1 (the mirror of the forward pairing) ----
     const float* dy = ts->dXtop.as<float>();        // gradient w.r.t. DO[D-1] (or Y0 when D == 1)
     const float* dO = ts->d_enc.as<float>();        // gradient w.r.t. O[D]
@@ -1000,97 +1116,94 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     float* dy_bufs[2] = {ts->dXtop.as<float>(), ts->dYl.as<float>()}; int dy_cur = 0;
     float* do_bufs[2] = {ts->dXl.as<float>(), ts->dOin.as<float>()}; int do_out = 0;
     for (int n = D - 1; n >= 1 && deep; --n) {
-        TLayer& ld = dec_layer(n);
-        TLayer& lf = enc_dir(n + 1, 0); TLayer& lb = enc_dir(n + 1, 1);
+        TLayer& ld = s.dec_layer(n);
+        TLayer& lf = s.enc_dir(n + 1, 0); TLayer& lb = s.enc_dir(n + 1, 1);
         const float* xin = n == 1 ? ts->Y0.as<float>() : ts->DO[n - 1].as<float>();
         const bool res_d = residual && n >= 2;
-        if (res_d) launch_mul_mask(dy, W, mdec_n(n), dy_bufs[dy_cur ^ 1], W, UB, W, st);
+        if (res_d) launch_mul_mask(dy, W, s.mdec_n(n), dy_bufs[dy_cur ^ 1], W, UB, W, st);
         {
-            LayerBwd one[1] = {{&ld, dy, W, mdec_n(n), nullptr, nullptr, h0base + (size_t)(n - 1) * B * W, c0base + (size_t)(n - 1) * B * W, dfin_c(n),
+            LayerBwd one[1] = {{&ld, dy, W, s.mdec_n(n), nullptr, nullptr, s.dec_h0(n), s.dec_c0(n), s.dfin_c(n),
                                 xin, W, dy_bufs[dy_cur ^ 1], W, res_d ? 1 : 0}};
             if (int rc = layers_backward(m, one, 1)) return rc;
         }
-        HIPCHK(hipMemcpyAsync(dfin_h(n), ld.dRec.as<float>(), (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-        bridge_backward(n);
+        HIPCHK(hipMemcpyAsync(s.dfin_h(n), ld.dRec.as<float>(), (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
+        bridge_backward(s, n);
         dy_cur ^= 1; dy = dy_bufs[dy_cur];
         // the BiLSTM n + 1: forward direction takes columns [0,W) of dO, backward direction [W,2W); both add into the gradient of their
         // shared input, whose cross sum (the Lambda is its own adjoint) is the gradient w.r.t. O[n]
         float* dXn = do_bufs[0]; float* dOn = do_bufs[1];
         LayerBwd pair[2] = {
-            {&lf, dO, ld_dO, menc_n(n + 1), nullptr, nullptr, nullptr, nullptr, ts->dcbuf.as<float>(),
+            {&lf, dO, ld_dO, s.menc_n(n + 1), nullptr, nullptr, nullptr, nullptr, ts->dcbuf.as<float>(),
              ts->XD[n + 1].as<float>(), 2 * W, dXn, 2 * W, 0},
-            {&lb, dO + W, ld_dO, menc_n(n + 1) ? menc_n(n + 1) + W : nullptr, dfin_h(n + 1), dfin_c(n + 1), nullptr, nullptr, ts->dcbuf2.as<float>(),
+            {&lb, dO + W, ld_dO, s.menc_n(n + 1) ? s.menc_n(n + 1) + W : nullptr, s.dfin_h(n + 1), s.dfin_c(n + 1), nullptr, nullptr, ts->dcbuf2.as<float>(),
              ts->XD[n + 1].as<float>(), 2 * W, dXn, 2 * W, 1}};
         if (int rc = layers_backward(m, pair, 2)) return rc;
         launch_cross_sum(dXn, dOn, TB * 2 * W, st);
         dO = dOn; ld_dO = 2 * W;
     }
     for (int n = D - 1; n >= 1 && !deep; --n) {
-        TLayer& ld = dec_layer(n);
-        TLayer& le = enc_layer(n + 1);
+        TLayer& ld = s.dec_layer(n);
+        TLayer& le = s.enc_layer(n + 1);
         const float* xin = n == 1 ? ts->Y0.as<float>() : ts->DO[n - 1].as<float>();
         // residual_connections: decoder layer n >= 2 / encoder layer n + 1 >= 3 pass their output gradient (times the mask) straight on to
         // their input as well: the input-gradient buffers start from it and the layers' data gradients are added
         const bool res_d = residual && n >= 2, res_e = residual && n + 1 >= 3;
-        if (res_d) launch_mul_mask(dy, W, mdec_n(n), dy_bufs[dy_cur ^ 1], W, UB, W, st);
-        if (res_e) launch_mul_mask(dO, ld_dO, menc_n(n + 1), do_bufs[do_out], le.kx, TB, W, st);
+        if (res_d) launch_mul_mask(dy, W, s.mdec_n(n), dy_bufs[dy_cur ^ 1], W, UB, W, st);
+        if (res_e) launch_mul_mask(dO, ld_dO, s.menc_n(n + 1), do_bufs[do_out], le.kx, TB, W, st);
         LayerBwd pair[2] = {
-            {&ld, dy, W, mdec_n(n), nullptr, nullptr, h0base + (size_t)(n - 1) * B * W, c0base + (size_t)(n - 1) * B * W, dfin_c(n),
+            {&ld, dy, W, s.mdec_n(n), nullptr, nullptr, s.dec_h0(n), s.dec_c0(n), s.dfin_c(n),
              xin, W, dy_bufs[dy_cur ^ 1], W, res_d ? 1 : 0},
-            {&le, dO, ld_dO, menc_n(n + 1), dfin_h(n + 1), dfin_c(n + 1), nullptr, nullptr, ts->dcbuf.as<float>(),
+            {&le, dO, ld_dO, s.menc_n(n + 1), s.dfin_h(n + 1), s.dfin_c(n + 1), nullptr, nullptr, ts->dcbuf.as<float>(),
              ts->O[n].as<float>(), le.kx, do_bufs[do_out], le.kx, res_e ? 1 : 0}};
         if (int rc = layers_backward(m, pair, 2)) return rc;
         // dL/dh0, dL/dc0 of the decoder layer go to the encoder layer of the same index
-        HIPCHK(hipMemcpyAsync(dfin_h(n), ld.dRec.as<float>(), (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-        bridge_backward(n);
+        HIPCHK(hipMemcpyAsync(s.dfin_h(n), ld.dRec.as<float>(), (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
+        bridge_backward(s, n);
         dy_cur ^= 1; dy = dy_bufs[dy_cur];
         dO = do_bufs[do_out]; ld_dO = le.kx; do_out ^= 1;
     }
-    if (det) launch_embed_segments(ts->G_(ts->iE), ts->seg_dec_off.as<int>(), ts->seg_dec_pos.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
+    if (s.det) launch_embed_segments(ts->G_(ts->iE), ts->seg_dec_off.as<int>(), ts->seg_dec_pos.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
     else launch_embed_scatter(ts->G_(ts->iE), ts->d_in.as<int>(), nullptr, dy, W, B, U, 1, V, W, st);
 
     // ---- encoder layer 1: forward direction takes columns [0,W) of dO1, backward direction [W,2W) ----
     {
         LayerBwd pair[2] = {
-            {Lfw, dO, ld_dO, menc_n(1), nullptr, nullptr, nullptr, nullptr, ts->dcbuf.as<float>(),
+            {Lfw, dO, ld_dO, s.menc_n(1), nullptr, nullptr, nullptr, nullptr, ts->dcbuf.as<float>(),
              ts->X0.as<float>(), W, ts->dX0.as<float>(), W, 0},
-            {Lbw, dO + W, ld_dO, menc_n(1) ? menc_n(1) + W : nullptr, dfin_h(1), dfin_c(1), nullptr, nullptr, ts->dcbuf2.as<float>(),
+            {Lbw, dO + W, ld_dO, s.menc_n(1) ? s.menc_n(1) + W : nullptr, s.dfin_h(1), s.dfin_c(1), nullptr, nullptr, ts->dcbuf2.as<float>(),
              ts->X0.as<float>(), W, ts->dX0.as<float>(), W, 1}};
         if (int rc = layers_backward(m, pair, 2)) return rc;
     }
-    if (det) launch_embed_segments(ts->G_(ts->iE), ts->seg_enc_off.as<int>(), ts->seg_enc_pos.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr,
-                                   ts->dX0.as<float>(), W, B, T, A, V, W, st);
-    else launch_embed_scatter(ts->G_(ts->iE), ts->e_idx.as<int>(), enc_val ? ts->e_val.as<float>() : nullptr, ts->dX0.as<float>(), W, B, T, A, V, W, st);
+    if (s.det) launch_embed_segments(ts->G_(ts->iE), ts->seg_enc_off.as<int>(), ts->seg_enc_pos.as<int>(), s.enc_val ? ts->e_val.as<float>() : nullptr,
+                                     ts->dX0.as<float>(), W, B, T, A, V, W, st);
+    else launch_embed_scatter(ts->G_(ts->iE), ts->e_idx.as<int>(), s.enc_val ? ts->e_val.as<float>() : nullptr, ts->dX0.as<float>(), W, B, T, A, V, W, st);
+    return 0;
+}
 
-    {
-        bool any = false;
-        if (int rc = recurrences_gave_up(any)) return rc;
-        if (any) return casv_train_step(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, dec_out, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out);
-        if (ts->rec_launches) ts->rec_penalty = 0;
+// One launch over all parameter tensors that are not frozen; lists of MULTI_MAX tensors at a time
+template <class Launch> static void over_tensors(TrainState* ts, int max_blocks, Launch&& launch) {
+    MultiTensor mt{};
+    for (auto& t : ts->tens) {
+        if (t.frozen) continue;
+        if (mt.count == MULTI_MAX) { launch(mt); mt = MultiTensor{}; }
+        multi_add(mt, t.w.as<float>(), t.g.as<float>(), t.m.as<float>(), t.v.as<float>(), (long long)t.n, max_blocks);
     }
-    if (ts->tn_ws_rc) {                    // (a weight gradient was not computed: no update, the step fails with the allocation's error)
-        (void)hipStreamSynchronize(st);
-        return ts->tn_ws_rc;
-    }
-    // ---- regulariser, clip, update ----
-    launch_reg(ts->W_(ts->iE), ts->G_(ts->iE), V, W, ts->loss.as<double>(), 1, st, parts);
-    // (norm and update over all parameter tensors as one launch each; lists of MULTI_MAX tensors at a time)
-    auto over_tensors = [&](int max_blocks, auto&& launch) {
-        MultiTensor mt{};
-        for (auto& t : ts->tens) {
-            if (t.frozen) continue;
-            if (mt.count == MULTI_MAX) { launch(mt); mt = MultiTensor{}; }
-            multi_add(mt, t.w.as<float>(), t.g.as<float>(), t.m.as<float>(), t.v.as<float>(), (long long)t.n, max_blocks);
-        }
-        launch(mt);
-    };
+    launch(mt);
+}
+
+// Phase 8 leaves the regulariser in the loss and the embedding's gradient, the gradients' norm, (mode 1) the clipped Adam update with
+// the derived layouts refreshed, and the step's loss and norm with the caller.
+static int update(Step& s, double* loss_out, double* norm_out) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    double* parts = s.parts;
+    launch_reg(ts->W_(ts->iE), ts->G_(ts->iE), s.V, s.W, ts->loss.as<double>(), 1, st, parts);
     // (few workgroups per tensor: every one of them ends in an atomic add on the ONE sum -- ~12 ns each, one after the other)
-    over_tensors(64, [&](const MultiTensor& mt) { launch_sumsq_multi(mt, ts->normsq.as<double>(), st, parts); });
-    if (mode == 1) {
+    over_tensors(ts, 64, [&](const MultiTensor& mt) { launch_sumsq_multi(mt, ts->normsq.as<double>(), st, parts); });
+    if (s.mode == 1) {
         ts->step += 1;
         const double b1 = ts->ap.beta1, b2 = ts->ap.beta2;
         const float lr_t = (float)(ts->ap.lr * sqrt(1.0 - pow(b2, (double)ts->step)) / (1.0 - pow(b1, (double)ts->step)));
-        over_tensors(2048, [&](const MultiTensor& mt) {
+        over_tensors(ts, 2048, [&](const MultiTensor& mt) {
             launch_adam_multi(mt, ts->normsq.as<double>(), ts->ap.clipnorm, lr_t, (float)b1, (float)b2, ts->ap.epsilon, st);
         });
         refresh_derived(m);
@@ -1102,8 +1215,71 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipStreamSynchronize(st));
     if (norm_out) *norm_out = sqrt(nsq);
     if (m->prof.on) m->prof.collect();
+    return CASV_OK;
+}
+
+// One attempt at the step, the phases in order.  *redo: a persistent recurrence gave up -- nothing has been updated, the back-off is
+// set (recurrences_gave_up) and the caller starts over.
+static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
+    casv_model* m = s.m; TrainState* ts = s.ts;
+    ts->B = s.B; ts->T = s.T; ts->U = s.U; ts->A = s.A;
+    m->encoded = false;                    // the final-state buffers are shared with the inference session
+    if (int rc = plan_buffers(s)) return rc;
+    if (int rc = stage_inputs(s)) return rc;
+    if (int rc = forward_layers(s)) return rc;
+    if (int rc = forward_cell(s)) return rc;
+    if (int rc = loss_head(s)) return rc;
+    if (int rc = recurrences_gave_up(m, *redo)) return rc;
+    if (*redo) return CASV_OK;
+    if (!s.training) {                     // K.in_train_phase: the regulariser counts only in the train phase
+        HIPCHK(hipMemcpyAsync(loss_out, ts->loss.p, 8, hipMemcpyDeviceToHost, s.st));
+        HIPCHK(hipStreamSynchronize(s.st));
+        if (norm_out) *norm_out = 0.0;
+        m->stat_train_launches = ts->rec_launches;
+        return CASV_OK;
+    }
+    if (int rc = backward_cell(s)) return rc;
+    if (int rc = backward_layers(s)) return rc;
+    if (int rc = recurrences_gave_up(m, *redo)) return rc;
+    if (*redo) return CASV_OK;
+    if (ts->rec_launches) ts->rec_penalty = 0;
+    if (ts->tn_ws_rc) {                    // (a weight gradient was not computed: no update, the step fails with the allocation's error)
+        (void)hipStreamSynchronize(s.st);
+        return ts->tn_ws_rc;
+    }
+    if (int rc = update(s, loss_out, norm_out)) return rc;
     m->stat_train_launches = ts->rec_launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
     return CASV_OK;
+}
+
+extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                               const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                               const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
+                               double* loss_out, double* norm_out) {
+    if (!m || !enc_idx || !dec_in || !dec_out || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
+    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
+    if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
+    OrderedScope ordered(m->deterministic);
+    Step s{};
+    s.m = m; s.ts = m->train; s.st = m->stream;
+    s.mode = mode; s.B = B; s.T = T; s.U = U; s.A = A;
+    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = weights;
+    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
+    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
+    s.TB = (long long)T * B; s.UB = (long long)U * B;
+    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
+    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
+    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
+    // A persistent recurrence that gave up sets the back-off, so the second attempt takes per-step launches only and cannot give up.
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool redo = false;
+        if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
+        if (!redo) return CASV_OK;
+    }
+    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
 }
 
 // Keras-layout view of the master weights (which = 0), of the last gradients (which = 1) or of Adam's m (2) / v (3).

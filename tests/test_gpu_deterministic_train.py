@@ -169,6 +169,76 @@ def test_deterministic_step_same_bits_whatever_the_launch_form():
         _assert_same_bits(ref, _session(d, W, V, w, batch, 2, options=opts))
 
 
+# ------------------------------------------------------------------------------------------------------------------ earlier shapes
+# A step's results do not depend on the shapes the session saw before: after a larger step every buffer of the session is larger
+# than the target needs and holds older contents, after a smaller one every buffer must grow.
+_HISTORY_MODELS = {'d2': (2, 32, 40, {}),
+                   # (the most per-layer buffers: both directions' own outputs, the cross sums, the bridged states, the top sum)
+                   'd3_all': (3, 64, 40, dict(deep_bidirectional_encoder=True, bridge_dense=True, residual_connections=True))}
+_HISTORY_TARGET = (4, 7)                                    # B, L
+_HISTORY_EARLIER = {'larger': (6, 12), 'smaller': (2, 3)}
+_HISTORY_RUNS = {}
+
+
+def _target_step(model, earlier, deterministic):
+    """The target batch's mode-2 loss, norm and gradients, its mode-0 loss and the statistic "train_persistent_launches" of its mode-2
+    step, in a session that ran `earlier` (None: nothing) first: one mode-2 step and one mode-0 step, which leave the weights alone.
+    Computed once per process."""
+    key = (model, earlier, deterministic)
+    if key not in _HISTORY_RUNS:
+        from cor_asv_ann_amd.engine import HipEngine
+        d, W, V, flags = _HISTORY_MODELS[model]
+        _, w, _, batch = _small_case(d, W, V, *_HISTORY_TARGET, flags=flags)
+        eng = HipEngine(d, W, V, **flags)
+        try:
+            eng.set_weights(w)
+            if deterministic:
+                eng.set_option('deterministic', 1)
+            eng.train_begin()
+            if earlier:
+                _, w0, _, b0 = _small_case(d, W, V, *_HISTORY_EARLIER[earlier], flags=flags)
+                assert all(np.array_equal(w0[k], w[k]) for k in w)
+                eng.train_step(*b0, mode=2)
+                eng.train_step(*b0[:5], None, mode=0)
+            out = dict(zip(('loss', 'norm'), eng.train_step(*batch, mode=2)))
+            out['launches'] = eng.stat('train_persistent_launches')
+            out['grads'] = eng.train_gradients()
+            out['eval'] = eng.train_step(*batch[:5], None, mode=0)[0]
+            eng.train_end()
+        finally:
+            eng.close()
+        _HISTORY_RUNS[key] = out
+    return _HISTORY_RUNS[key]
+
+
+@pytest.mark.parametrize('earlier', sorted(_HISTORY_EARLIER))
+@pytest.mark.parametrize('model', sorted(_HISTORY_MODELS))
+def test_deterministic_step_same_bits_whatever_shapes_came_before(model, earlier):
+    fresh, got = _target_step(model, None, True), _target_step(model, earlier, True)
+    assert got['loss'] == fresh['loss'] and got['norm'] == fresh['norm'] and got['eval'] == fresh['eval']
+    assert set(got['grads']) == set(fresh['grads'])
+    for k in fresh['grads']:
+        assert np.array_equal(got['grads'][k], fresh['grads'][k]), k
+
+
+@pytest.mark.parametrize('earlier', sorted(_HISTORY_EARLIER))
+def test_default_step_equals_oracle_whatever_shapes_came_before(earlier):
+    """The default step (persistent recurrences where the shape has them, float atomics: no bits to compare): the gradients
+    against the oracle (the tolerances of test_train_step_matches_oracle), and as many persistent launches as a fresh session takes."""
+    d, W, V, flags = _HISTORY_MODELS['d2']
+    cfg, w, (enc_in, dec_in, dec_out, wts, m), _ = _small_case(d, W, V, *_HISTORY_TARGET, flags=flags)
+    if 'oracle' not in _HISTORY_RUNS:
+        _HISTORY_RUNS['oracle'] = forward_backward(cfg, w, enc_in, dec_in, dec_out, wts, m)[1]
+    grads = _HISTORY_RUNS['oracle']
+    onorm = np.sqrt(sum(float((g.astype(np.float64) ** 2).sum()) for g in grads.values()))
+    fresh, got = _target_step('d2', None, False), _target_step('d2', earlier, False)
+    assert got['launches'] == fresh['launches']
+    for run in (fresh, got):
+        for k in grads:
+            scale = max(np.abs(grads[k]).max(), 1e-6 * onorm)
+            assert np.abs(run['grads'][k] - grads[k]).max() < 2e-3 * scale + 1e-7, k
+
+
 _CHILD = r'''
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1])

@@ -126,19 +126,65 @@ def test_restated_constants_and_conditions_are_the_sources():
     # every instantiation of the five kernels goes through those switches
     for text, kernel in ((bwd, tf.KERNEL['rec_bwd']), (top, tf.KERNEL['cell']), (topb, tf.KERNEL['cell_bwd']), (topb, tf.SPLIT_KERNEL)):
         assert set(int(x) for x in re.findall(r'%s<(\d+)>' % kernel, text)) <= set(tf.NT['rec']), kernel
-    # train.hip: the four places that decide, all with one condition; the cap; the cell's and the backward's own conditions
-    cond = 'if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < %d && m->ncu >= %d) {' % (tf.CAP, tf.MIN_CUS)
-    assert train.count(cond) == 4 and len(re.findall(r'rec_launches < \d+', train)) == 4
-    assert 'const unsigned* rec_abort[%d]' % tf.CAP in train and len(re.findall(r'rec_launches\+\+', train)) == 4
-    assert 'ENS(ts->rec_cnt, %d * train_recurrence_bwd_counter_bytes(B))' % tf.CAP in train
-    assert 'const int grid = top.hs_ld == W ? train_attention_cell_grid(ra, m->ncu) : 0' in train
-    assert 'plain = plain && l.kr == W;' in train and 'const int grid = plain ? train_recurrence_bwd_grid(ra, m->ncu) : 0;' in train
-    assert 'ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;' in train
+    # train.hip: ONE place that decides (persist_slot) and ONE that counts (persist_launched), called from the four sites; the cap as
+    # one named constant; the cell's and the backward's own conditions
+    cap = 'REC_LAUNCH_CAP'
+    assert len(re.findall(r'constexpr int %s = (\d+);' % cap, train)) == 1
+    assert int(re.search(r'constexpr int %s = (\d+);' % cap, train).group(1)) == tf.CAP
+    cond = 'if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < %s && m->ncu >= %d) {' % (cap, tf.MIN_CUS)
+    assert train.count(cond) == 1 and cond in _function(train, 'static unsigned* persist_slot(casv_model* m, TrainState* ts) {')
+    assert re.findall(r'rec_launches < \w+', train) == ['rec_launches < ' + cap] and train.count('persist_mode != 0') == 1
+    assert 'const unsigned* rec_abort[%s]' % cap in train and len(re.findall(r'rec_launches\+\+', train)) == 1
+    assert 'rec_launches++' in _function(train, 'static void persist_launched(TrainState* ts, unsigned* slot, size_t counter_bytes) {')
+    sites = {'layers_backward': 'static int layers_backward(', 'layers_forward': 'static int layers_forward(',
+             'forward_cell': 'static int forward_cell(', 'cell_backward_persistent': 'static int cell_backward_persistent('}
+    for name, head in sites.items():
+        body = _function(train, head)
+        assert len(re.findall(r'unsigned\* slot = persist_slot\(m, ts\)', body)) == 1 and body.count('ra.counters = slot;') == 1, name
+        assert len(re.findall(r'persist_launched\(ts, slot, %s\(B\)\);' % tf.COUNTER_BYTES[name], body)) == 1, name
+    assert len(re.findall(r'persist_slot\(m, ts\)', train)) == 4 and len(re.findall(r'persist_launched\(ts, slot, ', train)) == 4
+    # one slot size: the largest of the four kinds' counters, for the addresses, the allocation and the clear
+    body = _function(train, 'static size_t persist_slot_bytes(int B) {')
+    assert all(body.count(fn + '(B)') == 1 for fn in tf.COUNTER_BYTES.values()) and body.count('std::max(') == 3
+    assert 'persist_slot_bytes(ts->B) * ts->rec_launches' in _function(train, 'static unsigned* persist_slot(')
+    assert 'ENS(ts->rec_cnt, %s * persist_slot_bytes(B))' % cap in _function(train, 'static int plan_buffers(Step& s) {')
+    assert 'hipMemsetAsync(ts->rec_cnt.p, 0, %s * persist_slot_bytes(B), st)' % cap in _function(train, 'static int stage_inputs(Step& s) {')
+    assert train.count('persist_slot_bytes(') == 4
+    assert 'const int grid = top.hs_ld == W ? train_attention_cell_grid(ra, m->ncu) : 0' in _function(train, sites['forward_cell'])
+    body = _function(train, sites['layers_backward'])
+    assert 'plain = plain && l.kr == W;' in body and 'const int grid = plain ? train_recurrence_bwd_grid(ra, m->ncu) : 0;' in body
+    assert ('ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;'
+            in _function(train, sites['cell_backward_persistent']))
+
+
+_LAUNCH_SITE = r'layers_forward\(m, f, \d|launch_train_attention_cell\(|launch_train_attention_cell_bwd\(|layers_backward\(m, \w+, \d'
+
+
+def _step_functions(train):
+    """{name: body} of train.hip's functions that take the step's view."""
+    return {name: _function(train, head) for head, name in re.findall(r'^(static \w+ (\w+)\(Step&? s[,)])', train, re.M)}
+
+
+def _launch_sites(fns, name):
+    """The launch sites of a function of the step in the order of its text, those of the step's functions it calls in their place."""
+    out = []
+    body = fns[name][fns[name].index('{'):]
+    for hit in re.finditer(r'%s|\b(%s)\(s[,)]' % (_LAUNCH_SITE, '|'.join(fns)), body):
+        out += _launch_sites(fns, hit.group(1)) if hit.group(1) else [hit.group(0)]
+    return out
 
 
 def test_restated_order_of_launches_is_train_hip():
-    step = _function(_src('train.hip'), 'extern "C" int casv_train_step(')
-    order = re.findall(r'layers_forward\(m, f, \d|launch_train_attention_cell\(|launch_train_attention_cell_bwd\(|layers_backward\(m, \w+, \d', step)
+    train = _src('train.hip')
+    fns = _step_functions(train)
+    attempt = fns['train_attempt']
+    phases = re.findall(r'if \(int rc = (\w+)\(s[,)]', attempt)
+    assert phases == ['plan_buffers', 'stage_inputs', 'forward_layers', 'forward_cell', 'loss_head', 'backward_cell', 'backward_layers',
+                      'update']
+    assert set(phases) < set(fns) and not re.search(_LAUNCH_SITE, attempt)
+    step = _function(train, 'extern "C" int casv_train_step(')
+    assert step.count('train_attempt(s, ') == 1 and 'casv_train_step(m' not in step.split('{', 1)[1] and not re.search(_LAUNCH_SITE, step)
+    order = _launch_sites(fns, 'train_attempt')
     assert order == ['layers_forward(m, f, 2',                                      # encoder layer 1, both directions
                      'layers_forward(m, f, 2', 'layers_forward(m, f, 1',            # deep: layer n's directions, then decoder layer n - 1 alone
                      'layers_forward(m, f, 2',                                      # else: encoder layer n beside decoder layer n - 1
@@ -146,8 +192,14 @@ def test_restated_order_of_launches_is_train_hip():
                      'layers_backward(m, one, 1', 'layers_backward(m, pair, 2',     # deep: decoder layer n alone, then layer n + 1's directions
                      'layers_backward(m, pair, 2',                                  # else: decoder layer n beside encoder layer n + 1
                      'layers_backward(m, pair, 2']                                  # encoder layer 1
-    assert 'for (int n = 2; n <= D && deep; ++n)' in step and 'for (int n = 2; n <= D && !deep; ++n)' in step
-    assert 'for (int n = D - 1; n >= 1 && deep; --n)' in step and 'for (int n = D - 1; n >= 1 && !deep; --n)' in step
+    assert len(re.findall(_LAUNCH_SITE, train)) == len(order)       # (no launch site outside the attempt's phases)
+    assert _launch_sites(fns, 'forward_layers') == order[:4] and _launch_sites(fns, 'forward_cell') == order[4:5]
+    assert _launch_sites(fns, 'backward_cell') == order[5:6] and _launch_sites(fns, 'backward_layers') == order[6:]
+    fwd, bwd = fns['forward_layers'], fns['backward_layers']
+    assert 'for (int n = 2; n <= D && deep; ++n)' in fwd and 'for (int n = 2; n <= D && !deep; ++n)' in fwd
+    assert fwd.index('for (int n = 2; n <= D && deep; ++n)') < fwd.index('for (int n = 2; n <= D && !deep; ++n)')
+    assert 'for (int n = D - 1; n >= 1 && deep; --n)' in bwd and 'for (int n = D - 1; n >= 1 && !deep; --n)' in bwd
+    assert bwd.index('for (int n = D - 1; n >= 1 && deep; --n)') < bwd.index('for (int n = D - 1; n >= 1 && !deep; --n)')
     from oracle import ModelConfig
     plain = tf.sites(ModelConfig(depth=3, width=128, voc_size=40), 5, 7)
     assert [(k, l) for k, l, _ in plain] == [('rec', ('enc1_fw', 'enc1_bw')), ('rec', ('enc2', 'dec1')), ('rec', ('enc3', 'dec2')),

@@ -45,8 +45,8 @@ def _rows():
     rows = []
     # configs[3]: d4 W512 V256 B512 T = U = 100, C = W (depth > 1, not deep)
     W, B, T = 512, 512, 100
-    rows += [('c3_enc1bw_dWr_hprev', 4 * W, 4 * W, W, B * (T - 1), (4 * W, 0), (2 * W, W)),      # hp = H1 + W, ld 2W (train.hip:382)
-             ('c3_E', 256, 256, W, T * B, (256, 0), (W, 0)),                                     # dlog [UB][Vp] . G (train.hip:822)
+    rows += [('c3_enc1bw_dWr_hprev', 4 * W, 4 * W, W, B * (T - 1), (4 * W, 0), (2 * W, W)),      # hp = H1 + W, ld 2W (train.hip, layer_backward_finish)
+             ('c3_E', 256, 256, W, T * B, (256, 0), (W, 0)),                                     # dlog [UB][Vp] . G (train.hip, backward_cell)
              ('c3_att_dWaT', W, W, W, T * B, (W, 0), (2 * W, W)),                                # RecIn + C, ld kr = C + W (:967)
              ('c3_bridge', W, W, W, B, (W, 0), (W, 0))]                                          # K = B (:985)
     # mid size: d2 W256 B512 T64, where the split and the ordered split forms are taken

@@ -15,14 +15,17 @@ from tests import grad_noise_cases as gn
 
 # ------------------------------------------------------------------------------------------------------------------ the form
 ROW_BLOCK = 32                      # rows of a row block: RBM, QBM, TBM, VBM
-CAP = 16                            # persistent launches of one step (train.hip: rec_launches < 16, rec_abort[16])
-MIN_CUS = 64                        # train.hip: m->ncu >= 64
+CAP = 16                            # persistent launches of one step (train.hip: REC_LAUNCH_CAP -- persist_slot's gate, rec_abort[], rec_cnt's slots)
+MIN_CUS = 64                        # train.hip, persist_slot: m->ncu >= 64
 # the switch labels of the four *_grid functions (NT = W / 32) and the workgroups per CU their persist_blocks_per_cu calls request
 NT = {'rec': tuple(range(1, 17)), 'rec_bwd': (4, 8, 12, 16), 'cell': (4, 8, 16), 'cell_bwd': (4, 8, 16)}
 BLOCKS_PER_CU = {'rec': 2, 'rec_bwd': 2, 'cell': 1, 'cell_bwd': 1}
 KERNEL = {'rec': 'train_recurrence_kernel', 'rec_bwd': 'train_recurrence_bwd_kernel', 'cell': 'train_attention_cell_kernel',
           'cell_bwd': 'train_attention_cell_bwd_kernel'}
 SPLIT_KERNEL = 'train_attention_cell_bwd_rows_kernel'       # the cell's backward split: a second launch beside the first (same NT)
+# the four functions of train.hip that ask persist_slot for a launch, and whose counters each one's give-up word sits behind
+COUNTER_BYTES = {'layers_forward': 'train_recurrence_counter_bytes', 'layers_backward': 'train_recurrence_bwd_counter_bytes',
+                 'forward_cell': 'train_attention_cell_counter_bytes', 'cell_backward_persistent': 'train_attention_cell_bwd_counter_bytes'}
 
 
 def grid(kind, W, C, B, jobs, cus, per_cu):
@@ -64,10 +67,11 @@ def sites(cfg, T, U):
 
 def train_form(cfg, B, T, U, cus=256, blocks_per_cu=(2, 2, 1, 1), persistent=True):
     """The form of one mode-1 / mode-2 step (option "persistent" != 0, "deterministic" off, no back-off pending), restated from
-    casv_train_step, layers_forward, layers_backward and the four *_grid functions.
+    train.hip's persist_slot and its four callers (layers_forward, layers_backward, forward_cell, cell_backward_persistent) and the four
+    *_grid functions.
     -> dict(launches = per site dict(kind, kernel, NT, jobs, layers, lengths, persistent, split, capped), count = the persistent
-    launches of the step after the cap of 16 (the statistic "train_persistent_launches"), capped = the layers of the sites whose
-    shape has a persistent form but which come behind the 16th launch and run per step).
+    launches of the step after the cap CAP (the statistic "train_persistent_launches"), capped = the layers of the sites whose
+    shape has a persistent form but which come behind the CAP-th launch and run per step).
     split: the attention cell's backward takes its two-launch form (SPLIT_KERNEL beside the main kernel: one launch of the count) --
     predicted wherever that launch is persistent; a device on which the two do not fit together, CASV_TOPB_SPLIT=0 or a serialised
     dispatch take one launch instead."""
