@@ -142,6 +142,8 @@ struct casv_model {
     DevBuf b_rowrec, b_candidx, b_candval;                // wide beams: phase A's per-row results (beam_expand_kernel)
     // training session (train.hip)
     TrainState* train = nullptr;
+    // forward-only state of casv_score_targets outside a session (train.hip): built from the weights of commit number commit_gen
+    TrainState* score = nullptr; unsigned long long commit_gen = 0;
     // options
     int eos = 1;                                          // vocabulary index of '\n' (seq2seq.py:1255,1344,1402)
     bool use_graph = false;
@@ -251,4 +253,5 @@ int ensure_encoded(casv_model* m, int want);
 int settle_encoder(casv_model* m, const unsigned* flag = nullptr);
 
 int casv_train_release(casv_model* m);
+extern "C" int casv_score_release(casv_model* m);
 extern "C" int casv_comm_destroy(casv_model* m);

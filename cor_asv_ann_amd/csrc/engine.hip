@@ -96,6 +96,7 @@ extern "C" void casv_model_destroy(casv_model* m) {
     for (auto* v : {&m->br_hT, &m->br_hb, &m->br_cT, &m->br_cb}) for (auto& b : *v) b.release();
     m->br_tmp.release();
     (void)casv_train_release(m);
+    (void)casv_score_release(m);
     vendor_gemm_release(m->stream);
     (void)casv_comm_destroy(m);
     if (m->pin_active) { (void)hipHostFree(m->pin_active); for (int k = 0; k < 2; ++k) (void)hipEventDestroy(m->ev_active[k]); }
@@ -253,6 +254,7 @@ extern "C" int casv_commit_weights(casv_model* m) {
                 if (int rc = upload(s ? m->br_cb[n] : m->br_hb[n], m->host[b + "_b"])) return rc;
             }
     m->committed = true;
+    ++m->commit_gen;                    // (a scoring state built from the weights before is rebuilt: train.hip, score_state)
     return CASV_OK;
 }
 

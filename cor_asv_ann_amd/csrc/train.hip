@@ -20,6 +20,8 @@
 //   7 backward_layers  decoder / encoder pairs downwards, embedding                    -- give-up check
 //   8 update           regulariser, norm, clipped Adam, results
 // persist_slot is the one place that decides whether a recurrence goes persistent; persist_launched the one that counts it.
+// casv_score_targets (teacher-forced log-probabilities of given targets) makes the same two attempts (score_attempt): phases 1-4 as
+// they are, then the projection and the scoring head in place of the loss -- give-up check; on a forward-only state outside a session.
 #include "engine.h"
 #include "train_kernels.h"
 
@@ -72,6 +74,13 @@ struct TrainState {
     // The attention cell's backward recurrence as TWO launches side by side (train_persist_topb.hip, split_a): the second stream and
     // the events that tie it into the step; split_off: a step gave up with the two launches in flight -- one launch from then on.
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool split_off = false; int split_launch = -1;
+    // casv_score_targets: the head's results on the device in the caller's order -- logp / best / rank [B][U], nll / count [B], the
+    // window form of the attention rows -- and whether the buffers hold a scoring call's attention rows (score_B x score_U x score_T).
+    // forward_only: the state of a scoring call outside a session (m->score) -- weights in the train layout, the derived transposes,
+    // the forward buffers; no gradient, no Adam moment, no backward buffer.  commit_gen: the commit of the handle's weights it holds.
+    DevBuf s_logp, s_best, s_rank, s_nll, s_count, s_lo, s_w;
+    int score_B = 0, score_U = 0, score_T = 0;
+    bool forward_only = false; unsigned long long commit_gen = 0;
     int find(const std::string& n) const { for (size_t i = 0; i < tens.size(); ++i) if (tens[i].name == n) return (int)i; return -1; }
     float* W_(int i) { return tens[i].w.as<float>(); }
     float* G_(int i) { return tens[i].g.as<float>(); }
@@ -133,8 +142,10 @@ static int add_tensor(TrainState* ts, const std::string& name, const std::vector
     TTensor& t = ts->tens.back();
     t.name = name; t.n = host.size(); t.frozen = frozen;
     const size_t bytes = host.size() * 4;
-    if (t.w.ensure(bytes) || t.g.ensure(bytes) || t.m.ensure(bytes) || t.v.ensure(bytes)) return -1;
+    if (t.w.ensure(bytes)) return -1;
     if (hipMemcpy(t.w.p, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (ts->forward_only) return (int)ts->tens.size() - 1;       // (a scoring state: weights only)
+    if (t.g.ensure(bytes) || t.m.ensure(bytes) || t.v.ensure(bytes)) return -1;
     (void)hipMemset(t.m.p, 0, bytes); (void)hipMemset(t.v.p, 0, bytes); (void)hipMemset(t.g.p, 0, bytes);
     return (int)ts->tens.size() - 1;
 }
@@ -151,9 +162,7 @@ static bool is_frozen(const std::string& name, const std::string& csv) {
     return false;
 }
 
-int casv_train_release(casv_model* m) {
-    if (!m || !m->train) return 0;
-    TrainState* ts = m->train;
+static void release_state(casv_model* m, TrainState* ts) {
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
     if (ts->side) { (void)hipStreamSynchronize(ts->side); (void)hipStreamDestroy(ts->side); if (ts->ev_fork) (void)hipEventDestroy(ts->ev_fork); if (ts->ev_join) (void)hipEventDestroy(ts->ev_join); ts->side = nullptr; }
@@ -165,19 +174,30 @@ int casv_train_release(casv_model* m) {
         &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn,
         &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
         &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
-        &ts->seg_dec_pos};
+        &ts->seg_dec_pos, &ts->s_logp, &ts->s_best, &ts->s_rank, &ts->s_nll, &ts->s_count, &ts->s_lo, &ts->s_w};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : ts->O) b.release();
     for (auto& b : ts->DO) b.release();
     for (auto& b : ts->XD) b.release();
     delete ts;
+}
+int casv_train_release(casv_model* m) {
+    if (!m || !m->train) return 0;
+    release_state(m, m->train);
     m->train = nullptr;
     return 0;
 }
+// The forward-only state a scoring call outside a session built (casv_score_targets); allowed when there is none.
+extern "C" int casv_score_release(casv_model* m) {
+    if (!m) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->score) return CASV_OK;
+    release_state(m, m->score);
+    m->score = nullptr;
+    return CASV_OK;
+}
 
 // Refresh the layouts derived from the master tensors (after set-up and after every update).
-static void refresh_derived(casv_model* m) {
-    TrainState* ts = m->train;
+static void refresh_derived(casv_model* m, TrainState* ts) {
     const int W = m->W, V = m->V, Vp = m->Vp, C = m->C;
     for (auto& l : ts->layers) {
         launch_transpose(ts->W_(l.iwx), 4 * W, l.kx, l.kx, l.wxT.as<float>(), 4 * W, m->stream);
@@ -189,18 +209,10 @@ static void refresh_derived(casv_model* m) {
     for (auto& b : ts->bridge) launch_transpose(ts->W_(b.ikt), W, W, W, b.kn.as<float>(), W, m->stream);
 }
 
-extern "C" int casv_train_begin(casv_model* m, const casv_adam_params* ap, const char* frozen_csv) {
-    if (!m || !ap) return fail(CASV_ERR_ARG, "null argument");
-    if (m->W > 1024) return fail(CASV_ERR_ARG, "training supports width <= 1024");
-    HIPCHK(hipSetDevice(m->device));
-    for (auto& kv : m->expect)
-        if (!m->host.count(kv.first)) return fail(CASV_ERR_STATE, "weight '%s' has not been set", kv.first.c_str());
-    casv_train_release(m);
-    TrainState* ts = new TrainState();
-    m->train = ts;
-    ts->ap = *ap;
+// The handle's weights (Keras layout, m->host) as the step's packed tensors in ts, with the derived layouts: a session's state
+// (with gradients and Adam moments) or, ts->forward_only, a scoring state.  On an error the caller releases ts.
+static int build_state(casv_model* m, TrainState* ts, const std::string& fz) {
     const int W = m->W, D = m->D, C = m->C, Vp = m->Vp;
-    const std::string fz = frozen_csv ? frozen_csv : "";
     auto add_lstm = [&](const std::string& prefix, int kx, int kctx, bool reverse) -> int {
         std::vector<float> wx, wr, bias;
         pack_train_lstm(W, kx, kctx, m->host[prefix + "_K"], m->host[prefix + "_R"], m->host[prefix + "_b"], wx, wr, bias);
@@ -246,16 +258,29 @@ extern "C" int casv_train_begin(casv_model* m, const casv_adam_params* ap, const
                 if (br.ikt < 0 || br.ib < 0 || br.kn.ensure((size_t)W * W * 4)) rc |= -1;
                 ts->bridge.push_back(std::move(br));
             }
-    if (rc || ts->iE < 0 || ts->iUT < 0 || ts->iWaT < 0 || ts->ibUW < 0 || ts->iva < 0 || ts->ibv < 0) {
-        casv_train_release(m);
+    if (rc || ts->iE < 0 || ts->iUT < 0 || ts->iWaT < 0 || ts->ibUW < 0 || ts->iva < 0 || ts->ibv < 0)
         return fail(CASV_ERR_NOMEM, "could not allocate the training tensors");
-    }
     if (ts->ETp.ensure((size_t)W * Vp * 4) || ts->WaN.ensure((size_t)W * W * 4) || ts->UaN.ensure((size_t)C * W * 4) ||
-        ts->loss.ensure(16) || ts->normsq.ensure(16)) { casv_train_release(m); return fail(CASV_ERR_NOMEM, "out of memory"); }
+        ts->loss.ensure(16) || ts->normsq.ensure(16)) return fail(CASV_ERR_NOMEM, "out of memory");
     HIPCHK(hipMemset(ts->ETp.p, 0, (size_t)W * Vp * 4));
     ts->O.resize(D + 1); ts->DO.resize(D + 1); ts->XD.resize(D + 1);
-    refresh_derived(m);
+    refresh_derived(m, ts);
     HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
+}
+
+extern "C" int casv_train_begin(casv_model* m, const casv_adam_params* ap, const char* frozen_csv) {
+    if (!m || !ap) return fail(CASV_ERR_ARG, "null argument");
+    if (m->W > 1024) return fail(CASV_ERR_ARG, "training supports width <= 1024");
+    HIPCHK(hipSetDevice(m->device));
+    for (auto& kv : m->expect)
+        if (!m->host.count(kv.first)) return fail(CASV_ERR_STATE, "weight '%s' has not been set", kv.first.c_str());
+    casv_train_release(m);
+    (void)casv_score_release(m);
+    TrainState* ts = new TrainState();
+    m->train = ts;
+    ts->ap = *ap;
+    if (int rc = build_state(m, ts, frozen_csv ? frozen_csv : "")) { casv_train_release(m); return rc; }
     return CASV_OK;
 }
 
@@ -516,7 +541,7 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
         for (int j = 0; j < count; ++j) {
             TLayer& l = *a[j].l;
             ra.job[j] = RecJob{ts->W_(l.iwr), l.Z.as<float>(), l.hs, l.hs_ld, l.Cs.as<float>(), l.Gt.as<float>(), a[j].h0, a[j].c0, l.len,
-                               l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr};
+                               l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr};       // (a scoring state has no dRec: nullptr, nothing to clear)
         }
         ra.counters = slot;
         ra.fault = m->persist_mode == 2;       // (test of the give-up path)
@@ -586,28 +611,30 @@ static int plan_buffers(Step& s) {
     const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
     const long long TB = s.TB, UB = s.UB;
     const bool deep = s.deep;
+    const bool bwd = !ts->forward_only;     // (a scoring state holds no backward buffer: BWD(...) allocates in a session only)
 #define ENS(buf, bytes) if (int rc_ = (buf).ensure(bytes)) return rc_;
+#define BWD(buf, bytes) if (bwd) ENS(buf, bytes)
     ENS(ts->e_idx, TB * A * 4) ENS(ts->e_val, TB * A * 4) ENS(ts->d_in, UB * 4) ENS(ts->d_out, UB * 4) ENS(ts->d_w, UB * 4)
     ENS(ts->m_enc, (size_t)std::max(D + 1, 2 * D) * W * 4) ENS(ts->m_dec, (size_t)D * W * 4) ENS(ts->m_cell, (size_t)B * (W + C) * 4)
     ENS(ts->X0, TB * W * 4) ENS(ts->H1, TB * 2 * W * 4) ENS(ts->u, TB * W * 4) ENS(ts->Y0, UB * W * 4) ENS(ts->Ym, UB * W * 4)
     ENS(ts->WQ, UB * W * 4) ENS(ts->Ast, (size_t)(U + 1) * B * T * 4) ENS(ts->WIN, UB * 4)
     ENS(ts->RecIn, UB * (C + W) * 4) ENS(ts->logits, UB * Vp * 4)
-    ENS(ts->dG, UB * W * 4) ENS(ts->d_enc, TB * C * 4) ENS(ts->du, TB * W * 4) ENS(ts->DWQ, UB * W * 4) ENS(ts->DSrows, UB * 16 * 4) ENS(ts->dhatt, UB * W * 4)
-    ENS(ts->dfin, (size_t)2 * D * B * W * 4) ENS(ts->dcbuf, (size_t)B * W * 4)
-    ENS(ts->dX0, TB * W * 4) ENS(ts->dXtop, UB * W * 4) ENS(ts->dXl, TB * 2 * W * 4) ENS(ts->dYl, UB * W * 4) ENS(ts->dOin, TB * 2 * W * 4)
-    ENS(ts->dcbuf2, (size_t)B * W * 4) ENS(ts->dvaP, (size_t)B * W * 4) ENS(ts->dbvP, (size_t)B * 4)
+    BWD(ts->dG, UB * W * 4) BWD(ts->d_enc, TB * C * 4) BWD(ts->du, TB * W * 4) BWD(ts->DWQ, UB * W * 4) BWD(ts->DSrows, UB * 16 * 4) BWD(ts->dhatt, UB * W * 4)
+    BWD(ts->dfin, (size_t)2 * D * B * W * 4) BWD(ts->dcbuf, (size_t)B * W * 4)
+    BWD(ts->dX0, TB * W * 4) BWD(ts->dXtop, UB * W * 4) BWD(ts->dXl, TB * 2 * W * 4) BWD(ts->dYl, UB * W * 4) BWD(ts->dOin, TB * 2 * W * 4)
+    BWD(ts->dcbuf2, (size_t)B * W * 4) BWD(ts->dvaP, (size_t)B * W * 4) BWD(ts->dbvP, (size_t)B * 4)
     for (auto& l : ts->layers) {
         const bool enc = l.name.compare(0, 3, "enc") == 0;
         l.len = enc ? T : U;
         const long long rows = (long long)l.len * B;
-        ENS(l.Cs, rows * W * 4) ENS(l.Gt, rows * 4 * W * 4) ENS(l.Z, rows * 4 * W * 4) ENS(l.dRec, rows * l.kr * 4)
+        ENS(l.Cs, rows * W * 4) ENS(l.Gt, rows * 4 * W * 4) ENS(l.Z, rows * 4 * W * 4) BWD(l.dRec, rows * l.kr * 4)
         if (l.name == "enc1_fw") { l.hs = ts->H1.as<float>(); l.hs_ld = 2 * W; }
         else if (l.name == "enc1_bw") { l.hs = ts->H1.as<float>() + W; l.hs_ld = 2 * W; }
         else if (deep && enc && l.name.size() > 3 && l.name.compare(l.name.size() - 3, 3, "_fw") == 0) { ENS(l.Hown, rows * 2 * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = 2 * W; }
         else if (deep && enc) { l.hs = (&l - 1)->hs + W; l.hs_ld = 2 * W; }        // (a backward direction: the second half of its forward partner's rows)
         else { ENS(l.Hown, rows * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = W; }
     }
-    ENS(ts->rec_cnt, REC_LAUNCH_CAP * persist_slot_bytes(B)) ENS(ts->dcalt, (size_t)2 * B * W * 4)
+    ENS(ts->rec_cnt, REC_LAUNCH_CAP * persist_slot_bytes(B)) BWD(ts->dcalt, (size_t)2 * B * W * 4)
     if (s.det) {
         ENS(ts->sum_parts, (size_t)std::max(MULTI_MAX * 64, (W + 63) / 64 + V) * 8)
         ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
@@ -618,6 +645,7 @@ static int plan_buffers(Step& s) {
     for (int n = 2; n <= D && deep; ++n) ENS(ts->XD[n], TB * 2 * W * 4)
     for (int n = 1; n < D; ++n) ENS(ts->DO[n], UB * W * 4)
     ENS(m->hfin, (size_t)D * B * W * 4) ENS(m->cfin, (size_t)(D + 1) * B * W * 4)       // (shared with the inference session)
+#undef BWD
 #undef ENS
     s.hfin = m->hfin.as<float>(); s.cfin = m->cfin.as<float>();
     // bridge_dense (seq2seq.py:299-301): the decoder starts from tanh(state . K + b) of every encoder layer's final h and c
@@ -839,10 +867,10 @@ static int forward_cell(Step& s) {
     return 0;
 }
 
-// Phase 5 leaves the projection's input s.proj_in, the step's cross-entropy in ts->loss and (training) dL/dlogits in place of the logits.
-static int loss_head(Step& s) {
+// The tied output projection: leaves its input s.proj_in and the logits [U*B][Vp] (columns [V, Vp) are not written).
+static int projection(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
-    const int B = s.B, U = s.U, W = s.W, V = s.V, Vp = s.Vp;
+    const int W = s.W, V = s.V, Vp = s.Vp;
     const long long UB = s.UB;
     TLayer& top = s.top();
     // (residual_connections: the projection reads the cell's outputs PLUS the cell's input sequence, seq2seq.py:359-360 at the top layer)
@@ -852,6 +880,14 @@ static int loss_head(Step& s) {
         s.proj_in = ts->Ytop.as<float>();
     }
     { GemmArgs g = plain_gemm(s.proj_in, s.proj_ld, (int)UB, W, ts->W_(ts->iE), V, nullptr, ts->logits.as<float>(), Vp); run_plain(m, g); }
+    return 0;
+}
+
+// Phase 5 leaves the projection's input s.proj_in, the step's cross-entropy in ts->loss and (training) dL/dlogits in place of the logits.
+static int loss_head(Step& s) {
+    TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, U = s.U, V = s.V, Vp = s.Vp;
+    if (int rc = projection(s)) return rc;
     launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, s.inv_count, ts->loss.as<double>(),
                       s.training ? 1 : 0, st, s.parts);
     return 0;
@@ -1206,7 +1242,7 @@ static int update(Step& s, double* loss_out, double* norm_out) {
         over_tensors(ts, 2048, [&](const MultiTensor& mt) {
             launch_adam_multi(mt, ts->normsq.as<double>(), ts->ap.clipnorm, lr_t, (float)b1, (float)b2, ts->ap.epsilon, st);
         });
-        refresh_derived(m);
+        refresh_derived(m, ts);
     }
     double nsq = 0.0;
     HIPCHK(hipMemcpyAsync(loss_out, ts->loss.p, 8, hipMemcpyDeviceToHost, st));
@@ -1223,6 +1259,7 @@ static int update(Step& s, double* loss_out, double* norm_out) {
 static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
     casv_model* m = s.m; TrainState* ts = s.ts;
     ts->B = s.B; ts->T = s.T; ts->U = s.U; ts->A = s.A;
+    ts->score_B = 0;                       // (a scoring call's attention rows are overwritten)
     m->encoded = false;                    // the final-state buffers are shared with the inference session
     if (int rc = plan_buffers(s)) return rc;
     if (int rc = stage_inputs(s)) return rc;
@@ -1280,6 +1317,162 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         if (!redo) return CASV_OK;
     }
     return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
+}
+
+// ---- scoring: teacher-forced log-probabilities of given targets (kt:407 / s2s:491-497, the forward pass of a mode-0 step) ----
+// What a scoring call hands back: (B,U) arrays in the caller's order, (B) sums, the dense alignment rows (B,U,T) or nullptr.
+struct ScoreOut { float* logp; int32_t* best; int32_t* rank; double* nll; int32_t* count; float* align; };
+
+// The head: log-probability, argmax and rank of every row, the lines' sums; leaves them on the device in the caller's order.
+static int score_head(Step& s) {
+    TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, U = s.U, V = s.V, Vp = s.Vp;
+    if (int rc = projection(s)) return rc;
+    launch_score_rows(ts->logits.as<float>(), ts->d_out.as<int>(), B, U, V, Vp, ts->s_logp.as<float>(), ts->s_best.as<int>(),
+                      ts->s_rank.as<int>(), st);
+    launch_score_lines(ts->s_logp.as<float>(), ts->d_out.as<int>(), B, U, V, ts->s_nll.as<double>(), ts->s_count.as<int>(), st);
+    return 0;
+}
+
+// One attempt at a scoring call: the first four phases of the step, the scoring head, the give-up check (as a mode-0 step:
+// *redo -- a persistent forward recurrence gave up, the back-off is set and the caller starts over).
+static int score_attempt(Step s, const ScoreOut& out, bool* redo) {
+    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
+    const int B = s.B, T = s.T, U = s.U;
+    ts->B = B; ts->T = T; ts->U = U; ts->A = s.A;
+    ts->score_B = 0;
+    m->encoded = false;                    // the final-state buffers are shared with the inference session
+    if (int rc = plan_buffers(s)) return rc;
+    if (int rc = ts->s_logp.ensure(s.UB * 4)) return rc;
+    if (int rc = ts->s_best.ensure(s.UB * 4)) return rc;
+    if (int rc = ts->s_rank.ensure(s.UB * 4)) return rc;
+    if (int rc = ts->s_nll.ensure((size_t)B * 8)) return rc;
+    if (int rc = ts->s_count.ensure((size_t)B * 4)) return rc;
+    if (int rc = stage_inputs(s)) return rc;
+    if (int rc = forward_layers(s)) return rc;
+    if (int rc = forward_cell(s)) return rc;
+    if (int rc = score_head(s)) return rc;
+    HIPCHK(hipGetLastError());
+    if (int rc = recurrences_gave_up(m, *redo)) return rc;
+    if (*redo) return CASV_OK;
+    HIPCHK(hipMemcpyAsync(out.logp, ts->s_logp.p, s.UB * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out.best, ts->s_best.p, s.UB * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out.rank, ts->s_rank.p, s.UB * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out.nll, ts->s_nll.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out.count, ts->s_count.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    std::vector<float> rows;               // the attention rows as the cell left them, [U][B][T] behind the initial row
+    if (out.align) {
+        rows.resize((size_t)s.UB * T);
+        HIPCHK(hipMemcpyAsync(rows.data(), ts->Ast.as<float>() + (size_t)B * T, rows.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int b = 0; b < B && out.align; ++b)
+        for (int u = 0; u < U; ++u)
+            memcpy(out.align + ((size_t)b * U + u) * T, rows.data() + ((size_t)u * B + b) * T, (size_t)T * 4);
+    ts->score_B = B; ts->score_U = U; ts->score_T = T;
+    m->stat_train_launches = ts->rec_launches;      // (statistic "train_persistent_launches", as a mode-0 step reports it)
+    if (m->prof.on) m->prof.collect();
+    return CASV_OK;
+}
+
+// Outside a session the scoring call runs on a forward-only state of its own (m->score), built from the handle's committed weights
+// and kept until they are committed anew; the phases find it where they find a session's state, in m->train, for the call's duration.
+struct ScoreStateScope {
+    casv_model* m; bool borrowed;
+    ~ScoreStateScope() { if (borrowed) m->train = nullptr; }
+};
+static int score_state(casv_model* m) {
+    if (m->score && m->score->commit_gen == m->commit_gen) return CASV_OK;
+    (void)casv_score_release(m);
+    if (m->W > 1024) return fail(CASV_ERR_ARG, "scoring supports width <= 1024");
+    if (!m->committed) return fail(CASV_ERR_STATE, "casv_commit_weights must run first");
+    TrainState* ts = new TrainState();
+    ts->forward_only = true; ts->commit_gen = m->commit_gen;
+    m->score = ts;
+    if (int rc = build_state(m, ts, "")) { (void)casv_score_release(m); return rc; }
+    return CASV_OK;
+}
+
+extern "C" int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
+                                  const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                                  float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
+    if (!m || !enc_idx || !dec_in || !dec_out || !logp || !best || !rank || !nll || !count) return fail(CASV_ERR_ARG, "null argument");
+    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
+    const long long UB = (long long)U * B;
+    for (long long i = 0; i < UB; ++i) {     // (before anything is launched)
+        if (dec_out[i] < -1 || dec_out[i] >= m->V) return fail(CASV_ERR_ARG, "dec_out[%lld] = %d outside [-1, %d)", i, dec_out[i], m->V);
+        if (dec_in[i] < -1 || dec_in[i] >= m->V) return fail(CASV_ERR_ARG, "dec_in[%lld] = %d outside [-1, %d)", i, dec_in[i], m->V);
+    }
+    HIPCHK(hipSetDevice(m->device));
+    ScoreStateScope scope{m, false};
+    if (!m->train) {
+        if (int rc = score_state(m)) return rc;
+        m->train = m->score; scope.borrowed = true;
+    }
+    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));       // (the forward pass of a mode-0 step, in its arithmetic)
+    OrderedScope ordered(m->deterministic);
+    const std::vector<float> ones((size_t)UB, 1.0f);            // (stage_inputs stages the step's sample weights: the head reads none)
+    Step s{};
+    s.m = m; s.ts = m->train; s.st = m->stream;
+    s.mode = 0; s.B = B; s.T = T; s.U = U; s.A = A;
+    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = ones.data();
+    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
+    s.TB = (long long)T * B; s.UB = UB;
+    // (no masks, no regulariser; det / fused govern the backward pass and the ordered sums of the loss: the head has neither, and
+    // persist_slot and the launchers read the "deterministic" option from the handle)
+    s.training = false; s.det = false; s.fused = false;
+    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
+    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
+    const ScoreOut out{logp, best, rank, nll, count, align};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool redo = false;
+        if (int rc = score_attempt(s, out, &redo)) return rc;
+        if (!redo) return CASV_OK;
+    }
+    return fail(CASV_ERR_STATE, "the scoring call gave up twice: its second attempt took a persistent launch");
+}
+
+extern "C" int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w) {
+    if (!m || !lo || !w) return fail(CASV_ERR_ARG, "null argument");
+    TrainState* ts = m->train ? m->train : m->score;
+    if (!ts || !ts->score_B) return fail(CASV_ERR_STATE, "no scoring call to take alignments from");
+    if (K < 2 * m->cfg.window_width + 1 || K > 64) return fail(CASV_ERR_ARG, "K=%d: need at least 2*window_width+1 = %d weights per step (at most 64)", K, 2 * m->cfg.window_width + 1);
+    HIPCHK(hipSetDevice(m->device));
+    const size_t n = (size_t)ts->score_B * ts->score_U;
+    if (int rc = ts->s_lo.ensure(n * 4)) return rc;
+    if (int rc = ts->s_w.ensure(n * K * 4)) return rc;
+    launch_score_extract_sparse(ts->Ast.as<float>(), ts->WIN.as<int>(), ts->score_B, ts->score_U, ts->score_T, K, ts->s_lo.as<int>(),
+                                ts->s_w.as<float>(), m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lo, ts->s_lo.p, n * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(w, ts->s_w.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
+}
+
+// Test support: the head alone on the caller's logits (R,V), laid out with the library's row stride and the padding filled.
+extern "C" int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
+                                     float* logp, int32_t* best, int32_t* rank) {
+    if (!m || !logits || !target || !logp || !best || !rank) return fail(CASV_ERR_ARG, "null argument");
+    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
+    HIPCHK(hipSetDevice(m->device));
+    const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
+    std::vector<float> x((size_t)R * Vp, pad_value);
+    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
+    DevBuf dx, dt, dl, db, dr;
+    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
+        release_on_exit{{&dx, &dt, &dl, &db, &dr}, m->stream};
+    if (int rc = dx.ensure(x.size() * 4)) return rc;
+    for (DevBuf* b : {&dt, &dl, &db, &dr}) if (int rc = b->ensure((size_t)R * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dt.p, target, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
+    launch_score_rows(dx.as<float>(), dt.as<int>(), R, 1, V, Vp, dl.as<float>(), db.as<int>(), dr.as<int>(), m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(logp, dl.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(best, db.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(rank, dr.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
 }
 
 // Keras-layout view of the master weights (which = 0), of the last gradients (which = 1) or of Adam's m (2) / v (3).

@@ -23,6 +23,16 @@ void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, lon
 // parts (ordered form, "deterministic" train step): [min(ceil(B*U/4), 2048)] doubles of workspace, or nullptr
 void launch_softmax_ce(float* logits, const int* target, const float* weight, int B, int U, int V, int Vp, float inv_count,
                        double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
+// Scoring head (casv_score_targets): per row r = u * B + b of the logits [U*B][Vp] and target t = target[b][u], in the caller's
+// (B,U) order -- logp = log softmax(x)[t] in the log domain, unclipped (0 where t = -1); best = lowest index of the row's maximum;
+// rank = entries strictly above x[t] (-1 where unscored).  A row with a NaN among its V entries or a maximum that is not finite
+// gives NaN / -1 / -1.  Columns [V, Vp) are never read.
+void launch_score_rows(const float* logits, const int* target, int B, int U, int V, int Vp, float* logp, int* best, int* rank,
+                       hipStream_t st);
+// ... nll[b] = sum_u -(double)logp[b][u] over the scored positions in the order of u, count[b] = how many
+void launch_score_lines(const float* logp, const int* target, int B, int U, int V, double* nll, int* count, hipStream_t st);
+// ... the cell's attention rows Ast [U+1][B][T] / windows WIN [U][B] in window form, (B,U) order: lo, w [K] per step
+void launch_score_extract_sparse(const float* Ast, const int* WIN, int B, int U, int T, int K, int* lo, float* w, hipStream_t st);
 
 // The forward recurrence of up to two independent plain LSTM layers over all their time steps as ONE launch (train_persist.hip).
 struct RecJob {

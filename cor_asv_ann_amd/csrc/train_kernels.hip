@@ -218,6 +218,97 @@ void launch_softmax_ce(float* logits, const int* target, const float* weight, in
                        Vp, inv_count, loss, want_grad);
 }
 
+// ---- scoring head (casv_score_targets, kt:407 / s2s:491-497 without the clip): log-probability, argmax and rank per row ----
+// One wave per row, as softmax_ce_kernel; two passes over the row's first V columns (the padding columns [V, Vp) are never read):
+// the maximum and the NaN test, then the exponentials' sum, the lowest index of the maximum and the count of entries above the
+// target's.  Nothing is written back into the logits, no probability is formed: logp = (x[t] - m) - log(sum exp(x - m)).
+// The results go out in the caller's (B,U) order, src = b * U + u of row r = u * B + b.
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target, long long rows,
+                                                         int B, int U, int V, int Vp, float* __restrict__ logp, int* __restrict__ best,
+                                                         int* __restrict__ rank) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long long r = blockIdx.x * 4LL + wave; r < rows; r += 4LL * gridDim.x) {
+        const float* x = logits + r * Vp;
+        float m = -INFINITY;
+        int nan = 0;
+        for (int v = lane; v < V; v += 64) { const float xv = x[v]; nan |= xv != xv; m = fmaxf(m, xv); }      // (fmaxf passes a NaN by)
+        m = wave_butterfly(m, [](float a, float b) { return fmaxf(a, b); });
+        nan = wave_butterfly(nan, [](int a, int b) { return a | b; });
+        const bool valid = !nan && m > -INFINITY && m < INFINITY;
+        const long long src = (r % B) * U + r / B;
+        const int tg = target[src];
+        const bool scored = tg >= 0 && tg < V;
+        const float xt = scored ? x[tg] : 0.f;
+        float sum = 0.f;
+        int first = V, above = 0;
+        for (int v = lane; v < V; v += 64) {
+            const float xv = x[v];
+            sum += expf(xv - m);
+            if (xv == m) first = min(first, v);
+            above += xv > xt;
+        }
+        sum = wsum(sum);
+        first = wave_butterfly(first, [](int a, int b) { return min(a, b); });
+        above = wave_butterfly(above, [](int a, int b) { return a + b; });
+        if (lane == 0) {
+            logp[src] = !valid ? __builtin_nanf("") : scored ? (xt - m) - logf(sum) : 0.f;
+            best[src] = valid ? first : -1;
+            rank[src] = valid && scored ? above : -1;
+        }
+    }
+}
+void launch_score_rows(const float* logits, const int* target, int B, int U, int V, int Vp, float* logp, int* best, int* rank,
+                       hipStream_t st) {
+    const long long rows = (long long)B * U;
+    const long long wgs = std::min<long long>((rows + 3) / 4, 2048);
+    hipLaunchKernelGGL(score_rows_kernel, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, rows, B, U, V, Vp, logp, best, rank);
+}
+
+// ... and the lines' sums: nll[b] = sum over the scored positions of -(double)logp[b][u], one thread per line adding in the order
+// of u (one accumulator, no atomics: the same bits whatever the launch shape); count[b] = scored positions.
+__global__ __launch_bounds__(64) void score_lines_kernel(const float* __restrict__ logp, const int* __restrict__ target, int B, int U,
+                                                         int V, double* __restrict__ nll, int* __restrict__ count) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    double acc = 0.0;
+    int n = 0;
+    for (int u = 0; u < U; ++u) {
+        const int tg = target[(long long)b * U + u];
+        if (tg < 0 || tg >= V) continue;
+        acc += -(double)logp[(long long)b * U + u];
+        ++n;
+    }
+    nll[b] = acc;
+    count[b] = n;
+}
+void launch_score_lines(const float* logp, const int* target, int B, int U, int V, double* nll, int* count, hipStream_t st) {
+    hipLaunchKernelGGL(score_lines_kernel, dim3((B + 63) / 64), dim3(64), 0, st, logp, target, B, U, V, nll, count);
+}
+
+// ... and the window form of the cell's attention rows in the caller's (B,U) order: lo = first position of step u's window (-1: the
+// row is all NaN), w = its K weights (zeros beyond the window).  Ast [U+1][B][T] (row u + 1 belongs to step u), WIN [U][B].
+__global__ __launch_bounds__(256) void score_extract_sparse_kernel(const float* __restrict__ Ast, const int* __restrict__ WIN, int B, int U,
+                                                                   int T, int K, int* __restrict__ lo_out, float* __restrict__ w_out) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;       // (b, u)
+    if (i >= (long long)B * U) return;
+    const int b = (int)(i / U), u = (int)(i % U);
+    const int win = WIN[(long long)u * B + b];
+    const int lo = win & 0xffff, cnt = win >> 16;
+    float* w = w_out + i * K;
+    if (cnt <= 0) {
+        lo_out[i] = -1;
+        for (int k = 0; k < K; ++k) w[k] = __builtin_nanf("");
+        return;
+    }
+    lo_out[i] = lo;
+    const float* a = Ast + ((long long)(u + 1) * B + b) * T;
+    for (int k = 0; k < K; ++k) w[k] = (k < cnt && lo + k < T) ? a[lo + k] : 0.0f;
+}
+void launch_score_extract_sparse(const float* Ast, const int* WIN, int B, int U, int T, int K, int* lo, float* w, hipStream_t st) {
+    const long long n = (long long)B * U;
+    hipLaunchKernelGGL(score_extract_sparse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Ast, WIN, B, U, T, K, lo, w);
+}
+
 // ---- LSTM cell backward, pointwise part ----
 // dh = a*mask_a + b + c ; gates/dz in the interleaved column order of the fused weight
 __global__ void lstm_bwd_kernel(const LstmBwdBatch batch) {

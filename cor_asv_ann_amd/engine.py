@@ -384,6 +384,56 @@ class HipEngine(object):
     def train_end(self):
         nv.check(self.lib.casv_train_end(self.handle))
 
+    # -- scoring -------------------------------------------------------------------------------
+    def score_targets(self, enc_idx, enc_val, dec_in, dec_out, want_align=False):
+        """Teacher-forced log-probabilities of the targets dec_out (casv_score_targets; arrays as train_step, no weights, no masks).
+        Returns (logp float32 (B,U), best int32 (B,U), rank int32 (B,U), nll float64 (B), count int32 (B), align) with align = None,
+        the dense rows (B,U,T) (want_align=True) or the window form (lo (B,U), w (B,U,K)) (want_align='sparse').  Inside a training
+        session the session's weights score, outside one the committed weights (a forward-only state kept until score_release)."""
+        enc_idx = nv.carray(enc_idx, np.int32)
+        if enc_idx.ndim == 2:
+            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
+        B, T, A = enc_idx.shape
+        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        dec_in = nv.carray(dec_in, np.int32)
+        dec_out = nv.carray(dec_out, np.int32)
+        U = dec_in.shape[1]
+        assert dec_in.shape == dec_out.shape == (B, U)
+        logp = np.empty((B, U), np.float32)
+        best = np.empty((B, U), np.int32)
+        rank = np.empty((B, U), np.int32)
+        nll = np.empty((B,), np.float64)
+        count = np.empty((B,), np.int32)
+        sparse = want_align == 'sparse'
+        align = np.empty((B, U, T), np.float32) if want_align and not sparse else None
+        nv.check(self.lib.casv_score_targets(self.handle, B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), nv.ptr(dec_out),
+                                             nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count), nv.ptr(align)))
+        if sparse:
+            K = 2 * self.window_width + 1
+            lo = np.empty((B, U), np.int32)
+            w = np.empty((B, U, K), np.float32)
+            nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(lo), nv.ptr(w)))
+            align = (lo, w)
+        return logp, best, rank, nll, count, align
+
+    def score_release(self):
+        """Drop the forward-only state score_targets keeps outside a training session (allowed when there is none)."""
+        nv.check(self.lib.casv_score_release(self.handle))
+
+    def debug_score_rows(self, logits, target, pad_value=0.0):
+        """Test support (casv_debug_score_rows): the scoring head alone on logits (R,V) and targets (R); the padding columns of the
+        device rows hold pad_value.  Returns (logp, best, rank)."""
+        logits = nv.carray(logits, np.float32)
+        target = nv.carray(target, np.int32)
+        R, V = logits.shape
+        assert target.shape == (R,)
+        logp = np.empty((R,), np.float32)
+        best = np.empty((R,), np.int32)
+        rank = np.empty((R,), np.int32)
+        nv.check(self.lib.casv_debug_score_rows(self.handle, R, V, nv.ptr(logits), nv.ptr(target), float(pad_value), nv.ptr(logp),
+                                                nv.ptr(best), nv.ptr(rank)))
+        return logp, best, rank
+
     # -- measurement ---------------------------------------------------------------------------
     def profile(self, enable=True):
         """0/False = off, 1/True = every kernel class, 2 = only the dominant kernel (fused LSTM GEMM)."""

@@ -644,6 +644,41 @@ class Sequence2Sequence(object):
         raw = self._decode_prepared(prepared, fast, greedy, alignments, [bool(line) for line in lines])
         return self._results_of(lines, prepared, raw, fast, greedy, alignments)
 
+    def score_lines(self, sources, targets, conf=None, alignments=False):
+        """How probable the model finds each target line for its source line: the teacher-forced forward pass of `test_on_batch`
+        (keras_train.py:407) with the per-character quantities handed back (`HipEngine.score_targets`).  Each line must end in a
+        newline.  Returns (logprobs, scores, predictions, ranks, aligns), one entry per pair:
+        logprobs -- list of log p(target character | source, target characters before), newline included (natural log, unclipped);
+        scores -- mean -log p over the line, the convention of `correct_lines`' scores;
+        predictions -- the string of the characters the model finds most probable at each target position;
+        ranks -- list of ints: how many characters the model finds more probable than the target's (0 = the model agrees);
+        aligns -- [] (`alignments=False`), a `SparseAlignment` (True) or the list of T-wide rows ('dense'), as `correct_lines`.
+        A pair with an empty source or target is skipped as `evaluate` skips it: [], 0.0, '', [], [].  The remaining pairs are
+        scored in chunks of `batch_size`; a line's result depends on the padded lengths of its chunk (as in training: the
+        backward encoder direction walks the padding)."""
+        assert self.status == 2
+        assert len(sources) == len(targets) and (conf is None or len(conf) == len(sources))
+        from .training import batch_to_indices
+        eng = self._require_engine()
+        n = len(sources)
+        logprobs, scores, predictions = [[] for _ in range(n)], [0.0] * n, [''] * n
+        ranks, aligns = [[] for _ in range(n)], [[] for _ in range(n)]
+        want_align = False if not alignments else (True if alignments == 'dense' else 'sparse')
+        live = [j for j in range(n) if sources[j] and targets[j]]
+        for start in range(0, len(live), self.batch_size):
+            chunk = live[start:start + self.batch_size]
+            idx, val, dec_in, dec_out, _ = batch_to_indices(self, [sources[j] for j in chunk], [targets[j] for j in chunk],
+                                                            None if conf is None else [conf[j] for j in chunk])
+            logp, best, rank, nll, count, align = eng.score_targets(idx, val, dec_in, dec_out, want_align=want_align)
+            for i, j in enumerate(chunk):
+                k = int(count[i])               # (the scored positions are the first k: the target's characters)
+                logprobs[j] = logp[i, :k].tolist()
+                scores[j] = float(nll[i]) / max(k, 1)
+                predictions[j] = self._chars(best[i, :k][best[i, :k] >= 0])      # (-1, an invalid row: no character)
+                ranks[j] = rank[i, :k].tolist()
+                aligns[j] = self._alignment_rows(align, i, k, idx.shape[1])
+        return logprobs, scores, predictions, ranks, aligns
+
     def correct_batches(self, batches, fast=True, greedy=True, alignments=True, after_decode=None):
         """`correct_lines` over a stream of batches -- an iterable of `lines` or of `(lines, conf)` -- as a three-stage pipeline:
         a worker thread turns the next batch into index arrays, a second one drives the device (its C-ABI calls release the GIL),

@@ -211,6 +211,39 @@ int casv_train_sync_weights(casv_model* m);
  * (_resync_decoder after training, seq2seq.py:645). */
 int casv_train_end(casv_model* m);
 
+/* Teacher-forced log-probabilities of given targets: the forward pass of model.test_on_batch (keras_train.py:407) on the graph
+ * compiled at seq2seq.py:491-497, with the per-position quantities handed back instead of the batch's clipped cross-entropy.
+ * Arrays as casv_train_step: enc_idx / enc_val (B,T,A), dec_in / dec_out (B,U), -1 = true-zero row / unscored position; the two
+ * decoder arrays are independent.  An entry of dec_in or dec_out outside [-1, V) is CASV_ERR_ARG, found before anything is launched.
+ * Per position (b,u) with target t = dec_out[b][u], over the V logits x of the row:
+ *   logp = log softmax(x)[t], computed in the log domain in float32 and NOT clipped (0 where t = -1; -inf where x[t] = -inf);
+ *   best = lowest index of the row's maximum (scored or not); rank = number of entries strictly above x[t] (-1 where t = -1);
+ *   a row with a NaN entry or a maximum that is not finite gives logp = NaN, best = -1, rank = -1.
+ * Per line b: nll = sum over the scored positions of -(double)logp, added in double in the order of u (the same bits whatever the
+ * launch shape; NaN if a logp is), count = scored positions.  align: NULL, or (B,U,T) the attention weights the cell used at
+ * every step.  No masks, no regulariser; the arithmetic, "deterministic" and "persistent" govern the forward pass exactly as
+ * they govern a mode-0 casv_train_step, the give-up path included ("train_persistent_launches" / "train_give_ups" report it).
+ * Inside a training session the call uses the session's current weights and changes neither step count, moments nor gradients.
+ * Outside one it uses the weights of the last casv_commit_weights and needs no casv_train_begin: it keeps a forward-only state
+ * (weights in the train layout, forward buffers; no gradient, no Adam moment, no backward buffer) from call to call, rebuilds it
+ * when the weights are committed anew, and casv_score_release, casv_train_begin and casv_model_destroy drop it;
+ * casv_train_get_step still answers CASV_ERR_STATE afterwards.  Like casv_train_step the call shares the final-state buffers
+ * (hfin / cfin) with the inference session and leaves the handle without an encoded batch: casv_encode again before decoding. */
+int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
+                       const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                       float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align);
+/* The attention rows of the LAST casv_score_targets call (kt:407 / s2s:491-497) in window form, same conventions as
+ * casv_get_alignments_sparse: lo (B,U) first position of the window (-1: the row is all NaN), w (B,U,K) the weights from there
+ * (zeros beyond the window), K >= 2*window_width+1.  CASV_ERR_STATE once a train step or casv_score_release has run since. */
+int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w);
+/* Drop the forward-only state of casv_score_targets (kt:407 / s2s:491-497); allowed when there is none. */
+int casv_score_release(casv_model* m);
+/* Test support, like casv_debug_activation: the scoring head (kt:407 / s2s:491-497) alone on the caller's logits (R,V) and targets
+ * (R); the entry lays the rows out with the library's row stride Vp and fills the padding columns [V, Vp) with pad_value, which
+ * no output may depend on.  tests/test_gpu_score.py compares the results with float64. */
+int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
+                          float* logp, int32_t* best, int32_t* rank);
+
 /* Multi-GPU: lines are independent (seq2seq.py:113 stateful=False), so one process per GPU decodes a
  * contiguous shard of the lines with its own handle and NO data-path collective; what crosses the GPUs is one all-gather
  * of fixed-width result records per batch -- RCCL over xGMI.  The reference has no counterpart (single process,
