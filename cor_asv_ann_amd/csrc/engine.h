@@ -127,7 +127,7 @@ struct casv_model {
     int R = 0, S = 0;
     std::vector<DevBuf> st_h, st_c;
     DevBuf st_a, st_p, ctx, wq, logits, prev, pin, apos, amax1, d_step, d_line, d_nan;
-    DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (engine.hip, launch_step)
+    DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (decode.hip, launch_step)
     DevBuf o_idx, o_prob, o_align, st_win, sp_lo, sp_w;
     // lm_predict: per-step scratch of the LM output -- h of the LM cell [R][W] (its c [R][W] is written and
     // never read), LM logits [R][Vp], casv_decoder_step_lm's probabilities [R][Vp]; wide beams: the LM probability of every child
@@ -152,8 +152,6 @@ struct casv_model {
     bool fused_backward = true;                           // train step: cell backward fused into the step's data GEMM (gemm_bwd.hip)
     bool deterministic = false;                           // train step: every sum in a fixed order ("Reproducible training")
     bool lm_predict = false;                              // beam decode: children's costs from the decoder's context-free LM (option "lm_predict")
-    const int* skip_nact = nullptr;                       // beam decode: live rows per line, handed to the step's kernels when
-    int skip_group = 0;                                   // skipping can pay (wide beams, or a line has finished); rows per line
     // the captured step graph of the last decode configuration (option "graph"): kept across calls, rebuilt when the
     // configuration or any device buffer changes
     hipGraph_t step_graph = nullptr; hipGraphExec_t step_exec = nullptr; std::string step_graph_key;
@@ -244,7 +242,10 @@ inline void run_gemm(casv_model* m, int epi, GemmArgs& g) {
 }
 
 
-// encoder.hip, for the entry points that consume the encoder outputs (engine.hip):
+// decode.hip, for the result records (engine.hip): identity of the device buffers a finished decode leaves its results in
+unsigned long long decode_buffers_signature(const casv_model* m);
+
+// encoder.hip, for the entry points that consume the encoder outputs (decode.hip):
 // The encoder outputs in the arithmetic `want` of the entry point that is about to consume them (arithmetic_of): computed at the first
 // such call after casv_encode / casv_set_encoder_outputs, kept for further calls of the same arithmetic, redone for the other.
 int ensure_encoded(casv_model* m, int want);

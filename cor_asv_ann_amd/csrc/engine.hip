@@ -1,5 +1,5 @@
-// Host side of the C ABI (include/cor_asv_ann_hip.h): weight repacking, the decoder step (seq2seq.py:416-480) and the greedy /
-// beam decode loops (seq2seq.py:1215-1544).  The encoder pass (seq2seq.py:237-314) is encoder.hip.
+// Host side of the C ABI (include/cor_asv_ann_hip.h): the handle, weight repacking, result records, statistics, profile, debug entry
+// points and options.  The decode entry points are decode.hip, the encoder pass (seq2seq.py:237-314) encoder.hip, training train.hip.
 #include "engine.h"
 
 static std::map<std::string, size_t> expected_shapes(const casv_config& c) {
@@ -255,721 +255,6 @@ extern "C" int casv_commit_weights(casv_model* m) {
             }
     m->committed = true;
     ++m->commit_gen;                    // (a scoring state built from the weights before is rebuilt: train.hip, score_state)
-    return CASV_OK;
-}
-
-// ---- decode session ----
-// Identity of the device buffers a finished decode leaves its results in (casv_get_alignments_sparse reads them later through
-// raw pointers kept in last_beam): changes whenever one of them has been reallocated.
-static unsigned long long decode_buffers_signature(const casv_model* m) {
-    unsigned long long h = 1469598103934665603ull;
-    for (const DevBuf* b : {&m->st_a, &m->st_q, &m->st_win, &m->b_parent, &m->b_chr, &m->b_prob, &m->b_cum, &m->b_len, &m->b_exp, &m->b_k, &m->b_rejpos,
-                            &m->b_count, &m->b_fkey, &m->b_fid, &m->b_fn, &m->b_ftotal, &m->b_created, &m->bo_idx, &m->bo_prob, &m->bo_len,
-                            &m->bo_score, &m->o_idx, &m->o_prob, &m->d_idx, &m->d_val})
-        h = (h ^ (unsigned long long)(uintptr_t)b->p) * 1099511628211ull;
-    return h;
-}
-static int ensure_session(casv_model* m, int R, int S) {
-    const int W = m->W, Vp = m->Vp, C = m->C, T = m->T, D = m->D;
-    const size_t slots = (size_t)(S + 1) * R;
-    for (int n = 1; n <= D; ++n) {
-        if (int rc = m->st_h[n].ensure(slots * W * 4)) return rc;
-        if (int rc = m->st_c[n].ensure(slots * W * 4)) return rc;
-    }
-    if (int rc = m->st_a.ensure(slots * T * 4)) return rc;
-    if (int rc = m->st_p.ensure(slots * Vp * 4)) return rc;
-    if (int rc = m->st_win.ensure(slots * 4)) return rc;
-    if (int rc = m->ctx.ensure((size_t)R * C * 4)) return rc;
-    if (int rc = m->wq.ensure((size_t)R * W * 4)) return rc;
-    if (int rc = m->logits.ensure((size_t)R * Vp * 4)) return rc;
-    if (int rc = m->prev.ensure((size_t)R * 4)) return rc;
-    if (int rc = m->pin.ensure((size_t)R * Vp * 4)) return rc;
-    if (int rc = m->apos.ensure((size_t)R * 8)) return rc;
-    if (int rc = m->amax1.ensure((size_t)R * 4)) return rc;
-    if (int rc = m->d_step.ensure(16)) return rc;
-    if (int rc = m->d_nan.ensure(16)) return rc;
-    m->R = R; m->S = S;
-    return 0;
-}
-
-// Initial decoder state = encoder final states (seq2seq.py:339,352), zero alignment, zero input -- and whatever else the caller
-// wants cleared ahead of its first step (`ops`: result arrays, hand-off counters): ONE launch for all of it (a memset or row
-// scatter of its own costs ~5 us of an otherwise idle GPU each: 13 of them in front of every batch of configs[1]).
-static int init_root(casv_model* m, int rows_per_line, SmallOps ops = SmallOps{}) {
-    const int W = m->W, Vp = m->Vp, T = m->T, D = m->D, R = m->R, B = m->B;
-    // The operations of one launch run in no order among themselves: the initial alignment must not be both cleared and copied
-    // by it.  One row per line: the copy covers the whole slot.  Several: the clear goes ahead as a launch of its own.
-    bool ok = true;
-    if (!m->has_a0) ok = ops.fill(m->st_a.p, (size_t)R * T * 4);
-    else if (rows_per_line != 1 || R != B) HIPCHK(hipMemsetAsync(m->st_a.p, 0, (size_t)R * T * 4, m->stream));
-    if (m->has_a0) ok = ok && ops.rows(m->a0.as<float>(), T, m->st_a.as<float>(), T, B, T, rows_per_line);
-    ok = ok && ops.fill(m->st_p.p, (size_t)R * Vp * 4) && ops.fill(m->logits.p, (size_t)R * Vp * 4);
-    for (int n = 1; n <= D; ++n) {
-        ok = ok && ops.rows(m->hfin.as<float>() + (size_t)(n - 1) * B * W, W, m->st_h[n].as<float>(), W, B, W, rows_per_line);
-        ok = ok && ops.rows(m->cfin.as<float>() + (size_t)(n - 1) * B * W, W, m->st_c[n].as<float>(), W, B, W, rows_per_line);
-    }
-    ok = ok && ops.fill(m->d_step.p, 16) && ops.fill(m->d_nan.p, 16);
-    if (!ok || !launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-    return 0;
-}
-
-// One decoder_model step on R rows (seq2seq.py:416-480).  beam=true reads the input rows from `pin`,
-// otherwise from the previous slot of the score store (the fed-back softmax, seq2seq.py:1252).
-// lm=true (lm_predict, seq2seq.py:464-470) also computes the LM output: the top cell once more on the decoder's
-// own top-layer input and states with a zero context -- a second job of the top cell's launch that contracts the same packed weights
-// over the x and h segments only (the context rows are skipped: 0 . K_ctx) and leaves h in m->lm_h -- and its tied projection, a
-// job of the output projection's launch, into m->lm_logits.  Rows whose LM context would be NaN are marked by whoever reads the
-// logits (the beam step kernel; lm_softmax_kernel).  lm=false launches exactly what the step launched without the option.
-static void launch_step(casv_model* m, bool beam, int mode, const int* line, int rows_per_line,
-                        int* o_idx, float* o_prob, const int* step_ptr, int step_imm, bool softmax = true, bool lm = false) {
-    const int W = m->W, V = m->V, Vp = m->Vp, C = m->C, T = m->T, D = m->D, R = m->R;
-    const long long RW = (long long)R * W;
-    // previous-step rows of the state stores: the beam gathers its parents' expansions through `prev`; without a beam
-    // row r of step t simply continues row r of step t-1 (slot arithmetic, no index array and no kernel to fill one)
-    const int* prev = beam ? m->prev.as<int>() : nullptr;
-    auto hseg = [&](float* base, int off) {
-        return beam ? mkseg(base, W, W, off, prev) : mkseg(base, W, W, off, nullptr, RW, 1, 0);
-    };
-    const int* live = beam ? m->skip_nact : nullptr;      // set by casv_decode_beam when skipping can pay
-    // layer input: layer 1 takes the fed-back distribution itself (embedding folded into its weights,
-    // pack_dec1), layer n > 1 the output of layer n-1 at this step
-    auto xseg = [&](int n) {
-        if (n == 1)
-            return beam ? mkseg(m->pin.as<float>(), Vp, Vp, 0)
-                        : mkseg(m->st_p.as<float>(), Vp, Vp, 0, nullptr, (long long)R * Vp, 1, 0);
-        return mkseg(m->st_h[n - 1].as<float>(), W, W, 0, nullptr, RW, 1, 1);
-    };
-    auto xwidth = [&](int n) { return n == 1 ? Vp : W; };
-    // attention query of this step: h_{t-1} . W_a + b_UW (attention.py:539) -- depends only on the previous step, so it
-    // shares the launch of layer 1 (a job with the plain epilogue) instead of waiting behind the lower layers
-    // The beam search computes it AHEAD, once per expansion instead of once per child row: the query of step s + 1's rows is a
-    // function of their parent's h_D alone, so it rides in step s's output projection (same A operand: the new h_D rows, ungathered)
-    // into a store indexed like the state stores, and the attention rows fetch their parent's query through `prev` -- one launch
-    // less per step (the same contraction per row: the same bits).
-    const bool query_ahead = beam;
-    GemmArgs gq{};
-    gq.nseg = 1; gq.a[0] = query_ahead ? mkseg(m->st_h[D].as<float>(), W, W, 0, nullptr, RW, 1, 1) : hseg(m->st_h[D].as<float>(), 0);
-    gq.Bt = m->WaT.as<float>(); gq.bias = m->bUW.as<float>(); gq.M = R; gq.N = W; gq.Ktot = W; gq.b_static = 1;
-    gq.out = query_ahead ? mkslot(m->st_q.as<float>(), W, RW, 1, 1) : mkslot(m->wq.as<float>(), W);
-    gq.step_ptr = step_ptr; gq.step_imm = step_imm;
-    gq.nact = live; gq.nact_group = m->skip_group;
-    auto lower = [&](int n) {               // layer n < D on [x | h]
-        GemmArgs g{};
-        g.nseg = 2;
-        g.a[0] = xseg(n);
-        g.a[1] = hseg(m->st_h[n].as<float>(), xwidth(n));
-        g.Bt = m->dec[n].wt.as<float>(); g.bias = m->dec[n].bias.as<float>(); g.b_static = 1;
-        g.M = R; g.N = 4 * W; g.Ktot = xwidth(n) + W;
-        g.out = mkslot(m->st_h[n].as<float>(), W, RW, 1, 1);
-        g.c_in = hseg(m->st_c[n].as<float>(), 0);
-        g.c_out = mkslot(m->st_c[n].as<float>(), W, RW, 1, 1);
-        g.step_ptr = step_ptr; g.step_imm = step_imm;
-        g.nact = live; g.nact_group = m->skip_group;
-        return g;
-    };
-    if (D >= 2) {
-        GemmBatch b{};
-        b.g[0] = lower(1); b.count = 1;
-        if (!query_ahead) { b.g[1] = gq; b.g[1].epi_plain = 1; b.count = 2; }
-        run_gemm_batch(m, EPI_LSTM, b);
-    } else if (!query_ahead) {
-        run_gemm(m, EPI_PLAIN, gq);
-    }
-    {   // the attention rows need only the query: ahead of the remaining layers, which can then share one launch
-        AttnArgs a{};
-        a.wq = query_ahead ? m->st_q.as<float>() : m->wq.as<float>(); a.wq_rows = query_ahead ? prev : nullptr;
-        a.u = m->u.as<float>(); a.enc = m->enc_out; a.va = m->va.as<float>(); a.bv = m->bv.as<float>();
-        a.a_base = m->st_a.as<float>(); a.prev = prev; a.line = line; a.rows_per_line = rows_per_line;
-        a.ctx = m->ctx.as<float>(); a.R = R; a.T = T; a.W = W; a.C = C; a.window = m->cfg.window_width;
-        a.step_ptr = step_ptr; a.step_imm = step_imm; a.apos = m->apos.as<double>(); a.amax1 = m->amax1.as<int>(); a.nrows = nullptr;
-        a.u_line = (long long)T * W; a.u_time = W; a.enc_line = (long long)T * C; a.enc_time = C; a.win_out = nullptr;
-        a.win_store = m->st_win.as<int>();
-        a.nact = live; a.nact_group = m->skip_group;
-        hipEvent_t ev{};
-        const double win = 2.0 * m->cfg.window_width + 1;
-        m->prof_begin(PC_ATTN, (double)R * win * (4.0 * W + 2.0 * C), 4.0 * R * (win * (W + C) + W + 2.0 * T + C), ev);
-        launch_attention(a, m->stream);
-        m->prof_end(PC_ATTN, ev);
-    }
-    GemmArgs gtop{};
-    {   // top cell on [x | ctx] (attention.py:341-342, seq2seq.py:343-349)
-        GemmArgs& g = gtop;
-        g.nseg = 3;
-        g.a[0] = xseg(D);
-        g.a[1] = mkseg(m->ctx.as<float>(), C, C, xwidth(D));
-        g.a[2] = hseg(m->st_h[D].as<float>(), xwidth(D) + C);
-        g.Bt = m->dec[D].wt.as<float>(); g.bias = m->dec[D].bias.as<float>(); g.b_static = 1;
-        g.M = R; g.N = 4 * W; g.Ktot = xwidth(D) + C + W;
-        g.out = mkslot(m->st_h[D].as<float>(), W, RW, 1, 1);
-        g.c_in = hseg(m->st_c[D].as<float>(), 0);
-        g.c_out = mkslot(m->st_c[D].as<float>(), W, RW, 1, 1);
-        g.step_ptr = step_ptr; g.step_imm = step_imm;
-        g.nact = live; g.nact_group = m->skip_group;
-    }
-    for (int n = 2; n < D; ++n) { GemmArgs g = lower(n); run_gemm(m, EPI_LSTM, g); }
-    if (lm) {   // the LM cell beside the top cell: [x | 0] and the same h, c; its c goes to a scratch nothing reads
-        GemmBatch b{};
-        b.g[0] = gtop;
-        GemmArgs& g = b.g[1];
-        g = gtop;
-        g.nseg = 2;
-        g.a[1] = hseg(m->st_h[D].as<float>(), xwidth(D) + C);
-        g.a[2] = Seg{};
-        g.out = mkslot(m->lm_h.as<float>(), W);
-        g.c_out = mkslot(m->lm_c.as<float>(), W);
-        b.count = 2;
-        run_gemm_batch(m, EPI_LSTM, b);
-    } else run_gemm(m, EPI_LSTM, gtop);
-    {   // tied output projection (seq2seq.py:379)
-        GemmArgs g{};
-        g.nseg = 1; g.a[0] = mkseg(m->st_h[D].as<float>(), W, W, 0, nullptr, RW, 1, 1);
-        g.Bt = m->E.as<float>(); g.M = R; g.N = V; g.Ktot = W;
-        g.out = mkslot(m->logits.as<float>(), Vp);
-        g.step_ptr = step_ptr; g.step_imm = step_imm;
-        g.nact = live; g.nact_group = m->skip_group;
-        GemmArgs gl = g;                    // the LM's projection (seq2seq.py:468-469): the same tied weights on h of the LM cell
-        gl.a[0] = mkseg(m->lm_h.as<float>(), W, W, 0);
-        gl.out = mkslot(m->lm_logits.as<float>(), Vp);
-        if (query_ahead || lm) {
-            GemmBatch b{};
-            b.g[b.count++] = g;
-            if (query_ahead) b.g[b.count++] = gq;
-            if (lm) b.g[b.count++] = gl;
-            run_gemm_batch(m, EPI_PLAIN, b);
-        } else run_gemm(m, EPI_PLAIN, g);
-    }
-    if (softmax) {       // (the beam step kernel computes the rows it reads itself)
-        SoftmaxArgs a{};
-        a.logits = m->logits.as<float>(); a.p_base = m->st_p.as<float>(); a.R = R; a.V = V;
-        a.step_ptr = step_ptr; a.step_imm = step_imm; a.mode = mode; a.out_idx = o_idx; a.out_prob = o_prob; a.S = m->S;
-        a.nan_flag = m->d_nan.as<int>();
-        a.nact = live; a.nact_group = m->skip_group;
-        hipEvent_t ev{};
-        m->prof_begin(PC_SOFTMAX, 4.0 * R * V, 8.0 * R * V, ev);
-        launch_softmax(a, m->stream);
-        m->prof_end(PC_SOFTMAX, ev);
-    }
-}
-
-// casv_decoder_step and (lm_probs != nullptr) casv_decoder_step_lm
-static int decoder_step(casv_model* m, int32_t R, const int32_t* line, const float* p_in, const float* states_in, const float* a_in,
-                        float* probs, float* states_out, float* a_out, float* lm_probs) {
-    if (!m || !line || !p_in || !states_in || !a_in) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
-    if (R < 1) return fail(CASV_ERR_ARG, "R must be positive");
-    for (int r = 0; r < R; ++r) if (line[r] < 0 || line[r] >= m->B) return fail(CASV_ERR_ARG, "line[%d]=%d out of range", r, line[r]);
-    HIPCHK(hipSetDevice(m->device));
-    if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_CHAIN))) return rc;
-    if (int rc = settle_encoder(m); rc < 0) return rc;
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
-    const int W = m->W, V = m->V, Vp = m->Vp, T = m->T, D = m->D;
-    m->last_decode = 0;         // the step overwrites slots 0 and 1 of the stores casv_get_alignments_sparse would read
-    if (int rc = ensure_session(m, R, 1)) return rc;
-    if (int rc = m->d_line.ensure((size_t)R * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_line.p, line, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemsetAsync(m->st_p.p, 0, (size_t)R * Vp * 4, m->stream));
-    HIPCHK(hipMemsetAsync(m->logits.p, 0, (size_t)R * Vp * 4, m->stream));
-    HIPCHK(hipMemcpy2DAsync(m->st_p.p, (size_t)Vp * 4, p_in, (size_t)V * 4, (size_t)V * 4, R, hipMemcpyHostToDevice, m->stream));
-    for (int n = 1; n <= D; ++n) {
-        HIPCHK(hipMemcpyAsync(m->st_h[n].p, states_in + (size_t)(2 * n - 2) * R * W, (size_t)R * W * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(m->st_c[n].p, states_in + (size_t)(2 * n - 1) * R * W, (size_t)R * W * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    HIPCHK(hipMemcpyAsync(m->st_a.p, a_in, (size_t)R * T * 4, hipMemcpyHostToDevice, m->stream));
-    const bool lm = lm_probs != nullptr;
-    if (lm) {
-        if (int rc = m->lm_h.ensure((size_t)R * W * 4)) return rc;
-        if (int rc = m->lm_c.ensure((size_t)R * W * 4)) return rc;
-        if (int rc = m->lm_logits.ensure((size_t)R * Vp * 4)) return rc;
-        if (int rc = m->lm_probs.ensure((size_t)R * Vp * 4)) return rc;
-    }
-    launch_step(m, false, -1, m->d_line.as<int>(), 1, nullptr, nullptr, nullptr, 0, true, lm);
-    if (lm) {       // the step's query (m->wq) and window (slot 1 of the window store) give the LM's NaN rows
-        LmSoftmaxArgs a{};
-        a.logits = m->lm_logits.as<float>(); a.probs = m->lm_probs.as<float>(); a.wq = m->wq.as<float>();
-        a.va = m->va.as<float>(); a.bv = m->bv.as<float>(); a.win = m->st_win.as<int>() + R; a.R = R; a.V = V; a.W = W;
-        launch_lm_softmax(a, m->stream);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (probs) HIPCHK(hipMemcpy2D(probs, (size_t)V * 4, m->st_p.as<float>() + (size_t)R * Vp, (size_t)Vp * 4, (size_t)V * 4, R, hipMemcpyDeviceToHost));
-    if (states_out)
-        for (int n = 1; n <= D; ++n) {
-            HIPCHK(hipMemcpy(states_out + (size_t)(2 * n - 2) * R * W, m->st_h[n].as<float>() + (size_t)R * W, (size_t)R * W * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(states_out + (size_t)(2 * n - 1) * R * W, m->st_c[n].as<float>() + (size_t)R * W, (size_t)R * W * 4, hipMemcpyDeviceToHost));
-        }
-    if (a_out) HIPCHK(hipMemcpy(a_out, m->st_a.as<float>() + (size_t)R * T, (size_t)R * T * 4, hipMemcpyDeviceToHost));
-    if (lm) HIPCHK(hipMemcpy2D(lm_probs, (size_t)V * 4, m->lm_probs.as<float>(), (size_t)Vp * 4, (size_t)V * 4, R, hipMemcpyDeviceToHost));
-    return CASV_OK;
-}
-
-extern "C" int casv_decoder_step(casv_model* m, int32_t R, const int32_t* line, const float* p_in,
-                                 const float* states_in, const float* a_in, float* probs, float* states_out,
-                                 float* a_out) {
-    return decoder_step(m, R, line, p_in, states_in, a_in, probs, states_out, a_out, nullptr);
-}
-
-extern "C" int casv_decoder_step_lm(casv_model* m, int32_t R, const int32_t* line, const float* p_in,
-                                    const float* states_in, const float* a_in, float* probs, float* states_out,
-                                    float* a_out, float* lm_probs) {
-    if (!lm_probs) return fail(CASV_ERR_ARG, "null argument");
-    return decoder_step(m, R, line, p_in, states_in, a_in, probs, states_out, a_out, lm_probs);
-}
-
-// Runs iterations of `body(step_ptr, step_imm)` (which launches one step).  Eagerly the host passes the step number as
-// an immediate -- no kernel has to fetch it from memory first (a dependent load of a line another kernel just wrote, at
-// the head of every launch) and no kernel has to advance it.  Under "graph" the iterations are replays of ONE hipGraph
-// captured at the first call, whose kernels read the step from device memory and whose last node advances it.
-struct StepRunner {
-    casv_model* m; std::string key;
-    // The captured kernels hold raw pointers.  Reallocations are covered by the buffer generation; the encoder outputs switch
-    // between buffers WITHOUT one (casv_encode: H1 / Ha / Hb / Hc, casv_set_encoder_outputs: Hc; an initial alignment or not),
-    // so their identity is part of the key too.
-    StepRunner(casv_model* m_, const std::string& key_)
-        : m(m_), key(key_ + "/" + std::to_string(g_devbuf_generation) + "/" + std::to_string((unsigned long long)(uintptr_t)m_->enc_out) +
-                     "/" + std::to_string((unsigned long long)(uintptr_t)m_->u.p) + "/" + std::to_string((int)m_->has_a0) +
-                     "/" + std::to_string(gemm_split_bf16()) + "." + std::to_string(gemm_split_epoch())) {}
-    static void drop(casv_model* m) {
-        if (m->step_exec) { (void)hipStreamSynchronize(m->stream); (void)hipGraphExecDestroy(m->step_exec); m->step_exec = nullptr; }
-        if (m->step_graph) { (void)hipGraphDestroy(m->step_graph); m->step_graph = nullptr; }
-        m->step_graph_key.clear();
-    }
-    template <class F> int run(int first, int n, F body) {
-        if (m->use_graph && !m->prof.on) {
-            if (!m->step_exec || m->step_graph_key != key) {
-                drop(m);
-                if (gemm_split_bf16() >= 2) {       // (split arithmetic: the weight images are made ahead of the recording, not inside it)
-                    const int W = m->W, C = m->C, D = m->D, Vp = m->Vp;
-                    for (int n = 1; n <= D; ++n)
-                        gemm_split_prepare(m->dec[n].wt.as<float>(), 4 * W, (n == 1 ? Vp : W) + W + (n == D && D > 1 ? C : 0) + (D == 1 ? C : 0), m->stream);
-                    gemm_split_prepare(m->WaT.as<float>(), W, W, m->stream);
-                }
-                HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-                body(m->d_step.as<int>(), 0);
-                launch_advance_step(m->d_step.as<int>(), m->stream);
-                hipError_t e = hipStreamEndCapture(m->stream, &m->step_graph);        // also the way out of a failed capture
-                if (e != hipSuccess) { m->step_graph = nullptr; return fail(CASV_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e)); }
-                e = hipGraphInstantiate(&m->step_exec, m->step_graph, nullptr, nullptr, 0);
-                if (e != hipSuccess) { m->step_exec = nullptr; drop(m); return fail(CASV_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-                m->step_graph_key = key;
-            }
-            for (int s = 0; s < n; ++s) HIPCHK(hipGraphLaunch(m->step_exec, m->stream));
-            return 0;
-        }
-        for (int s = 0; s < n; ++s) body(nullptr, first + s);
-        return 0;
-    }
-};
-
-// All S greedy steps in ONE launch of the persistent decoder (persist.hip): small batches, where the per-step kernels are
-// bound by launch and memory latency.  Same results bit for bit (tested), same state / alignment / window stores.
-static bool persist_applies(const casv_model* m, int B) {
-    if (m->persist_mode == 0) return false;
-    if (arithmetic_of(m, ENTRY_CHAIN)) return false;   // (the persistent kernels are fp32-input kernels: not mixed with split launches)
-    if (m->ncu < 64 || m->D > 8) return false;
-    int kmax = m->W;
-    for (int n = 1; n <= m->D; ++n) kmax = std::max(kmax, m->dec[n].kin + m->W);
-    const size_t lds = (size_t)16 * (kmax + 4) * 4;
-    const int per_cu = persist_decode_blocks_per_cu(lds);
-    if (per_cu < 1) return false;                                  // the staged rows must fit the LDS
-    if (m->persist_mode == 1) return B <= 4096;
-    // by size: the persistent kernel wins while a workgroup owns at most two tiles per layer (measured: depth 2, width 512: 64
-    // lines 9.3 vs 20.9 ms, 256 lines 32.5 vs 21.4 ms; depth 2, width 256: 512 lines 11.4 vs 14.7 ms)
-    const int g_lstm = std::max(1, m->ncu * per_cu * 4 / 8), ntile = ((B + 15) / 16) * (m->W / 16);
-    return B <= 512 && (ntile + g_lstm - 1) / g_lstm <= 2;
-}
-static int decode_greedy_persistent(casv_model* m, int mode, int S) {
-    std::lock_guard<std::mutex> lock(g_persist_mutex);
-    const int W = m->W, Vp = m->Vp, C = m->C, T = m->T, D = m->D, R = m->R;
-    const size_t slots = (size_t)(S + 1) * R;
-    if (int rc = m->p_ctx.ensure(slots * C * 4)) return rc;
-    if (int rc = m->p_wq.ensure(slots * W * 4)) return rc;
-    if (int rc = m->p_logits.ensure(slots * Vp * 4)) return rc;
-    if (m->p_counters.cap < persist_counter_bytes(R, D)) return fail(CASV_ERR_STATE, "hand-off counters not set up");      // (cleared by the caller's set-up launch)
-    PersistArgs pa{};
-    pa.R = R; pa.D = D; pa.W = W; pa.V = m->V; pa.Vp = Vp; pa.C = C; pa.T = T; pa.S = S; pa.mode = mode;
-    for (int n = 1; n <= D; ++n) {
-        pa.layer[n - 1].w = m->dec[n].pw.as<float>(); pa.layer[n - 1].bias = m->dec[n].pbias.as<float>();
-        pa.layer[n - 1].Kt = m->dec[n].kin + W;
-        pa.h[n - 1] = m->st_h[n].as<float>(); pa.c[n - 1] = m->st_c[n].as<float>();
-    }
-    pa.wa = m->WaP.as<float>(); pa.bUW = m->bUW.as<float>(); pa.e = m->EP.as<float>();
-    pa.ctx = m->p_ctx.as<float>(); pa.wq = m->p_wq.as<float>(); pa.logits = m->p_logits.as<float>();
-    AttnArgs a{};
-    a.u = m->u.as<float>(); a.enc = m->enc_out; a.va = m->va.as<float>(); a.bv = m->bv.as<float>();
-    a.a_base = m->st_a.as<float>(); a.prev = nullptr; a.line = nullptr; a.rows_per_line = 1;
-    a.R = R; a.T = T; a.W = W; a.C = C; a.window = m->cfg.window_width;
-    a.u_line = (long long)T * W; a.u_time = W; a.enc_line = (long long)T * C; a.enc_time = C;
-    a.win_store = m->st_win.as<int>();
-    pa.att = a;
-    pa.out_idx = m->o_idx.as<int>(); pa.out_prob = m->o_prob.as<float>(); pa.nan_flag = m->d_nan.as<int>();
-    pa.counters = m->p_counters.as<unsigned>();
-    const int nrb = (R + 15) / 16, nug = W / 16;
-    const int nq4 = (W / 16 + 3) / 4, nl4 = (Vp / 16 + 3) / 4;
-    int kmax = W;
-    for (int n = 1; n <= D; ++n) kmax = std::max(kmax, pa.layer[n - 1].Kt);
-    pa.lda = kmax + 4;
-    // Every workgroup must be resident at once (they wait for each other): as many per CU as the runtime's occupancy query
-    // admits for this kernel with these staged rows (at most two).  The roles share the slots 4 : 1 : 2 (tiles, attention, plain).
-    const int per_cu = persist_decode_blocks_per_cu(persist_lds_bytes(pa));
-    if (per_cu < 1) return fail(CASV_ERR_ARG, "persistent decoder: rows of %d floats do not fit the LDS", kmax);
-    const int wgslots = m->ncu * per_cu;
-    pa.g_lstm = std::min(nrb * nug, wgslots * 4 / 8);
-    pa.g_plain = std::min(nrb * (nq4 + nl4), std::max(wgslots * 2 / 8, 4));
-    // (attention: one workgroup per four rows where the slots the other roles leave allow it -- a wave then keeps its row, persist.hip)
-    pa.g_att = std::min(nrb * 4, std::max(std::max(wgslots / 8, 4), wgslots - pa.g_lstm - pa.g_plain));
-#ifdef CASV_PERSIST_PROF
-    static DevBuf profbuf;
-    if (int rc = profbuf.ensure((32 + 2048) * 8)) return rc;
-    HIPCHK(hipMemsetAsync(profbuf.p, 0, (32 + 2048) * 8, m->stream));
-    pa.prof = profbuf.as<unsigned long long>();
-#endif
-    hipEvent_t pev{};
-    {   // executed FLOPs of the launch: every step's layer, query and logits contractions over all rows; bytes: what a step
-        // must move per row (state in and out, attention window, logits) -- SURVEY.md section 8(d)'s Q_row
-        double fl = 0;
-        for (int n = 1; n <= D; ++n) fl += 2.0 * R * 4.0 * W * pa.layer[n - 1].Kt;
-        fl += 2.0 * R * W * W + 2.0 * R * Vp * W;
-        const double by = 4.0 * R * (4.0 * D * W + 11.0 * (W + C) + 2.0 * m->V + 2.0 * T);
-        m->prof_begin(PC_PERSIST, fl * S, by * S, pev);
-    }
-    persist_order_before(m->device, m->stream);
-    if (launch_persist_decode(pa, m->stream)) return fail(CASV_ERR_ARG, "persistent decoder: rows of %d floats do not fit the LDS", kmax);
-    persist_order_after(m->device, m->stream);
-    m->prof_end(PC_PERSIST, pev);
-    HIPCHK(hipGetLastError());
-#ifdef CASV_PERSIST_PROF
-    {
-        unsigned long long h[32];
-        HIPCHK(hipMemcpyAsync(h, profbuf.p, sizeof h, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        const char* names[4] = {"layer1 (wait stats kloop cell publish gap)", "upper  (wait - kloop cell publish gap)", "att    (wait row publish)", "plain  (wait kloop publish)"};
-        if (getenv("CASV_PERSIST_PLACEMENT")) {
-            const int grid = pa.g_lstm + pa.g_att + pa.g_plain;
-            std::vector<unsigned long long> hw(grid);
-            HIPCHK(hipMemcpy(hw.data(), profbuf.as<unsigned long long>() + 32, (size_t)grid * 8, hipMemcpyDeviceToHost));
-            std::map<unsigned, std::string> cu;
-            for (int g = 0; g < grid; ++g) {
-                const unsigned h = (unsigned)hw[g], xcc = (unsigned)(hw[g] >> 32) & 15;
-                const unsigned key = (xcc << 16) | (((h >> 13) & 7) << 8) | (((h >> 12) & 1) << 4) | ((h >> 8) & 15);   // xcc, se, sh, cu
-                cu[key] += g < pa.g_lstm ? 'L' : g < pa.g_lstm + pa.g_att ? 'A' : 'P';
-            }
-            std::map<std::string, int> hist;
-            for (auto& kv : cu) hist[kv.second]++;
-            fprintf(stderr, "persist placement (%zu CUs):", cu.size());
-            for (auto& kv : hist) fprintf(stderr, " %s x%d", kv.first.c_str(), kv.second);
-            fprintf(stderr, "\n");
-        }
-        for (int r = 0; r < 4; ++r) {
-            fprintf(stderr, "persist prof %s us/step:", names[r]);
-            for (int k = 0; k < 6; ++k) fprintf(stderr, " %.2f", h[r * 8 + k] * 0.01 / S);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    // the launch's give-up word, set aside beside the encoder's (the caller brings both to the host with the results)
-    {
-        SmallOps ops{};
-        ops.rows(reinterpret_cast<const float*>(persist_give_up_word(m->p_counters.as<unsigned>(), persist_counter_bytes(R, D))), 1, m->d_flags.as<float>() + 1, 1, 1, 1, 1);
-        if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-    }
-    return 0;
-}
-
-extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_t* out_idx, float* out_prob,
-                                  int32_t* out_len, float* out_align) {
-    if (!m || !out_idx || !out_prob) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
-    if (mode != 0 && mode != 1) return fail(CASV_ERR_ARG, "mode must be 0 or 1");
-    if (S < 1 || S > 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "S=%d out of range 1..%d", S, 2 * CASV_MAX_T);
-    HIPCHK(hipSetDevice(m->device));
-    if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_CHAIN))) return rc;
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
-    const int B = m->B, T = m->T;
-    m->last_decode = 0;         // until this call has succeeded there is nothing to take alignments from
-    if (int rc = ensure_session(m, B, S)) return rc;
-    if (int rc = m->o_idx.ensure((size_t)B * S * 4)) return rc;
-    if (int rc = m->o_prob.ensure((size_t)B * S * 4)) return rc;
-    if (int rc = m->d_flags.ensure(64)) return rc;
-    // results and flags come back through a pinned staging buffer: three queued copies, ONE wait for the device
-    const size_t nres = (size_t)B * S * 4, need = 2 * nres + 64;
-    const bool staged = need <= m->pin_limit;                // (very large results go straight to the caller's arrays)
-    if (m->pin_out_cap < (staged ? need : 64)) {
-        const size_t want = staged ? need : 64;
-        if (m->pin_out) { (void)hipHostFree(m->pin_out); m->pin_out = nullptr; m->pin_out_cap = 0; }
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_out), want, hipHostMallocDefault));
-        m->pin_out_cap = want;
-    }
-    unsigned* const pin_flags = reinterpret_cast<unsigned*>(staged ? m->pin_out + 2 * nres : m->pin_out);
-    bool persistent = persist_applies(m, B) && !persist_backed_off(m->persist_backoff);
-    auto begin = [&](bool with_counters) -> int {        // the set-up of a run, as one launch
-        SmallOps ops{};
-        ops.fill(m->o_idx.p, nres); ops.fill(m->o_prob.p, nres);
-        ops.fill(m->d_flags.as<unsigned>() + 1, 4);
-        if (with_counters) {
-            const size_t cbytes = persist_counter_bytes(B, m->D);
-            if (int rc = m->p_counters.ensure(cbytes)) return rc;
-            ops.fill(m->p_counters.p, cbytes);
-        }
-        return init_root(m, 1, ops);
-    };
-    for (int attempt = 0; ; ++attempt) {
-        if (int rc = begin(persistent)) return rc;
-        if (persistent) {
-            if (int rc = decode_greedy_persistent(m, mode, S)) return rc;
-        } else {
-            char key[96];
-            snprintf(key, sizeof key, "greedy/%d/%d/%d/%d/%d", mode, B, T, S, m->eos);
-            StepRunner runner(m, key);
-            if (int rc = runner.run(0, S, [&](const int* step_ptr, int step_imm) {
-                    launch_step(m, false, mode, nullptr, 1, m->o_idx.as<int>(), m->o_prob.as<float>(), step_ptr, step_imm);
-                })) return rc;
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(staged ? (void*)m->pin_out : (void*)out_idx, m->o_idx.p, nres, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(staged ? (void*)(m->pin_out + nres) : (void*)out_prob, m->o_prob.p, nres, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipMemcpyAsync(pin_flags, m->d_flags.p, 8, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        const unsigned* flags = pin_flags;
-        // a persistent launch whose hand-off wait ran out (its workgroups were not all resident: another process running a
-        // persistent kernel on this GPU) loses nothing -- the per-step kernels compute the same values; start over with them
-        const bool enc_was_persistent = m->enc_check_pending;
-        const int redone = settle_encoder(m, &flags[0]);
-        if (redone < 0) return redone;
-        const bool dec_aborted = persistent && flags[1] != 0;
-        if (dec_aborted) { persist_note_abort(m->persist_backoff, "decoder"); persistent = false; }
-        // the back-off is reset only by an attempt in which NO persistent launch gave up (an encoder that keeps losing residency
-        // must not restart its penalty at 16 because the decoder behind it happened to run through)
-        if (!redone && !dec_aborted && (persistent || enc_was_persistent)) m->persist_backoff.penalty = 0;
-        if (!redone && !dec_aborted) break;
-        if (attempt >= 2) return fail(CASV_ERR_STATE, "persistent launches keep giving up");
-    }
-    if (staged) { memcpy(out_idx, m->pin_out, nres); memcpy(out_prob, m->pin_out + nres, nres); }
-    // mode 1 stops a line at its end-of-line character (seq2seq.py:1344); np.nanargmax raises only if an all-NaN row
-    // turns up BEFORE that (the device marks such a step with a NaN probability) -- rows keep stepping in lockstep
-    // after their line has ended, and what they produce there is nobody's business
-    bool nan_before_end = false;
-    for (int b = 0; b < B; ++b) {
-        int len = S;
-        if (mode == 1)
-            for (int s = 0; s < S; ++s) {
-                const float pr = out_prob[(size_t)b * S + s];
-                if (pr != pr) { nan_before_end = true; len = s + 1; break; }
-                if (out_idx[(size_t)b * S + s] == m->eos) { len = s + 1; break; }
-            }
-        if (out_len) out_len[b] = len;
-    }
-    if (out_align) {   // store_a slot s+1 row b -> (b, s, :)
-        for (int s = 0; s < S; ++s)
-            HIPCHK(hipMemcpy2DAsync(out_align + (size_t)s * T, (size_t)S * T * 4, m->st_a.as<float>() + (size_t)(s + 1) * B * T,
-                                    (size_t)T * 4, (size_t)T * 4, B, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-    }
-    if (m->prof.on) m->prof.collect();
-    m->last_decode = 1; m->last_S = S; m->last_rows = B; m->last_mode = mode; m->last_signature = decode_buffers_signature(m);
-    if (nan_before_end && mode == 1) return fail(CASV_ERR_NAN, "All-NaN slice encountered");
-    return CASV_OK;
-}
-
-extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32_t S, int32_t* out_idx, float* out_prob,
-                                int32_t* out_len, double* out_score, int32_t* out_rej, float* out_align,
-                                int32_t* n_found, int32_t* n_steps) {
-    if (!m || !bp || !out_idx || !out_prob || !out_len || !out_score || !n_found) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
-    const int N = bp->batch_size;
-    if (N < 1 || N > CASV_MAX_BEAM_N) return fail(CASV_ERR_ARG, "batch_size (hypotheses per step) %d out of range 1..%d", N, CASV_MAX_BEAM_N);
-    if (bp->beam_width_in < 1) return fail(CASV_ERR_ARG, "beam_width_in %d must be positive", bp->beam_width_in);
-    // children per expansion: at most min(beam_width_in, V) inside the beam plus the rejection candidate beyond it
-    const int CM = (bp->beam_width_in < m->V ? bp->beam_width_in : m->V) + 1;
-    if (bp->max_results < 1 || bp->max_results > 64) return fail(CASV_ERR_ARG, "max_results out of range 1..64");
-    if (S < 1 || S > 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "S=%d out of range 1..%d", S, 2 * CASV_MAX_T);
-    if (1LL + (long long)S * N * CM >= (1LL << 31) || (long long)(S + 1) * m->B * N >= (1LL << 31))
-        return fail(CASV_ERR_ARG, "search too large: S * batch_size * (beam_width_in + 1) nodes per line overflow int32 (decode fewer lines or steps per call)");
-    HIPCHK(hipSetDevice(m->device));
-    if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_SEARCH))) return rc;
-    // (a persistent encoder launch's give-up word is looked at below, where this call first waits for the device anyway)
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_SEARCH));         // the search: bf16x3-split operands by default (engine.h)
-    const int B = m->B, T = m->T, R = B * N, MR = bp->max_results;
-    m->last_decode = 0;         // until this call has succeeded there is nothing to take alignments from
-    if (int rc = ensure_session(m, R, S)) return rc;
-    if (int rc = m->st_q.ensure((size_t)(S + 1) * R * m->W * 4)) return rc;
-    if (int rc = init_root(m, N)) return rc;
-    {   // the root expansions' attention query (slot 0: the encoder's final h_D), as every later step's output projection leaves it
-        const int W = m->W, D = m->D;
-        GemmArgs gq{};
-        gq.nseg = 1; gq.a[0] = mkseg(m->st_h[D].as<float>(), W, W, 0);
-        gq.Bt = m->WaT.as<float>(); gq.bias = m->bUW.as<float>(); gq.M = R; gq.N = W; gq.Ktot = W; gq.b_static = 1;
-        gq.out = mkslot(m->st_q.as<float>(), W);
-        run_gemm(m, EPI_PLAIN, gq);
-    }
-    BeamState s{};
-    s.B = B; s.T = T; s.V = m->V; s.S = S; s.R = R;
-    s.node_cap = 1 + S * N * CM; s.q_cap = 2 * T * N; s.f_cap = 64; s.g_cap = N * CM;
-    const size_t NC = (size_t)B * s.node_cap;
-#define ENS(buf, bytes) if (int rc = (buf).ensure(bytes)) return rc;
-    ENS(m->b_parent, NC * 4) ENS(m->b_chr, NC * 4) ENS(m->b_prob, NC * 4) ENS(m->b_cum, NC * 8) ENS(m->b_len, NC * 4)
-    ENS(m->b_exp, NC * 4) ENS(m->b_k, NC * 4) ENS(m->b_rejpos, NC * 4) ENS(m->b_pos, NC * 8) ENS(m->b_is1, NC * 4)
-    ENS(m->b_count, (size_t)B * 4) ENS(m->b_created, (size_t)(S + 1) * R * CM * 2)
-    ENS(m->b_qkey, (size_t)2 * B * s.q_cap * 8) ENS(m->b_qid, (size_t)2 * B * s.q_cap * 4) ENS(m->b_qn, (size_t)2 * B * 4)
-    ENS(m->b_fkey, (size_t)B * s.f_cap * 8) ENS(m->b_fid, (size_t)B * s.f_cap * 4) ENS(m->b_fn, (size_t)B * 4) ENS(m->b_ftotal, (size_t)B * 4)
-    ENS(m->b_beamnode, (size_t)R * 4) ENS(m->b_nact, (size_t)B * 4) ENS(m->b_done, (size_t)B * 4)
-    ENS(m->b_steps, (size_t)B * 4) ENS(m->b_active, 16)
-    ENS(m->b_gkey, (size_t)2 * B * s.g_cap * 8) ENS(m->b_gid, (size_t)2 * B * s.g_cap * 4)
-    if (N >= 64) { ENS(m->b_rowrec, (size_t)R * sizeof(RowRec)) ENS(m->b_candidx, (size_t)R * CM * 2) ENS(m->b_candval, (size_t)R * CM * 4) }
-    const bool lm = m->lm_predict;          // (read at every call)
-    if (lm) {
-        ENS(m->lm_h, (size_t)R * m->W * 4) ENS(m->lm_c, (size_t)R * m->W * 4) ENS(m->lm_logits, (size_t)R * m->Vp * 4)
-        if (N >= 64) ENS(m->b_candlm, (size_t)R * CM * 4)
-    }
-    const size_t OR = (size_t)B * MR;
-    ENS(m->bo_idx, OR * S * 4) ENS(m->bo_prob, OR * S * 4) ENS(m->bo_len, OR * 4) ENS(m->bo_score, OR * 8) ENS(m->bo_rej, OR * S * 4)
-    ENS(m->bo_found, (size_t)B * 4) ENS(m->bo_nsteps, (size_t)B * 4)
-    if (out_align) ENS(m->bo_align, OR * S * T * 4)
-#undef ENS
-    s.n_parent = m->b_parent.as<int>(); s.n_chr = m->b_chr.as<int>(); s.n_prob = m->b_prob.as<float>();
-    s.n_cum = m->b_cum.as<double>(); s.n_len = m->b_len.as<int>(); s.n_exp = m->b_exp.as<int>(); s.n_k = m->b_k.as<int>();
-    s.n_rejpos = m->b_rejpos.as<int>(); s.n_pos = m->b_pos.as<double>(); s.n_is1 = m->b_is1.as<int>();
-    s.n_count = m->b_count.as<int>(); s.created = m->b_created.as<short>();
-    s.q_key = m->b_qkey.as<double>(); s.q_id = m->b_qid.as<int>(); s.q_n = m->b_qn.as<int>();
-    s.g_key = m->b_gkey.as<double>(); s.g_id = m->b_gid.as<int>();
-    s.f_key = m->b_fkey.as<double>(); s.f_id = m->b_fid.as<int>(); s.f_n = m->b_fn.as<int>(); s.f_total = m->b_ftotal.as<int>();
-    s.beam_node = m->b_beamnode.as<int>(); s.nact = m->b_nact.as<int>();
-    s.line_done = m->b_done.as<int>(); s.line_steps = m->b_steps.as<int>(); s.active_lines = m->b_active.as<int>();
-    s.prev = m->prev.as<int>(); s.p_in = m->pin.as<float>(); s.p_base = m->st_p.as<float>();
-    s.apos = m->apos.as<double>(); s.amax1 = m->amax1.as<int>(); s.src_rej = m->d_srcrej.as<int>();
-    s.step_ptr = m->d_step.as<int>();
-    if (N >= 64) { s.rowrec = m->b_rowrec.as<RowRec>(); s.cand_idx = m->b_candidx.as<short>(); s.cand_val = m->b_candval.as<float>(); }
-    if (lm) {
-        s.lm_q = m->st_q.as<float>(); s.lm_va = m->va.as<float>(); s.lm_bv = m->bv.as<float>(); s.lm_win = m->st_win.as<int>(); s.W = m->W;
-        if (N >= 64) s.cand_lm = m->b_candlm.as<float>();
-    }
-    BeamParams p{};
-    p.N = N; p.width_in = bp->beam_width_in; p.width_out = bp->beam_width_out; p.max_results = MR;
-    p.threshold_in = bp->beam_threshold_in; p.rejection = bp->rejection_threshold; p.cost0 = bp->cost0; p.eos = m->eos;
-
-    // Tiles / rows without a live hypothesis are skipped by the step's kernels (their state is never read).  Worth the
-    // extra load per workgroup from the start when a line's N rows span whole tiles (beams fill up over the first
-    // steps), otherwise once a line has finished; not under graph replay, whose kernel arguments are fixed at capture.
-    m->skip_nact = (N >= 128 && !m->use_graph) ? m->b_nact.as<int>() : nullptr; m->skip_group = N;
-    launch_beam_init(s, p, m->stream);
-    auto body = [&](const int* step_ptr, int step_imm) {
-        launch_step(m, true, -1, nullptr, N, nullptr, nullptr, step_ptr, step_imm, false, lm);
-        hipEvent_t ev{};
-        m->prof_begin(PC_BEAM, 0.0, 4.0 * R * ((lm ? 3.0 : 2.0) * m->Vp), ev);
-        BeamState sb = s;
-        sb.step_ptr = step_ptr; sb.step_imm = step_imm; sb.logits = m->logits.as<float>();
-        if (lm) sb.lm_logits = m->lm_logits.as<float>();
-        launch_beam_step(sb, p, m->stream);
-        m->prof_end(PC_BEAM, ev);
-    };
-    // The host looks at the number of unfinished lines every `chunk` iterations -- one chunk behind: the count of chunk k
-    // travels to pinned host memory while chunk k+1 is already queued, so the GPU never waits for the host (a blocking poll
-    // cost 150 us of idle GPU every 16 steps).  A search that ends early runs at most one chunk of empty iterations.
-    const int chunk = 16;
-    int done_steps = 0;
-    char key[256];
-    snprintf(key, sizeof key, "beam/%d/%d/%d/%d/%d/%d/%d/%.17g/%.17g/%.17g/%d%s", B, T, S, N, p.width_in, p.width_out, MR, p.threshold_in,
-             p.rejection, p.cost0, p.eos, lm ? "/lm" : "");
-    StepRunner runner(m, key);
-    if (!m->pin_active) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_active), 3 * sizeof(int), hipHostMallocDefault));      // ([2]: the encoder's give-up word)
-        for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&m->ev_active[k], hipEventDisableTiming));
-    }
-    // The persistent encoder's give-up word travels with the first count.  A pass that gave up is redone per step (settle_encoder)
-    // and the search starts over on its outputs: nothing decoded from the abandoned pass is trusted.
-    const bool enc_pending = m->enc_check_pending;
-    if (enc_pending) HIPCHK(hipMemcpyAsync(&m->pin_active[2], m->d_flags.p, 4, hipMemcpyDeviceToHost, m->stream));
-    bool enc_settled = !enc_pending;
-    auto settle_now = [&](int& redone) {          // behind a wait that covers the copy above
-        const unsigned flag = (unsigned)m->pin_active[2];
-        redone = settle_encoder(m, &flag);
-        if (redone == 0) m->persist_backoff.penalty = 0;
-        enc_settled = true;
-        return redone < 0 ? redone : 0;
-    };
-    int pending = -1;                       // slot whose copy is in flight
-    int slot = 0;
-    while (done_steps < S) {
-        const int n = (S - done_steps) < chunk ? (S - done_steps) : chunk;
-        if (int rc = runner.run(done_steps, n, body)) return rc;
-        done_steps += n;
-        HIPCHK(hipMemcpyAsync(&m->pin_active[slot], m->b_active.p, 4, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipEventRecord(m->ev_active[slot], m->stream));
-        if (pending >= 0) {                 // the chunk before this one
-            HIPCHK(hipEventSynchronize(m->ev_active[pending]));
-            if (!enc_settled) {
-                int redone = 0;
-                if (int rc = settle_now(redone)) return rc;
-                if (redone) { m->skip_nact = nullptr; m->skip_group = 0; return casv_decode_beam(m, bp, S, out_idx, out_prob, out_len, out_score, out_rej, out_align, n_found, n_steps); }
-            }
-            const int active = m->pin_active[pending];
-            if (active <= 0) break;
-            if (active < B && !m->use_graph) m->skip_nact = m->b_nact.as<int>();
-        }
-        pending = slot; slot ^= 1;
-    }
-    m->skip_nact = nullptr; m->skip_group = 0;
-    BeamOut o{};
-    o.idx = m->bo_idx.as<int>(); o.prob = m->bo_prob.as<float>(); o.len = m->bo_len.as<int>(); o.score = m->bo_score.as<double>();
-    o.rejpos = m->bo_rej.as<int>(); o.align = out_align ? m->bo_align.as<float>() : nullptr; o.n_found = m->bo_found.as<int>();
-    o.n_steps = m->bo_nsteps.as<int>(); o.a_base = m->st_a.as<float>();
-    {
-        SmallOps ops{};
-        ops.fill(m->bo_idx.p, OR * S * 4); ops.fill(m->bo_prob.p, OR * S * 4); ops.fill(m->bo_rej.p, OR * S * 4, 0xffffffffu);
-        if (!launch_small_ops(ops, m->stream)) return fail(CASV_ERR_STATE, "too many set-up operations for one launch");
-    }
-#ifdef CASV_BEAM_PROF
-    { HIPCHK(hipStreamSynchronize(m->stream)); casv::beam_prof_dump(m->S); }
-#endif
-#ifdef CASV_GEMM_PROF
-    { HIPCHK(hipStreamSynchronize(m->stream)); casv::gemm_prof_dump(); casv::skinny_prof_dump(); }
-#endif
-    launch_beam_extract(s, p, o, m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_idx, o.idx, OR * S * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_prob, o.prob, OR * S * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_len, o.len, OR * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_score, o.score, OR * 8, hipMemcpyDeviceToHost, m->stream));
-    if (out_rej) HIPCHK(hipMemcpyAsync(out_rej, o.rejpos, OR * S * 4, hipMemcpyDeviceToHost, m->stream));
-    if (out_align) HIPCHK(hipMemcpyAsync(out_align, o.align, OR * S * T * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(n_found, o.n_found, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-    if (n_steps) HIPCHK(hipMemcpyAsync(n_steps, o.n_steps, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(m->stat_beam, m->b_active.as<int>() + 1, 12, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (!enc_settled) {                     // (a search of at most two chunks: no count was waited for)
-        int redone = 0;
-        if (int rc = settle_now(redone)) return rc;
-        if (redone) return casv_decode_beam(m, bp, S, out_idx, out_prob, out_len, out_score, out_rej, out_align, n_found, n_steps);
-    }
-    if (m->prof.on) m->prof.collect();
-    m->last_decode = 2; m->last_S = S; m->last_rows = (int)OR; m->last_beam = s; m->last_beam_params = p;
-    m->last_signature = decode_buffers_signature(m);
-    return CASV_OK;
-}
-
-extern "C" int casv_get_alignments_sparse(casv_model* m, int32_t K, int32_t* out_lo, float* out_w) {
-    if (!m || !out_lo || !out_w) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->last_decode) return fail(CASV_ERR_STATE, "no decode call to take alignments from");
-    // last_beam holds raw pointers into the handle's buffers: refuse once any of them may have moved
-    if (m->last_signature != decode_buffers_signature(m)) { m->last_decode = 0; return fail(CASV_ERR_STATE, "the decode results have been released (a later call reallocated device buffers)"); }
-    if (K < 2 * m->cfg.window_width + 1 || K > 64) return fail(CASV_ERR_ARG, "K=%d: need at least 2*window_width+1 = %d weights per step (at most 64)", K, 2 * m->cfg.window_width + 1);
-    HIPCHK(hipSetDevice(m->device));
-    const size_t n = (size_t)m->last_rows * m->last_S;
-    if (int rc = m->sp_lo.ensure(n * 4)) return rc;
-    if (int rc = m->sp_w.ensure(n * K * 4)) return rc;
-    SparseAlignOut sp{m->sp_lo.as<int>(), m->sp_w.as<float>(), K, m->st_win.as<int>()};
-    if (m->last_decode == 1) {
-        launch_greedy_extract_sparse(m->st_a.as<float>(), m->st_win.as<int>(), m->last_rows, m->last_S, m->T, sp, m->stream);
-    } else {
-        HIPCHK(hipMemsetAsync(sp.lo, 0, n * 4, m->stream));
-        HIPCHK(hipMemsetAsync(sp.w, 0, n * K * 4, m->stream));
-        BeamOut o{};
-        o.a_base = m->st_a.as<float>();
-        launch_beam_extract_sparse(m->last_beam, m->last_beam_params, o, sp, m->stream);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_lo, sp.lo, n * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_w, sp.w, n * K * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
     return CASV_OK;
 }
 

@@ -1,5 +1,5 @@
 // Host side of a persistent launch -- one whose workgroups wait for each other (handoff.h) -- shared by every kernel file that has
-// one (persist.hip, persist_split.hip, train_persist*.hip) and by the hosts that plan and launch them (engine.hip, encoder.hip,
+// one (persist.hip, persist_split.hip, train_persist*.hip) and by the hosts that plan and launch them (decode.hip, encoder.hip,
 // train.hip): how many workgroups are resident at once, where the hand-off counters keep the launch's give-up word, and the order
 // and the back-off of the decode path's launches within the process.
 #pragma once
@@ -44,7 +44,7 @@ template <class K> inline int persist_blocks_per_cu(K* kernel, size_t lds, int c
 inline size_t persist_counters_bytes(size_t n) { return (n * 32 + 32) * sizeof(unsigned); }
 inline unsigned* persist_give_up_word(unsigned* counters, size_t counter_bytes) { return counters + counter_bytes / sizeof(unsigned) - 32; }
 
-// ---- order and back-off of the decode path's launches (engine.hip, encoder.hip) ----
+// ---- order and back-off of the decode path's launches (decode.hip, encoder.hip) ----
 // These launches are serialised inside the process: two of them together can want more workgroup slots than the chip has, and
 // workgroups that spin on peers which are not resident never make room for them.  (Across processes the bounded spins catch that
 // case: the launch gives up and the caller falls back to the per-step kernels.)  On the host the mutex orders the ENQUEUEING of
