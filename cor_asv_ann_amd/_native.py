@@ -64,6 +64,7 @@ SIGNATURES = {
     'casv_train_sync_weights': (c_int, [c_void_p]),
     'casv_train_end': (c_int, [c_void_p]),
     'casv_score_targets': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 10),
+    'casv_score_candidates': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 10),
     'casv_score_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_score_release': (c_int, [c_void_p]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

@@ -22,6 +22,8 @@
 // persist_slot is the one place that decides whether a recurrence goes persistent; persist_launched the one that counts it.
 // casv_score_targets (teacher-forced log-probabilities of given targets) makes the same two attempts (score_attempt): phases 1-4 as
 // they are, then the projection and the scoring head in place of the loss -- give-up check; on a forward-only state outside a session.
+// casv_score_candidates is the same call with N targets per source: the encoder side of the forward phases works on the Be sources,
+// the decoder side on the B = Be * N rows (Step::Be / N, TLayer::rows); casv_train_step and casv_score_targets have Be = B, N = 1.
 #include "engine.h"
 #include "train_kernels.h"
 
@@ -32,6 +34,7 @@ struct TTensor { std::string name; DevBuf w, g, m, v; size_t n = 0; bool frozen 
 struct TLayer {
     std::string name;
     int kx = 0, kr = 0, len = 0;
+    int rows = 0;                          // rows per time step: the step's B, an encoder layer of a candidates call its Be sources (plan_buffers)
     bool reverse = false;
     int iwx = -1, iwr = -1, ib = -1;
     DevBuf wxT, wrT;                       // derived: [kx][4W], [kr][4W]
@@ -56,8 +59,10 @@ struct TrainState {
     // (the B operand of the data gradient); the bridged states, and the tanh' products of the backward pass
     struct Bridge { int ikt = -1, ib = -1; DevBuf kn; };
     std::vector<Bridge> bridge;            // [2 * (n - 1) + s]
-    DevBuf hbr, cbr, brtmp, Ytop;          // [D][B][W] bridged final states; scratch [B][W]; residual_connections: top output + its input [U*B][W]
-    int B = 0, T = 0, U = 0, A = 0;
+    DevBuf hbr, cbr, brtmp, Ytop;          // [D][Be][W] bridged final states; scratch [Be][W]; residual_connections: top output + its input [U*B][W]
+    DevBuf h0rep, c0rep;                   // casv_score_candidates, N > 1: the decoder's initial states [D][B][W], every source's rows N times
+    int B = 0, T = 0, U = 0, A = 0;        // B: the step's batch = the decoder's rows
+    int Be = 0, N = 1;                     // the encoder's lines and the decoder rows per line, Be * N == B (N > 1: casv_score_candidates only)
     DevBuf e_idx, e_val, d_in, d_out, d_w, m_enc, m_dec, m_cell;
     DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
     std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])
@@ -169,7 +174,7 @@ static void release_state(casv_model* m, TrainState* ts) {
     for (auto& t : ts->tens) { t.w.release(); t.g.release(); t.m.release(); t.v.release(); }
     for (auto& l : ts->layers) { l.wxT.release(); l.wrT.release(); l.Hown.release(); l.Cs.release(); l.Gt.release(); l.Z.release(); l.dRec.release(); }
     for (auto& b : ts->bridge) b.kn.release();
-    for (DevBuf* b : {&ts->hbr, &ts->cbr, &ts->brtmp, &ts->Ytop}) b->release();
+    for (DevBuf* b : {&ts->hbr, &ts->cbr, &ts->brtmp, &ts->Ytop, &ts->h0rep, &ts->c0rep}) b->release();
     DevBuf* bufs[] = {&ts->ETp, &ts->WaN, &ts->UaN, &ts->e_idx, &ts->e_val, &ts->d_in, &ts->d_out, &ts->d_w, &ts->m_enc, &ts->m_dec,
         &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn,
         &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
@@ -337,7 +342,7 @@ static void run_gemm_tn(casv_model* m, const float* A, long long lda, int M, int
 // One recurrent step of a layer as a GEMM job; k = processing index (time t = k, or len-1-k when reversed).
 static GemmArgs layer_step_job(casv_model* m, TLayer& l, int k, const float* h0, const float* c0, const float* rec_in /*top cell*/) {
     TrainState* ts = m->train;
-    const int W = m->W, B = ts->B;
+    const int W = m->W, B = l.rows;
     const int mul = l.reverse ? -1 : 1, add_t = l.reverse ? l.len - 1 : 0, add_p = l.reverse ? l.len : -1;
     GemmArgs g{};
     g.nseg = 1;
@@ -362,7 +367,7 @@ static int time_of(const TLayer& l, int k) { return l.reverse ? l.len - 1 - k : 
 // Z = x . Wx^T + b for every time step (one GEMM)
 static void layer_input_gemm(casv_model* m, TLayer& l, const float* x, long long ldx) {
     TrainState* ts = m->train;
-    GemmArgs g = plain_gemm(x, ldx, l.len * ts->B, l.kx, ts->W_(l.iwx), 4 * m->W, ts->W_(l.ib), l.Z.as<float>(), 4 * m->W);
+    GemmArgs g = plain_gemm(x, ldx, l.len * l.rows, l.kx, ts->W_(l.iwx), 4 * m->W, ts->W_(l.ib), l.Z.as<float>(), 4 * m->W);
     run_plain(m, g);
 }
 
@@ -525,7 +530,9 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
 }
 
 // Forward recurrence of up to two independent plain layers: ONE persistent launch (train_persist.hip) where the shape has
-// one and the device is ours, else one launch per step for both (the two are interchangeable bit for bit).
+// one and the device is ours, else one launch per step for both (the two are interchangeable bit for bit).  Each layer walks its
+// own rows (TLayer.rows): in a candidates call the encoder's job has Be of them beside the decoder's B -- the persistent launch
+// keeps B's grid and counters (RecJob.rows), the per-step launch's jobs carry their own M.
 // om / om_ld / omask: the layer's outputs once more, times the next layer's per-unit dropout mask (nullptr: times one) -- written by
 // the persistent recurrence itself; *masked tells the caller whether it was (the per-step launches leave it to launch_mul_mask).
 struct LayerFwd { TLayer* l; const float* h0; const float* c0; float* om = nullptr; long long om_ld = 0; const float* omask = nullptr; };
@@ -541,14 +548,15 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
         for (int j = 0; j < count; ++j) {
             TLayer& l = *a[j].l;
             ra.job[j] = RecJob{ts->W_(l.iwr), l.Z.as<float>(), l.hs, l.hs_ld, l.Cs.as<float>(), l.Gt.as<float>(), a[j].h0, a[j].c0, l.len,
-                               l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr};       // (a scoring state has no dRec: nullptr, nothing to clear)
+                               l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr,        // (a scoring state has no dRec: nullptr, nothing to clear)
+                               l.rows == B ? 0 : l.rows};                           // (the encoder's job of a candidates call: Be < B rows)
         }
         ra.counters = slot;
         ra.fault = m->persist_mode == 2;       // (test of the give-up path)
         if (const int grid = train_recurrence_grid(ra, m->ncu)) {
             hipEvent_t ev{};
             double flops = 0;
-            for (int j = 0; j < count; ++j) flops += 2.0 * B * 4.0 * W * W * a[j].l->len;
+            for (int j = 0; j < count; ++j) flops += 2.0 * a[j].l->rows * 4.0 * W * W * a[j].l->len;
             m->prof_begin(PC_PERSIST, flops, 0.0, ev);
             launch_train_recurrence(ra, grid, m->stream);
             m->prof_end(PC_PERSIST, ev);
@@ -571,7 +579,8 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
 // next.  casv_train_step fills the first three groups once; every attempt starts from a copy and its phases fill in the rest.
 struct Step {
     casv_model* m; TrainState* ts; hipStream_t st;
-    int mode, B, T, U, A;
+    int mode, B, T, U, A;           // B: the step's batch, the decoder's rows
+    int Be, N;                      // the encoder's lines, decoder rows per line: Be * N == B (casv_train_step: Be = B, N = 1)
     const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
     const float* mask_enc; const float* mask_dec; const float* mask_cell;
     int W, V, Vp, C, D;
@@ -580,7 +589,8 @@ struct Step {
     // recurrence, hence no give-up fallback; no fused backward step), no split-K in the launcher, the K-major contractions'
     // shares added in order, the workgroups' loss / norm parts added by one ordered pass, the embedding gradient per character
     bool training, det, fused, deep, residual, bridged;
-    // plan_buffers: the encoder's final states [n-1][B][W], the decoder's initial states (the bridged ones with bridge_dense), the
+    // plan_buffers: the encoder's final states [n-1][Be][W], the decoder's initial states [n-1][B][W] (the bridged ones with
+    // bridge_dense; N > 1: either, every row N times), the
     // gradients w.r.t. the final states [n-1][0|1][B][W], the ordered sums' parts (deterministic only)
     float* hfin; float* cfin; const float* h0base; const float* c0base; float* dfin; double* parts;
     // stage_inputs: the dropout masks on the device (nullptr: none) -- enc = 2W + (D-1)*W floats (deep: D * 2W), dec = (D-1)*W floats,
@@ -608,7 +618,7 @@ struct Step {
 // view's pointers into the state buffers (read behind the calls that may have moved them).
 static int plan_buffers(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts;
-    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
+    const int B = s.B, Be = s.Be, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
     const long long TB = s.TB, UB = s.UB;
     const bool deep = s.deep;
     const bool bwd = !ts->forward_only;     // (a scoring state holds no backward buffer: BWD(...) allocates in a session only)
@@ -625,8 +635,8 @@ static int plan_buffers(Step& s) {
     BWD(ts->dcbuf2, (size_t)B * W * 4) BWD(ts->dvaP, (size_t)B * W * 4) BWD(ts->dbvP, (size_t)B * 4)
     for (auto& l : ts->layers) {
         const bool enc = l.name.compare(0, 3, "enc") == 0;
-        l.len = enc ? T : U;
-        const long long rows = (long long)l.len * B;
+        l.len = enc ? T : U; l.rows = enc ? Be : B;
+        const long long rows = (long long)l.len * l.rows;
         ENS(l.Cs, rows * W * 4) ENS(l.Gt, rows * 4 * W * 4) ENS(l.Z, rows * 4 * W * 4) BWD(l.dRec, rows * l.kr * 4)
         if (l.name == "enc1_fw") { l.hs = ts->H1.as<float>(); l.hs_ld = 2 * W; }
         else if (l.name == "enc1_bw") { l.hs = ts->H1.as<float>() + W; l.hs_ld = 2 * W; }
@@ -639,7 +649,8 @@ static int plan_buffers(Step& s) {
         ENS(ts->sum_parts, (size_t)std::max(MULTI_MAX * 64, (W + 63) / 64 + V) * 8)
         ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
     }
-    if (s.bridged) { ENS(ts->hbr, (size_t)D * B * W * 4) ENS(ts->cbr, (size_t)D * B * W * 4) ENS(ts->brtmp, (size_t)B * W * 4) }
+    if (s.bridged) { ENS(ts->hbr, (size_t)D * Be * W * 4) ENS(ts->cbr, (size_t)D * Be * W * 4) ENS(ts->brtmp, (size_t)Be * W * 4) }
+    if (s.N > 1) { ENS(ts->h0rep, (size_t)D * B * W * 4) ENS(ts->c0rep, (size_t)D * B * W * 4) }
     if (s.residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
     for (int n = 1; n <= D; ++n) ENS(ts->O[n], TB * ((n == 1 || deep) ? 2 * W : W) * 4)
     for (int n = 2; n <= D && deep; ++n) ENS(ts->XD[n], TB * 2 * W * 4)
@@ -650,6 +661,7 @@ static int plan_buffers(Step& s) {
     s.hfin = m->hfin.as<float>(); s.cfin = m->cfin.as<float>();
     // bridge_dense (seq2seq.py:299-301): the decoder starts from tanh(state . K + b) of every encoder layer's final h and c
     s.h0base = s.bridged ? ts->hbr.as<float>() : s.hfin; s.c0base = s.bridged ? ts->cbr.as<float>() : s.cfin;
+    if (s.N > 1) { s.h0base = ts->h0rep.as<float>(); s.c0base = ts->c0rep.as<float>(); }     // (filled layer by layer: repeat_states)
     s.dfin = ts->dfin.as<float>();
     s.parts = s.det ? ts->sum_parts.as<double>() : nullptr;
     return 0;
@@ -682,7 +694,7 @@ static int stage_inputs(Step& s) {
     HIPCHK(hipMemcpyAsync(ts->d_out.p, s.dec_out, UB * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_w.p, s.weights, UB * 4, hipMemcpyHostToDevice, st));
     if (s.det) {
-        char_segments(s.enc_idx, B, T, A, V, ts->h_seg_enc_off, ts->h_seg_enc_pos);
+        char_segments(s.enc_idx, s.Be, T, A, V, ts->h_seg_enc_off, ts->h_seg_enc_pos);
         char_segments(s.dec_in, B, U, 1, V, ts->h_seg_dec_off, ts->h_seg_dec_pos);
         HIPCHK(hipMemcpyAsync(ts->seg_enc_off.p, ts->h_seg_enc_off.data(), (size_t)(V + 1) * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ts->seg_enc_pos.p, ts->h_seg_enc_pos.data(), ts->h_seg_enc_pos.size() * 4, hipMemcpyHostToDevice, st));
@@ -710,7 +722,7 @@ static int stage_inputs(Step& s) {
 static void bridge_forward(Step& s, int n) {
     if (!s.bridged) return;
     casv_model* m = s.m; TrainState* ts = s.ts;
-    const int B = s.B, W = s.W;
+    const int B = s.Be, W = s.W;
     for (int s_ = 0; s_ < 2; ++s_) {
         const TrainState::Bridge& br = ts->bridge[2 * (n - 1) + s_];
         const float* src = (s_ ? s.cfin : s.hfin) + (size_t)(n - 1) * B * W;
@@ -722,17 +734,27 @@ static void bridge_forward(Step& s, int n) {
     }
 }
 
+// N > 1: the decoder's initial states of layer n (1-based) = encoder layer n's final (bridged) states, every source's row once per
+// candidate -- right behind that layer's final-state copy / bridge, ahead of the launch that walks decoder layer n
+static void repeat_states(Step& s, int n) {
+    if (s.N == 1) return;
+    TrainState* ts = s.ts;
+    const size_t src = (size_t)(n - 1) * s.Be * s.W, dst = (size_t)(n - 1) * s.B * s.W;
+    launch_repeat_rows((s.bridged ? ts->hbr.as<float>() : s.hfin) + src, ts->h0rep.as<float>() + dst, s.Be, s.N, s.W, s.st);
+    launch_repeat_rows((s.bridged ? ts->cbr.as<float>() : s.cfin) + src, ts->c0rep.as<float>() + dst, s.Be, s.N, s.W, s.st);
+}
+
 // Phase 3 leaves every encoder layer's and every decoder layer's below the cell outputs, cell states and gates, the masked outputs
 // O[n] / DO[n], the final states (and the bridged ones), the cell's input sequence s.y, the attended sequence s.enc_out and its
 // projection u.
 static int forward_layers(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
-    const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;
+    const int B = s.B, Be = s.Be, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;      // (Be: the encoder's rows, B: the decoder's)
     const long long TB = s.TB, UB = s.UB;
     const bool deep = s.deep, residual = s.residual;
     float* hfin = s.hfin; float* cfin = s.cfin;
     TLayer* Lfw = &ts->layers[0]; TLayer* Lbw = &ts->layers[1];
-    launch_embed_tm(ts->W_(ts->iE), ts->e_idx.as<int>(), s.enc_val ? ts->e_val.as<float>() : nullptr, ts->X0.as<float>(), B, T, A, V, W, st);
+    launch_embed_tm(ts->W_(ts->iE), ts->e_idx.as<int>(), s.enc_val ? ts->e_val.as<float>() : nullptr, ts->X0.as<float>(), Be, T, A, V, W, st);
     layer_input_gemm(m, *Lfw, ts->X0.as<float>(), W);
     layer_input_gemm(m, *Lbw, ts->X0.as<float>(), W);
     bool masked1 = false;
@@ -742,9 +764,10 @@ static int forward_layers(Step& s) {
         if (int rc = layers_forward(m, f, 2, &masked1)) return rc;
     }
     // final states handed to the decoder: layer 1 = backward direction after t = 0 (seq2seq.py:280)
-    HIPCHK(hipMemcpy2DAsync(hfin, (size_t)W * 4, Lbw->hs, (size_t)2 * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(cfin, Lbw->Cs.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(hfin, (size_t)W * 4, Lbw->hs, (size_t)2 * W * 4, (size_t)W * 4, Be, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(cfin, Lbw->Cs.p, (size_t)Be * W * 4, hipMemcpyDeviceToDevice, st));
     bridge_forward(s, 1);
+    repeat_states(s, 1);
     if (!masked1) launch_mul_mask(ts->H1.as<float>(), 2 * W, s.menc_n(1), ts->O[1].as<float>(), 2 * W, TB, 2 * W, st);
     launch_embed_tm(ts->W_(ts->iE), ts->d_in.as<int>(), nullptr, ts->Y0.as<float>(), B, U, 1, V, W, st);
     // Encoder layer n and decoder layer n-1 depend only on encoder layer n-1 / decoder layer n-2, so the two
@@ -764,9 +787,10 @@ static int forward_layers(Step& s) {
                                    {&lb, nullptr, nullptr, ts->O[n].as<float>() + W, 2 * W, s.menc_n(n) ? s.menc_n(n) + W : nullptr}};
             if (int rc = layers_forward(m, f, 2, &maskede)) return rc;
         }
-        HIPCHK(hipMemcpy2DAsync(hfin + (size_t)(n - 1) * B * W, (size_t)W * 4, lb.hs, (size_t)2 * W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * B * W, lb.Cs.p, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(hfin + (size_t)(n - 1) * Be * W, (size_t)W * 4, lb.hs, (size_t)2 * W * 4, (size_t)W * 4, Be, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * Be * W, lb.Cs.p, (size_t)Be * W * 4, hipMemcpyDeviceToDevice, st));
         bridge_forward(s, n);
+        repeat_states(s, n);
         if (!maskede) launch_mul_mask(lf.hs, 2 * W, s.menc_n(n), ts->O[n].as<float>(), 2 * W, TB, 2 * W, st);
         const bool res_n = residual && n >= 3;
         {
@@ -791,9 +815,10 @@ static int forward_layers(Step& s) {
                                    {&ld, s.dec_h0(n - 1), s.dec_c0(n - 1), res_n ? nullptr : ts->DO[n - 1].as<float>(), W, s.mdec_n(n - 1)}};
             if (int rc = layers_forward(m, f, 2, &maskedn)) return rc;
         }
-        HIPCHK(hipMemcpyAsync(hfin + (size_t)(n - 1) * B * W, le.hs + (long long)(T - 1) * B * W, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * B * W, le.Cs.as<float>() + (long long)(T - 1) * B * W, (size_t)B * W * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(hfin + (size_t)(n - 1) * Be * W, le.hs + (long long)(T - 1) * Be * W, (size_t)Be * W * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(cfin + (size_t)(n - 1) * Be * W, le.Cs.as<float>() + (long long)(T - 1) * Be * W, (size_t)Be * W * 4, hipMemcpyDeviceToDevice, st));
         bridge_forward(s, n);
+        repeat_states(s, n);
         if (res_n) {
             launch_add_mul_mask(le.hs, W, ts->O[n - 1].as<float>(), W, s.menc_n(n), ts->O[n].as<float>(), W, TB, W, st);
             launch_add_mul_mask(ld.hs, W, y, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
@@ -827,11 +852,11 @@ static int forward_cell(Step& s) {
     HIPCHK(hipMemcpy2DAsync(ts->RecIn.as<float>() + C, (size_t)(C + W) * 4, h0t, (size_t)W * 4, (size_t)W * 4, B, hipMemcpyDeviceToDevice, st));
     AttnArgs att{};         // what every step's attention rows share
     att.u = ts->u.as<float>(); att.enc = s.enc_out; att.va = ts->W_(ts->iva); att.bv = ts->W_(ts->ibv);
-    att.a_base = ts->Ast.as<float>(); att.prev = nullptr; att.line = nullptr; att.rows_per_line = 1;
+    att.a_base = ts->Ast.as<float>(); att.prev = nullptr; att.line = nullptr; att.rows_per_line = s.N;     // (decoder row r attends source r / N)
     att.ctx_ld = C + W; att.ctx_mask = mcell ? mcell + W : nullptr; att.ctx_mask_ld = W + C;
     att.R = B; att.T = T; att.W = W; att.C = C; att.window = m->cfg.window_width;
     att.apos = nullptr; att.amax1 = nullptr; att.nrows = nullptr;
-    att.u_line = W; att.u_time = (long long)B * W; att.enc_line = C; att.enc_time = (long long)B * C;
+    att.u_line = W; att.u_time = (long long)s.Be * W; att.enc_line = C; att.enc_time = (long long)s.Be * C;
     bool top_persistent = false;
     if (unsigned* slot = persist_slot(m, ts)) {
         // ONE launch for the whole recurrence of the cell (train_persist_top.hip)
@@ -1258,7 +1283,7 @@ static int update(Step& s, double* loss_out, double* norm_out) {
 // set (recurrences_gave_up) and the caller starts over.
 static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
     casv_model* m = s.m; TrainState* ts = s.ts;
-    ts->B = s.B; ts->T = s.T; ts->U = s.U; ts->A = s.A;
+    ts->B = s.B; ts->Be = s.Be; ts->N = s.N; ts->T = s.T; ts->U = s.U; ts->A = s.A;
     ts->score_B = 0;                       // (a scoring call's attention rows are overwritten)
     m->encoded = false;                    // the final-state buffers are shared with the inference session
     if (int rc = plan_buffers(s)) return rc;
@@ -1302,7 +1327,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     OrderedScope ordered(m->deterministic);
     Step s{};
     s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = mode; s.B = B; s.T = T; s.U = U; s.A = A;
+    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
     s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = weights;
     s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
     s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
@@ -1339,7 +1364,7 @@ static int score_head(Step& s) {
 static int score_attempt(Step s, const ScoreOut& out, bool* redo) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
     const int B = s.B, T = s.T, U = s.U;
-    ts->B = B; ts->T = T; ts->U = U; ts->A = s.A;
+    ts->B = B; ts->Be = s.Be; ts->N = s.N; ts->T = T; ts->U = U; ts->A = s.A;
     ts->score_B = 0;
     m->encoded = false;                    // the final-state buffers are shared with the inference session
     if (int rc = plan_buffers(s)) return rc;
@@ -1393,11 +1418,13 @@ static int score_state(casv_model* m) {
     return CASV_OK;
 }
 
-extern "C" int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
-                                  const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
-                                  float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
-    if (!m || !enc_idx || !dec_in || !dec_out || !logp || !best || !rank || !nll || !count) return fail(CASV_ERR_ARG, "null argument");
-    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
+// The scoring call on Be sources with N given targets each (decoder row r = b * N + n reads source b's encoder pass): the range
+// check over all rows before anything is launched, the state, at most two attempts.
+static int score_call(casv_model* m, int32_t Be, int32_t N, int32_t T, int32_t U, int32_t A,
+                      const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out, const ScoreOut& out) {
+    if (!m || !enc_idx || !dec_in || !dec_out || !out.logp || !out.best || !out.rank || !out.nll || !out.count) return fail(CASV_ERR_ARG, "null argument");
+    if (Be < 1 || N < 1 || T < 1 || U < 1 || A < 1 || (long long)Be * N > INT32_MAX) return fail(CASV_ERR_ARG, "bad shape");
+    const int B = Be * N;
     const long long UB = (long long)U * B;
     for (long long i = 0; i < UB; ++i) {     // (before anything is launched)
         if (dec_out[i] < -1 || dec_out[i] >= m->V) return fail(CASV_ERR_ARG, "dec_out[%lld] = %d outside [-1, %d)", i, dec_out[i], m->V);
@@ -1414,22 +1441,36 @@ extern "C" int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U
     const std::vector<float> ones((size_t)UB, 1.0f);            // (stage_inputs stages the step's sample weights: the head reads none)
     Step s{};
     s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = 0; s.B = B; s.T = T; s.U = U; s.A = A;
+    s.mode = 0; s.B = B; s.Be = Be; s.N = N; s.T = T; s.U = U; s.A = A;
     s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = ones.data();
     s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * B; s.UB = UB;
+    s.TB = (long long)T * Be; s.UB = UB;
     // (no masks, no regulariser; det / fused govern the backward pass and the ordered sums of the loss: the head has neither, and
     // persist_slot and the launchers read the "deterministic" option from the handle)
     s.training = false; s.det = false; s.fused = false;
     s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
     s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
-    const ScoreOut out{logp, best, rank, nll, count, align};
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool redo = false;
         if (int rc = score_attempt(s, out, &redo)) return rc;
         if (!redo) return CASV_OK;
     }
     return fail(CASV_ERR_STATE, "the scoring call gave up twice: its second attempt took a persistent launch");
+}
+
+extern "C" int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
+                                  const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                                  float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
+    return score_call(m, B, 1, T, U, A, enc_idx, enc_val, dec_in, dec_out, ScoreOut{logp, best, rank, nll, count, align});
+}
+
+// N candidate targets per source on ONE encoder pass (kt:407 / s2s:491-497 as casv_score_targets, whose N = 1 call this is): the
+// embedding, the encoder stack, its final states and u = enc_out . U_a are computed for the B sources; every decoder row -- the
+// decoder layers, the attention cell, the projection, the head -- for the B * N candidates, row b * N + n on source b.
+extern "C" int casv_score_candidates(casv_model* m, int32_t B, int32_t N, int32_t T, int32_t U, int32_t A,
+                                     const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                                     float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
+    return score_call(m, B, N, T, U, A, enc_idx, enc_val, dec_in, dec_out, ScoreOut{logp, best, rank, nll, count, align});
 }
 
 extern "C" int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w) {

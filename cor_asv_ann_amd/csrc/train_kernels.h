@@ -16,6 +16,8 @@ void launch_mul_mask(const float* in, long long ld_in, const float* mask, float*
 // residual_connections (seq2seq.py:284-291,359-360): out[r][f] = (a[r][f] + b[r][f]) * mask[f] (mask nullptr: times one)
 void launch_add_mul_mask(const float* a, long long lda, const float* b, long long ldb, const float* mask, float* out, long long ld_out,
                          long long rows, int F, hipStream_t st);
+// out[r * N + n][f] = in[r][f] for `rows` rows of F floats: a source's states, once per candidate (casv_score_candidates)
+void launch_repeat_rows(const float* in, float* out, long long rows, int N, int F, hipStream_t st);
 // bridge_dense backward (seq2seq.py:299-301): dy[i] *= 1 - y[i]^2
 void launch_tanh_bwd(float* dy, const float* y, long long n, hipStream_t st);
 void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, long long ld_mask, float* out, long long ld_out,
@@ -44,6 +46,8 @@ struct RecJob {
     int len, reverse;
     float* om; long long om_ld; const float* omask;   // optional second copy of the outputs, times a per-unit mask [W] (the next layer's dropped-out input) or nullptr
     float* zero;                     // optional [len][B][W]: cleared tile by tile along the way (the backward pass's dL/dh accumulator of this layer)
+    int rows;                        // this job's rows where they are fewer than RecArgs.B (0 = B): every "B" of the shapes above is then this
+                                     // count; the grid, the counters and the give-up word stay those of B, the row blocks beyond leave at once
 };
 struct RecArgs { RecJob job[2]; int njobs, B, W; unsigned* counters; int fault; };   // fault: test of the give-up path (one workgroup leaves early)
 size_t train_recurrence_counter_bytes(int B);

@@ -133,6 +133,19 @@ void launch_add_mul_mask(const float* a, long long lda, const float* b, long lon
     const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(add_mul_mask_kernel, dim3(blocks), dim3(256), 0, st, a, lda, b, ldb, mask, out, ld_out, rows, F);
 }
+// ---- out[r * N + n][f] = in[r][f]: every row N times in a row (casv_score_candidates: a source's final states for its N candidates) ----
+__global__ void repeat_rows_kernel(const float* __restrict__ in, float* __restrict__ out, long long rows, int N, int F) {
+    const long long n = rows * N * F;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / F; const int f = (int)(i % F);
+        out[i] = in[(r / N) * F + f];
+    }
+}
+void launch_repeat_rows(const float* in, float* out, long long rows, int N, int F, hipStream_t st) {
+    const long long n = rows * N * F;
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(repeat_rows_kernel, dim3(blocks), dim3(256), 0, st, in, out, rows, N, F);
+}
 __global__ void tanh_bwd_kernel(float* __restrict__ dy, const float* __restrict__ y, long long n) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dy[i] *= 1.0f - y[i] * y[i];
 }

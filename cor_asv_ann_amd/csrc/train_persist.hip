@@ -14,6 +14,11 @@
 // leave at once (16 B per thread and stage: one memory round trip per step, not one per stage -- these lines were written by
 // other XCDs a moment ago and miss every cache); then gemm_skinny.hip's K loop, stage by stage through the same LDS image with
 // the same MFMA sequence, and its cell epilogue.  Results are therefore those of the per-step launches bit for bit (tested).
+//
+// The two jobs of a launch may differ in rows (casv_score_candidates: encoder layer n on the Be sources beside decoder layer n - 1
+// on Be * N candidates).  The grid, the (layer, row block, unit group) mapping and the counters are those of RecArgs.B, the larger
+// count; a job with RecJob.rows < B uses its own rows for strides, clamps and guards, and its workgroups beyond them leave at once.
+// Nothing here waits for the whole grid -- hand-offs are per (job, row block) -- so the idle workgroups are harmless.
 #include "common.h"
 #include "handoff.h"
 #include "persist_host.h"
@@ -48,9 +53,12 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
     unsigned* const counter = ra.counters + (long long)(jb * nrb + rb) * 32;
     unsigned* const abort_w = ra.counters + (long long)2 * nrb * 32;
     const int len = job.len;
+    // the job's own rows: its strides [len][R][..], row clamps and store guards; the mapping and the counters above are ra.B's alone
+    const int R = job.rows ? job.rows : B;
+    if (m0 >= R) return;        // (a row block beyond the smaller job's rows: nobody waits for it -- the hand-offs are per (job, row block))
 
     const int srow = tid >> 3, sk = 4 * (tid & 7);
-    int mrow = m0 + srow; mrow = mrow < B ? mrow : B - 1;
+    int mrow = m0 + srow; mrow = mrow < R ? mrow : R - 1;
     const float* bp[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) bp[i] = job.Wr + (long long)(n0 + srow + 32 * i) * W + sk;
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
     float cst[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        int m = m0 + q + 8 * wave + 4 * lh; m = m < B ? m : B - 1;
+        int m = m0 + q + 8 * wave + 4 * lh; m = m < R ? m : R - 1;
         cst[q] = job.c0 ? job.c0[(long long)m * W + u] : 0.0f;
     }
 
@@ -104,15 +112,15 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
         if (ra.fault && blockIdx.x == 0 && k == 1) return;      // (test: a workgroup that never hands on -- its peers must give up)
         const int t = job.reverse ? len - 1 - k : k, tp = job.reverse ? t + 1 : t - 1;
         const float* arow = k == 0 ? (job.h0 ? job.h0 + (long long)mrow * W + sk : nullptr)
-                                   : job.hs + ((long long)tp * B + mrow) * job.hs_ld + sk;
+                                   : job.hs + ((long long)tp * R + mrow) * job.hs_ld + sk;
         // x.Wx + b of this step's elements
         float zpre[4][4];
         {
-            const float* zin0 = job.Z + (long long)t * B * (4 * W);
+            const float* zin0 = job.Z + (long long)t * R * (4 * W);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int m = m0 + q + 8 * wave + 4 * lh;
-                const float* zr = zin0 + (long long)(m < B ? m : B - 1) * (4 * W) + n0 + l31;
+                const float* zr = zin0 + (long long)(m < R ? m : R - 1) * (4 * W) + n0 + l31;
                 zpre[q][0] = zr[0]; zpre[q][1] = zr[32]; zpre[q][2] = zr[64]; zpre[q][3] = zr[96];
             }
         }
@@ -174,18 +182,18 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
             for (int c = 0; c < 4; ++c) z[q][c] = s_gate[c][4 * wave + q][lane];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { z[q][0] += zpre[q][0]; z[q][1] += zpre[q][1]; z[q][2] += zpre[q][2]; z[q][3] += zpre[q][3]; }
-        float* cout = job.Cs + (long long)t * B * W;
-        float* hout = job.hs + (long long)t * B * job.hs_ld;
-        float* gout = job.Gt + (long long)t * B * (4 * W);
-        float* mout = job.om ? job.om + (long long)t * B * job.om_ld : nullptr;        // the outputs once more, masked: the next layer's input
+        float* cout = job.Cs + (long long)t * R * W;
+        float* hout = job.hs + (long long)t * R * job.hs_ld;
+        float* gout = job.Gt + (long long)t * R * (4 * W);
+        float* mout = job.om ? job.om + (long long)t * R * job.om_ld : nullptr;        // the outputs once more, masked: the next layer's input
         // (the layer's dL/dh accumulator of the backward pass, cleared here 16 bytes per thread and step instead of by a fill of the
         // whole buffer in front of the backward pass: these stores cost nothing beside the epilogue's own)
-        if (job.zero && m0 + srow < B)
-            *reinterpret_cast<f32x4*>(job.zero + ((long long)t * B + m0 + srow) * W + ug * 32 + sk) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (job.zero && m0 + srow < R)
+            *reinterpret_cast<f32x4*>(job.zero + ((long long)t * R + m0 + srow) * W + ug * 32 + sk) = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int m = m0 + q + 8 * wave + 4 * lh;
-            if (m < B) {
+            if (m < R) {
                 const LstmCellOut cell = lstm_cell(z[q][0] + 0.f, z[q][1] + 0.f, z[q][2] + 0.f, z[q][3] + 0.f, cst[q]);
                 cst[q] = cell.c;
                 cout[(long long)m * W + u] = cell.c;

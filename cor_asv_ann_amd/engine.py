@@ -416,6 +416,40 @@ class HipEngine(object):
             align = (lo, w)
         return logp, best, rank, nll, count, align
 
+    def score_candidates(self, enc_idx, enc_val, dec_in, dec_out, want_align=False):
+        """N candidate targets per source on one encoder pass (casv_score_candidates): enc_idx / enc_val (B,T[,A]) as score_targets,
+        dec_in / dec_out (B,N,U); candidate n of source b is decoder row b * N + n and reads source b's encoder pass.  A candidate
+        whose dec_out row is all -1 is padding (a source with fewer than N candidates): logp 0, rank -1, count 0, nll 0.0.  Returns
+        (logp (B,N,U), best (B,N,U), rank (B,N,U), nll float64 (B,N), count (B,N), align) with align = None, the dense rows (B,N,U,T)
+        (want_align=True) or the window form (lo (B,N,U), w (B,N,U,K)) (want_align='sparse'); everything else as score_targets, whose
+        results are this call's at N = 1."""
+        enc_idx = nv.carray(enc_idx, np.int32)
+        if enc_idx.ndim == 2:
+            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
+        B, T, A = enc_idx.shape
+        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        dec_in = nv.carray(dec_in, np.int32)
+        dec_out = nv.carray(dec_out, np.int32)
+        assert dec_in.ndim == 3 and dec_in.shape == dec_out.shape and dec_in.shape[0] == B
+        N, U = dec_in.shape[1:]
+        logp = np.empty((B, N, U), np.float32)
+        best = np.empty((B, N, U), np.int32)
+        rank = np.empty((B, N, U), np.int32)
+        nll = np.empty((B, N), np.float64)
+        count = np.empty((B, N), np.int32)
+        sparse = want_align == 'sparse'
+        align = np.empty((B, N, U, T), np.float32) if want_align and not sparse else None
+        nv.check(self.lib.casv_score_candidates(self.handle, B, N, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
+                                                nv.ptr(dec_out), nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count),
+                                                nv.ptr(align)))
+        if sparse:
+            K = 2 * self.window_width + 1
+            lo = np.empty((B, N, U), np.int32)
+            w = np.empty((B, N, U, K), np.float32)
+            nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(lo), nv.ptr(w)))
+            align = (lo, w)
+        return logp, best, rank, nll, count, align
+
     def score_release(self):
         """Drop the forward-only state score_targets keeps outside a training session (allowed when there is none)."""
         nv.check(self.lib.casv_score_release(self.handle))

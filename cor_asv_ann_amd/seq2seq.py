@@ -679,6 +679,57 @@ class Sequence2Sequence(object):
                 aligns[j] = self._alignment_rows(align, i, k, idx.shape[1])
         return logprobs, scores, predictions, ranks, aligns
 
+    def score_candidates(self, sources, candidates, conf=None, alignments=False):
+        """`score_lines` for several candidate targets per source -- rescoring an n-best list -- with ONE encoder pass per source
+        (`HipEngine.score_candidates`) instead of one per pair.  `candidates[j]` is the list of target lines of `sources[j]`, each
+        ending in a newline.  Returns (logprobs, scores, predictions, ranks, aligns): each a list per source of per-candidate
+        entries, in input order, with `score_lines`' meaning.  An empty candidate, or any candidate of an empty source, is the
+        skipped entry [], 0.0, '', [], []; a source without candidates gives empty lists.  The sources with something to score are
+        taken in order into chunks: a chunk grows while (its sources) x (the largest candidate count among them) stays within
+        max(`batch_size`, that count) decoder rows -- a source with more than `batch_size` candidates goes alone.  The chunk's N is
+        that largest count, shorter lists are filled with padding candidates; as in `score_lines` a result depends on the padded
+        lengths of its chunk."""
+        assert self.status == 2
+        assert len(sources) == len(candidates) and (conf is None or len(conf) == len(sources))
+        from .training import batch_to_indices
+        eng = self._require_engine()
+        logprobs = [[[] for _ in c] for c in candidates]
+        scores = [[0.0 for _ in c] for c in candidates]
+        predictions = [['' for _ in c] for c in candidates]
+        ranks = [[[] for _ in c] for c in candidates]
+        aligns = [[[] for _ in c] for c in candidates]
+        want_align = False if not alignments else (True if alignments == 'dense' else 'sparse')
+        live = [(j, [k for k, line in enumerate(candidates[j]) if line]) for j in range(len(sources)) if sources[j]]
+        live = [(j, ks) for j, ks in live if ks]
+        chunks, chunk, most = [], [], 0
+        for j, ks in live:
+            grown = max(most, len(ks))
+            if chunk and (len(chunk) + 1) * grown > max(self.batch_size, grown):
+                chunks.append((chunk, most))
+                chunk, grown = [], len(ks)
+            chunk.append((j, ks))
+            most = grown
+        if chunk:
+            chunks.append((chunk, most))
+        for chunk, N in chunks:
+            flat = [candidates[j][ks[n]] if n < len(ks) else '' for j, ks in chunk for n in range(N)]     # ('': a padding candidate, all -1)
+            idx, val, dec_in, dec_out, _ = batch_to_indices(self, [sources[j] for j, _ in chunk], flat,
+                                                            None if conf is None else [conf[j] for j, _ in chunk])
+            U = dec_in.shape[1]
+            logp, best, rank, nll, count, align = eng.score_candidates(idx, val, dec_in.reshape(len(chunk), N, U),
+                                                                       dec_out.reshape(len(chunk), N, U), want_align=want_align)
+            if align is not None:           # (rows b * N + n, as _alignment_rows indexes them)
+                align = tuple(a.reshape((-1,) + a.shape[2:]) for a in align) if isinstance(align, tuple) else align.reshape((-1,) + align.shape[2:])
+            for b, (j, ks) in enumerate(chunk):
+                for n, k in enumerate(ks):
+                    c = int(count[b, n])
+                    logprobs[j][k] = logp[b, n, :c].tolist()
+                    scores[j][k] = float(nll[b, n]) / max(c, 1)
+                    predictions[j][k] = self._chars(best[b, n, :c][best[b, n, :c] >= 0])
+                    ranks[j][k] = rank[b, n, :c].tolist()
+                    aligns[j][k] = self._alignment_rows(align, b * N + n, c, idx.shape[1])
+        return logprobs, scores, predictions, ranks, aligns
+
     def correct_batches(self, batches, fast=True, greedy=True, alignments=True, after_decode=None):
         """`correct_lines` over a stream of batches -- an iterable of `lines` or of `(lines, conf)` -- as a three-stage pipeline:
         a worker thread turns the next batch into index arrays, a second one drives the device (its C-ABI calls release the GIL),

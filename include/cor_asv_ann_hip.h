@@ -232,9 +232,23 @@ int casv_train_end(casv_model* m);
 int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
                        const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
                        float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align);
-/* The attention rows of the LAST casv_score_targets call (kt:407 / s2s:491-497) in window form, same conventions as
- * casv_get_alignments_sparse: lo (B,U) first position of the window (-1: the row is all NaN), w (B,U,K) the weights from there
- * (zeros beyond the window), K >= 2*window_width+1.  CASV_ERR_STATE once a train step or casv_score_release has run since. */
+/* N candidate targets per source on ONE encoder pass (keras_train.py:407 / seq2seq.py:491-497 -- kt:407 / s2s:491-497 -- as
+ * casv_score_targets, which is the N = 1 call of the same code): B sources enc_idx / enc_val (B,T,A), N targets each dec_in /
+ * dec_out (B,N,U).  Decoder row r = b * N + n reads the encoder outputs, u = enc_out . U_a and the final states of source b: the
+ * embedding, the encoder stack and u are computed B times, not B * N times, and the encoder's buffers are held once per source.
+ * logp / best / rank (B,N,U), nll / count (B,N), align NULL or (B,N,U,T): every definition, the NaN rules, "not clipped", the
+ * arithmetic, "deterministic" / "persistent" with the give-up path, the forward-only state outside a session, the behaviour inside
+ * one, the sharing of hfin / cfin and "leaves the handle without an encoded batch" are casv_score_targets'.  A source with fewer
+ * than N candidates pads with candidates whose dec_out row is all -1 (their dec_in may be all -1 too): logp 0, rank -1, count 0,
+ * nll +0.0.  N < 1 is CASV_ERR_ARG; the [-1, V) check runs over all B*N*U entries before anything is launched.
+ * casv_score_get_alignments_sparse afterwards returns the (B*N, U) rows. */
+int casv_score_candidates(casv_model* m, int32_t B, int32_t N, int32_t T, int32_t U, int32_t A,
+                          const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                          float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align);
+/* The attention rows of the LAST casv_score_targets / casv_score_candidates call (kt:407 / s2s:491-497) in window form, same
+ * conventions as casv_get_alignments_sparse: lo (B,U) first position of the window (-1: the row is all NaN), w (B,U,K) the weights
+ * from there (zeros beyond the window), K >= 2*window_width+1; after casv_score_candidates B is its B*N rows.  CASV_ERR_STATE once
+ * a train step or casv_score_release has run since. */
 int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w);
 /* Drop the forward-only state of casv_score_targets (kt:407 / s2s:491-497); allowed when there is none. */
 int casv_score_release(casv_model* m);
