@@ -111,7 +111,7 @@ __device__ __forceinline__ float lm_prob(const BeamState& s, const int r, const 
 // ... and whether the row is NaN: its context (row_kernels.h, lm_context_nan: the window of this step, the parent's query) or a logit
 __device__ __forceinline__ bool lm_row_nan(const BeamState& s, const int r, const int step, const LmStats& st, const int lane) {
     const int win = s.lm_win[(long long)(step + 1) * s.R + r];
-    return lm_context_nan(s.lm_q + (long long)s.prev[r] * s.W, s.lm_va, s.lm_bv, s.W, win < 0 ? 0 : win >> 16, lane) || st.sum != st.sum;
+    return lm_context_nan(s.lm_q + (long long)s.prev[r] * s.W, s.lm_va, s.lm_bv, s.W, win_count(win), lane) || st.sum != st.sum;
 }
 
 // Phase A1 for expansion row i of `line` (one wave): the row's softmax (when the step hands over logits), the rejection

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void lm_softmax_kernel(const LmSoftmaxArgs a) 
     for (int v = lane; v < V; v += 64) sum += expf(x[v] - m);
     sum = wave_sum(sum);
     const int win = a.win[r];
-    const bool cnan = lm_context_nan(a.wq + (long long)r * a.W, a.va, a.bv, a.W, win < 0 ? 0 : win >> 16, lane);
+    const bool cnan = lm_context_nan(a.wq + (long long)r * a.W, a.va, a.bv, a.W, win_count(win), lane);
     for (int v = lane; v < Vp; v += 64) p[v] = v < V ? (cnan ? __builtin_nanf("") : expf(x[v] - m) / sum) : 0.0f;
 }
 void launch_lm_softmax(const LmSoftmaxArgs& a, hipStream_t stream) {

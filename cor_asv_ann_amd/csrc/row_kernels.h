@@ -31,7 +31,8 @@ __device__ __forceinline__ void wave_argmax(float& best, int& bidx) {
 
 // ---------------------------------------------------------------------------------------------
 // attention.py:526-575.  Only the <= 2*window+1 positions that survive the window mask are evaluated
-// (the reference evaluates all T and multiplies by a 0/1 mask, attention.py:540-569: same values).
+// (the reference evaluates all T and multiplies by a 0/1 mask, attention.py:540-569: the same values, with one declared exception
+// -- an energy that overflows exp OUTSIDE the window makes the reference's row NaN through inf * 0; it is not looked at here).
 //   t' = sum_s a_prev[s]*s + 1 (float64 accumulate, rounded once to fp32 -- see oracle/model.py)
 //   keep s with |t' - s| <= window ; e[s] = exp(tanh(wq + u[s]).v_a + b_v) ; a' = e / sum e
 //   ctx = sum_s a'[s] * enc[s]
@@ -42,6 +43,11 @@ constexpr int ATT_ROWS = 8;      // rows (waves) per workgroup: the N=8 hypothes
 // One decoder row r at `step` (reads alignment slot `step` or the parent's, writes slot step + 1), in three parts so that
 // a workgroup can stage the attended rows between them (attention_line_kernel); attention_row chains them on global memory.
 struct AttWin { int s_lo, cnt; };
+// The window store's entry of a row: s_lo | cnt << 16; -1 = no window.  Negative with WIN_UNDERFLOW = a window whose energies all
+// underflowed: the row is NaN at all T positions like an empty window's (every reader of the row tests `win < 0`), but the window
+// itself had cnt positions -- what the LM's attention, which has its own energy, asks (win_count).
+constexpr int WIN_UNDERFLOW = (int)0x80000000;
+__device__ __forceinline__ int win_count(const int win) { return win == -1 ? 0 : (win & ~WIN_UNDERFLOW) >> 16; }
 
 // (1) t' = sum_s a_prev[s] * s + 1 and the window |t' - s| <= window_width (attention.py:553-567).  acc = this lane's share of the
 // sum: a_prev[s] * s over s = lane, lane + 64, ... in ascending order, in float64.
@@ -156,19 +162,23 @@ __device__ __forceinline__ void att_normalise(const AttnArgs& a, const int r, co
         }
     }
     if (!write) return;
+    // No window, or every energy of the window underflowed to 0: the reference divides its masked row by a zero sum -- 0/0 at ALL T
+    // positions, not only inside the window.  (e[] holds the window's NaNs already: the context and the next step's window follow
+    // from them, in registers as from memory.)
+    const bool empty = cnt <= 0 || denom == 0.0f;
     for (int s = lane; s < T; s += 64) {
         float v = 0.0f;
-        if (cnt <= 0) v = nanv;                 // 0/0 everywhere, as in the reference
+        if (empty) v = nanv;
 #pragma unroll
         for (int i = 0; i < MAXWIN; ++i)
             if (i < cnt && s == s_lo + i) v = e[i];
         aout[s] = v;
     }
     if (lane == 0) {
-        if (a.apos) a.apos[r] = cnt <= 0 ? (double)nanv : pos;
+        if (a.apos) a.apos[r] = empty ? (double)nanv : pos;
         if (a.amax1) a.amax1[r] = (amax == 1.0f) ? 1 : 0;
-        if (a.win_out) a.win_out[r] = cnt > 0 ? (s_lo | (cnt << 16)) : 0;
-        if (a.win_store) a.win_store[(long long)(step + 1) * a.R + r] = cnt > 0 ? (s_lo | (cnt << 16)) : -1;
+        if (a.win_out) a.win_out[r] = !empty ? (s_lo | (cnt << 16)) : 0;
+        if (a.win_store) a.win_store[(long long)(step + 1) * a.R + r] = !empty ? (s_lo | (cnt << 16)) : cnt > 0 ? (WIN_UNDERFLOW | s_lo | (cnt << 16)) : -1;
     }
 }
 template <bool HANDOFF, int WB, class URow>

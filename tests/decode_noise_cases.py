@@ -146,12 +146,13 @@ def device_encoder(case, w, inputs):
 # ---------------------------------------------------------------------------------------------------------------------------
 # decoder step
 
-def build_step(case, seed=7):
+def build_step(case, seed=7, window=None):
     """cfg, float32 weights, and the step-0 inputs: line (R,), enc (lines,T,C), states [h1,c1,...], a (R,T), p_in (R,V).
+    window: the attention's window width (ModelConfig.window; step_engine hands it to the device), None = the default 5.
     Row kinds by r % 8: 0 one-hot, 1 all zero (t' = 1), 2 spread near the start, 3 spread at the end (window partly off the line),
     4 empty window (t' > T + 4), 5-7 spread over three neighbours anywhere."""
     name, d, W, V, R, T, nl, steps = case
-    cfg = ModelConfig(depth=d, width=W, voc_size=V)
+    cfg = ModelConfig(depth=d, width=W, voc_size=V) if window is None else ModelConfig(depth=d, width=W, voc_size=V, window=window)
     w = make_weights(cfg, emb_scale=4.0)
     rng = np.random.default_rng(seed)
     for k in w:
@@ -223,7 +224,7 @@ def device_step(eng, line, states, a, p_in):
 
 def step_engine(cfg, w, enc, arithmetic):
     from cor_asv_ann_amd.engine import HipEngine
-    eng = HipEngine(cfg.depth, cfg.width, cfg.voc_size)
+    eng = HipEngine(cfg.depth, cfg.width, cfg.voc_size, window_width=cfg.window)
     eng.set_weights(w)
     eng.set_option('arithmetic', arithmetic)
     nl, T = enc.shape[:2]

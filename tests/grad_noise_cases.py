@@ -50,14 +50,15 @@ MID = ('mid_d2_w256_b512', 2, 256, 40, 512, 63, 4.0, True, {}, 1, ())
 ALL = CASES + [MID]
 
 
-def build(case, seed=4, source=None):
+def build(case, seed=4, source=None, window=None):
     """cfg, float32 weights, oracle inputs (enc_in, dec_in, dec_out, wts, masks) and the device batch of a case.
     source: None -- every source line has the targets' L characters and the end character; S -- the source lines have S characters
     and the end character (the targets keep L: the two lengths are separate), and about a third of them are shorter, the
     shortest of one character (where S = 1: the end character alone): the positions behind a line's end are zero rows for the oracle (the reference
-    runs its LSTMs over them unmasked) and index -1 for the device."""
+    runs its LSTMs over them unmasked) and index -1 for the device.
+    window: the attention's window width (ModelConfig.window; hand the same to `device`), None = the default 5."""
     name, d, W, V, B, L, es, with_masks, flags, A, frozen = case
-    cfg = ModelConfig(depth=d, width=W, voc_size=V, **flags)
+    cfg = ModelConfig(depth=d, width=W, voc_size=V, **flags) if window is None else ModelConfig(depth=d, width=W, voc_size=V, window=window, **flags)
     w = make_weights(cfg, emb_scale=es)
     rng = np.random.default_rng(seed)
     for k in w:
@@ -122,11 +123,11 @@ def ratios(got, o32, o64):
     return out
 
 
-def device(case, w, batch, path, deterministic, probe=None):
+def device(case, w, batch, path, deterministic, probe=None, window=None):
     """(loss, norm, grads) of one mode-2 train step on the device.  probe(eng): called behind the step, inside its session."""
     from cor_asv_ann_amd.engine import HipEngine
     name, d, W, V, B, L, es, with_masks, flags, A, frozen = case
-    eng = HipEngine(d, W, V, **flags)
+    eng = HipEngine(d, W, V, **flags) if window is None else HipEngine(d, W, V, window_width=window, **flags)
     try:
         eng.set_weights(w)
         eng.set_option('persistent', -1 if path == 'fused' else 0)

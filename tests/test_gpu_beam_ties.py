@@ -24,13 +24,9 @@ os.environ.setdefault('CASV_POISON', '1')      # read once by the library, at it
 from oracle.decode import decode_sequence_beam
 from tests.lm_oracle import decode_sequence_beam_lm
 from tests.tie_models import CASES, BY_NAME, groups_of, run_search
+from tests.tie_models import bits as _bits, same_bits as _same_bits, against_the_oracle as _against_the_oracle
 
-RT, AT = 2e-4, 2e-6
 _oracle = {}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _expected(case, lm):
@@ -102,51 +98,6 @@ def _decode(eng, case, idx):
         out.append(dict(n_found=int(res['n_found'][j]), n_steps=int(res['n_steps'][j]), results=rows,
                         empty=res['len'][j * MR + len(rows):(j + 1) * MR].copy()))
     return out
-
-
-def _same_bits(a, b, what):
-    assert len(a) == len(b)
-    for j, (x, y) in enumerate(zip(a, b)):
-        assert (x['n_found'], x['n_steps'], len(x['results'])) == (y['n_found'], y['n_steps'], len(y['results'])), (what, j)
-        for k, (p, q) in enumerate(zip(x['results'], y['results'])):
-            for key in ('idx', 'rej', 'lo'):
-                assert np.array_equal(p[key], q[key]), (what, j, k, key)
-            for key in ('prob', 'align', 'w'):
-                assert np.array_equal(_bits(p[key]), _bits(q[key])), (what, j, k, key)
-            assert p['score'].view(np.int64) == q['score'].view(np.int64), (what, j, k)
-
-
-def _against_the_oracle(case, got, want, c_i):
-    T, V = case.T, case.V
-    exact = {int(_bits(np.float32(1) / np.float32(V)))}
-    if case.rejection:
-        exact.add(int(_bits(np.float32(case.rejection))))
-    for j, (dev, (res, stats, rej, _)) in enumerate(zip(got, want)):
-        assert dev['n_found'] == stats['finals'] and dev['n_steps'] == stats['steps'], (j, dev['n_found'], dev['n_steps'], stats)
-        assert len(dev['results']) == min(len(res), case.max_results), j
-        assert not dev['empty'].any(), j
-        for k, d in enumerate(dev['results']):
-            text, probs, score, aligns = res[k][:4]
-            where = (case.name, j, k, text)
-            assert list(d['idx']) == [c_i[ch] for ch in text], where
-            assert list(d['rej']) == rej[k], where
-            p = np.asarray(probs, np.float32)
-            pinned = np.isin(_bits(p), list(exact))
-            assert np.array_equal(_bits(d['prob'])[pinned], _bits(p)[pinned]), where
-            assert np.allclose(d['prob'], p, rtol=RT, atol=0), where
-            assert abs(d['score'] - score) <= RT * abs(score), where
-            a = np.asarray(aligns, np.float32).reshape(len(text), T)
-            assert np.allclose(d['align'], a, rtol=RT, atol=AT), where
-            window = np.zeros_like(d['align'])
-            for s in range(len(text)):
-                if rej[k][s] >= 0:
-                    assert np.array_equal(d['align'][s], np.eye(T, dtype=np.float32)[rej[k][s]]), where
-                    assert d['lo'][s] == rej[k][s] and d['w'][s, 0] == 1 and not d['w'][s, 1:].any(), where
-                assert d['lo'][s] >= 0, where
-                n = min(d['w'].shape[1], T - int(d['lo'][s]))
-                window[s, d['lo'][s]:d['lo'][s] + n] = d['w'][s, :n]
-                assert not d['w'][s, n:].any(), where
-            assert np.array_equal(_bits(window), _bits(d['align'])), where
 
 
 VARIANTS = [(c.name, a, False) for c in CASES for a in (0, 2)] + [(c.name, a, True) for c in CASES if c.lm for a in (0, 2)]

@@ -110,18 +110,30 @@ def beam_form(N, V, width_in, T):
 
 # ------------------------------------------------------------------------------------------------------------------ search
 RULES = ('tie_low', 'insort_right', 'stop_ge', 'cap_other_end')
+# ... and of the rejection rule (tests/steer_models.py: models whose attention rows are steered, so that the rule decides)
+REJECTION_RULES = ('round_half_up', 'is1_ignored', 'is1_from_attention_row', 'mis_not_tested')
+# ... and the threshold of the misalignment moved to either side of 0.1: 0.09 lets a misalignment of 2/21 out, 0.13 lets 1/9 and 1/8 in
+THRESHOLD_RULES = ('mis_below_0_09', 'mis_below_0_13')
 
 
-def search(m, source_seq, encoder_outputs, rules=(), trace=None, lm=False):
+def search(m, source_seq, encoder_outputs, rules=(), trace=None, lm=False, beyond_line=None):
     """oracle/decode.py decode_sequence_beam, line for line, with
     rules  'tie_low'        candidate ties towards the LOWER index
            'insort_right'   children (and finished hypotheses) inserted behind their equals
            'stop_ge'        `>=` in the stop test
            'cap_other_end'  the queue cap keeps the other end
+           'round_half_up'            the source position rounded as floor(x + 0.5) instead of half-to-even
+           'is1_ignored'              a one-hot parent alignment treated like any other
+           'is1_from_attention_row'   "one-hot" asked of the step's own attention row instead of the parent's alignment
+           'mis_not_tested'           the rejection candidate added whatever the misalignment
+           'mis_below_0_09', 'mis_below_0_13'   the misalignment compared with 0.09 / 0.13 instead of 0.1
+    beyond_line  'no_candidate': a source position beyond the line gives no rejection candidate -- the device's documented
+           deviation -- where the reference, and this function without the switch, raise IndexError
     trace  a dict that receives what the case table promises (see the keys below)
     lm     lm_predict: a child's cost comes from the LM's row (tests/lm_oracle.py decode_sequence_beam_lm)
     -> list of (text, probs, score, alignments, rejection positions), best first, and the stats dict."""
-    assert set(rules) <= set(RULES)
+    assert set(rules) <= set(RULES + REJECTION_RULES + THRESHOLD_RULES) and beyond_line in (None, 'no_candidate')
+    mis_limit = 0.09 if 'mis_below_0_09' in rules else 0.13 if 'mis_below_0_13' in rules else 0.1
     insort = insort_right if 'insort_right' in rules else insort_left
     V = m.voc_size
     i_c = m.mapping[1]
@@ -134,7 +146,15 @@ def search(m, source_seq, encoder_outputs, rules=(), trace=None, lm=False):
     final_beam = []
     max_batches = T * 2
     tr = dict(tied_pops=0, width_cut_ties=0, cap_cut_ties=0, queue_max=0, finals_max=0, finals_per_pop_max=0, new_keys_max=0,
-              rej_inside=0, rej_behind=0, rej_index0=0, rej_raised=0)
+              rej_inside=0, rej_behind=0, rej_index0=0, rej_raised=0,
+              # the rejection rule, per expanded row behind a parent of length > 1: an ordinary parent's misalignment below / not
+              # below 0.1; round() met a half and went to the even neighbour below / above; the parent one-hot because the
+              # attention gave such a row / because it is a rejection; the source position beyond the line; an eligible row
+              # whose source row is all zero
+              rej_mis_inside=0, rej_mis_outside=0, half_down=0, half_up=0, is1_by_attention=0, is1_by_rejection=0, beyond_line=0,
+              zero_source_row=0,
+              # ... and, behind ordinary parents, the largest misalignment below 0.1 and the smallest not below it (None: none met)
+              mis_inside_max=None, mis_outside_min=None)
     steps_run = 0
     for l in range(max_batches):
         beam = []
@@ -173,21 +193,35 @@ def search(m, source_seq, encoder_outputs, rules=(), trace=None, lm=False):
             scores = scores_output[i]
             alignment = states[-1][0]
             misalignment = 0.0
+            is1 = False
             if node.length > 1:
                 prev_alignment = node.alignment
                 prev_source_pos = float(np.matmul(np.asarray(prev_alignment, np.float64), np.arange(T)))
                 source_pos = float(np.matmul(alignment.astype(np.float64), np.arange(T)))
                 misalignment = abs(source_pos - prev_source_pos - 1)
-                if np.max(prev_alignment) == 1.0:
+                is1 = bool(np.max(alignment if 'is1_from_attention_row' in rules else prev_alignment) == 1.0) and 'is1_ignored' not in rules
+                if is1:
                     source_pos = int(prev_source_pos) + 1
+                    tr['is1_by_rejection' if node.rejpos >= 0 else 'is1_by_attention'] += 1
                 else:
-                    source_pos = int(round(source_pos))
+                    tr['rej_mis_inside' if misalignment < 0.1 else 'rej_mis_outside'] += 1
+                    if misalignment < 0.1:
+                        tr['mis_inside_max'] = misalignment if tr['mis_inside_max'] is None else max(tr['mis_inside_max'], misalignment)
+                    else:
+                        tr['mis_outside_min'] = misalignment if tr['mis_outside_min'] is None else min(tr['mis_outside_min'], misalignment)
+                    if source_pos - np.floor(source_pos) == 0.5:
+                        tr['half_down' if int(np.floor(source_pos)) % 2 == 0 else 'half_up'] += 1
+                    source_pos = int(np.floor(source_pos + 0.5)) if 'round_half_up' in rules else int(round(source_pos))
             else:
                 source_pos = 0
-            source_scores = source_seq[source_pos]
-            if (m.rejection_threshold
-                    and (misalignment < 0.1 or (len(node.alignment) and np.max(node.alignment) == 1.0))
-                    and np.any(source_scores)):
+            eligible = misalignment < mis_limit or is1 or 'mis_not_tested' in rules
+            if source_pos >= T and beyond_line == 'no_candidate':
+                tr['beyond_line'] += 1
+                source_scores = np.zeros_like(source_seq[0])
+            else:
+                source_scores = source_seq[source_pos]
+                tr['zero_source_row'] += bool(m.rejection_threshold and eligible and not np.any(source_scores))
+            if m.rejection_threshold and eligible and np.any(source_scores):
                 rej_idx = int(np.nanargmax(source_scores))
                 if float(scores[rej_idx]) < m.rejection_threshold:
                     scores[rej_idx] = m.rejection_threshold
@@ -399,3 +433,58 @@ CASES = [
 ]
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
+
+
+# ------------------------------------------------------------------------------------------------------------------ device results
+# What the GPU tests of the tables (tests/test_gpu_beam_ties.py, tests/test_gpu_steered_attention.py) share: results of
+# casv_decode_beam cut to their lengths, against each other bit for bit and against `search`.
+RT, AT = 2e-4, 2e-6
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def same_bits(a, b, what):
+    assert len(a) == len(b)
+    for j, (x, y) in enumerate(zip(a, b)):
+        assert (x['n_found'], x['n_steps'], len(x['results'])) == (y['n_found'], y['n_steps'], len(y['results'])), (what, j)
+        for k, (p, q) in enumerate(zip(x['results'], y['results'])):
+            for key in ('idx', 'rej', 'lo'):
+                assert np.array_equal(p[key], q[key]), (what, j, k, key)
+            for key in ('prob', 'align', 'w'):
+                assert np.array_equal(bits(p[key]), bits(q[key])), (what, j, k, key)
+            assert p['score'].view(np.int64) == q['score'].view(np.int64), (what, j, k)
+
+
+def against_the_oracle(case, got, want, c_i):
+    T, V = case.T, case.V
+    exact = {int(bits(np.float32(1) / np.float32(V)))}
+    if case.rejection:
+        exact.add(int(bits(np.float32(case.rejection))))
+    for j, (dev, (res, stats, rej, _)) in enumerate(zip(got, want)):
+        assert dev['n_found'] == stats['finals'] and dev['n_steps'] == stats['steps'], (j, dev['n_found'], dev['n_steps'], stats)
+        assert len(dev['results']) == min(len(res), case.max_results), j
+        assert not dev['empty'].any(), j
+        for k, d in enumerate(dev['results']):
+            text, probs, score, aligns = res[k][:4]
+            where = (case.name, j, k, text)
+            assert list(d['idx']) == [c_i[ch] for ch in text], where
+            assert list(d['rej']) == rej[k], where
+            p = np.asarray(probs, np.float32)
+            pinned = np.isin(bits(p), list(exact))
+            assert np.array_equal(bits(d['prob'])[pinned], bits(p)[pinned]), where
+            assert np.allclose(d['prob'], p, rtol=RT, atol=0), where
+            assert abs(d['score'] - score) <= RT * abs(score), where
+            a = np.asarray(aligns, np.float32).reshape(len(text), T)
+            assert np.allclose(d['align'], a, rtol=RT, atol=AT), where
+            window = np.zeros_like(d['align'])
+            for s in range(len(text)):
+                if rej[k][s] >= 0:
+                    assert np.array_equal(d['align'][s], np.eye(T, dtype=np.float32)[rej[k][s]]), where
+                    assert d['lo'][s] == rej[k][s] and d['w'][s, 0] == 1 and not d['w'][s, 1:].any(), where
+                assert d['lo'][s] >= 0, where
+                n = min(d['w'].shape[1], T - int(d['lo'][s]))
+                window[s, d['lo'][s]:d['lo'][s] + n] = d['w'][s, :n]
+                assert not d['w'][s, n:].any(), where
+            assert np.array_equal(bits(window), bits(d['align'])), where
