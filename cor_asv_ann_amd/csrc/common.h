@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gemm_args.h"      // Seg, SlotPtr, GemmArgs, GemmBatch, TnArgs, TnLaunch
+#include "gemm_plan.h"      // GemmContext, GemmSwitches, the launch plans
 
 namespace casv {
 
@@ -90,131 +92,54 @@ __device__ __forceinline__ LstmCellOut lstm_cell(float zi, float zf, float zg, f
 }
 
 
-// One K-segment of a GEMM's A operand: rows of `width` floats (a multiple of 32) taken from
-//   base + slot * slot_stride + row_id * ld,   slot = step * step_mul + step_add,
-// where row_id = rows ? rows[m] : m.  `skip_first` drops the segment (treated as zeros) at
-// step 0 -- the zero initial LSTM state of the encoder.
-struct Seg {
-    const float* base;
-    const int* rows;
-    long long slot_stride;
-    int step_mul, step_add;
-    int ld;
-    int width;
-    int skip_first;
-    int koff;   // offset of this segment in the fused weight's K dimension
-    const float* first_base;   // if set: at step 0 the rows come from first_base + m * ld (initial LSTM state)
-};
-
-// Output / state pointer that moves with the step the same way.
-struct SlotPtr {
-    float* base;
-    long long slot_stride;
-    int step_mul, step_add;
-    int ld;
-};
-
-struct GemmArgs {
-    Seg a[3];
-    int nseg;
-    const float* Bt;      // [N][Ktot], K contiguous (LSTM: rows in gate-interleaved order)
-    const float* bias;    // [N] (same order) or nullptr
-    int M, N, Ktot;
-    SlotPtr out;          // PLAIN: C[M][N]; LSTM: h'[M][N/4]
-    // LSTM epilogue only
-    Seg c_in;             // previous cell state rows (width = units), skip_first = zero state
-    SlotPtr c_out;
-    SlotPtr zinit;        // LSTM: pre-activation term added to the contraction, [M][4U] interleaved (x.K + b of all steps, precomputed)
-    SlotPtr gates_out;    // training: activated gates i,f,g,o, [M][4U] in the interleaved column order (or null)
-    SlotPtr out2;         // training: a second copy of h (the next step's cell input rows [ctx | h]) (or null)
-    const int* nact;      // beam decode: live rows per line (0 = search finished); a tile without a live row is skipped --
-    int nact_group;       // rows per line                                   its rows are never read
-    int epi_plain;        // job of an EPI_LSTM launch that takes the PLAIN epilogue (lets independent GEMMs of both kinds share a launch)
-    int accumulate;       // PLAIN: C += A.B^T instead of C = (weight-gradient sums)
-    int out_zeroed;       // PLAIN with split-K: the caller has already cleared the output (no memset per launch)
-    int kgroups;          // 2 = allow the two-wave-group split-K variant (train step; changes the summation order)
-    int xcd_rows;         // XCD-aware tile order: the 8 XCDs form an xcd_rows x (8/xcd_rows) grid over the tile grid (0 = off)
-    int b_static;         // Bt changes only at casv_commit_weights (inference weights): the split-bf16 experiment may keep a pre-split image of it
-    const void* Bimg;     // set by launch_gemm_split256: that image (gemm_split.hip), or nullptr
-    int ksplit;           // PLAIN: 0/1 = one block per tile; n > 1 = K split over n blocks (float atomics into C);
-                          // -1 = let the launcher choose (train step only: sums become order-dependent)
-    // step source
-    int step_imm;
-    const int* step_ptr;
-};
-
-enum { EPI_PLAIN = 0, EPI_LSTM = 1 };
-
-// Up to four independent GEMMs in one launch (blockIdx.y selects the job): the two directions of the
-// bidirectional encoder layer, or the (layer, time) cells on one anti-diagonal of the stacked encoder.
-constexpr int GEMM_MAX_JOBS = 4;
-struct GemmBatch {
-    GemmArgs g[GEMM_MAX_JOBS];
-    int count;
-};
-
-// C[M][N] (+)= sum_k A[k][m] * B[k][n] for operands that lie K-major (gemm_tn.hip: weight gradients of the train step).
-// lda / ldb / M / N multiples of 4, 16-byte aligned bases; rows m >= Mstore are computed but not stored (padded operand).
-struct TnArgs {
-    const float* A; long long lda; const float* B; long long ldb; float* C; long long ldc;
-    int M, Mstore, N, K;
-    int accumulate;      // C += (gradient sums) instead of C =
-    int out_zeroed;      // C = with a split K: the caller has cleared C already
-    float* colsum;       // optional [Mstore]: += sum_k A[k][m] (the bias gradient that goes with a weight gradient)
-    int nsplit;          // set by launch_gemm_tn: K shares of the launch
-    float* part;         // ordered form (launch_gemm_tn_ordered): K share z stores its partial tile at part[z][Mstore][N] ...
-    float* colpart;      // ... and its column sums at colpart[z][Mstore]; a second pass adds the shares in z order
-};
-int launch_gemm_tn(const TnArgs& g, hipStream_t stream);           // returns the K shares launched
-// the same contraction on bf16x3-split operands (gemm_tn_split.hip); false: no such form for the shape.  *shares: K shares launched
-bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream, int* shares = nullptr);
-// The same contraction with its sums in a fixed order (the train step's "deterministic" option): K shares chosen from the shape alone,
-// each share's partial stored, then added in share order -- no float atomics.  Needs gemm_tn_ordered_floats(g) floats at `ws`.
-struct TnLaunch { int split, shares, nonempty; };   // which kernel ran (1: gemm_tn_split.hip), K shares launched, shares holding k-tiles
-size_t gemm_tn_ordered_floats(const TnArgs& g);
-TnLaunch launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream);
-// The weight-gradient launch as the train step makes it: the ordered form when `ordered_ws` is given, else under the calling thread's
-// arithmetic the split kernel where the shape has that form, else the fp32-input kernel.
-TnLaunch launch_gemm_tn_any(const TnArgs& g, float* ordered_ws, hipStream_t stream);
-void launch_gemm(int epi, const GemmArgs& g, hipStream_t stream);
-void launch_gemm_batch(int epi, const GemmBatch& b, hipStream_t stream);
-void launch_gemm_skinny(int epi, const GemmBatch& b, int ksplit, int rows, hipStream_t stream);
+// ---- GEMM launchers: the decision is the plan (gemm_plan.h), these run it.  ctx: the handle's (casv_model::gemm) ----
+const GemmSwitches& gemm_switches();       // the process-wide switches (gemm.hip: read from the environment when the library is loaded)
+void launch_gemm(const GemmContext& ctx, int epi, const GemmArgs& g, hipStream_t stream);
+void launch_gemm_batch(const GemmContext& ctx, int epi, const GemmBatch& b, hipStream_t stream);
+// the same for a plan the caller has made already (plan_gemm_launches(ctx, gemm_switches(), epi, b))
+void run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream);
+void run_gemm_skinny(int epi, const GemmLaunchPlan& l, hipStream_t stream);        // gemm_skinny.hip: FORM_SKINNY_32 / _64
+void run_gemm_split256(int epi, const GemmLaunchPlan& l, hipStream_t stream);      // gemm_split.hip: FORM_SPLIT_256
+bool gemm_split256_ready();                // gemm_split.hip: its kernels have their dynamic LDS on the current device
+// The weight-gradient launch as the train step makes it (plan_gemm_tn): the ordered form when `ordered_ws` is given -- it needs
+// gemm_tn_ordered_floats(ctx, g) floats there --, else under the context's arithmetic the split kernel where the shape has that form,
+// else the fp32-input kernel.
+size_t gemm_tn_ordered_floats(const GemmContext& ctx, const TnArgs& g);
+TnLaunch launch_gemm_tn_any(const GemmContext& ctx, const TnArgs& g, float* ordered_ws, hipStream_t stream);
+bool run_gemm_tn_split(bool part, int grid, const TnArgs& g, hipStream_t stream);   // gemm_tn_split.hip; false: the kernel cannot get its LDS
 // optional vendor path for plain contractions C[M][N] (+)= A[M][K] . Bt[N][K]^T (+ bias) (vendor_gemm.hip); false = not taken
 bool vendor_gemm_nt(const float* A, long long lda, long long M, int K, const float* Bt, int N, const float* bias, float* C, long long ldc,
                     int accumulate, hipStream_t stream);
 void vendor_gemm_release(hipStream_t stream);         // frees the vendor path's workspace of a stream (model destruction)
-bool gemm_is_skinny(int epi, const GemmBatch& b);     // which tile shape launch_gemm_batch will pick
 // tile shape of the GEMM launches: -1 = by size (default), 0 = always 128x128, 1 = always 32x128 (same results)
 void set_gemm_tile_mode(int mode);
 // arithmetic of the GEMM launches (gemm.hip): 0 = fp32-input matrix instruction, 1 / 2 = bf16x3-split operands (three bf16 per fp32
 // value, six products, fp32 accumulation) on the bf16 matrix instruction -- fp32-accurate sums, another summation order
 void set_gemm_split_override(int v);       // process-wide: -1 none (every entry point's own choice), 0 / 1 / 2 = all launches of the decode path
 int gemm_split_override();
-int gemm_split_enter(int mode);            // arithmetic of the launches the calling thread enqueues from here on; returns the previous one
-struct SplitScope {                        // ... for the lifetime of a scope (the C-ABI entry points, engine.h: arithmetic_of)
-    int prev;
-    explicit SplitScope(int mode) : prev(gemm_split_enter(mode)) {}
-    ~SplitScope() { gemm_split_enter(prev); }
-    SplitScope(const SplitScope&) = delete; SplitScope& operator=(const SplitScope&) = delete;
-};
-bool gemm_split256_wants(int epi, const GemmArgs& g);
 #ifdef CASV_S2_CLOCK
 void s2_clock_dump();
 #endif
 void gemm_split_prepare(const float* Bt, int N, int K, hipStream_t stream);    // makes the image of a weight buffer now (ahead of a graph recording)
 void gemm_split_invalidate(const float* Bt);     // drops the pre-split image of a weight buffer (call where it changes or is released); nullptr: all
-bool launch_gemm_split256(int epi, const GemmBatch& b, hipStream_t stream);     // false: not launched (the caller takes another path)
-int gemm_split_bf16();                     // the calling thread's current arithmetic (SplitScope)
-int gemm_ordered_enter(int on);            // 1: the calling thread's launches sum in a fixed order (no split-K, no float atomics); returns the previous
-int gemm_ordered();
-struct OrderedScope {
-    int prev;
-    explicit OrderedScope(bool on) : prev(gemm_ordered_enter(on ? 1 : 0)) {}
-    ~OrderedScope() { gemm_ordered_enter(prev); }
-    OrderedScope(const OrderedScope&) = delete; OrderedScope& operator=(const OrderedScope&) = delete;
-};
 long gemm_split_epoch();                   // changes whenever the option or a pre-split weight image does (key of captured step graphs)
 void gemm_split_bump_epoch();
+// C[rows][cols] (row stride ld) = 0 on the stream: partial sums of a split K are added atomically and start from zero
+inline void gemm_clear(float* c, long long rows, long long cols, long long ld, hipStream_t stream) {
+    if (ld == cols) (void)hipMemsetAsync(c, 0, (size_t)rows * cols * sizeof(float), stream);
+    else (void)hipMemset2DAsync(c, (size_t)ld * sizeof(float), 0, (size_t)cols * sizeof(float), rows, stream);
+}
+// The dynamic-LDS size of a kernel function: the attribute belongs to the (function, device) pair -- a second model on another
+// device needs its own --, so every function keeps one of these.  false: the runtime refused.
+struct LdsAttribute { bool set[64] = {false}; };
+inline bool gemm_dynamic_lds(LdsAttribute& a, const void* fn, int bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && a.set[dev]) return true;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (dev >= 0 && dev < 64) a.set[dev] = true;
+    return true;
+}
 
 // ---- small kernels (decode_kernels.hip) ----
 struct AttnArgs {

@@ -271,7 +271,7 @@ static int decoder_step(casv_model* m, int32_t R, const int32_t* line, const flo
     HIPCHK(hipSetDevice(m->device));
     if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_CHAIN))) return rc;
     if (int rc = settle_encoder(m); rc < 0) return rc;
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     const int W = m->W, V = m->V, Vp = m->Vp, T = m->T, D = m->D;
     m->last_decode = 0;         // the step overwrites slots 0 and 1 of the stores casv_get_alignments_sparse would read
     if (int rc = ensure_session(m, R, 1)) return rc;
@@ -339,7 +339,7 @@ struct StepRunner {
     StepRunner(casv_model* m_, const std::string& key_)
         : m(m_), key(key_ + "/" + std::to_string(g_devbuf_generation) + "/" + std::to_string((unsigned long long)(uintptr_t)m_->enc_out) +
                      "/" + std::to_string((unsigned long long)(uintptr_t)m_->u.p) + "/" + std::to_string((int)m_->has_a0) +
-                     "/" + std::to_string(gemm_split_bf16()) + "." + std::to_string(gemm_split_epoch())) {}
+                     "/" + std::to_string(m->gemm.arithmetic) + "." + std::to_string(gemm_split_epoch())) {}
     static void drop(casv_model* m) {
         if (m->step_exec) { (void)hipStreamSynchronize(m->stream); (void)hipGraphExecDestroy(m->step_exec); m->step_exec = nullptr; }
         if (m->step_graph) { (void)hipGraphDestroy(m->step_graph); m->step_graph = nullptr; }
@@ -349,7 +349,7 @@ struct StepRunner {
         if (m->use_graph && !m->prof.on) {
             if (!m->step_exec || m->step_graph_key != key) {
                 drop(m);
-                if (gemm_split_bf16() >= 2) {       // (split arithmetic: the weight images are made ahead of the recording, not inside it)
+                if (m->gemm.arithmetic >= 2) {       // (split arithmetic: the weight images are made ahead of the recording, not inside it)
                     const int W = m->W, C = m->C, D = m->D, Vp = m->Vp;
                     for (int n = 1; n <= D; ++n)
                         gemm_split_prepare(m->dec[n].wt.as<float>(), 4 * W, (n == 1 ? Vp : W) + W + (n == D && D > 1 ? C : 0) + (D == 1 ? C : 0), m->stream);
@@ -601,7 +601,7 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
     if (S < 1 || S > 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "S=%d out of range 1..%d", S, 2 * CASV_MAX_T);
     HIPCHK(hipSetDevice(m->device));
     if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_CHAIN))) return rc;
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     const int B = m->B, T = m->T;
     m->last_decode = 0;         // until this call has succeeded there is nothing to take alignments from
     GreedyCall c{};
@@ -842,7 +842,7 @@ extern "C" int casv_decode_beam(casv_model* m, const casv_beam_params* bp, int32
     HIPCHK(hipSetDevice(m->device));
     if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_SEARCH))) return rc;
     // (a persistent encoder launch's give-up word is looked at in the search, where this call first waits for the device anyway)
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_SEARCH));         // the search: bf16x3-split operands by default (engine.h)
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_SEARCH));         // the search: bf16x3-split operands by default (engine.h)
     BeamCall c{};
     c.B = m->B; c.T = m->T; c.N = N; c.R = m->B * N; c.S = S; c.MR = bp->max_results; c.CM = CM;
     c.OR = (size_t)m->B * c.MR; c.lm = m->lm_predict;

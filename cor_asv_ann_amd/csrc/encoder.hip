@@ -238,7 +238,7 @@ static void attention_dense(casv_model* m) {
 // the greedy decode, or the first other consumer of the outputs); a launch that gave up is redone with the per-step kernels then.
 // (Waiting here cost every batch of configs[1] a host round trip with the GPU idle between its encoder and its decoder's set-up.)
 static int run_encoder(casv_model* m, bool try_persistent) {
-    SplitScope arithmetic(m->enc_arith < 0 ? 0 : m->enc_arith);   // (set by ensure_encoded; its own scope: settle_encoder redoes an encoder from inside any entry point)
+    SplitScope arithmetic(m, m->enc_arith < 0 ? 0 : m->enc_arith);   // (set by ensure_encoded; its own scope: settle_encoder redoes an encoder from inside any entry point)
     const int B = m->B, T = m->T, A = m->A, W = m->W, D = m->D;
     const size_t BT = (size_t)B * T;
     if (int rc = m->d_flags.ensure(64)) return rc;
@@ -321,7 +321,7 @@ int ensure_encoded(casv_model* m, int want) {
         if (int rc = run_encoder(m, true)) { m->enc_arith = -1; return rc; }
         return 0;
     }
-    SplitScope arithmetic(want);        // (on outputs that were handed in)
+    SplitScope arithmetic(m, want);        // (on outputs that were handed in)
     attention_dense(m);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { m->enc_arith = -1; return fail(CASV_ERR_HIP, "attention_dense launch failed: %s", hipGetErrorString(e)); }
     return 0;

@@ -110,6 +110,7 @@ struct casv_model {
     bool persist_fault_split = false;                     // test support (option "persistent" = 3): the split persistent encoder gives up (persist_split.hip)
     PersistBackoff persist_backoff;                       // after a persistent launch gave up waiting (persist_host.h)
     int ncu = 0;
+    GemmContext gemm{0, 0, 0};                            // what the GEMM launchers decide by (gemm_plan.h): ncu, and the arithmetic / ordered sums of the running entry point (SplitScope, OrderedScope)
     LstmW enc_fw, enc_bw;
     std::vector<LstmW> enc_dfw, enc_dbw;                  // deep_bidirectional_encoder: the two directions of layer n >= 2 at index n
     std::vector<DevBuf> br_hT, br_hb, br_cT, br_cb;        // bridge_dense: Dense kernels transposed [W][W] and biases of layer n at index n
@@ -202,6 +203,22 @@ inline int arithmetic_of(const casv_model* m, int entry) {
     return a >= 0 ? a : (entry == ENTRY_CHAIN ? 0 : 2);
 }
 
+// The arithmetic of the launches a handle enqueues, for the lifetime of a scope (the C-ABI entry points).  Saved and restored, so a
+// scope inside another one works: settle_encoder redoes an encoder from inside any entry point (encoder.hip).
+struct SplitScope {
+    casv_model* m; int prev;
+    SplitScope(casv_model* m_, int mode) : m(m_), prev(m_->gemm.arithmetic) { m->gemm.arithmetic = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
+    ~SplitScope() { m->gemm.arithmetic = prev; }
+    SplitScope(const SplitScope&) = delete; SplitScope& operator=(const SplitScope&) = delete;
+};
+// ... and ordered sums: while on, the handle's launches sum in a fixed order (no split-K, no float atomics)
+struct OrderedScope {
+    casv_model* m; int prev;
+    OrderedScope(casv_model* m_, bool on) : m(m_), prev(m_->gemm.ordered) { m->gemm.ordered = on ? 1 : 0; }
+    ~OrderedScope() { m->gemm.ordered = prev; }
+    OrderedScope(const OrderedScope&) = delete; OrderedScope& operator=(const OrderedScope&) = delete;
+};
+
 inline int upload(DevBuf& b, const std::vector<float>& v) {
     if (int rc = b.ensure(v.size() * sizeof(float))) return rc;
     HIPCHK(hipMemcpy(b.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -220,7 +237,8 @@ inline SlotPtr mkslot(float* base, int ld, long long slot_stride = 0, int mul = 
 
 inline void run_gemm_batch(casv_model* m, int epi, GemmBatch& b) {
     hipEvent_t a{};
-    const int cls = epi == EPI_LSTM ? (m->prof.on && gemm_is_skinny(epi, b) ? PC_LSTM_SMALL : PC_LSTM) : PC_GEMM;
+    const GemmPlan plan = plan_gemm_launches(m->gemm, gemm_switches(), epi, b);      // planned once: the profile class and the launches
+    const int cls = epi == EPI_LSTM ? (m->prof.on && gemm_plan_is_skinny(plan) ? PC_LSTM_SMALL : PC_LSTM) : PC_GEMM;
     double fl = 0, by = 0;
     for (int j = 0; j < b.count; ++j) {
         const GemmArgs& g = b.g[j];
@@ -230,7 +248,7 @@ inline void run_gemm_batch(casv_model* m, int epi, GemmBatch& b) {
         by += 4.0 * ((double)g.M * kact + (double)g.N * kact + (double)g.M * g.N);
     }
     m->prof_begin(cls, fl, by, a);
-    launch_gemm_batch(epi, b, m->stream);
+    run_gemm_plan(m->gemm, epi, b, plan, m->stream);
     m->prof_end(cls, a);
 }
 

@@ -54,6 +54,7 @@ extern "C" int casv_model_create(const casv_config* cfg, int device_id, casv_mod
     casv_model* m = new casv_model();
     m->cfg = *cfg; m->device = device_id;
     { hipDeviceProp_t prop{}; if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) m->ncu = prop.multiProcessorCount; }
+    m->gemm.ncu = m->ncu;
     m->W = cfg->width; m->V = cfg->voc_size; m->Vp = (cfg->voc_size + 31) & ~31; m->D = cfg->depth;
     m->C = (cfg->depth == 1 || cfg->deep_bidirectional_encoder) ? 2 * cfg->width : cfg->width;
     m->expect = expected_shapes(*cfg);
@@ -377,7 +378,7 @@ extern "C" int casv_debug_gemm(casv_model* m, int32_t lstm, int32_t M, int32_t N
     if (!m || !ms_per_launch) return fail(CASV_ERR_ARG, "null argument");
     if (K % 32 || (lstm && N % 128)) return fail(CASV_ERR_ARG, "K must be a multiple of 32 (and N of 128 for lstm)");
     HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     DevBuf A, Bt, bias, C, cst, rows;
     DebugBuffers release_on_exit{{&A, &Bt, &bias, &C, &cst, &rows}, &Bt, m->stream};
     if (int rc = A.ensure((size_t)M * K * 4)) return rc;
@@ -404,9 +405,9 @@ extern "C" int casv_debug_gemm(casv_model* m, int32_t lstm, int32_t M, int32_t N
     if (lstm) { g.c_in = mkseg(cst.as<float>(), N / 4, N / 4, 0, rows.as<int>()); g.c_out = mkslot(cst.as<float>() + (size_t)M * N / 2, N / 4); }
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) launch_gemm(lstm ? EPI_LSTM : EPI_PLAIN, g, m->stream);
+    for (int i = 0; i < 3; ++i) launch_gemm(m->gemm, lstm ? EPI_LSTM : EPI_PLAIN, g, m->stream);
     HIPCHK(hipEventRecord(e0, m->stream));
-    for (int i = 0; i < iters; ++i) launch_gemm(lstm ? EPI_LSTM : EPI_PLAIN, g, m->stream);
+    for (int i = 0; i < iters; ++i) launch_gemm(m->gemm, lstm ? EPI_LSTM : EPI_PLAIN, g, m->stream);
     HIPCHK(hipEventRecord(e1, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     float t = 0; HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -425,7 +426,7 @@ extern "C" int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int3
     if (!m || !A_ || !Bt_ || !C_) return fail(CASV_ERR_ARG, "null argument");
     if (M < 1 || N < 1 || K < 32 || K % 32) return fail(CASV_ERR_ARG, "M, N positive, K a positive multiple of 32");
     HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_CHAIN));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     DevBuf A, Bt, bias, C;
     DebugBuffers release_on_exit{{&A, &Bt, &bias, &C}, &Bt, m->stream};
     if (int rc = A.ensure((size_t)M * K * 4)) return rc;
@@ -443,7 +444,7 @@ extern "C" int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int3
         TnArgs t{};
         t.A = A.as<float>(); t.lda = M; t.B = Bt.as<float>(); t.ldb = N; t.C = C.as<float>(); t.ldc = N;
         t.M = M; t.Mstore = M; t.N = N; t.K = K; t.accumulate = 0; t.out_zeroed = 0; t.colsum = nullptr;
-        if (!(gemm_split_bf16() && launch_gemm_tn_split(t, m->stream))) launch_gemm_tn(t, m->stream);
+        (void)launch_gemm_tn_any(m->gemm, t, nullptr, m->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(C_, C.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));
@@ -456,7 +457,7 @@ extern "C" int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int3
     if (flags & 1) g.ksplit = -1;               // the launcher may split K over workgroups (train step's plain contractions)
     if (flags & 2) g.kgroups = 2;               // ... and over two wave groups of a workgroup
     if (flags & 4) g.b_static = 1;              // Bt is a weight: the split-bf16 arithmetic may keep a pre-split image of it
-    launch_gemm(EPI_PLAIN, g, m->stream);
+    launch_gemm(m->gemm, EPI_PLAIN, g, m->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(C_, C.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -475,7 +476,7 @@ extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, i
         return fail(CASV_ERR_ARG, "M and N positive multiples of 4, 1 <= Mstore <= M, K positive");
     if (lda < M || ldb < N || ldc < N || lda % 4 || ldb % 4) return fail(CASV_ERR_ARG, "lda >= M, ldb >= N (multiples of 4), ldc >= N");
     HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
     const size_t na = (size_t)(K - 1) * lda + M, nb = (size_t)(K - 1) * ldb + N;
     const size_t nc = (size_t)(Mstore - 1) * ldc + N, nc_all = (size_t)M * ldc + N;      // (guard: every row of M and one more)
     DevBuf A, B, C, cs, ws;
@@ -496,10 +497,10 @@ extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, i
     t.colsum = (flags & 2) ? cs.as<float>() : nullptr;
     float* wsp = nullptr;
     if (flags & 4) {
-        if (int rc = ws.ensure(gemm_tn_ordered_floats(t) * 4)) return rc;
+        if (int rc = ws.ensure(gemm_tn_ordered_floats(m->gemm, t) * 4)) return rc;
         wsp = ws.as<float>();
     }
-    const TnLaunch r = launch_gemm_tn_any(t, wsp, m->stream);
+    const TnLaunch r = launch_gemm_tn_any(m->gemm, t, wsp, m->stream);
     HIPCHK(hipGetLastError());
     m->stat_tn[0] = r.split; m->stat_tn[1] = r.shares; m->stat_tn[2] = r.nonempty;
     std::vector<uint32_t> guard(nc_all - nc), cguard((size_t)(M + 1 - Mstore));

@@ -15,7 +15,7 @@
 // K-contiguous in LDS with a +4-float row pad (80-B rows: ds_read_b128 is conflict-free for its 16-lane
 // groups) and double-buffered; each lane reads four consecutive k per ds_read_b128 and feeds them to
 // four MFMAs (the k order inside a tile is permuted identically for A and B, which a sum allows).
-// Small launches take the 32x128-tile variant of gemm_skinny.hip instead (plan_gemm; same values bit for bit).
+// Small launches take the 32x128-tile variant of gemm_skinny.hip instead (gemm_plan.h; same values bit for bit).
 #include "common.h"
 #include <cstdlib>
 #include <cstdio>
@@ -768,266 +768,80 @@ __global__ __launch_bounds__(256 * KS, 2) void gemm_kernel(const GemmBatch batch
     gemm_tile<EPI, KS, SPLIT>(g, bm, bn, blockIdx.z, gridDim.z, smem_all);
 }
 
+static_assert(BM == gemm_shape::BM && BN == gemm_shape::BN && BK == gemm_shape::BK, "gemm_plan.h plans these tiles");
+static_assert(GEMM_LDS_BYTES == gemm_shape::LDS_FP32 && 2 * SPLIT_BUF_FLOATS * 4 == gemm_shape::LDS_SPLIT128 && CELL_LDS_BYTES + STASH_LDS_BYTES == gemm_shape::LDS_EPILOGUE, "gemm_plan.h plans these LDS sizes");
+
+// The switches of the launchers: the environment is read here, once, when the library is loaded; options "tile" and "split_bf16"
+// of casv_set_option act on the same object (gemm_plan.h: GemmSwitches).
+static GemmSwitches gemm_switches_from_env() {
+    GemmSwitches s;
+    auto digit = [](const char* name, int hi, int otherwise) { const char* e = getenv(name); return e && e[0] >= '0' && e[0] <= '0' + hi && !e[1] ? e[0] - '0' : otherwise; };
+    auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+    s.tile_mode = digit("CASV_GEMM_TILE", 2, -1);
+    s.split_override = digit("CASV_SPLIT_BF16", 2, -1);
+    s.tail_cut = !off("CASV_TAIL_CUT");
+    s.split_tail_cut = !off("CASV_SPLIT_TAIL_CUT");
+    s.tn_split = !off("CASV_TN_SPLIT");
+    s.split_images = !off("CASV_SPLIT_IMAGES");
+    { const char* e = getenv("CASV_DEBUG_LDS_PAD"); s.lds_pad = e ? atoi(e) : 0; }
+    return s;
+}
+static GemmSwitches g_switches = gemm_switches_from_env();
+const GemmSwitches& gemm_switches() { return g_switches; }
+void set_gemm_tile_mode(int mode) { g_switches.tile_mode = mode; }
+long gemm_split_epoch() { return g_switches.epoch; }
+void gemm_split_bump_epoch() { ++g_switches.epoch; }
+void set_gemm_split_override(int v) { v = v < -1 ? -1 : v > 2 ? 2 : v; if (v != g_switches.split_override) ++g_switches.epoch; g_switches.split_override = v; }
+int gemm_split_override() { return g_switches.split_override; }
+
 template <int EPI, int KS, bool SPLIT = false>
-static void launch_one(const GemmBatch& bb, int blocks, int ksplit, hipStream_t stream) {
-    // (CASV_DEBUG_LDS_PAD: measurement aid -- extra dynamic LDS, e.g. 16384 leaves room for ONE workgroup per CU)
-    static const int lds_pad = [] { const char* e = getenv("CASV_DEBUG_LDS_PAD"); return e ? atoi(e) : 0; }();
-    const int lds_bytes = (SPLIT ? 2 * SPLIT_BUF_FLOATS * 4 : GEMM_LDS_BYTES * KS) + CELL_LDS_BYTES + STASH_LDS_BYTES + lds_pad;
-    // the attribute belongs to the (function, device) pair: a second model on another device needs its own
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<EPI, KS, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_kernel<EPI, KS, SPLIT>), dim3(blocks, bb.count, ksplit), dim3(256 * KS), lds_bytes, stream, bb);
+static void launch_one(const GemmLaunchPlan& l, hipStream_t stream) {
+    static LdsAttribute attr;
+    (void)gemm_dynamic_lds(attr, reinterpret_cast<const void*>(&gemm_kernel<EPI, KS, SPLIT>), l.lds_bytes);
+    hipLaunchKernelGGL((gemm_kernel<EPI, KS, SPLIT>), dim3(l.grid_x, l.grid_y, l.grid_z), dim3(l.block), l.lds_bytes, stream, l.batch);
 }
 
-static int g_tile_mode = [] { const char* e = getenv("CASV_GEMM_TILE"); return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : -1; }();   // -1 by size, 0 = 128x128, 1 = 32x128, 2 = 64x128 where possible
-void set_gemm_tile_mode(int mode) { g_tile_mode = mode; }
-// Arithmetic of a GEMM launch: 0 = the fp32-input matrix instruction (k-ordered fmaf chain), 1 / 2 = bf16x3-split
-// operands on the bf16 matrix instruction with fp32 accumulation (1: gemm_tile's SPLIT variant, 128x128 tiles; 2: 256x256 tiles,
-// gemm_split.hip, where a job fills the chip that way, else as 1 -- both give the same bits).  WHICH of them a launch takes is
-// decided by the C-ABI entry point that enqueues it (engine.h, arithmetic_of: the handle's "arithmetic" option; by default the beam
-// search's decoder steps take 2 and everything else 0) and announced to the launcher for the calling thread (SplitScope).
-// The process-wide override (option "split_bf16" / CASV_SPLIT_BF16 = 0, 1 or 2 in the environment when the library is loaded)
-// puts EVERY launch of the decode path of every handle on one arithmetic: tests and A/B measurements.
-static int g_split_override = [] { const char* e = getenv("CASV_SPLIT_BF16"); return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : -1; }();
-static thread_local int t_split_bf16 = 0;
-// (a captured step graph bakes in the arithmetic and the addresses of the pre-split weight images: both are part of its key through
-// this counter -- engine.hip, StepRunner)
-static long g_split_epoch = 0;
-long gemm_split_epoch() { return g_split_epoch; }
-void gemm_split_bump_epoch() { ++g_split_epoch; }
-void set_gemm_split_override(int v) { v = v < -1 ? -1 : v > 2 ? 2 : v; if (v != g_split_override) ++g_split_epoch; g_split_override = v; }
-int gemm_split_override() { return g_split_override; }
-int gemm_split_enter(int mode) { const int prev = t_split_bf16; t_split_bf16 = mode < 0 ? 0 : mode > 2 ? 2 : mode; return prev; }
-int gemm_split_bf16() { return t_split_bf16; }
-// Ordered sums (the train step's "deterministic" option): while set, no launch of the calling thread splits K
-// over workgroups -- every element is ONE k-ordered chain, nothing is added atomically, whatever the shape asks for.
-static thread_local int t_ordered = 0;
-int gemm_ordered_enter(int on) { const int prev = t_ordered; t_ordered = on ? 1 : 0; return prev; }
-int gemm_ordered() { return t_ordered; }
-
-static int count_ktiles(const GemmArgs& g) {
-    int ktiles = 0;
-    for (int i = 0; i < g.nseg; ++i) ktiles += g.a[i].width / BK;
-    return ktiles;
-}
-
-// Tile shape and split-K factor of a launch.  Launches that would occupy at most half the CUs as 128x128 tiles (even
-// after split-K) run as 32x128 tiles: 4x the workgroups, same values ...
-struct GemmPlan { int blocks, sblocks, ksplit; bool skinny; int srows; };
-static GemmPlan plan_gemm(int epi, const GemmBatch& b) {
-    GemmPlan p{0, 0, 1, false, 32};
-    for (int j = 0; j < b.count; ++j) {
-        const int nbn = (b.g[j].N + BN - 1) / BN;
-        const int nb = ((b.g[j].M + BM - 1) / BM) * nbn, ns = ((b.g[j].M + 31) / 32) * nbn;
-        p.blocks = nb > p.blocks ? nb : p.blocks;
-        p.sblocks = ns > p.sblocks ? ns : p.sblocks;
-    }
-    bool splittable = epi == EPI_PLAIN;         // split-K: every job of the batch must ask for it and share the shape
-    for (int j = 0; j < b.count; ++j)
-        if (b.g[j].step_ptr || b.g[j].ksplit == 0 || b.g[j].ksplit == 1 || b.g[j].ksplit != b.g[0].ksplit || b.g[j].Ktot != b.g[0].Ktot ||
-            b.g[j].M != b.g[0].M || b.g[j].N != b.g[0].N) splittable = false;
-    if (t_ordered) splittable = false;
-    auto choose_ksplit = [&](int grid, int want) {
-        if (!splittable) return 1;
-        const int ktiles = count_ktiles(b.g[0]);
-        int ks = b.g[0].ksplit;
-        if (ks < 0) {                           // fill the chip, keep >= 16 k-tiles per workgroup
-            ks = (want + grid - 1) / grid;
-            if (ks > ktiles / 16) ks = ktiles / 16;
+// Runs a plan: per launch the clears, then the kernel of its form.
+static void run_launches(int epi, const GemmPlan& plan, hipStream_t stream) {
+    for (int i = 0; i < plan.count; ++i) {
+        const GemmLaunchPlan& l = plan.launch[i];
+        for (int j = 0; j < l.batch.count; ++j) {
+            if (!(l.clear_jobs >> j & 1)) continue;
+            // the slot to clear is computed from the immediate step: split-K jobs never take their step from device memory
+            // (the planner keeps ksplit at 1 for them)
+            const GemmArgs& g = l.batch.g[j];
+            gemm_clear(g.out.base + (long long)(g.step_imm * g.out.step_mul + g.out.step_add) * g.out.slot_stride, g.M, g.N, g.out.ld, stream);
         }
-        if (ks > ktiles) ks = ktiles;
-        return ks < 1 ? 1 : ks;
-    };
-    p.ksplit = choose_ksplit(p.blocks * b.count, 512);
-    // ... and so do launches of more than one but less than two 128x128 tiles per CU: half the CUs would carry two workgroups
-    // and set the pace while the others idle (the encoder's anti-diagonals of three layers at 1024 lines: 384 tiles, 168 us;
-    // as 1536 tiles of 32x128: 140 us)
-    static const int ncu = [] { hipDeviceProp_t pr{}; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-    const int grid = p.blocks * b.count * p.ksplit;
-    p.skinny = g_tile_mode == 1 || (g_tile_mode < 0 && (grid <= 128 || (grid > ncu && grid < 2 * ncu)));
-    if (p.skinny) p.ksplit = choose_ksplit(p.sblocks * b.count, 1024);
-    // Split-K launches of few rows (the train step's per-time-step data GEMMs: 512 rows, K = 2048): 32x128 tiles with just enough
-    // K splits for ONE round of workgroups.  As 128x128 tiles they needed eight splits to fill the chip, and the eight partial
-    // tiles per output went through float atomics -- 16.8 MB per launch at the memory side's ~1.3 TB/s = 13 of the launch's
-    // 36 us.  Measured on the train step of configs[3] (splits 2 / 3 / 4 / 6 / 8 of 32x128 tiles: 90.2 / 91.8 / 87.9 / 89.9 /
-    // 94.2 ms per step; 128x128 tiles with four splits 103.2; before 94.1).
-    if (g_tile_mode < 0 && splittable && b.g[0].ksplit < 0 && b.g[0].M <= 1024) {
-        p.skinny = true;
-        p.ksplit = choose_ksplit(p.sblocks * b.count, 512);
+        const bool lstm = epi == EPI_LSTM, two = l.form == FORM_FP32_128_2WG;
+        if (l.form == FORM_SKINNY_32 || l.form == FORM_SKINNY_64) run_gemm_skinny(epi, l, stream);
+        else if (l.form == FORM_SPLIT_256) run_gemm_split256(epi, l, stream);
+        else if (l.form == FORM_SPLIT_128) { if (lstm) launch_one<EPI_LSTM, 1, true>(l, stream); else launch_one<EPI_PLAIN, 1, true>(l, stream); }
+        else if (lstm) { if (two) launch_one<EPI_LSTM, 2>(l, stream); else launch_one<EPI_LSTM, 1>(l, stream); }
+        else { if (two) launch_one<EPI_PLAIN, 2>(l, stream); else launch_one<EPI_PLAIN, 1>(l, stream); }
     }
-    // 64 x 128 tiles (gemm_skinny.hip, two row blocks per workgroup) for launches without split-K that leave at most one 128x128
-    // workgroup per CU, or go as 32-row tiles, while 64-row tiles still put two on every CU: the encoder at 1024 lines -- layer 1's
-    // two directions (256 tiles of 128x128) and the anti-diagonals of the layers above (384)
-    // (fused-LSTM launches only: the plain-epilogue launch it would also catch, the page call's logits -- 10240 x 640 x 512 --, runs
-    // 67.6 us as 32-row tiles and 75.6 us as 64-row tiles)
-    if ((epi == EPI_LSTM || g_tile_mode == 2) && !splittable && p.ksplit == 1) {
-        int blocks64 = 0;
-        for (int j = 0; j < b.count; ++j) blocks64 = std::max(blocks64, ((b.g[j].M + 63) / 64) * ((b.g[j].N + BN - 1) / BN));
-        const bool fits = blocks64 * b.count >= 2 * ncu;
-        if (g_tile_mode == 2 || (g_tile_mode < 0 && fits && (p.skinny || grid < 2 * ncu))) { p.skinny = true; p.srows = 64; }
-    }
-    return p;
-}
-bool gemm_is_skinny(int epi, const GemmBatch& b) { return plan_gemm(epi, b).skinny; }
-static bool train_launch(const GemmBatch& b) {        // (the train step's fused-LSTM launches carry side outputs the decode path never has)
-    for (int j = 0; j < b.count; ++j) if (b.g[j].zinit.base || b.g[j].gates_out.base || b.g[j].out2.base) return true;
-    return false;
-}
-static bool splittable_launch(int epi, const GemmBatch& b) {        // (a launch whose jobs ask for split-K: never re-planned below)
-    if (epi != EPI_PLAIN) return false;
-    for (int j = 0; j < b.count; ++j) if (b.g[j].ksplit != 0 && b.g[j].ksplit != 1) return true;
-    return false;
 }
 
-// Train step's big plain contractions (GemmArgs.ksplit = -1: the caller leaves the launch form to the launcher; M = 51 712 rows):
-// a 128x128 tile grid that ends in a partial round of workgroups -- 1 616 tiles on 512 slots = 3.16 rounds -- spends the time of
-// most of a round on its last few tiles (a workgroup alone on its CU still needs ~2/3 of the time two of them share).  The row
-// blocks of that partial round go as a second launch of 32-row (64-row) tiles instead: four (two) times the workgroups for the same
-// rows, every element contracted by the same k-ordered chain (gemm_skinny.hip: same bits, no split-K, nothing atomic).
-// CASV_TAIL_CUT=0 switches it off (A/B measurements).
-static bool cut_partial_round(int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream) {
-    static const bool enabled = [] { const char* e = getenv("CASV_TAIL_CUT"); return !(e && e[0] == '0'); }();
-    if (!enabled || epi != EPI_PLAIN || b.count != 1 || plan.ksplit != 1 || plan.skinny || g_tile_mode >= 0 || t_split_bf16) return false;
-    const GemmArgs& g = b.g[0];
-    if (g.ksplit != -1 || g.step_ptr || g.nact || g.Bimg) return false;
-    for (int i = 0; i < g.nseg; ++i) if (g.a[i].rows || g.a[i].skip_first || g.a[i].first_base) return false;    // rows at base + m * ld only
-    static const int ncu = [] { hipDeviceProp_t pr{}; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-    const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN, slots = 2 * ncu;
-    const int tiles = nbm * nbn, rounds = tiles / slots, rem = tiles % slots;
-    if (rounds < 1 || rem == 0 || rem * 4 > slots * 3) return false;         // (a last round that is three quarters full is left alone)
-    const int main_bm = (rounds * slots) / nbn;
-    if (main_bm < 1 || main_bm >= nbm) return false;
-    GemmBatch bm{}, bt{};
-    bm.count = bt.count = 1;
-    GemmArgs& gm = bm.g[0]; GemmArgs& gt = bt.g[0];
-    gm = g; gt = g;
-    gm.M = main_bm * BM; gm.ksplit = 0;                                      // (0: one block per tile, and no second look at this function)
-    gt.M = g.M - gm.M; gt.ksplit = 0;
-    for (int i = 0; i < g.nseg; ++i) gt.a[i].base += (long long)gm.M * g.a[i].ld;
-    gt.out.base += (long long)gm.M * g.out.ld;
-    launch_gemm_batch(epi, bm, stream);
-    const int tail_tiles = (nbm - main_bm) * nbn;
-    launch_gemm_skinny(epi, bt, 1, tail_tiles * 4 <= 2 * slots ? 32 : 64, stream);
-    return true;
-}
-
-// Split arithmetic, 256x256 tiles (gemm_split.hip: ONE workgroup per CU): a grid of more than one round of workgroups that ends in
-// a partial round -- the page call's 10 240 rows x 2048 gate columns = 320 tiles on 256 CUs: the second round occupies a quarter
-// of the chip for the time of a whole one -- keeps its whole rounds; the rows of the partial round (and a ragged last row block)
-// go as 128x128 split tiles, which contract every element with the same instruction sequence (same bits: tests/test_gpu_split.py).
-// The tail job addresses its rows through offset pointers (no kernel knows about the cut).  false: the job stays as it is.
-static bool split256_cut_rows(int epi, const GemmArgs& g, GemmArgs& head, GemmArgs& tail) {
-    static const bool enabled = [] { const char* e = getenv("CASV_SPLIT_TAIL_CUT"); return !(e && e[0] == '0'); }();
-    static const int ncu = [] { hipDeviceProp_t pr{}; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-    if (!enabled || g.N <= 0 || g.N % 256 || g.M < 256) return false;
-    const int nbn = g.N / 256, nbm = g.M / 256, tiles = nbm * nbn;
-    const int rounds = tiles / ncu, rem = tiles % ncu;
-    int main_bm;
-    if (rounds >= 1 && rem > 0 && rem * 4 <= ncu * 3) main_bm = (rounds * ncu) / nbn;      // (a last round that is three quarters full is left alone)
-    else if (g.M % 256) main_bm = nbm;                                                      // ragged last row block only
-    else return false;
-    if (main_bm < 1 || (long long)main_bm * 256 >= g.M) return false;
-    const int m_off = main_bm * 256;
-    if (g.nact && (g.nact_group <= 0 || m_off % g.nact_group)) return false;
-    head = g; tail = g;
-    head.M = m_off; tail.M = g.M - m_off;
-    auto shift = [&](Seg& sg) {
-        if (!sg.base && !sg.first_base) return;
-        if (sg.rows) sg.rows += m_off; else if (sg.base) sg.base += (long long)m_off * sg.ld;
-        if (sg.first_base) sg.first_base += (long long)m_off * sg.ld;
-    };
-    for (int i = 0; i < g.nseg; ++i) shift(tail.a[i]);
-    shift(tail.c_in);
-    for (SlotPtr* sp : {&tail.out, &tail.c_out, &tail.zinit, &tail.gates_out, &tail.out2})
-        if (sp->base) sp->base += (long long)m_off * sp->ld;
-    if (g.nact) tail.nact += m_off / g.nact_group;
-    (void)epi;
-    return true;
-}
-
-void launch_gemm_batch(int epi, const GemmBatch& b, hipStream_t stream) {
-    const GemmPlan plan = plan_gemm(epi, b);
-    if (cut_partial_round(epi, b, plan, stream)) return;
-    const int blocks = plan.blocks, ksplit = plan.ksplit;
-    bool skinny = plan.skinny;
-    // split-bf16 experiment: a launch that would go as 64- or 32-row tiles only because 128x128 tiles leave CUs idle (the
-    // encoder's cells at 1024 lines: 256 / 384 tiles; the attention-query job) runs faster as 128x128 tiles on the bf16
-    // instruction, one workgroup per CU, than as small tiles on the fp32-input one (c3: 190.9 -> 178 ms per batch)
-    // ... and every other inference launch too, whatever tile shape was asked for: with the option on, all GEMM launches of the
-    // decode path share ONE arithmetic (128x128 and 256x256 split tiles give the same bits), so that a row's result does not depend
-    // on the batch it sits in -- the property the fp32-input kernels have among themselves.  (The train step's per-time-step launches
-    // keep the fp32-input small tiles: its persistent recurrences, which they must equal, are fp32-input kernels.)
-    if (t_split_bf16 && skinny && ksplit == 1 && !splittable_launch(epi, b) && !train_launch(b)) skinny = false;
-    // XCD-aware tile order: minimise (A bytes x column-splits + B bytes x row-splits) over the 8 = xr * xc splits
-    GemmBatch bb = b;
-    for (int j = 0; j < bb.count; ++j) {
-        GemmArgs& g = bb.g[j];
-        const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
-        g.xcd_rows = 0;
-        if ((nbm * nbn) % 8 != 0 || nbm * nbn != blocks) continue;
-        double best = 0; int best_xr = 0;
-        for (int xr = 1; xr <= 8; xr *= 2) {
-            const int xc = 8 / xr;
-            if (nbm % xr || nbn % xc) continue;
-            const double cost = (double)g.M * xc + (double)g.N * xr;     // both operands share K
-            if (!best_xr || cost < best) { best = cost; best_xr = xr; }
+void run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream) {
+    for (int i = 0; i < plan.count; ++i)
+        if (plan.launch[i].form == FORM_SPLIT_256 && !gemm_split256_ready()) {
+            // (the 256x256 kernels cannot get their LDS: the whole batch as 128x128 split tiles, the same bits)
+            GemmContext small = ctx;
+            small.arithmetic = 1;
+            run_launches(epi, plan_gemm_launches(small, g_switches, epi, b), stream);
+            return;
         }
-        g.xcd_rows = best_xr;
-    }
-    for (int j = 0; j < b.count && ksplit > 1; ++j) {
-        const GemmArgs& g = b.g[j];
-        if (g.accumulate || g.out_zeroed) continue;   // partial sums are added atomically: start from zero
-        // the slot to clear is computed from the immediate step: split-K jobs never take their step from device memory
-        // (plan_gemm keeps ksplit at 1 for them)
-        float* cbase = g.out.base + (long long)(g.step_imm * g.out.step_mul + g.out.step_add) * g.out.slot_stride;
-        if (g.out.ld == g.N) (void)hipMemsetAsync(cbase, 0, (size_t)g.M * g.N * sizeof(float), stream);
-        else (void)hipMemset2DAsync(cbase, (size_t)g.out.ld * sizeof(float), 0, (size_t)g.N * sizeof(float), g.M, stream);
-    }
-    if (skinny) { launch_gemm_skinny(epi, bb, ksplit, plan.srows, stream); return; }
-    // wave-group split-K (train step only, GemmArgs.kgroups): worth it while the grid leaves CUs idle
-    bool two = true;
-    for (int j = 0; j < b.count; ++j)
-        if (b.g[j].kgroups != 2 || count_ktiles(b.g[j]) / ksplit < 16) two = false;
-    if (blocks * b.count * ksplit > 256) two = false;
-    if (t_split_bf16 && !two) {
-        if (t_split_bf16 >= 2 && ksplit == 1) {
-            // jobs that fill the chip as 256x256 tiles go to gemm_split.hip; the rest of the batch follows as a launch of its own
-            GemmBatch big{}, rest{};
-            for (int j = 0; j < b.count; ++j) {
-                GemmArgs head = b.g[j], tail{};
-                // (a job whose 256x256 grid ends in a partial round of workgroups, or in a ragged row block: whole rounds here, the
-                // remaining rows as 128x128 split tiles -- the same bits -- in the launch of the rest)
-                const bool cut = split256_cut_rows(epi, b.g[j], head, tail);
-                if (gemm_split256_wants(epi, head)) {
-                    big.g[big.count++] = head;
-                    if (cut && rest.count < GEMM_MAX_JOBS) { rest.g[rest.count++] = tail; continue; }
-                    if (cut) { big.g[big.count - 1] = b.g[j]; }      // (no room for the tail job: the job stays whole)
-                    continue;
-                }
-                rest.g[rest.count] = b.g[j]; if (epi == EPI_PLAIN) rest.g[rest.count].epi_plain = 0; ++rest.count;
-            }
-            if (big.count && launch_gemm_split256(epi, big, stream)) {
-                if (rest.count) launch_gemm_batch(epi, rest, stream);
-                return;
-            }
-        }
-        if (epi == EPI_LSTM) launch_one<EPI_LSTM, 1, true>(bb, blocks, ksplit, stream); else launch_one<EPI_PLAIN, 1, true>(bb, blocks, ksplit, stream);
-        return;
-    }
-    if (epi == EPI_LSTM) { if (two) launch_one<EPI_LSTM, 2>(bb, blocks, ksplit, stream); else launch_one<EPI_LSTM, 1>(bb, blocks, ksplit, stream); }
-    else { if (two) launch_one<EPI_PLAIN, 2>(bb, blocks, ksplit, stream); else launch_one<EPI_PLAIN, 1>(bb, blocks, ksplit, stream); }
+    run_launches(epi, plan, stream);
 }
 
-void launch_gemm(int epi, const GemmArgs& g, hipStream_t stream) {
+void launch_gemm_batch(const GemmContext& ctx, int epi, const GemmBatch& b, hipStream_t stream) {
+    run_gemm_plan(ctx, epi, b, plan_gemm_launches(ctx, g_switches, epi, b), stream);
+}
+
+void launch_gemm(const GemmContext& ctx, int epi, const GemmArgs& g, hipStream_t stream) {
     GemmBatch b;
     b.g[0] = g;
     b.count = 1;
-    launch_gemm_batch(epi, b, stream);
+    launch_gemm_batch(ctx, epi, b, stream);
 }
 
 }  // namespace casv

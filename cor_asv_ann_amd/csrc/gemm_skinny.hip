@@ -430,20 +430,17 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(const GemmBatch bat
 #endif
 }
 
-// rows = 32 or 64 per tile (gemm.hip's plan)
-void launch_gemm_skinny(int epi, const GemmBatch& b, int ksplit, int rows, hipStream_t stream) {
-    int blocks = 0;
-    for (int j = 0; j < b.count; ++j) {
-        const int nb = ((b.g[j].M + rows - 1) / rows) * ((b.g[j].N + SBN - 1) / SBN);
-        blocks = nb > blocks ? nb : blocks;
-    }
-    const dim3 grid(blocks, b.count, ksplit);
-    if (rows == 64) {
-        if (epi == EPI_LSTM) hipLaunchKernelGGL((gemm_skinny_kernel<EPI_LSTM, 2>), grid, dim3(256), 0, stream, b);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI_PLAIN, 2>), grid, dim3(256), 0, stream, b);
+static_assert(SBN == gemm_shape::BN, "gemm_plan.h plans these tiles");
+
+// 32 or 64 rows per tile, as the plan says (gemm_plan.h)
+void run_gemm_skinny(int epi, const GemmLaunchPlan& l, hipStream_t stream) {
+    const dim3 grid(l.grid_x, l.grid_y, l.grid_z);
+    if (l.form == FORM_SKINNY_64) {
+        if (epi == EPI_LSTM) hipLaunchKernelGGL((gemm_skinny_kernel<EPI_LSTM, 2>), grid, dim3(l.block), l.lds_bytes, stream, l.batch);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI_PLAIN, 2>), grid, dim3(l.block), l.lds_bytes, stream, l.batch);
     } else {
-        if (epi == EPI_LSTM) hipLaunchKernelGGL((gemm_skinny_kernel<EPI_LSTM, 1>), grid, dim3(256), 0, stream, b);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI_PLAIN, 1>), grid, dim3(256), 0, stream, b);
+        if (epi == EPI_LSTM) hipLaunchKernelGGL((gemm_skinny_kernel<EPI_LSTM, 1>), grid, dim3(l.block), l.lds_bytes, stream, l.batch);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI_PLAIN, 1>), grid, dim3(l.block), l.lds_bytes, stream, l.batch);
     }
 }
 

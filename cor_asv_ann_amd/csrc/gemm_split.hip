@@ -680,20 +680,16 @@ static const void* split_image_of(const float* Bt, int N, int K, hipStream_t str
     g_images[{dev, Bt}] = SplitImage{img, N, K};
     return img;
 }
-static bool split256_set_attributes() {        // the dynamic-LDS size of the four variants, once per device (not inside a recording)
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && attr_set[dev]) return true;
+static_assert(S2_BM == gemm_shape::S2_BM && S2_BN == gemm_shape::S2_BN && S2_BK == gemm_shape::S2_BK && S2_LDS == gemm_shape::LDS_SPLIT256, "gemm_plan.h plans these tiles");
+bool gemm_split256_ready() {        // the dynamic-LDS size of the four variants, once per device (not inside a recording)
+    static LdsAttribute attr[4];
     const void* fns[4] = {reinterpret_cast<const void*>(&gemm_split256_kernel<EPI_PLAIN, false>), reinterpret_cast<const void*>(&gemm_split256_kernel<EPI_LSTM, false>),
                           reinterpret_cast<const void*>(&gemm_split256_kernel<EPI_PLAIN, true>), reinterpret_cast<const void*>(&gemm_split256_kernel<EPI_LSTM, true>)};
-    for (const void* fn : fns)
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    for (int i = 0; i < 4; ++i) if (!gemm_dynamic_lds(attr[i], fns[i], S2_LDS)) return false;
     return true;
 }
 void gemm_split_prepare(const float* Bt, int N, int K, hipStream_t stream) {
-    (void)split256_set_attributes();
+    (void)gemm_split256_ready();
     if (Bt && N > 0 && N % S2_BN == 0 && K > 0 && K % S2_BK == 0) (void)split_image_of(Bt, N, K, stream);
 }
 void gemm_split_invalidate(const float* Bt) {        // the image(s) of one weight buffer; nullptr: all
@@ -704,61 +700,21 @@ void gemm_split_invalidate(const float* Bt) {        // the image(s) of one weig
     }
 }
 
-// Which jobs of a launch can go as 256x256 tiles: whole tiles only, inference outputs only (no gate / second-h / precomputed-term
-// side channels of the train step), K segments in whole tiles.
-static bool split256_job_ok(int epi, const GemmArgs& g) {
-    if (g.M <= 0 || g.M % S2_BM || g.N % S2_BN || g.nseg < 1) return false;
-    if (g.accumulate || g.ksplit > 1 || g.zinit.base || g.gates_out.base || g.out2.base) return false;
-    for (int i = 0; i < g.nseg; ++i) if (g.a[i].width % S2_BK || g.a[i].koff % 4 || g.a[i].ld % 4) return false;
-    if (g.Ktot % 4) return false;
-    if (epi == EPI_LSTM && !g.epi_plain && (!g.c_out.base || !g.c_in.base)) return false;
-    return true;
-}
-
-bool gemm_split256_wants(int epi, const GemmArgs& g) {
-    return split256_job_ok(epi, g) && (g.M / S2_BM) * (g.N / S2_BN) >= 128;      // fewer tiles: the smaller tile shapes do better
-}
-
-// true: launched.  false: not eligible as a whole (the caller takes the 128x128 path).
-bool launch_gemm_split256(int epi, const GemmBatch& b, hipStream_t stream) {
-    int blocks = 0;
-    GemmBatch bb = b;
-    for (int j = 0; j < b.count; ++j) {
-        if (!split256_job_ok(epi, b.g[j])) return false;
-        GemmArgs& g = bb.g[j];
-        const int nbm = g.M / S2_BM, nbn = g.N / S2_BN;
-        blocks = nbm * nbn > blocks ? nbm * nbn : blocks;
+// One 256x256 launch of a plan (gemm_plan.h: which jobs go this way, their grid and tile order, and which of them are asked for a
+// weight image).  Every job of the launch must get its image, else the launch stages B itself (same values).
+void run_gemm_split256(int epi, const GemmLaunchPlan& l, hipStream_t stream) {
+    GemmBatch bb = l.batch;
+    bool bimg = l.want_image;
+    for (int j = 0; j < l.image_jobs && (j == 0 || bb.g[j - 1].Bimg); ++j) {
+        bb.g[j].Bimg = split_image_of(bb.g[j].Bt, bb.g[j].N, bb.g[j].Ktot, stream);
+        bimg = bimg && bb.g[j].Bimg != nullptr;
     }
-    for (int j = 0; j < b.count; ++j) {
-        GemmArgs& g = bb.g[j];
-        const int nbm = g.M / S2_BM, nbn = g.N / S2_BN;
-        g.xcd_rows = 0;
-        if ((nbm * nbn) % 8 != 0 || nbm * nbn != blocks) continue;
-        double best = 0; int best_xr = 0;
-        for (int xr = 1; xr <= 8; xr *= 2) {
-            const int xc = 8 / xr;
-            if (nbm % xr || nbn % xc) continue;
-            const double cost = (double)g.M * xc + (double)g.N * xr;
-            if (!best_xr || cost < best) { best = cost; best_xr = xr; }
-        }
-        g.xcd_rows = best_xr;
-    }
-    // weight images: every job of the launch must have one (static weights, K in whole tiles)
-    static const bool images_off = [] { const char* e = getenv("CASV_SPLIT_IMAGES"); return e && e[0] == '0'; }();
-    bool bimg = !images_off;
-    for (int j = 0; j < bb.count && bimg; ++j) bimg = bb.g[j].b_static && bb.g[j].Ktot % S2_BK == 0;
-    for (int j = 0; j < bb.count && bimg; ++j) {
-        for (int i = 0; i < bb.g[j].nseg; ++i) if (bb.g[j].a[i].koff % S2_BK) bimg = false;
-        if (bimg) { bb.g[j].Bimg = split_image_of(bb.g[j].Bt, bb.g[j].N, bb.g[j].Ktot, stream); bimg = bb.g[j].Bimg != nullptr; }
-    }
-    if (!split256_set_attributes()) return false;
     const int e = (epi == EPI_LSTM ? 1 : 0) + (bimg ? 2 : 0);
-    const dim3 grid(blocks, bb.count, 1);
-    if (e == 3) hipLaunchKernelGGL((gemm_split256_kernel<EPI_LSTM, true>), grid, dim3(512), S2_LDS, stream, bb);
-    else if (e == 2) hipLaunchKernelGGL((gemm_split256_kernel<EPI_PLAIN, true>), grid, dim3(512), S2_LDS, stream, bb);
-    else if (e == 1) hipLaunchKernelGGL((gemm_split256_kernel<EPI_LSTM, false>), grid, dim3(512), S2_LDS, stream, bb);
-    else hipLaunchKernelGGL((gemm_split256_kernel<EPI_PLAIN, false>), grid, dim3(512), S2_LDS, stream, bb);
-    return true;
+    const dim3 grid(l.grid_x, l.grid_y, l.grid_z);
+    if (e == 3) hipLaunchKernelGGL((gemm_split256_kernel<EPI_LSTM, true>), grid, dim3(l.block), l.lds_bytes, stream, bb);
+    else if (e == 2) hipLaunchKernelGGL((gemm_split256_kernel<EPI_PLAIN, true>), grid, dim3(l.block), l.lds_bytes, stream, bb);
+    else if (e == 1) hipLaunchKernelGGL((gemm_split256_kernel<EPI_LSTM, false>), grid, dim3(l.block), l.lds_bytes, stream, bb);
+    else hipLaunchKernelGGL((gemm_split256_kernel<EPI_PLAIN, false>), grid, dim3(l.block), l.lds_bytes, stream, bb);
 }
 
 }  // namespace casv

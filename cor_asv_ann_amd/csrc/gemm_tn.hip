@@ -26,8 +26,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CASV_TN_XCD_ORDER 1         // 0: tile index fastest (the order of rounds 3-4; A/B builds)
 #endif
 constexpr int TBM = 128, TBN = 128, TBK = 16;
-constexpr int T_TILE = TBK * 128;
-constexpr int TS_BK_SPLIT = 16;                        // k-tile of gemm_tn_split.hip                       // floats of one operand tile in LDS ([k][128])
+constexpr int T_TILE = TBK * 128;                      // floats of one operand tile in LDS ([k][128])
 
 template <bool PART>        // PART: the ordered form's epilogue (partials stored per K share, launch_gemm_tn_ordered)
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
@@ -235,24 +234,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs g) {
     }
 }
 
-// `accumulate` = 0 with a split K needs a cleared C: the caller says so (out_zeroed) or gets a memset here.
-int launch_gemm_tn(const TnArgs& g, hipStream_t stream) {
-    const int nbm = (g.M + TBM - 1) / TBM, nbn = (g.N + TBN - 1) / TBN;
-    const int tiles = nbm * nbn, ktiles = (g.K + TBK - 1) / TBK;
-    // fill the chip (512 workgroup slots), keep >= 64 k-tiles per workgroup so that the atomic epilogue stays a small part
-    int ks = (512 + tiles - 1) / tiles;
-    if (ks > ktiles / 64) ks = ktiles / 64;
-    if (ks < 1) ks = 1;
-    if (ks > 1 && !g.accumulate && !g.out_zeroed) {
-        if (g.ldc == g.N) (void)hipMemsetAsync(g.C, 0, (size_t)g.Mstore * g.N * sizeof(float), stream);
-        else (void)hipMemset2DAsync(g.C, (size_t)g.ldc * sizeof(float), 0, (size_t)g.N * sizeof(float), g.Mstore, stream);
-    }
-    TnArgs gg = g;
-    gg.nsplit = ks;
-    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(tiles * ks), dim3(256), 0, stream, gg);
-    return ks;
-}
-
 // ---- ordered form ----
 // C[m][n] (+)= part[0][m][n] + part[1][m][n] + ... in share order; colsum[m] += colpart[0][m] + colpart[1][m] + ...
 __global__ void tn_reduce_kernel(const float* __restrict__ part, const float* __restrict__ colpart, int nz, int Mstore, int N,
@@ -272,56 +253,32 @@ __global__ void tn_reduce_kernel(const float* __restrict__ part, const float* __
         }
 }
 
-bool gemm_tn_split_shares(const TnArgs& g, int& ks);      // gemm_tn_split.hip: the ordered form's shares on 256x256 split tiles
+static_assert(TBM == gemm_shape::TN_BM && TBN == gemm_shape::TN_BN && TBK == gemm_shape::TN_BK, "gemm_plan.h plans these tiles");
 
-// K shares of the ordered form: a function of the shape only (not of the device's CU count), and the shares that hold k-tiles at all
-static void tn_ordered_plan(const TnArgs& g, bool& split, int& ks, int& nz) {
-    split = gemm_split_bf16() && gemm_tn_split_shares(g, ks);
-    int ktiles;
-    if (split) ktiles = g.K / 16;
-    else {
-        const int tiles = ((g.M + TBM - 1) / TBM) * ((g.N + TBN - 1) / TBN);
-        ktiles = (g.K + TBK - 1) / TBK;
-        ks = (512 + tiles - 1) / tiles;
-        if (ks > ktiles / 64) ks = ktiles / 64;
-        if (ks < 1) ks = 1;
-    }
-    const int per = (ktiles + ks - 1) / ks;
-    nz = per > 0 ? (ktiles + per - 1) / per : 1;
-}
-size_t gemm_tn_ordered_floats(const TnArgs& g) {
-    bool split; int ks, nz;
-    tn_ordered_plan(g, split, ks, nz);
-    return (size_t)nz * g.Mstore * ((size_t)g.N + 1);
-}
-void launch_gemm_tn_split_part(const TnArgs& g, hipStream_t stream);        // gemm_tn_split.hip
+size_t gemm_tn_ordered_floats(const GemmContext& ctx, const TnArgs& g) { return gemm_tn_plan_floats(plan_gemm_tn(ctx, gemm_switches(), g, true), g); }
 
-TnLaunch launch_gemm_tn_ordered(const TnArgs& g, float* ws, hipStream_t stream) {
-    bool split; int ks, nz;
-    tn_ordered_plan(g, split, ks, nz);
+// Runs the plan of one contraction (gemm_plan.h, plan_gemm_tn): the clear, the kernel, the ordered form's second pass.
+TnLaunch launch_gemm_tn_any(const GemmContext& ctx, const TnArgs& g, float* ordered_ws, hipStream_t stream) {
+    TnPlan p = plan_gemm_tn(ctx, gemm_switches(), g, ordered_ws != nullptr);
+    if (p.clear) gemm_clear(g.C, g.Mstore, g.N, g.ldc, stream);
     TnArgs gg = g;
-    gg.nsplit = ks;
-    gg.part = ws; gg.colpart = ws + (size_t)nz * g.Mstore * g.N;
-    if (split) launch_gemm_tn_split_part(gg, stream);
-    else hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(((g.M + TBM - 1) / TBM) * ((g.N + TBN - 1) / TBN) * ks), dim3(256), 0, stream, gg);
-    const long long mn = (long long)g.Mstore * g.N;
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)std::min<long long>((mn + 255) / 256, 2048)), dim3(256), 0, stream,
-                       gg.part, gg.colpart, nz, g.Mstore, g.N, g.C, g.ldc, g.accumulate, g.colsum);
-    return TnLaunch{split ? 1 : 0, ks, nz};
-}
-
-// K shares of a split-K launch that hold k-tiles at all (the last share may be partly filled)
-static int tn_nonempty_shares(int ktiles, int ks) {
-    const int per = (ktiles + ks - 1) / ks;
-    return per > 0 ? (ktiles + per - 1) / per : 1;
-}
-
-TnLaunch launch_gemm_tn_any(const TnArgs& g, float* ordered_ws, hipStream_t stream) {
-    if (ordered_ws) return launch_gemm_tn_ordered(g, ordered_ws, stream);
-    int ks = 0;
-    if (gemm_split_bf16() && launch_gemm_tn_split(g, stream, &ks)) return TnLaunch{1, ks, tn_nonempty_shares(g.K / TS_BK_SPLIT, ks)};
-    ks = launch_gemm_tn(g, stream);
-    return TnLaunch{0, ks, tn_nonempty_shares((g.K + TBK - 1) / TBK, ks)};
+    gg.nsplit = p.shares;
+    if (ordered_ws) { gg.part = ordered_ws; gg.colpart = ordered_ws + (size_t)p.nonempty * g.Mstore * g.N; }
+    const bool split = p.kernel == TN_SPLIT || p.kernel == TN_SPLIT_PART;
+    if (split && !run_gemm_tn_split(p.kernel == TN_SPLIT_PART, p.grid, gg, stream) && p.kernel == TN_SPLIT) {
+        // (the split kernel cannot get its LDS: the fp32-input kernel, as under arithmetic 0)
+        GemmContext plain = ctx;
+        plain.arithmetic = 0;
+        p = plan_gemm_tn(plain, gemm_switches(), g, false);
+        if (p.clear) gemm_clear(g.C, g.Mstore, g.N, g.ldc, stream);
+        gg.nsplit = p.shares;
+    }
+    if (p.kernel == TN_FP32) hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(p.grid), dim3(p.block), p.lds_bytes, stream, gg);
+    if (p.kernel == TN_FP32_PART) hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(p.grid), dim3(p.block), p.lds_bytes, stream, gg);
+    if (p.reduce_grid)
+        hipLaunchKernelGGL(tn_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, stream,
+                           gg.part, gg.colpart, p.nonempty, g.Mstore, g.N, g.C, g.ldc, g.accumulate, g.colsum);
+    return TnLaunch{p.kernel == TN_SPLIT || p.kernel == TN_SPLIT_PART ? 1 : 0, p.shares, p.nonempty};
 }
 
 }  // namespace casv

@@ -170,59 +170,18 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_split256_kernel(const TnArgs g
         }
 }
 
-// true: launched.  false: the shape has no 256x256 split form (the caller takes the fp32-input kernel).
-bool launch_gemm_tn_split(const TnArgs& g, hipStream_t stream, int* shares) {
-    static const bool off = [] { const char* e = getenv("CASV_TN_SPLIT"); return e && e[0] == '0'; }();
-    if (off) return false;
-    if (g.M <= 0 || g.N <= 0 || g.M % TS_BM || g.N % TS_BN || g.K < 64 * TS_BK || g.K % TS_BK) return false;
-    if (g.Mstore <= 0 || g.Mstore > g.M) return false;
-    static const int ncu = [] { hipDeviceProp_t pr{}; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-    const int tiles = (g.M / TS_BM) * (g.N / TS_BN), ktiles = g.K / TS_BK;
-    // one workgroup per CU: fill the chip, keep >= 64 k-tiles per workgroup so that the atomic epilogue stays a small part
-    int ks = ncu / tiles;
-    if (ks > ktiles / 64) ks = ktiles / 64;
-    if (ks < 1) ks = 1;
-    if (tiles * ks < ncu / 2) return false;                 // (too few workgroups for this tile shape: the fp32-input kernel's 128x128 tiles fill the chip better)
-    if (ks > 1 && !g.accumulate && !g.out_zeroed) {
-        if (g.ldc == g.N) (void)hipMemsetAsync(g.C, 0, (size_t)g.Mstore * g.N * sizeof(float), stream);
-        else (void)hipMemset2DAsync(g.C, (size_t)g.ldc * sizeof(float), 0, (size_t)g.N * sizeof(float), g.Mstore, stream);
-    }
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-    TnArgs gg = g;
-    gg.nsplit = ks;
-    hipLaunchKernelGGL(gemm_tn_split256_kernel<false>, dim3(tiles * ks), dim3(512), TS_LDS, stream, gg);
-    if (shares) *shares = ks;
-    return true;
-}
+static_assert(TS_BM == gemm_shape::TS_BM && TS_BN == gemm_shape::TS_BN && TS_BK == gemm_shape::TS_BK && TS_LDS == gemm_shape::LDS_TN_SPLIT, "gemm_plan.h plans these tiles");
 
-// The ordered form (launch_gemm_tn_ordered): the shares as above for a chip of 256 CUs whatever the device has, so that the
-// partition -- and with it every bit of the result -- follows from the shape alone.  false: no split form for the shape.
-bool gemm_tn_split_shares(const TnArgs& g, int& ks) {
-    static const bool off = [] { const char* e = getenv("CASV_TN_SPLIT"); return e && e[0] == '0'; }();
-    if (off) return false;
-    if (g.M <= 0 || g.N <= 0 || g.M % TS_BM || g.N % TS_BN || g.K < 64 * TS_BK || g.K % TS_BK) return false;
-    if (g.Mstore <= 0 || g.Mstore > g.M) return false;
-    const int tiles = (g.M / TS_BM) * (g.N / TS_BN), ktiles = g.K / TS_BK;
-    ks = 256 / tiles;
-    if (ks > ktiles / 64) ks = ktiles / 64;
-    if (ks < 1) ks = 1;
-    return tiles * ks >= 128;
-}
-void launch_gemm_tn_split_part(const TnArgs& g, hipStream_t stream) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS);
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_split256_kernel<true>, dim3((g.M / TS_BM) * (g.N / TS_BN) * g.nsplit), dim3(512), TS_LDS, stream, g);
+// The split kernel of a plan (gemm_plan.h, plan_gemm_tn: TN_SPLIT, or TN_SPLIT_PART for the ordered form).  false: not launched,
+// the kernel cannot get its LDS (the caller takes the fp32-input kernel; the ordered form has decided its kernel from the shape
+// alone and launches regardless).
+bool run_gemm_tn_split(bool part, int grid, const TnArgs& g, hipStream_t stream) {
+    static LdsAttribute attr[2];
+    const void* fn = !part ? reinterpret_cast<const void*>(&gemm_tn_split256_kernel<false>) : reinterpret_cast<const void*>(&gemm_tn_split256_kernel<true>);
+    if (!gemm_dynamic_lds(attr[part], fn, TS_LDS) && !part) return false;
+    if (part) hipLaunchKernelGGL(gemm_tn_split256_kernel<true>, dim3(grid), dim3(512), TS_LDS, stream, g);
+    else hipLaunchKernelGGL(gemm_tn_split256_kernel<false>, dim3(grid), dim3(512), TS_LDS, stream, g);
+    return true;
 }
 
 }  // namespace casv

@@ -328,14 +328,14 @@ static void run_gemm_tn(casv_model* m, const float* A, long long lda, int M, int
     m->prof_begin(PC_GEMM, 2.0 * Mstore * (double)N * (double)K, 4.0 * ((double)K * (M + N) + (double)Mstore * N), ev);
     // (the step's arithmetic, engine.h ENTRY_TRAIN: the big weight gradients on bf16x3-split operands where the shape has that form)
     if (m->deterministic) {             // K shares from the shape alone, their partials added in share order (gemm_tn.hip)
-        const size_t bytes = gemm_tn_ordered_floats(g) * sizeof(float);
+        const size_t bytes = gemm_tn_ordered_floats(m->gemm, g) * sizeof(float);
         TrainState* ts = m->train;
         if (bytes > ts->tn_ws.cap) {
             (void)hipStreamSynchronize(m->stream);
             if (int rc = ts->tn_ws.ensure(bytes)) { if (!ts->tn_ws_rc) ts->tn_ws_rc = rc; m->prof_end(PC_GEMM, ev); return; }
         }
-        (void)launch_gemm_tn_any(g, ts->tn_ws.as<float>(), m->stream);
-    } else (void)launch_gemm_tn_any(g, nullptr, m->stream);
+        (void)launch_gemm_tn_any(m->gemm, g, ts->tn_ws.as<float>(), m->stream);
+    } else (void)launch_gemm_tn_any(m->gemm, g, nullptr, m->stream);
     m->prof_end(PC_GEMM, ev);
 }
 
@@ -1323,8 +1323,8 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
     if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
     HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
-    OrderedScope ordered(m->deterministic);
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
+    OrderedScope ordered(m, m->deterministic);
     Step s{};
     s.m = m; s.ts = m->train; s.st = m->stream;
     s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
@@ -1436,8 +1436,8 @@ static int score_call(casv_model* m, int32_t Be, int32_t N, int32_t T, int32_t U
         if (int rc = score_state(m)) return rc;
         m->train = m->score; scope.borrowed = true;
     }
-    SplitScope arithmetic(arithmetic_of(m, ENTRY_TRAIN));       // (the forward pass of a mode-0 step, in its arithmetic)
-    OrderedScope ordered(m->deterministic);
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (the forward pass of a mode-0 step, in its arithmetic)
+    OrderedScope ordered(m, m->deterministic);
     const std::vector<float> ones((size_t)UB, 1.0f);            // (stage_inputs stages the step's sample weights: the head reads none)
     Step s{};
     s.m = m; s.ts = m->train; s.st = m->stream;
