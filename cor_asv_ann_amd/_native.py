@@ -37,6 +37,24 @@ class BeamParams(Structure):
                 ('cost0', c_double)]
 
 
+class DebugRows(Structure):
+    """casv_debug_rows: an input of casv_debug_gemm_jobs whose rows move with the step (K segment, cell state, zinit)"""
+    _fields_ = [('pool', c_void_p), ('rows', c_void_p), ('first', c_void_p), ('slots', c_int32), ('pool_rows', c_int32),
+                ('ld', c_int32), ('width', c_int32), ('koff', c_int32), ('step_mul', c_int32), ('step_add', c_int32),
+                ('skip_first', c_int32)]
+
+
+class DebugOut(Structure):
+    _fields_ = [('data', c_void_p), ('slots', c_int32), ('ld', c_int32), ('step_mul', c_int32), ('step_add', c_int32)]
+
+
+class DebugJob(Structure):
+    _fields_ = [('M', c_int32), ('N', c_int32), ('Ktot', c_int32), ('nseg', c_int32), ('a', DebugRows * 3), ('c_in', DebugRows),
+                ('zinit', DebugRows), ('Bt', c_void_p), ('bias', c_void_p), ('out', DebugOut), ('c_out', DebugOut),
+                ('gates_out', DebugOut), ('out2', DebugOut), ('nact', c_void_p), ('nact_lines', c_int32), ('nact_group', c_int32),
+                ('b_static', c_int32), ('epi_plain', c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in the header is listed here and checked at load
 SIGNATURES = {
     'casv_last_error': (c_char_p, []),
@@ -76,6 +94,7 @@ SIGNATURES = {
     'casv_debug_contract_tn': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                        c_void_p, c_int64, c_void_p]),
     'casv_debug_activation': (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    'casv_debug_gemm_jobs': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), c_int32, c_int32]),
     'casv_set_option': (c_int, [c_void_p, c_char_p, c_int64]),
     'casv_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_comm_unique_id': (c_int, [c_void_p]),

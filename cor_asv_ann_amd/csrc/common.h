@@ -96,8 +96,9 @@ __device__ __forceinline__ LstmCellOut lstm_cell(float zi, float zf, float zg, f
 const GemmSwitches& gemm_switches();       // the process-wide switches (gemm.hip: read from the environment when the library is loaded)
 void launch_gemm(const GemmContext& ctx, int epi, const GemmArgs& g, hipStream_t stream);
 void launch_gemm_batch(const GemmContext& ctx, int epi, const GemmBatch& b, hipStream_t stream);
-// the same for a plan the caller has made already (plan_gemm_launches(ctx, gemm_switches(), epi, b))
-void run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream);
+// the same for a plan the caller has made already (plan_gemm_launches(ctx, gemm_switches(), epi, b)); returns the plan it ran --
+// the caller's, or the 128x128 one that stands in where the 256x256 kernels cannot get their LDS
+GemmPlan run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream);
 void run_gemm_skinny(int epi, const GemmLaunchPlan& l, hipStream_t stream);        // gemm_skinny.hip: FORM_SKINNY_32 / _64
 void run_gemm_split256(int epi, const GemmLaunchPlan& l, hipStream_t stream);      // gemm_split.hip: FORM_SPLIT_256
 bool gemm_split256_ready();                // gemm_split.hip: its kernels have their dynamic LDS on the current device

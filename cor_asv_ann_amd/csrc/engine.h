@@ -162,6 +162,7 @@ struct casv_model {
     int stat_beam[3] = {0, 0, 0};                         // last beam decode: most new hypotheses of one line in one step; rows stepped
     int stat_enc_persistent = 0;                          // the encoder pass behind the last entry point ran as ONE persistent launch and was not redone
     int stat_train_launches = 0; long long stat_train_give_ups = 0;   // train step: persistent launches of the last step that was not redone; steps redone after a give-up (train.hip)
+    int stat_jobs[2] = {0, 0};                            // last casv_debug_gemm_jobs: bit f = a launch of GemmForm f ran, launches of the plan
     int stat_tn[3] = {0, 0, 0};                           // last casv_debug_contract_tn: split kernel (0/1), K shares launched, shares holding k-tiles
                                                           // and distinct parent expansions among them (N <= 16 only)
     Prof prof;

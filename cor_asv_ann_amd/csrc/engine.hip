@@ -326,6 +326,8 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "encoder_persistent")) { *value = m->stat_enc_persistent; return CASV_OK; }
     if (!strcmp(key, "train_persistent_launches")) { *value = m->stat_train_launches; return CASV_OK; }
     if (!strcmp(key, "train_give_ups")) { *value = m->stat_train_give_ups; return CASV_OK; }
+    if (!strcmp(key, "gemm_jobs_forms")) { *value = m->stat_jobs[0]; return CASV_OK; }
+    if (!strcmp(key, "gemm_jobs_launches")) { *value = m->stat_jobs[1]; return CASV_OK; }
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }
@@ -363,12 +365,26 @@ extern "C" int casv_profile_read(casv_model* m, const char* name, int64_t* launc
 
 // The operand buffers of the two debug entry points: released on EVERY way out (an early return on a failed allocation or copy
 // must not leak M*K + N*K + M*N floats), behind the stream's work, and the pre-split image a split launch made of Bt with them.
+// (casv_debug_gemm_jobs has as many buffers and weights as its jobs describe: `owned` are made by put() and deleted here, `weights`
+// are further weight buffers whose images go)
 struct DebugBuffers {
     std::vector<DevBuf*> bufs; DevBuf* weight; hipStream_t stream;
+    std::vector<DevBuf*> owned = {}; std::vector<const float*> weights = {};
     ~DebugBuffers() {
         (void)hipStreamSynchronize(stream);
         if (weight && weight->p) gemm_split_invalidate(weight->as<float>());
+        for (const float* w : weights) gemm_split_invalidate(w);
         for (DevBuf* b : bufs) b->release();
+        for (DevBuf* b : owned) { b->release(); delete b; }
+    }
+    // a device copy of n elements of 4 bytes (src == nullptr: n elements of 0xFF bytes); nullptr: see rc
+    void* put(const void* src, size_t n, int& rc) {
+        DevBuf* b = new DevBuf();
+        owned.push_back(b);
+        if ((rc = b->ensure((n ? n : 1) * 4))) return nullptr;
+        const hipError_t e = src ? hipMemcpyAsync(b->p, src, n * 4, hipMemcpyHostToDevice, stream) : hipMemsetAsync(b->p, 0xff, (n ? n : 1) * 4, stream);
+        if (e != hipSuccess) { rc = fail(CASV_ERR_HIP, "copy of a debug operand failed: %s", hipGetErrorString(e)); return nullptr; }
+        return b->p;
     }
 };
 
@@ -511,6 +527,157 @@ extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, i
     HIPCHK(hipStreamSynchronize(m->stream));
     for (uint32_t v : guard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past row Mstore - 1 of C");
     for (uint32_t v : cguard) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "the launch stored past colsum[Mstore - 1]");
+    return CASV_OK;
+}
+
+// Test support: one batch of forward jobs with the whole operand machinery of gemm_args.h, on host data (casv_debug_gemm_jobs).
+// Nothing is launched unless every address a kernel can form from the arguments lies inside a buffer allocated here: the kernels
+// clamp rows to M - 1 and columns to N - 1, read [0, width) of a row, rows[m] for every m < M (live or not), the cell state's N / 4
+// units, nact[line] for every line of the job; they store rows < M only.
+namespace {
+constexpr long long DEBUG_JOBS_MAX_FLOATS = 1LL << 28;      // per buffer (1 GiB)
+// the slot a step selects; false: outside [0, slots)
+bool debug_slot_ok(int step, int mul, int add, int slots) {
+    const long long s = (long long)step * mul + add;
+    return s >= 0 && s < slots;
+}
+// an input part of job j (K segment, cell state, zinit) at every step of `steps`
+int check_debug_rows(const casv_debug_rows& r, const char* what, int j, int M, const int* steps, int nsteps) {
+    if (!r.pool) return fail(CASV_ERR_ARG, "job %d %s: no pool", j, what);
+    if (r.slots < 1 || r.slots > 64 || r.pool_rows < 1 || r.width < 1 || r.ld < r.width || r.ld % 4 || r.ld > (1 << 16))
+        return fail(CASV_ERR_ARG, "job %d %s: slots in [1, 64], pool_rows >= 1, ld >= width >= 1, ld a multiple of 4", j, what);
+    if ((long long)r.slots * r.pool_rows * r.ld > DEBUG_JOBS_MAX_FLOATS) return fail(CASV_ERR_ARG, "job %d %s: pool too large", j, what);
+    if (std::abs((long long)r.step_mul) > 64 || std::abs((long long)r.step_add) > 4096) return fail(CASV_ERR_ARG, "job %d %s: step_mul / step_add out of range", j, what);
+    if (r.skip_first != 0 && r.skip_first != 1) return fail(CASV_ERR_ARG, "job %d %s: skip_first is 0 or 1", j, what);
+    if (r.rows) { for (int m = 0; m < M; ++m) if (r.rows[m] < 0 || r.rows[m] >= r.pool_rows) return fail(CASV_ERR_ARG, "job %d %s: rows[%d] = %d outside [0, %d)", j, what, m, r.rows[m], r.pool_rows); }
+    else if (r.pool_rows < M) return fail(CASV_ERR_ARG, "job %d %s: %d pool rows for %d ungathered rows", j, what, r.pool_rows, M);
+    for (int i = 0; i < nsteps; ++i) {
+        if (steps[i] == 0 && (r.skip_first || r.first)) continue;         // (the pool is not read at step 0)
+        if (!debug_slot_ok(steps[i], r.step_mul, r.step_add, r.slots)) return fail(CASV_ERR_ARG, "job %d %s: step %d selects a slot outside [0, %d)", j, what, steps[i], r.slots);
+    }
+    return CASV_OK;
+}
+int check_debug_out(const casv_debug_out& o, const char* what, int j, int M, int width, const int* steps, int nsteps) {
+    if (!o.data) return fail(CASV_ERR_ARG, "job %d %s: no data", j, what);
+    if (o.slots < 1 || o.slots > 64 || o.ld < width || o.ld % 4 || o.ld > (1 << 16)) return fail(CASV_ERR_ARG, "job %d %s: slots in [1, 64], ld >= %d and a multiple of 4", j, what, width);
+    if (((long long)o.slots * M + 1) * o.ld > DEBUG_JOBS_MAX_FLOATS) return fail(CASV_ERR_ARG, "job %d %s: too large", j, what);
+    if (std::abs((long long)o.step_mul) > 64 || std::abs((long long)o.step_add) > 4096) return fail(CASV_ERR_ARG, "job %d %s: step_mul / step_add out of range", j, what);
+    for (int i = 0; i < nsteps; ++i)
+        if (!debug_slot_ok(steps[i], o.step_mul, o.step_add, o.slots)) return fail(CASV_ERR_ARG, "job %d %s: step %d selects a slot outside [0, %d)", j, what, steps[i], o.slots);
+    return CASV_OK;
+}
+int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, int nsteps) {
+    const bool lstm = epi == EPI_LSTM && !d.epi_plain;
+    if (d.M < 1 || d.M > (1 << 16) || d.N < 1 || d.N > (1 << 14) || d.Ktot < 32 || d.Ktot > (1 << 14) || d.Ktot % 4 || d.nseg < 1 || d.nseg > 3)
+        return fail(CASV_ERR_ARG, "job %d: M in [1, 65536], N in [1, 16384], Ktot in [32, 16384] and a multiple of 4, 1..3 segments", j);
+    if (lstm && d.N % 128) return fail(CASV_ERR_ARG, "job %d: N must be a multiple of 128 for the LSTM epilogue", j);
+    if (!d.Bt) return fail(CASV_ERR_ARG, "job %d: no Bt", j);
+    if ((d.b_static != 0 && d.b_static != 1) || (d.epi_plain != 0 && d.epi_plain != 1)) return fail(CASV_ERR_ARG, "job %d: b_static and epi_plain are 0 or 1", j);
+    long long wsum = 0;
+    for (int i = 0; i < d.nseg; ++i) {
+        const casv_debug_rows& r = d.a[i];
+        const std::string what = "segment " + std::to_string(i);
+        if (int rc = check_debug_rows(r, what.c_str(), j, d.M, steps, nsteps)) return rc;
+        if (r.width % 32) return fail(CASV_ERR_ARG, "job %d %s: width %d is no multiple of 32", j, what.c_str(), r.width);
+        if (r.koff < 0 || r.koff % 4 || (long long)r.koff + r.width > d.Ktot) return fail(CASV_ERR_ARG, "job %d %s: koff a non-negative multiple of 4, koff + width <= Ktot", j, what.c_str());
+        wsum += r.width;
+    }
+    if (wsum > d.Ktot) return fail(CASV_ERR_ARG, "job %d: the segments' widths sum to %lld > Ktot = %d", j, wsum, d.Ktot);
+    if (int rc = check_debug_out(d.out, "out", j, d.M, lstm ? d.N / 4 : d.N, steps, nsteps)) return rc;
+    if (lstm) {
+        if (int rc = check_debug_rows(d.c_in, "c_in", j, d.M, steps, nsteps)) return rc;
+        if (d.c_in.width != d.N / 4) return fail(CASV_ERR_ARG, "job %d c_in: width must be N / 4", j);
+        if (int rc = check_debug_out(d.c_out, "c_out", j, d.M, d.N / 4, steps, nsteps)) return rc;
+        if (d.zinit.pool) {
+            if (int rc = check_debug_rows(d.zinit, "zinit", j, d.M, steps, nsteps)) return rc;
+            if (d.zinit.width != d.N || d.zinit.pool_rows != d.M || d.zinit.rows || d.zinit.first || d.zinit.skip_first)
+                return fail(CASV_ERR_ARG, "job %d zinit: width = N, pool_rows = M, no rows / first / skip_first", j);
+        }
+        if (d.gates_out.data) if (int rc = check_debug_out(d.gates_out, "gates_out", j, d.M, d.N, steps, nsteps)) return rc;
+        if (d.out2.data) if (int rc = check_debug_out(d.out2, "out2", j, d.M, d.N / 4, steps, nsteps)) return rc;
+    } else if (d.zinit.pool || d.gates_out.data || d.out2.data || d.c_out.data) {
+        return fail(CASV_ERR_ARG, "job %d: c_out, zinit, gates_out and out2 belong to LSTM jobs", j);
+    }
+    if (d.nact) {
+        if (d.nact_group < 1 || d.nact_lines != (d.M + d.nact_group - 1) / d.nact_group) return fail(CASV_ERR_ARG, "job %d: nact needs nact_group >= 1 and one entry per line", j);
+        for (int l = 0; l < d.nact_lines; ++l) if (d.nact[l] < 0 || d.nact[l] > d.nact_group) return fail(CASV_ERR_ARG, "job %d: nact[%d] outside [0, nact_group]", j, l);
+    }
+    return CASV_OK;
+}
+}  // namespace
+
+extern "C" int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr) {
+    if (!m || !jobs) return fail(CASV_ERR_ARG, "null argument");
+    if ((epi != EPI_PLAIN && epi != EPI_LSTM) || count < 1 || count > GEMM_MAX_JOBS || step < 0 || step > 4096 || (step_by_ptr != 0 && step_by_ptr != 1))
+        return fail(CASV_ERR_ARG, "epi 0 / 1, 1..%d jobs, step in [0, 4096], step_by_ptr 0 / 1", GEMM_MAX_JOBS);
+    // (a step that arrives through the device word: the arguments' immediate step is 0, and must be harmless if a kernel took it)
+    const int steps[2] = {step, 0};
+    const int nsteps = step_by_ptr ? 2 : 1;
+    for (int j = 0; j < count; ++j) if (int rc = check_debug_job(epi, jobs[j], j, steps, nsteps)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
+    DebugBuffers dev{{}, nullptr, m->stream};
+    int rc = CASV_OK;
+    const int* step_word = nullptr;
+    if (step_by_ptr) { step_word = static_cast<const int*>(dev.put(&step, 1, rc)); if (rc) return rc; }
+    struct Back { const casv_debug_out* o; float* d; size_t rows; };
+    std::vector<Back> back;
+    GemmBatch b{};
+    b.count = count;
+    for (int j = 0; j < count; ++j) {
+        const casv_debug_job& d = jobs[j];
+        const bool lstm = epi == EPI_LSTM && !d.epi_plain;
+        GemmArgs& g = b.g[j];
+        auto seg = [&](const casv_debug_rows& r, Seg& s) {
+            s = Seg{};
+            s.base = static_cast<const float*>(dev.put(r.pool, (size_t)r.slots * r.pool_rows * r.ld, rc)); if (rc) return;
+            if (r.rows) { s.rows = static_cast<const int*>(dev.put(r.rows, (size_t)d.M, rc)); if (rc) return; }
+            if (r.first) { s.first_base = static_cast<const float*>(dev.put(r.first, (size_t)d.M * r.ld, rc)); if (rc) return; }
+            s.slot_stride = (long long)r.pool_rows * r.ld; s.step_mul = r.step_mul; s.step_add = r.step_add;
+            s.ld = r.ld; s.width = r.width; s.skip_first = r.skip_first; s.koff = r.koff;
+        };
+        auto out = [&](const casv_debug_out& o, SlotPtr& p) {
+            const size_t rows = (size_t)o.slots * d.M;
+            p = SlotPtr{};
+            p.base = static_cast<float*>(dev.put(nullptr, (rows + 1) * o.ld, rc)); if (rc) return;      // (one guard row behind the last slot)
+            p.slot_stride = (long long)d.M * o.ld; p.step_mul = o.step_mul; p.step_add = o.step_add; p.ld = o.ld;
+            back.push_back(Back{&o, p.base, rows});
+        };
+        g.M = d.M; g.N = d.N; g.Ktot = d.Ktot; g.nseg = d.nseg;
+        for (int i = 0; i < d.nseg; ++i) { seg(d.a[i], g.a[i]); if (rc) return rc; }
+        g.Bt = static_cast<const float*>(dev.put(d.Bt, (size_t)d.N * d.Ktot, rc)); if (rc) return rc;
+        dev.weights.push_back(g.Bt);
+        if (d.bias) { g.bias = static_cast<const float*>(dev.put(d.bias, (size_t)d.N, rc)); if (rc) return rc; }
+        out(d.out, g.out); if (rc) return rc;
+        if (lstm) {
+            seg(d.c_in, g.c_in); if (rc) return rc;
+            out(d.c_out, g.c_out); if (rc) return rc;
+            if (d.zinit.pool) {
+                Seg z; seg(d.zinit, z); if (rc) return rc;
+                g.zinit = mkslot(const_cast<float*>(z.base), z.ld, z.slot_stride, z.step_mul, z.step_add);
+            }
+            if (d.gates_out.data) { out(d.gates_out, g.gates_out); if (rc) return rc; }
+            if (d.out2.data) { out(d.out2, g.out2); if (rc) return rc; }
+        }
+        if (d.nact) { g.nact = static_cast<const int*>(dev.put(d.nact, (size_t)d.nact_lines, rc)); if (rc) return rc; g.nact_group = d.nact_group; }
+        g.epi_plain = epi == EPI_LSTM ? d.epi_plain : 0;
+        g.b_static = d.b_static;
+        g.step_imm = step_by_ptr ? 0 : step; g.step_ptr = step_word;
+    }
+    // (launch_gemm_batch, keeping the plan that ran for the statistic)
+    const GemmPlan plan = run_gemm_plan(m->gemm, epi, b, plan_gemm_launches(m->gemm, gemm_switches(), epi, b), m->stream);
+    HIPCHK(hipGetLastError());
+    m->stat_jobs[0] = 0; m->stat_jobs[1] = plan.count;
+    for (int i = 0; i < plan.count; ++i) m->stat_jobs[0] |= 1 << plan.launch[i].form;
+    std::vector<std::vector<uint32_t>> guards(back.size());
+    for (size_t i = 0; i < back.size(); ++i) {
+        const size_t n = back[i].rows * back[i].o->ld;
+        guards[i].resize(back[i].o->ld);
+        HIPCHK(hipMemcpyAsync(back[i].o->data, back[i].d, n * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(guards[i].data(), back[i].d + n, guards[i].size() * 4, hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (const auto& gd : guards) for (uint32_t v : gd) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "a launch stored past the last row of an output");
     return CASV_OK;
 }
 

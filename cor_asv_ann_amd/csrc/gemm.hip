@@ -821,20 +821,22 @@ static void run_launches(int epi, const GemmPlan& plan, hipStream_t stream) {
     }
 }
 
-void run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream) {
+GemmPlan run_gemm_plan(const GemmContext& ctx, int epi, const GemmBatch& b, const GemmPlan& plan, hipStream_t stream) {
     for (int i = 0; i < plan.count; ++i)
         if (plan.launch[i].form == FORM_SPLIT_256 && !gemm_split256_ready()) {
             // (the 256x256 kernels cannot get their LDS: the whole batch as 128x128 split tiles, the same bits)
             GemmContext small = ctx;
             small.arithmetic = 1;
-            run_launches(epi, plan_gemm_launches(small, g_switches, epi, b), stream);
-            return;
+            const GemmPlan instead = plan_gemm_launches(small, g_switches, epi, b);
+            run_launches(epi, instead, stream);
+            return instead;
         }
     run_launches(epi, plan, stream);
+    return plan;
 }
 
 void launch_gemm_batch(const GemmContext& ctx, int epi, const GemmBatch& b, hipStream_t stream) {
-    run_gemm_plan(ctx, epi, b, plan_gemm_launches(ctx, g_switches, epi, b), stream);
+    (void)run_gemm_plan(ctx, epi, b, plan_gemm_launches(ctx, g_switches, epi, b), stream);
 }
 
 void launch_gemm(const GemmContext& ctx, int epi, const GemmArgs& g, hipStream_t stream) {

@@ -529,6 +529,60 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_activation(self.handle, w, n, nv.ptr(x), nv.ptr(out)))
         return out
 
+    def debug_gemm_jobs(self, epi, jobs, step, step_by_ptr=False):
+        """Test support (casv_debug_gemm_jobs): ONE batch of forward GEMM jobs (epi 0 plain, 1 fused LSTM cell) with the whole
+        operand machinery of csrc/gemm_args.h, on host data.  A job is an object with the attributes M, N, Ktot, segs, c_in, zinit, Bt,
+        bias, out, c_out, gates_out, out2, nact, nact_group, b_static, epi_plain; an input part (segment, c_in, zinit) has pool
+        (slots, pool_rows, ld) float32, width, koff, rows, first, step_mul, step_add, skip_first; an output is (slots, ld, step_mul,
+        step_add) or None (tests/lstm_gemm_cases.py builds them).  Returns (outputs, forms, launches): per job a dict name ->
+        (slots, M, ld) float32 with every byte the launch did not store to still 0xFF, the bit mask of the GemmForms of the plan that
+        ran, and the number of its launches."""
+        keep, cjobs, results = [], (nv.DebugJob * len(jobs))(), []
+
+        def arr(a, dtype):
+            if a is None:
+                return None
+            a = nv.carray(a, dtype)
+            keep.append(a)
+            return a.ctypes.data
+
+        def rows(dst, part):
+            pool = nv.carray(part.pool, np.float32)
+            assert pool.ndim == 3
+            dst.slots, dst.pool_rows, dst.ld = pool.shape
+            dst.pool, dst.rows, dst.first = arr(pool, np.float32), arr(part.rows, np.int32), arr(part.first, np.float32)
+            assert part.rows is None or len(part.rows) == job.M
+            assert part.first is None or np.shape(part.first) == (job.M, dst.ld)
+            dst.width, dst.koff, dst.step_mul, dst.step_add, dst.skip_first = part.width, part.koff, part.step_mul, part.step_add, int(part.skip_first)
+
+        def out(dst, spec, name, res):
+            if spec is None:
+                return
+            slots, ld, mul, add = spec
+            res[name] = np.empty((slots, job.M, ld), np.float32)
+            dst.data, dst.slots, dst.ld, dst.step_mul, dst.step_add = res[name].ctypes.data, slots, ld, mul, add
+
+        for cj, job in zip(cjobs, jobs):
+            res = {}
+            cj.M, cj.N, cj.Ktot, cj.nseg = job.M, job.N, job.Ktot, len(job.segs)
+            assert 1 <= len(job.segs) <= 3 and np.shape(job.Bt) == (job.N, job.Ktot)
+            for i, sg in enumerate(job.segs):
+                rows(cj.a[i], sg)
+            if job.c_in is not None:
+                rows(cj.c_in, job.c_in)
+            if job.zinit is not None:
+                rows(cj.zinit, job.zinit)
+            cj.Bt, cj.bias = arr(job.Bt, np.float32), arr(job.bias, np.float32)
+            assert job.bias is None or np.shape(job.bias) == (job.N,)
+            for name in ('out', 'c_out', 'gates_out', 'out2'):
+                out(getattr(cj, name), getattr(job, name), name, res)
+            if job.nact is not None:
+                cj.nact, cj.nact_lines, cj.nact_group = arr(job.nact, np.int32), len(job.nact), job.nact_group
+            cj.b_static, cj.epi_plain = int(job.b_static), int(job.epi_plain)
+            results.append(res)
+        nv.check(self.lib.casv_debug_gemm_jobs(self.handle, int(epi), len(jobs), cjobs, int(step), int(bool(step_by_ptr))))
+        return results, self.stat('gemm_jobs_forms'), self.stat('gemm_jobs_launches')
+
     def alignments_sparse(self, rows, steps, K=None):
         """Window form of the last decode call's soft alignments: (lo int32 (rows, S), w float32 (rows, S, K))."""
         K = int(K or 2 * self.window_width + 1)

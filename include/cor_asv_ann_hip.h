@@ -326,6 +326,47 @@ int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, int32_t Msto
  * which = 0: out[i] = tanh(in[i]); 1: out[i] = sigmoid(in[i]); 2: the LSTM cell on in[5i .. 5i+4] = (z_i, z_f, z_g, z_o, c_prev)
  * -> out[2i] = c, out[2i+1] = h.  tests/test_gpu_activations.py compares them with float64. */
 int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* in, float* out);
+/* Test support: ONE batch of 1..4 forward GEMM jobs on the caller's host data through the launcher every GEMM of the path goes
+ * through (launch_gemm_batch), with everything of csrc/gemm_args.h that a plain contraction never uses: K segments with their own
+ * koff and ld, gathered rows, step addressing, the step-0 forms, the cell state, live rows, mixed batches.  epi: 0 = plain
+ * epilogue for every job, 1 = fused LSTM cell (a job with epi_plain set takes the plain epilogue inside that launch).  The options
+ * "tile" and "split_bf16" select tile shape and arithmetic as for casv_debug_contract.
+ *   casv_debug_rows: an input whose rows move with the step -- pool [slots][pool_rows][ld]; row m of the job is row
+ *   (rows ? rows[m] : m) of slot step * step_mul + step_add; at step 0 a part with skip_first counts as zeros, one with `first`
+ *   ([M][ld]) takes row m of `first` instead.  K segments: width (a multiple of 32) and koff place it in Bt's K dimension.  c_in:
+ *   width = N / 4.  zinit (optional, pool = NULL: none): pool_rows = M, width = N, no rows / first / skip_first.
+ *   casv_debug_out: an output [slots][M][ld] on the host (data = NULL: absent); the call returns ALL slots: the addressed one
+ *   as the launch left it, every byte nothing was stored to as 0xFF.
+ *   step: its value; step_by_ptr = 1: the kernels read it from a device word and the immediate step of the arguments is 0 (the
+ *   job must then be valid at step 0 too).
+ * Everything is checked on the host before anything is launched (CASV_ERR_ARG): every row index in [0, pool_rows), every slot the
+ * step selects inside its pool, widths multiples of 32, N a multiple of 128 for LSTM jobs, koff + width <= Ktot and the widths'
+ * sum <= Ktot, every ld >= its width and a multiple of 4, nact (optional; values in [0, nact_group]) one entry per line of
+ * nact_group rows.  Every output has one guard row behind its last slot: a store there is CASV_ERR_STATE.  casv_get_stat then
+ * reports "gemm_jobs_forms" (bit f = a launch of GemmForm f, csrc/gemm_plan.h, was part of the plan that ran) and
+ * "gemm_jobs_launches" (its launches).  tests/test_gpu_lstm_gemm.py compares every form with a float64 reference. */
+typedef struct casv_debug_rows {
+    const float* pool;
+    const int32_t* rows;
+    const float* first;
+    int32_t slots, pool_rows, ld, width, koff, step_mul, step_add, skip_first;
+} casv_debug_rows;
+typedef struct casv_debug_out {
+    float* data;
+    int32_t slots, ld, step_mul, step_add;
+} casv_debug_out;
+typedef struct casv_debug_job {
+    int32_t M, N, Ktot, nseg;
+    casv_debug_rows a[3], c_in, zinit;
+    const float* Bt;            /* [N][Ktot]; LSTM: rows gate-interleaved [unit/32][gate i,f,c,o][unit%32] */
+    const float* bias;          /* [N] or NULL */
+    casv_debug_out out, c_out, gates_out, out2;
+    const int32_t* nact;        /* [nact_lines] or NULL */
+    int32_t nact_lines, nact_group;
+    int32_t b_static;           /* Bt counts as a weight: the split arithmetic may keep a pre-split image of it for the call */
+    int32_t epi_plain;
+} casv_debug_job;
+int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr);
 /* Options: "graph" = replay the decode step through a captured hipGraph (1) or launch kernels eagerly (0);
  * "persistent" = greedy decoding through the persistent decoder (all steps in ONE launch, workgroups hand rows to each
  * other through memory: small batches, where a step is too short for a launch per kernel): -1 by batch size (default:
@@ -384,6 +425,7 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * sorted in runs and merged by rank); "encoder_persistent" = 1 if the encoder pass behind the last entry point ran as ONE
  * persistent launch and was not redone per step, else 0 (0 also where the entry point reused an encoding it found);
  * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
+ * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
  * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
  * give-up on this handle so far. */

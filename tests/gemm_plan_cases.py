@@ -1077,3 +1077,550 @@ EXPECTED = {
         '=> split=1 shares=8 nonempty=8 floats=8404992',
     ],
 }
+
+# ---- tests/test_gpu_lstm_gemm.py: every case of tests/lstm_gemm_cases.py under every option setting it runs with (the lines equal
+# lstm_gemm_cases.plan_line: tests/test_lstm_gemm_cases.py), and what the planner refuses: side outputs as 256x256 tiles ----
+for _line in '''\
+G lstm_a_bias_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_bias_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_bias_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_bias_split1_step2 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_bias_split2_image_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1
+G lstm_a_bias_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_nobias_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_nobias_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_nobias_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_nobias_split1_step2 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_a_nobias_split2_image_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1
+G lstm_a_nobias_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_b_step_plus_tile0_step3 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_plus_tile1_step3 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_plus_tile2_step3 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_plus_split1_step3 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_plus_split2_image_step3 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1 bstatic=1
+G lstm_b_step_plus_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_minus_tile0_step3 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_minus_tile1_step3 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_minus_tile2_step3 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_minus_split1_step3 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_b_step_minus_split2_image_step3 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1 bstatic=1
+G lstm_b_step_minus_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=3 crows=1
+G lstm_c_skip_first_tile0_step0 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_c_skip_first_tile0_step1 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1
+G lstm_c_skip_first_tile1_step0 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_c_skip_first_tile1_step1 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1
+G lstm_c_skip_first_tile2_step0 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_c_skip_first_tile2_step1 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1
+G lstm_c_skip_first_split1_step0 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_c_skip_first_split1_step1 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1
+G lstm_c_skip_first_split2_image_step0 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1 bstatic=1
+G lstm_c_skip_first_split2_image_step1 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1 bstatic=1
+G lstm_c_skip_first_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_c_skip_first_split2_staging_step1 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=2 step=1 crows=1
+G lstm_c_first_base_tile0_step0 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_c_first_base_tile0_step1 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1
+G lstm_c_first_base_tile1_step0 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_c_first_base_tile1_step1 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1
+G lstm_c_first_base_tile2_step0 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_c_first_base_tile2_step1 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1
+G lstm_c_first_base_split1_step0 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_c_first_base_split1_step1 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1
+G lstm_c_first_base_split2_image_step0 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1 bstatic=1
+G lstm_c_first_base_split2_image_step1 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1 bstatic=1
+G lstm_c_first_base_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_c_first_base_split2_staging_step1 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=2 skip=0 step=1 crows=1
+G lstm_d_two_jobs_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_two_jobs_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_two_jobs_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_two_jobs_split1_step2 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_two_jobs_split2_image_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1
+G lstm_d_two_jobs_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_plain_rider_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1
+G lstm_d_plain_rider_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1
+G lstm_d_plain_rider_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1
+G lstm_d_plain_rider_split1_step2 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1
+G lstm_d_plain_rider_split2_image_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 bstatic=1
+G lstm_d_plain_rider_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1
+G lstm_d_four_jobs_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_four_jobs_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_four_jobs_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_four_jobs_split1_step2 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_d_four_jobs_split2_image_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 bstatic=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 bstatic=1
+G lstm_d_four_jobs_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=130 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 ; M=200 N=96 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=2 epiplain=1 ; M=44 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1
+G lstm_e_straddle_dead_tile0_step2 epi=1 tile=0 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_dead_tile1_step2 epi=1 tile=1 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_dead_tile2_step2 epi=1 tile=2 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_dead_split1_step2 epi=1 tile=-1 arith=1 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_dead_split2_image_step2 epi=1 tile=-1 arith=2 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48 bstatic=1
+G lstm_e_straddle_dead_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_live_tile0_step2 epi=1 tile=0 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_live_tile1_step2 epi=1 tile=1 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_live_tile2_step2 epi=1 tile=2 arith=0 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_live_split1_step2 epi=1 tile=-1 arith=1 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_straddle_live_split2_image_step2 epi=1 tile=-1 arith=2 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48 bstatic=1
+G lstm_e_straddle_live_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=384 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=48
+G lstm_e_finished_lines_tile0_step2 epi=1 tile=0 arith=0 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256
+G lstm_e_finished_lines_tile1_step2 epi=1 tile=1 arith=0 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256
+G lstm_e_finished_lines_tile2_step2 epi=1 tile=2 arith=0 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256
+G lstm_e_finished_lines_split1_step2 epi=1 tile=-1 arith=1 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256
+G lstm_e_finished_lines_split2_image_step2 epi=1 tile=-1 arith=2 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256 bstatic=1
+G lstm_e_finished_lines_split2_staging_step2 epi=1 tile=-1 arith=2 ; M=1024 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 nact=256
+G lstm_f_side_outputs_tile0_step2 epi=1 tile=0 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 zinit=1 gates=1 out2=1
+G lstm_f_side_outputs_tile1_step2 epi=1 tile=1 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 zinit=1 gates=1 out2=1
+G lstm_f_side_outputs_tile2_step2 epi=1 tile=2 arith=0 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 zinit=1 gates=1 out2=1
+G lstm_p_plain_launch_tile0_step2 epi=0 tile=0 arith=0 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2
+G lstm_p_plain_launch_tile1_step2 epi=0 tile=1 arith=0 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2
+G lstm_p_plain_launch_tile2_step2 epi=0 tile=2 arith=0 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2
+G lstm_p_plain_launch_split1_step2 epi=0 tile=-1 arith=1 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2
+G lstm_p_plain_launch_split2_image_step2 epi=0 tile=-1 arith=2 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 bstatic=1
+G lstm_p_plain_launch_split2_staging_step2 epi=0 tile=-1 arith=2 ; M=300 N=200 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2
+G lstm_s_8448_split1_step0 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_s_8448_split1_step3 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1
+G lstm_s_8448_split2_image_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 bstatic=1
+G lstm_s_8448_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 bstatic=1
+G lstm_s_8448_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_s_8448_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1
+G lstm_s_8492_split1_step0 epi=1 tile=-1 arith=1 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_s_8492_split1_step3 epi=1 tile=-1 arith=1 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1
+G lstm_s_8492_split2_image_step0 epi=1 tile=-1 arith=2 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 bstatic=1
+G lstm_s_8492_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 bstatic=1
+G lstm_s_8492_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1
+G lstm_s_8492_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8492 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1
+G lstm_s_8192_lines_of_8_split1_step0 epi=1 tile=-1 arith=1 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8
+G lstm_s_8192_lines_of_8_split1_step3 epi=1 tile=-1 arith=1 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8
+G lstm_s_8192_lines_of_8_split2_image_step0 epi=1 tile=-1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8 bstatic=1
+G lstm_s_8192_lines_of_8_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8 bstatic=1
+G lstm_s_8192_lines_of_8_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8
+G lstm_s_8192_lines_of_8_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8
+G lstm_s_8448_lines_of_8_split1_step0 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8
+G lstm_s_8448_lines_of_8_split1_step3 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8
+G lstm_s_8448_lines_of_8_split2_image_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8 bstatic=1
+G lstm_s_8448_lines_of_8_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8 bstatic=1
+G lstm_s_8448_lines_of_8_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=0 crows=1 nact=8
+G lstm_s_8448_lines_of_8_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 nact=8
+G lstm_s_first_base_split1_step0 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_s_first_base_split1_step3 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=3 crows=1
+G lstm_s_first_base_split2_image_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=0 crows=1 bstatic=1
+G lstm_s_first_base_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=3 crows=1 bstatic=1
+G lstm_s_first_base_split2_staging_step0 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=0 crows=1
+G lstm_s_first_base_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=2 skip=0 step=3 crows=1
+G lstm_s_step_split1_step3 epi=1 tile=-1 arith=1 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=0 step=3 crows=1 ; M=8192 N=1024 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=3 epiplain=1
+G lstm_s_step_split2_image_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=0 step=3 crows=1 bstatic=1 ; M=8192 N=1024 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=3 epiplain=1 bstatic=1
+G lstm_s_step_split2_staging_step3 epi=1 tile=-1 arith=2 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=0 step=3 crows=1 ; M=8192 N=1024 segs=64 koffs=16 lds=96 Ktot=96 rows=1 first=0 skip=0 step=3 epiplain=1
+G lstm_s_8448_split2_image_ncu304 epi=1 tile=-1 arith=2 ncu=304 ; M=8448 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 Ktot=160 rows=3 first=0 skip=2 step=3 crows=1 bstatic=1
+G lstm_f_side_outputs_split1 epi=1 tile=-1 arith=1 ; M=300 N=256 segs=32,64,32 koffs=96,32,0 lds=64,96,64 Ktot=128 rows=3 first=0 skip=0 step=2 crows=1 zinit=1 gates=1 out2=1
+G lstm_chip_filling_split2 epi=1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 rows=3 crows=1 bstatic=1
+G lstm_side_outputs_chip_filling_split2 epi=1 arith=2 ; M=8192 N=2048 segs=64,64,32 koffs=96,32,0 lds=96,96,64 rows=3 crows=1 bstatic=1 zinit=1 gates=1 out2=1
+'''.splitlines():
+    CASES.append((_line.split()[1], _line))
+
+EXPECTED.update({
+    'lstm_a_bias_tile0_step2': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_bias_tile1_step2': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_bias_tile2_step2': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_bias_split1_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_bias_split2_image_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_bias_split2_staging_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_tile0_step2': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_tile1_step2': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_tile2_step2': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_split1_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_split2_image_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_a_nobias_split2_staging_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_tile0_step3': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_tile1_step3': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_tile2_step3': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_split1_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_split2_image_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_plus_split2_staging_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_tile0_step3': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_tile1_step3': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_tile2_step3': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_split1_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_split2_image_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_b_step_minus_split2_staging_step3': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile0_step0': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile0_step1': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile1_step0': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile1_step1': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile2_step0': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_tile2_step1': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split1_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split1_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split2_image_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split2_image_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split2_staging_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_skip_first_split2_staging_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile0_step0': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile0_step1': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile1_step0': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile1_step1': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile2_step0': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_tile2_step1': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split1_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split1_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split2_image_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split2_image_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split2_staging_step0': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_c_first_base_split2_staging_step1': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_tile0_step2': [
+        'L g128 epi=1 grid=6,2,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_tile1_step2': [
+        'L k32 epi=1 grid=20,2,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_tile2_step2': [
+        'L k64 epi=1 grid=10,2,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_split1_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_split2_image_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_two_jobs_split2_staging_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_tile0_step2': [
+        'L g128 epi=1 grid=6,2,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_tile1_step2': [
+        'L k32 epi=1 grid=20,2,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_tile2_step2': [
+        'L k64 epi=1 grid=10,2,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_split1_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_split2_image_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_plain_rider_split2_staging_step2': [
+        'L s128 epi=1 grid=6,2,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_tile0_step2': [
+        'L g128 epi=1 grid=6,4,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_tile1_step2': [
+        'L k32 epi=1 grid=20,4,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_tile2_step2': [
+        'L k64 epi=1 grid=10,4,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_split1_step2': [
+        'L s128 epi=1 grid=6,4,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_split2_image_step2': [
+        'L s128 epi=1 grid=6,4,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_d_four_jobs_split2_staging_step2': [
+        'L s128 epi=1 grid=6,4,1 block=256 lds=77824 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=130 N=256 ks=0 xcd=0 ep=0 a0=20100000000/20800000000/0 a1=20200000000/20900000000/0 a2=20300000000/0/0 c=20400000000/20500000000/0 o=21000000000 co=21100000000 z=0 go=0 o2=0 na=0 | M=200 N=96 ks=0 xcd=0 ep=1 a0=30100000000/30800000000/0 c=0/0/0 o=31000000000 co=0 z=0 go=0 o2=0 na=0 | M=44 N=256 ks=0 xcd=0 ep=0 a0=40100000000/40800000000/0 a1=40200000000/40900000000/0 a2=40300000000/0/0 c=40400000000/40500000000/0 o=41000000000 co=41100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_e_straddle_dead_tile0_step2': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_dead_tile1_step2': [
+        'L k32 epi=1 grid=24,1,1 block=256 lds=0 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_dead_tile2_step2': [
+        'L k64 epi=1 grid=12,1,1 block=256 lds=0 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_dead_split1_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_dead_split2_image_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_dead_split2_staging_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_tile0_step2': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_tile1_step2': [
+        'L k32 epi=1 grid=24,1,1 block=256 lds=0 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_tile2_step2': [
+        'L k64 epi=1 grid=12,1,1 block=256 lds=0 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_split1_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_split2_image_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_straddle_live_split2_staging_step2': [
+        'L s128 epi=1 grid=6,1,1 block=256 lds=77824 img=0/0 | M=384 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_tile0_step2': [
+        'L g128 epi=1 grid=16,1,1 block=256 lds=69632 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_tile1_step2': [
+        'L k32 epi=1 grid=64,1,1 block=256 lds=0 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_tile2_step2': [
+        'L k64 epi=1 grid=32,1,1 block=256 lds=0 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_split1_step2': [
+        'L s128 epi=1 grid=16,1,1 block=256 lds=77824 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_split2_image_step2': [
+        'L s128 epi=1 grid=16,1,1 block=256 lds=77824 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_e_finished_lines_split2_staging_step2': [
+        'L s128 epi=1 grid=16,1,1 block=256 lds=77824 img=0/0 | M=1024 N=256 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_f_side_outputs_tile0_step2': [
+        'L g128 epi=1 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=11200000000 go=11300000000 o2=11400000000 na=0',
+    ],
+    'lstm_f_side_outputs_tile1_step2': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=11200000000 go=11300000000 o2=11400000000 na=0',
+    ],
+    'lstm_f_side_outputs_tile2_step2': [
+        'L k64 epi=1 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=11200000000 go=11300000000 o2=11400000000 na=0',
+    ],
+    'lstm_p_plain_launch_tile0_step2': [
+        'L g128 epi=0 grid=6,1,1 block=256 lds=69632 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_p_plain_launch_tile1_step2': [
+        'L k32 epi=0 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_p_plain_launch_tile2_step2': [
+        'L k64 epi=0 grid=10,1,1 block=256 lds=0 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_p_plain_launch_split1_step2': [
+        'L s128 epi=0 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_p_plain_launch_split2_image_step2': [
+        'L s128 epi=0 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_p_plain_launch_split2_staging_step2': [
+        'L s128 epi=0 grid=6,1,1 block=256 lds=77824 img=0/0 | M=300 N=200 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=0/0/0 o=11000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split1_step0': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split1_step3': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split2_image_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split2_image_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split2_staging_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split2_staging_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split1_step0': [
+        'L s128 epi=1 grid=1072,1,1 block=256 lds=77824 img=0/0 | M=8492 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split1_step3': [
+        'L s128 epi=1 grid=1072,1,1 block=256 lds=77824 img=0/0 | M=8492 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split2_image_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=48,1,1 block=256 lds=77824 img=0/0 | M=300 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split2_image_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=48,1,1 block=256 lds=77824 img=0/0 | M=300 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split2_staging_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=48,1,1 block=256 lds=77824 img=0/0 | M=300 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8492_split2_staging_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=48,1,1 block=256 lds=77824 img=0/0 | M=300 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8192_lines_of_8_split1_step0': [
+        'L s128 epi=1 grid=1024,1,1 block=256 lds=77824 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8192_lines_of_8_split1_step3': [
+        'L s128 epi=1 grid=1024,1,1 block=256 lds=77824 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8192_lines_of_8_split2_image_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8192_lines_of_8_split2_image_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8192_lines_of_8_split2_staging_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8192_lines_of_8_split2_staging_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8448_lines_of_8_split1_step0': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8448_lines_of_8_split1_step3': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+    ],
+    'lstm_s_8448_lines_of_8_split2_image_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=11500001000',
+    ],
+    'lstm_s_8448_lines_of_8_split2_image_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=11500001000',
+    ],
+    'lstm_s_8448_lines_of_8_split2_staging_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=11500001000',
+    ],
+    'lstm_s_8448_lines_of_8_split2_staging_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=11500000000',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=11500001000',
+    ],
+    'lstm_s_first_base_split1_step0': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_first_base_split1_step3': [
+        'L s128 epi=1 grid=1056,1,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_first_base_split2_image_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/10d00300000 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_first_base_split2_image_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/10d00300000 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_first_base_split2_staging_step0': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/10d00300000 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_first_base_split2_staging_step3': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/10d00000000 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/10d00300000 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_step_split1_step3': [
+        'L s128 epi=1 grid=1056,2,1 block=256 lds=77824 img=0/0 | M=8448 N=2048 ks=0 xcd=2 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=8192 N=1024 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_step_split2_image_step3': [
+        'L s256 epi=1 grid=256,2,1 block=512 lds=163840 img=1/2 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=8192 N=1024 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_step_split2_staging_step3': [
+        'L s256 epi=1 grid=256,2,1 block=512 lds=163840 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0 | M=8192 N=1024 ks=0 xcd=0 ep=1 a0=20100000000/20800000000/0 c=0/0/0 o=21000000000 co=0 z=0 go=0 o2=0 na=0',
+        'L s128 epi=1 grid=32,1,1 block=256 lds=77824 img=0/0 | M=256 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800008000/0 a1=10200000000/10900008000/0 a2=10300200000/0/0 c=10400000000/10500008000/0 o=11001000000 co=11101000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_s_8448_split2_image_ncu304': [
+        'L s256 epi=1 grid=264,1,1 block=512 lds=163840 img=1/1 | M=8448 N=2048 ks=0 xcd=1 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_f_side_outputs_split1': [
+        'L k32 epi=1 grid=20,1,1 block=256 lds=0 img=0/0 | M=300 N=256 ks=0 xcd=0 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=11200000000 go=11300000000 o2=11400000000 na=0',
+    ],
+    'lstm_chip_filling_split2': [
+        'L s256 epi=1 grid=256,1,1 block=512 lds=163840 img=1/1 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=0 go=0 o2=0 na=0',
+    ],
+    'lstm_side_outputs_chip_filling_split2': [
+        'L s128 epi=1 grid=1024,1,1 block=256 lds=77824 img=0/0 | M=8192 N=2048 ks=0 xcd=4 ep=0 a0=10100000000/10800000000/0 a1=10200000000/10900000000/0 a2=10300000000/0/0 c=10400000000/10500000000/0 o=11000000000 co=11100000000 z=11200000000 go=11300000000 o2=11400000000 na=0',
+    ],
+})

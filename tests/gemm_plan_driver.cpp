@@ -19,7 +19,8 @@ using namespace casv;
 // ---- cases ----
 typedef std::map<std::string, long long> Keys;
 static long long key(const Keys& k, const char* name, long long otherwise) { auto it = k.find(name); return it == k.end() ? otherwise : it->second; }
-static Keys parse_keys(const std::string& text, std::vector<int>* segs) {
+// (segs=, koffs=, lds=: comma-separated lists, one entry per K segment; koffs / lds default to ascending offsets and ld = width)
+static Keys parse_keys(const std::string& text, std::vector<int>* segs, std::vector<int>* koffs = nullptr, std::vector<int>* lds = nullptr) {
     Keys k;
     std::istringstream in(text);
     std::string tok;
@@ -27,18 +28,19 @@ static Keys parse_keys(const std::string& text, std::vector<int>* segs) {
         const size_t eq = tok.find('=');
         if (eq == std::string::npos) { fprintf(stderr, "bad token %s\n", tok.c_str()); exit(2); }
         const std::string name = tok.substr(0, eq), val = tok.substr(eq + 1);
-        if (name == "segs" && segs) {
+        std::vector<int>* list = name == "segs" ? segs : name == "koffs" ? koffs : name == "lds" ? lds : nullptr;
+        if (list) {
             std::istringstream vs(val);
             std::string w;
-            while (std::getline(vs, w, ',')) segs->push_back(atoi(w.c_str()));
+            while (std::getline(vs, w, ',')) list->push_back(atoi(w.c_str()));
         } else k[name] = atoll(val.c_str());
     }
     return k;
 }
 template <class T> static T* fake(int job, int slot) { return reinterpret_cast<T*>(((unsigned long long)(job + 1) << 40) + ((unsigned long long)slot << 32)); }
 static GemmArgs make_job(int epi, int j, const std::string& text) {
-    std::vector<int> segs;
-    const Keys k = parse_keys(text, &segs);
+    std::vector<int> segs, koffs, lds;
+    const Keys k = parse_keys(text, &segs, &koffs, &lds);
     GemmArgs g{};
     g.M = (int)key(k, "M", 0); g.N = (int)key(k, "N", 0);
     if (segs.empty()) segs.push_back((int)key(k, "K", 0));
@@ -50,9 +52,10 @@ static GemmArgs make_job(int epi, int j, const std::string& text) {
         if (key(k, "rows", 0) >> i & 1) s.rows = fake<const int>(j, 8 + i);
         if (key(k, "first", 0) >> i & 1) s.first_base = fake<const float>(j, 12 + i);
         s.skip_first = key(k, "skip", 0) >> i & 1;
-        s.width = segs[i]; s.ld = (int)key(k, "ld", segs[i]); s.koff = koff;
-        koff += segs[i];
+        s.width = segs[i]; s.ld = i < (int)lds.size() ? lds[i] : (int)key(k, "ld", segs[i]); s.koff = i < (int)koffs.size() ? koffs[i] : koff;
+        koff = s.koff + segs[i];
     }
+    if (!koffs.empty()) { koff = 0; for (int i = 0; i < g.nseg; ++i) koff = std::max(koff, g.a[i].koff + g.a[i].width); }
     g.Ktot = (int)key(k, "Ktot", koff);
     g.Bt = fake<const float>(j, 22); g.bias = fake<const float>(j, 23);
     const bool lstm = epi == EPI_LSTM && !key(k, "epiplain", 0);

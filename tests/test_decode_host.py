@@ -68,7 +68,7 @@ def test_what_moved_and_what_stayed():
     for entry in ('casv_decode_greedy', 'casv_decode_beam', 'casv_get_alignments_sparse', 'casv_decoder_step', 'casv_decoder_step_lm'):
         assert 'extern "C" int %s(' % entry in decode and entry + '(' not in engine
     for entry in ('casv_model_create', 'casv_model_destroy', 'casv_commit_weights', 'casv_records_append', 'casv_get_stat',
-                  'casv_profile', 'casv_debug_gemm', 'casv_set_option', 'casv_synchronize'):
+                  'casv_profile', 'casv_debug_gemm', 'casv_debug_gemm_jobs', 'casv_set_option', 'casv_synchronize'):
         assert 'extern "C" int %s(' % entry in engine or 'extern "C" void %s(' % entry in engine
     assert 'm->Vp = (cfg->voc_size + 31) & ~31;' in engine
     with open(os.path.join(CSRC, 'Makefile')) as f:
