@@ -178,7 +178,7 @@ static GemmArgs lm_projection_of(const casv_model* m, const GemmArgs& proj) {
     return g;
 }
 
-// What every launch of the attention rows shares -- the per-step launch below and the persistent decoder (persist_plan) must agree
+// What every launch of the attention rows shares -- the per-step launch below and the persistent decoder (persist_args) must agree
 // on it for the two forms to give the same bits: encoder side, alignment and window stores, shapes; one row per line in row order.
 // The per-step fields (query, parents, lines, context, step, live rows) are the caller's.
 static AttnArgs attention_args(const casv_model* m) {
@@ -376,32 +376,28 @@ struct StepRunner {
 // All S greedy steps in ONE launch of the persistent decoder (persist.hip): small batches, where the per-step kernels are
 // bound by launch and memory latency.  Same results bit for bit (tested), same state / alignment / window stores.
 
-// widest contraction of any task of the launch: its staged activation rows hold that many floats (+ 4 of padding, PersistArgs::lda)
-static int persist_kmax(const casv_model* m) {
-    int kmax = m->W;
-    for (int n = 1; n <= m->D; ++n) kmax = std::max(kmax, m->dec[n].kin + m->W);
-    return kmax;
+// Whether a greedy decode over B lines is the persistent launch, and that launch's figures: persist_plan.h on this model's shape, the
+// device's CUs and the workgroups per CU the runtime admits for the kernel with these staged rows (not asked where the option or the
+// arithmetic rule the launch out anyway).  The last plan stays readable (statistics "decoder_persist_*").
+static PersistDecPlan plan_decode(casv_model* m, int B) {
+    const PersistDecShape s{m->D, m->W, m->Vp, m->C};
+    const int arithmetic = arithmetic_of(m, ENTRY_CHAIN);
+    const int per_cu = m->persist_mode == 0 || arithmetic ? 0 : persist_decode_blocks_per_cu(persist_dec_lds_bytes(s));
+    const PersistDecPlan plan = plan_persist_decode(s, B, m->ncu, per_cu, m->persist_mode, arithmetic);
+    m->stat_dec_plan[0] = plan.per_cu; m->stat_dec_plan[1] = plan.g_lstm; m->stat_dec_plan[2] = plan.g_att; m->stat_dec_plan[3] = plan.g_plain;
+    return plan;
 }
-static bool persist_applies(const casv_model* m, int B) {
-    if (m->persist_mode == 0) return false;
-    if (arithmetic_of(m, ENTRY_CHAIN)) return false;   // (the persistent kernels are fp32-input kernels: not mixed with split launches)
-    if (m->ncu < 64 || m->D > 8) return false;
-    // (the launch's own figure: persist_lds_bytes is 16 * lda * sizeof(float), and persist_plan sets lda = persist_kmax + 4)
-    const size_t lds = (size_t)16 * (persist_kmax(m) + 4) * 4;
-    const int per_cu = persist_decode_blocks_per_cu(lds);
-    if (per_cu < 1) return false;                                  // the staged rows must fit the LDS
-    if (m->persist_mode == 1) return B <= 4096;
-    // by size: the persistent kernel wins while a workgroup owns at most two tiles per layer (measured: depth 2, width 512: 64
-    // lines 9.3 vs 20.9 ms, 256 lines 32.5 vs 21.4 ms; depth 2, width 256: 512 lines 11.4 vs 14.7 ms)
-    const int g_lstm = std::max(1, m->ncu * per_cu * 4 / 8), ntile = ((B + 15) / 16) * (m->W / 16);
-    return B <= 512 && (ntile + g_lstm - 1) / g_lstm <= 2;
+// Whether this call is the persistent launch: its plan applies and no back-off is pending (which this question uses one call of).
+static bool persist_applies(casv_model* m, int B, PersistDecPlan& plan) {
+    plan = plan_decode(m, B);
+    return plan.applies && !persist_backed_off(m->persist_backoff);
 }
-static int persist_does_not_fit(const casv_model* m) {
-    return fail(CASV_ERR_ARG, "persistent decoder: rows of %d floats do not fit the LDS", persist_kmax(m));
+static int persist_does_not_fit(const PersistDecPlan& plan) {
+    return fail(CASV_ERR_ARG, "persistent decoder: rows of %d floats do not fit the LDS", plan.kmax);
 }
 
-// The launch's arguments, and its workgroups split over the three roles.
-static int persist_plan(const casv_model* m, int mode, int S, PersistArgs& pa) {
+// The launch's arguments; its workgroups split over the three roles as planned.
+static void persist_args(const casv_model* m, const PersistDecPlan& plan, int mode, int S, PersistArgs& pa) {
     const int W = m->W, Vp = m->Vp, C = m->C, T = m->T, D = m->D, R = m->R;
     pa.R = R; pa.D = D; pa.W = W; pa.V = m->V; pa.Vp = Vp; pa.C = C; pa.T = T; pa.S = S; pa.mode = mode;
     for (int n = 1; n <= D; ++n) {
@@ -414,19 +410,8 @@ static int persist_plan(const casv_model* m, int mode, int S, PersistArgs& pa) {
     pa.att = attention_args(m);
     pa.out_idx = m->o_idx.as<int>(); pa.out_prob = m->o_prob.as<float>(); pa.nan_flag = m->d_nan.as<int>();
     pa.counters = m->p_counters.as<unsigned>();
-    const int nrb = (R + 15) / 16, nug = W / 16;
-    const int nq4 = (W / 16 + 3) / 4, nl4 = (Vp / 16 + 3) / 4;
-    pa.lda = persist_kmax(m) + 4;
-    // Every workgroup must be resident at once (they wait for each other): as many per CU as the runtime's occupancy query
-    // admits for this kernel with these staged rows (at most two).  The roles share the slots 4 : 1 : 2 (tiles, attention, plain).
-    const int per_cu = persist_decode_blocks_per_cu(persist_lds_bytes(pa));
-    if (per_cu < 1) return persist_does_not_fit(m);
-    const int wgslots = m->ncu * per_cu;
-    pa.g_lstm = std::min(nrb * nug, wgslots * 4 / 8);
-    pa.g_plain = std::min(nrb * (nq4 + nl4), std::max(wgslots * 2 / 8, 4));
-    // (attention: one workgroup per four rows where the slots the other roles leave allow it -- a wave then keeps its row, persist.hip)
-    pa.g_att = std::min(nrb * 4, std::max(std::max(wgslots / 8, 4), wgslots - pa.g_lstm - pa.g_plain));
-    return 0;
+    pa.lda = plan.lda;
+    pa.g_lstm = plan.g_lstm; pa.g_plain = plan.g_plain; pa.g_att = plan.g_att;
 }
 
 #ifdef CASV_PERSIST_PROF
@@ -462,15 +447,15 @@ static int persist_prof_dump(casv_model* m, const PersistArgs& pa) {
 }
 #endif
 
-static int decode_greedy_persistent(casv_model* m, int mode, int S) {
+static int decode_greedy_persistent(casv_model* m, const PersistDecPlan& plan, int mode, int S) {
     std::lock_guard<std::mutex> lock(g_persist_mutex);
     const int W = m->W, Vp = m->Vp, C = m->C, T = m->T, D = m->D, R = m->R;
     const size_t slots = (size_t)(S + 1) * R;
-    const BufPlan plan[] = {{&m->p_ctx, slots * C * 4}, {&m->p_wq, slots * W * 4}, {&m->p_logits, slots * Vp * 4}};
-    if (int rc = ensure_all(plan)) return rc;
-    if (m->p_counters.cap < persist_counter_bytes(R, D)) return fail(CASV_ERR_STATE, "hand-off counters not set up");      // (cleared by the caller's set-up launch)
+    const BufPlan bufs[] = {{&m->p_ctx, slots * C * 4}, {&m->p_wq, slots * W * 4}, {&m->p_logits, slots * Vp * 4}};
+    if (int rc = ensure_all(bufs)) return rc;
+    if (m->p_counters.cap < plan.counter_bytes) return fail(CASV_ERR_STATE, "hand-off counters not set up");      // (cleared by the caller's set-up launch)
     PersistArgs pa{};
-    if (int rc = persist_plan(m, mode, S, pa)) return rc;
+    persist_args(m, plan, mode, S, pa);
 #ifdef CASV_PERSIST_PROF
     if (int rc = g_persist_profbuf.ensure((32 + 2048) * 8)) return rc;
     HIPCHK(hipMemsetAsync(g_persist_profbuf.p, 0, (32 + 2048) * 8, m->stream));
@@ -486,7 +471,7 @@ static int decode_greedy_persistent(casv_model* m, int mode, int S) {
         m->prof_begin(PC_PERSIST, fl * S, by * S, pev);
     }
     persist_order_before(m->device, m->stream);
-    if (launch_persist_decode(pa, m->stream)) return persist_does_not_fit(m);
+    if (launch_persist_decode(pa, m->stream)) return persist_does_not_fit(plan);
     persist_order_after(m->device, m->stream);
     m->prof_end(PC_PERSIST, pev);
     HIPCHK(hipGetLastError());
@@ -495,7 +480,7 @@ static int decode_greedy_persistent(casv_model* m, int mode, int S) {
 #endif
     // the launch's give-up word, set aside beside the encoder's (the caller brings both to the host with the results)
     SmallOps ops{};
-    ops.rows(reinterpret_cast<const float*>(persist_give_up_word(m->p_counters.as<unsigned>(), persist_counter_bytes(R, D))), 1, m->d_flags.as<float>() + 1, 1, 1, 1, 1);
+    ops.rows(reinterpret_cast<const float*>(persist_give_up_word(m->p_counters.as<unsigned>(), plan.counter_bytes)), 1, m->d_flags.as<float>() + 1, 1, 1, 1, 1);
     if (!launch_small_ops(ops, m->stream)) return too_many_ops();
     return 0;
 }
@@ -508,6 +493,7 @@ struct GreedyCall {
     size_t nres;                    // bytes of one result array [B][S]
     bool staged;                    // results come back through the pinned staging buffer (very large ones go straight to the caller's arrays)
     unsigned* pin_flags;            // pinned: [0] the encoder's give-up word, [1] the decoder's
+    PersistDecPlan plan;            // the persistent launch of the call, if it has one
 };
 
 // results and flags come back through a pinned staging buffer: three queued copies, ONE wait for the device
@@ -530,7 +516,7 @@ static int greedy_begin(casv_model* m, const GreedyCall& c, bool with_counters) 
     ops.fill(m->o_idx.p, c.nres); ops.fill(m->o_prob.p, c.nres);
     ops.fill(m->d_flags.as<unsigned>() + 1, 4);
     if (with_counters) {
-        const size_t cbytes = persist_counter_bytes(m->B, m->D);
+        const size_t cbytes = c.plan.counter_bytes;
         if (int rc = m->p_counters.ensure(cbytes)) return rc;
         ops.fill(m->p_counters.p, cbytes);
     }
@@ -541,7 +527,7 @@ static int greedy_begin(casv_model* m, const GreedyCall& c, bool with_counters) 
 // decoder (`persistent` is then off for the next attempt) or of the encoder, which has been redone per step.
 static int greedy_attempt(casv_model* m, const GreedyCall& c, bool& persistent, bool& again) {
     if (persistent) {
-        if (int rc = decode_greedy_persistent(m, c.mode, c.S)) return rc;
+        if (int rc = decode_greedy_persistent(m, c.plan, c.mode, c.S)) return rc;
     } else {
         char key[96];
         snprintf(key, sizeof key, "greedy/%d/%d/%d/%d/%d", c.mode, m->B, m->T, c.S, m->eos);
@@ -565,7 +551,7 @@ static int greedy_attempt(casv_model* m, const GreedyCall& c, bool& persistent, 
     const int redone = settle_encoder(m, &flags[0]);
     if (redone < 0) return redone;
     const bool dec_aborted = persistent && flags[1] != 0;
-    if (dec_aborted) { persist_note_abort(m->persist_backoff, "decoder"); persistent = false; }
+    if (dec_aborted) { persist_note_abort(m->persist_backoff, "decoder"); ++m->stat_decode_give_ups; persistent = false; }     // (statistic "decode_give_ups"; the encoder's: settle_encoder)
     // the back-off is reset only by an attempt in which NO persistent launch gave up (an encoder that keeps losing residency
     // must not restart its penalty at 16 because the decoder behind it happened to run through)
     if (!redone && !dec_aborted && (persistent || enc_was_persistent)) m->persist_backoff.penalty = 0;
@@ -610,7 +596,8 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
     const BufPlan plan[] = {{&m->o_idx, c.nres}, {&m->o_prob, c.nres}, {&m->d_flags, 64}};
     if (int rc = ensure_all(plan)) return rc;
     if (int rc = greedy_staging(m, c)) return rc;
-    bool persistent = persist_applies(m, B) && !persist_backed_off(m->persist_backoff);
+    m->stat_dec_persistent = 0;
+    bool persistent = persist_applies(m, B, c.plan);
     for (int attempt = 0; ; ++attempt) {
         bool again = false;
         if (int rc = greedy_begin(m, c, persistent)) return rc;
@@ -618,6 +605,7 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
         if (!again) break;
         if (attempt >= 2) return fail(CASV_ERR_STATE, "persistent launches keep giving up");
     }
+    m->stat_dec_persistent = persistent ? 1 : 0;       // (statistic "decoder_persistent": a launch that gave up has switched it off)
     if (c.staged) { memcpy(out_idx, m->pin_out, c.nres); memcpy(out_prob, m->pin_out + c.nres, c.nres); }
     const bool nan_before_end = greedy_lengths(m, c, out_len);
     if (out_align) {   // store_a slot s+1 row b -> (b, s, :)

@@ -6,39 +6,18 @@
 // ---- the persistent forms: the whole recurrence as ONE launch (same values bit for bit as the per-step launches) ----
 // persist.hip on the fp32-input chain (tiles of 16 rows x 16 units, weights packed for it, staged rows of `lda` floats in LDS);
 // persist_split.hip in the split arithmetic (tiles of 32 rows x 32 units, the per-step launches' own weights, a fixed LDS size).
-struct PersistEncPlan {
-    enum Form { NONE, CHAIN, SPLIT } form = NONE;
-    int grid = 0;                   // workgroups, all resident at once
-    size_t counter_bytes = 0;       // their hand-off counters
-};
-static int persist_enc_lda(const casv_model* m) { return (m->D >= 2 ? 3 * m->W : 2 * m->W) + 4; }
-// Rows up to which the split-arithmetic persistent encoder is the default form of a pass (option "persistent" = -1): the largest
-// batch of profiles/split_persist_encoder_timing.json at which its median lies below the per-step launches' by more than the
-// spread of the repetitions.
-constexpr int SPLIT_PERSIST_DEFAULT_ROWS = 256;
-// Whether a pass over B lines has a persistent form, and that form's launch -- planned once, for the decision and the launch alike.
-static PersistEncPlan plan_persist_enc(const casv_model* m, int B) {
-    const PersistEncPlan none{};
-    if (m->persist_mode == 0 || m->ncu < 64 || m->D > 8) return none;
-    if (m->cfg.residual_connections && m->D >= 3) return none;   // (the layers' sums of seq2seq.py:284-291 have no persistent form)
-    if (m->cfg.deep_bidirectional_encoder && m->D >= 2) return none;
-    const int W = m->W, D = m->D;
+// Whether a pass over B lines has a persistent form, and that form's launch -- planned once, for the decision and the launch alike:
+// persist_plan.h on this model's shape, the device's CUs and the workgroups per CU the runtime admits for the form's kernel (not
+// asked where the option rules the launch out anyway).  The last plan stays readable (statistics "encoder_persist_*").
+static PersistEncPlan plan_persist_enc(casv_model* m, int B) {
+    const PersistEncShape s{m->D, m->W, m->cfg.residual_connections != 0, m->cfg.deep_bidirectional_encoder != 0};
     const bool split = m->enc_arith > 0;
-    const int side = split ? 32 : 16;
-    const int per_cu = split ? persist_split_encode_blocks_per_cu()
-                             : persist_encode_blocks_per_cu((size_t)16 * persist_enc_lda(m) * 4);      // 0: the staged rows do not fit the LDS
-    if (per_cu < 1) return none;
-    const int ntile = ((B + side - 1) / side) * (W / side), grid = std::min(std::max(2, D - 1) * ntile, per_cu * m->ncu);
-    // tiles per workgroup in the launch's two phases (layer 1's two directions; the layers above)
-    const int own1 = (2 * ntile + grid - 1) / grid, ownn = ((D - 1) * ntile + grid - 1) / grid;
-    const int maxt = split ? persist_split_enc_max_tiles() : persist_enc_max_tiles();
-    if (own1 > maxt || ownn > maxt) return none;
-    const bool pays = m->persist_mode == 1 ? B <= 4096
-                    : split ? B <= SPLIT_PERSIST_DEFAULT_ROWS
-                            : B <= 512 && own1 <= 2 && ownn <= 2;
-    if (!pays) return none;
-    return {split ? PersistEncPlan::SPLIT : PersistEncPlan::CHAIN, grid,
-            split ? persist_split_enc_counter_bytes(B, D) : persist_enc_counter_bytes(B, D)};
+    const int per_cu = m->persist_mode == 0 ? 0
+                     : split ? persist_split_encode_blocks_per_cu()
+                             : persist_encode_blocks_per_cu(persist_enc_lds_bytes(s));      // 0: the staged rows do not fit the LDS
+    const PersistEncPlan plan = plan_persist_encode(s, B, m->ncu, per_cu, m->persist_mode, split);
+    m->stat_enc_plan[0] = plan.per_cu; m->stat_enc_plan[1] = plan.form == PersistEncPlan::NONE ? 0 : plan.grid;
+    return plan;
 }
 
 template <class Args>
@@ -63,7 +42,7 @@ static int launch_persist_enc(casv_model* m, const PersistEncPlan& plan, float* 
     HIPCHK(hipMemsetAsync(m->p_enc_counters.p, 0, plan.counter_bytes, m->stream));
     PersistEncArgs pc{}; PersistSplitEncArgs ps{};
     if (split) { fill_persist_enc_args(m, false, lout, ps); ps.inject = m->persist_fault_split ? 1 : 0; }
-    else { fill_persist_enc_args(m, true, lout, pc); pc.lda = persist_enc_lda(m); }
+    else { fill_persist_enc_args(m, true, lout, pc); pc.lda = persist_enc_lda(PersistEncShape{D, W, false, false}); }
 #ifdef CASV_PERSIST_PROF
     static DevBuf eprof;
     if (!split) {
@@ -306,6 +285,7 @@ int settle_encoder(casv_model* m, const unsigned* flag) {
     m->enc_check_pending = false;
     if (!aborted) { if (!flag) m->persist_backoff.penalty = 0; return 0; }      // (with `flag` the caller has a second launch to account for before the back-off is reset)
     persist_note_abort(m->persist_backoff, "encoder");
+    ++m->stat_decode_give_ups;          // (statistic "decode_give_ups")
     if (int rc = run_encoder(m, false)) return rc;      // (also takes the statistic "encoder_persistent" back)
     return 1;
 }

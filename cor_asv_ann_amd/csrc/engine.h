@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 #include "persist_host.h"
+#include "persist_plan.h"
 #include "../../include/cor_asv_ann_hip.h"
 
 #include <cstdio>
@@ -161,6 +162,10 @@ struct casv_model {
     int* pin_active = nullptr; hipEvent_t ev_active[2] = {nullptr, nullptr};   // beam decode: unfinished-line count, read one chunk behind
     int stat_beam[3] = {0, 0, 0};                         // last beam decode: most new hypotheses of one line in one step; rows stepped
     int stat_enc_persistent = 0;                          // the encoder pass behind the last entry point ran as ONE persistent launch and was not redone
+    int stat_dec_persistent = 0;                          // the last casv_decode_greedy delivered the results of the persistent launch (one that gave up: 0)
+    long long stat_decode_give_ups = 0;                   // persistent launches of the decode path (encoder passes, greedy decoder) that gave up on this handle so far
+    int stat_dec_plan[4] = {0, 0, 0, 0};                  // last plan of the persistent decoder (decode.hip, plan_decode): workgroups per CU, g_lstm, g_att, g_plain
+    int stat_enc_plan[2] = {0, 0};                        // last plan of a persistent encoder pass (encoder.hip, plan_persist_enc): workgroups per CU, grid (0: no form)
     int stat_train_launches = 0; long long stat_train_give_ups = 0;   // train step: persistent launches of the last step that was not redone; steps redone after a give-up (train.hip)
     int stat_jobs[2] = {0, 0};                            // last casv_debug_gemm_jobs: bit f = a launch of GemmForm f ran, launches of the plan
     int stat_tn[3] = {0, 0, 0};                           // last casv_debug_contract_tn: split kernel (0/1), K shares launched, shares holding k-tiles

@@ -324,6 +324,14 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "beam_sort_capacity")) { *value = 4096; return CASV_OK; }
     if (!strcmp(key, "cus")) { *value = m->ncu; return CASV_OK; }
     if (!strcmp(key, "encoder_persistent")) { *value = m->stat_enc_persistent; return CASV_OK; }
+    if (!strcmp(key, "decoder_persistent")) { *value = m->stat_dec_persistent; return CASV_OK; }
+    if (!strcmp(key, "decode_give_ups")) { *value = m->stat_decode_give_ups; return CASV_OK; }
+    if (!strcmp(key, "decoder_persist_per_cu")) { *value = m->stat_dec_plan[0]; return CASV_OK; }
+    if (!strcmp(key, "decoder_persist_g_lstm")) { *value = m->stat_dec_plan[1]; return CASV_OK; }
+    if (!strcmp(key, "decoder_persist_g_att")) { *value = m->stat_dec_plan[2]; return CASV_OK; }
+    if (!strcmp(key, "decoder_persist_g_plain")) { *value = m->stat_dec_plan[3]; return CASV_OK; }
+    if (!strcmp(key, "encoder_persist_per_cu")) { *value = m->stat_enc_plan[0]; return CASV_OK; }
+    if (!strcmp(key, "encoder_persist_grid")) { *value = m->stat_enc_plan[1]; return CASV_OK; }
     if (!strcmp(key, "train_persistent_launches")) { *value = m->stat_train_launches; return CASV_OK; }
     if (!strcmp(key, "train_give_ups")) { *value = m->stat_train_give_ups; return CASV_OK; }
     if (!strcmp(key, "gemm_jobs_forms")) { *value = m->stat_jobs[0]; return CASV_OK; }

@@ -424,6 +424,13 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
  * sorted in runs and merged by rank); "encoder_persistent" = 1 if the encoder pass behind the last entry point ran as ONE
  * persistent launch and was not redone per step, else 0 (0 also where the entry point reused an encoding it found);
+ * "decoder_persistent" = 1 if the last casv_decode_greedy delivered the results of its ONE persistent launch (csrc/persist.hip),
+ * 0 if it stepped kernel by kernel -- by the option, the shape, the back-off, or because the launch gave up and the decode was
+ * redone; "decode_give_ups" = persistent launches of the decode path (encoder passes and greedy decoders) that gave up on this
+ * handle so far; the figures of the last plan (csrc/persist_plan.h) -- "decoder_persist_per_cu" = workgroups per CU the runtime
+ * admits for the persistent decoder at this model's staged rows, "decoder_persist_g_lstm" / "_g_att" / "_g_plain" = workgroups
+ * per role (all 0 where the option, the arithmetic, the device or the depth rule the launch out), "encoder_persist_per_cu" and
+ * "encoder_persist_grid" = the same figure and the workgroups of the last encoder pass that was planned (grid 0: no form);
  * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
  * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its

@@ -1,5 +1,5 @@
 """The search's encoder pass in the split arithmetic, per-step launches against the persistent launch (csrc/persist_split.hip):
-where does the persistent form win?  The row limit of the option "persistent" = -1 (encoder.hip, SPLIT_PERSIST_DEFAULT_ROWS) is
+where does the persistent form win?  The row limit of the option "persistent" = -1 (persist_plan.h, PERSIST_SPLIT_DEFAULT_ROWS) is
 read off this table.
 
 For depth 2 / width 512 / V 640 and depth 4 / width 512 / V 256, lines of 100 positions, B in {8, 40, 64, 128, 256, 512}: wall

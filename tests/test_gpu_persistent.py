@@ -39,6 +39,7 @@ def test_persistent_equals_per_step_kernels_bit_for_bit(d, W, V, B, L, es):
         eng.set_option('persistent', persistent)
         eng.encode(idx)
         encs[persistent] = eng.encoder_outputs()
+        assert eng.stat('encoder_persistent') == persistent, 'the form the option asks for is the form that ran'
     assert np.array_equal(encs[0][0], encs[1][0]), 'encoder outputs'
     for a, b in zip(encs[0][1], encs[1][1]):
         assert np.array_equal(a, b), 'encoder final states'
@@ -51,6 +52,8 @@ def test_persistent_equals_per_step_kernels_bit_for_bit(d, W, V, B, L, es):
                 out[persistent] = eng.decode_greedy(mode=mode, want_align=True)
             except NativeError as err:
                 out[persistent] = err.code
+            # (a launch that gave up falls back to the per-step kernels silently: the comparison would be per-step against per-step)
+            assert (eng.stat('encoder_persistent'), eng.stat('decoder_persistent')) == (persistent, persistent), (mode, persistent)
         eng.set_option('persistent', -1)
         if isinstance(out[0], int) or isinstance(out[1], int):
             assert out[0] == out[1], (mode, out[0] if isinstance(out[0], int) else 'ok', out[1] if isinstance(out[1], int) else 'ok')
@@ -63,6 +66,7 @@ def test_persistent_equals_per_step_kernels_bit_for_bit(d, W, V, B, L, es):
                     assert np.array_equal(a[j, :n], b[j, :n], equal_nan=True), (mode, name, j)
             else:
                 assert np.array_equal(a, b, equal_nan=True), (mode, name)
+    assert eng.stat('decode_give_ups') == 0
     eng.close()
 
 
