@@ -19,7 +19,7 @@
 //   6 backward_cell    tied projection, attention cell, the cell's and the attention's parameters
 //   7 backward_layers  decoder / encoder pairs downwards, embedding                    -- give-up check
 //   8 update           regulariser, norm, clipped Adam, results
-// persist_slot is the one place that decides whether a recurrence goes persistent; persist_launched the one that counts it.
+// train_plan.h decides and counts the persistent launches of a step; persist_launch is the one place that asks it and launches.
 // casv_score_targets (teacher-forced log-probabilities of given targets) makes the same two attempts (score_attempt): phases 1-4 as
 // they are, then the projection and the scoring head in place of the loss -- give-up check; on a forward-only state outside a session.
 // casv_score_candidates is the same call with N targets per source: the encoder side of the forward phases works on the Be sources,
@@ -44,8 +44,6 @@ struct TLayer {
 };
 
 }  // namespace
-
-constexpr int REC_LAUNCH_CAP = 16;         // persistent launches of one train step: the slots of rec_cnt, the words of rec_abort
 
 struct TrainState {
     casv_adam_params ap{};
@@ -74,8 +72,8 @@ struct TrainState {
     int tn_ws_rc = 0;                      // the ordered contractions' workspace could not be had this step (its error, reported by the step)
     DevBuf tn_ws, sum_parts, seg_enc_off, seg_enc_pos, seg_dec_off, seg_dec_pos;
     std::vector<int> h_seg_enc_off, h_seg_enc_pos, h_seg_dec_off, h_seg_dec_pos;
-    DevBuf rec_cnt; int rec_launches = 0, rec_checked = 0, rec_skip = 0, rec_penalty = 0;   // persistent recurrences: counters per launch, back-off
-    const unsigned* rec_abort[REC_LAUNCH_CAP] = {nullptr};    // ... and where each launch leaves its "gave up" word
+    DevBuf rec_cnt; TrainStepPlan plan; int rec_checked = 0, rec_skip = 0, rec_penalty = 0;   // persistent recurrences: counters per launch, the step's launches, back-off
+    const unsigned* rec_abort[TRAIN_LAUNCH_CAP] = {nullptr};    // ... and where each launch leaves its "gave up" word
     // The attention cell's backward recurrence as TWO launches side by side (train_persist_topb.hip, split_a): the second stream and
     // the events that tie it into the step; split_off: a step gave up with the two launches in flight -- one launch from then on.
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool split_off = false; int split_launch = -1;
@@ -91,25 +89,62 @@ struct TrainState {
     float* G_(int i) { return tens[i].g.as<float>(); }
 };
 
-// The one place that decides whether a recurrence of the step goes persistent: the hand-off counters of the step's next persistent
-// launch, or nullptr -- the option is off, the step is deterministic, the back-off holds (rec_skip), the step has had its
-// REC_LAUNCH_CAP launches or the device is too small.  (The caller still asks its own kind's *_grid whether the shape has a form.)
-// Every launch takes one slot of rec_cnt, and the slots are of one size whatever the kind of launch: the largest of the four
-// kinds' counters (the backward recurrence's: 16 per 32-row block against 12, 3 and 2).  The give-up word sits inside the
-// slot at the END OF THE KIND'S OWN counters (persist_host.h), which is why persist_launched takes that kind's size.
-static size_t persist_slot_bytes(int B) {
-    return std::max(std::max(train_recurrence_counter_bytes(B), train_recurrence_bwd_counter_bytes(B)),
-                    std::max(train_attention_cell_counter_bytes(B), train_attention_cell_bwd_counter_bytes(B)));
-}
-static unsigned* persist_slot(casv_model* m, TrainState* ts) {
-    if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < REC_LAUNCH_CAP && m->ncu >= 64) {
-        return reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + persist_slot_bytes(ts->B) * ts->rec_launches);
+// CASV_ATTN_DEFER and CASV_TOPB_SPLIT, read once, as train_plan.h takes them.
+// CASV_ATTN_DEFER: d_enc / du summed behind the cell's backward recurrence instead of by float atomics inside it (attn_bwd.h,
+// DEFER; the recurrence has forms 0, 1 and 3 only).  CASV_TOPB_SPLIT: the attention backward of the samples as a launch of its own on
+// a second stream, resident beside the big one: it then runs under the h tiles instead of behind them (CASV_TOPB_SPLIT=0: one launch).
+// Two launches that hand rows to each other must be resident TOGETHER: where the runtime serialises kernel dispatch
+// (rocprofv3 --pmc sets ROCPROF_COUNTERS; AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING) the side launch would never see
+// the main one's counters -- one launch there, said once on stderr (profiles taken that way describe that form).
+static TrainSwitches read_train_switches() {
+    TrainSwitches sw{1, true};
+    if (const char* e = getenv("CASV_ATTN_DEFER")) { const int v = atoi(e); sw.defer = v == 3 ? 3 : v == 0 ? 0 : 1; }
+    const char* e = getenv("CASV_TOPB_SPLIT");
+    if (e && e[0] == '0') { sw.split = false; return sw; }
+    auto on = [](const char* name) { const char* v = getenv(name); return v && v[0] && !(v[0] == '0' && !v[1]); };
+    const char* why = getenv("ROCPROF_COUNTERS") ? "ROCPROF_COUNTERS (counter collection)" : on("AMD_SERIALIZE_KERNEL") ? "AMD_SERIALIZE_KERNEL" :
+                      on("HIP_LAUNCH_BLOCKING") ? "HIP_LAUNCH_BLOCKING" : nullptr;
+    if (why && !(e && e[0] == '1')) {       // (CASV_TOPB_SPLIT=1 insists)
+        fprintf(stderr, "cor_asv_ann_hip: kernel dispatch is serialised (%s): the attention cell's backward runs as ONE launch "
+                        "(the two-launch form needs both resident together)\n", why);
+        sw.split = false;
     }
-    return nullptr;
+    return sw;
 }
-// ... and the launch into that slot has been issued: where it leaves its "gave up" word, for recurrences_gave_up
-static void persist_launched(TrainState* ts, unsigned* slot, size_t counter_bytes) {
-    ts->rec_abort[ts->rec_launches++] = persist_give_up_word(slot, counter_bytes);
+
+// The one place that asks train_plan.h whether a site of the step goes persistent, and launches it if so.  It hands the plan what
+// only the device and the environment know -- the residency figure of the kind's kernel, and for the cell's backward the switches
+// and whether its two launches fit a CU -- where the step's gate is open at all; `launch(plan, counters)` fills the kernel's
+// arguments and issues it (0 or an error) inside the PC_PERSIST bracket; the launch's give-up word is noted for recurrences_gave_up.
+// *persistent: the site ran this way -- else the caller takes its per-step form.
+static TrainSite persist_site(TrainKind kind, const TrainShape& shape, bool plain = true, int T = 0) {
+    return TrainSite{kind, shape, 0, plain, T, TrainSwitches{0, false}, false, false};
+}
+template <class Launch>
+static int persist_launch(casv_model* m, TrainSite site, double flops, bool* persistent, Launch&& launch) {
+    TrainState* ts = m->train;
+    *persistent = false;
+    const TrainGate gate{m->persist_mode, m->deterministic, ts->rec_skip != 0, m->ncu};
+    if (train_gate_open(gate) && site.plain) {
+        const int W = site.shape.W;
+        site.per_cu = site.kind == TRAIN_REC ? train_recurrence_blocks_per_cu(W) : site.kind == TRAIN_REC_BWD ? train_recurrence_bwd_blocks_per_cu(W)
+                    : site.kind == TRAIN_CELL ? train_attention_cell_blocks_per_cu(W) : train_attention_cell_bwd_blocks_per_cu(W);
+        if (site.kind == TRAIN_CELL_BWD) {
+            static const TrainSwitches sw = read_train_switches();
+            site.sw = sw; site.split_off = ts->split_off;
+            site.rows_fit = train_attention_cell_bwd_rows_fit(W);
+        }
+    }
+    const TrainLaunch plan = ts->plan.next(gate, site);
+    if (!plan.persistent) return 0;
+    unsigned* counters = reinterpret_cast<unsigned*>(static_cast<char*>(ts->rec_cnt.p) + plan.slot_offset);
+    hipEvent_t ev{};
+    m->prof_begin(PC_PERSIST, flops, 0.0, ev);
+    if (int rc = launch(plan, counters)) return rc;
+    m->prof_end(PC_PERSIST, ev);
+    ts->rec_abort[plan.slot] = persist_give_up_word(counters, plan.counter_bytes);
+    *persistent = true;
+    return 0;
 }
 
 static int gate_row(int W, int u, int g) { return (u / 32) * 128 + g * 32 + (u % 32); }
@@ -460,30 +495,20 @@ static int layers_backward(casv_model* m, const LayerBwd* a, int count) {
         else HIPCHK(hipMemsetAsync(a[j].dc, 0, (size_t)B * W * 4, m->stream));
         maxlen = std::max(maxlen, a[j].l->len);
     }
-    bool persistent = false;
-    if (unsigned* slot = persist_slot(m, ts)) {
-        RecBwdArgs ra{};
-        ra.njobs = count; ra.B = B; ra.W = W;
-        bool plain = true;
-        for (int j = 0; j < count; ++j) {
-            TLayer& l = *a[j].l;
-            plain = plain && l.kr == W;
-            ra.job[j] = RecBwdJob{l.wrT.as<float>(), a[j].dOut, a[j].ld_out, a[j].mask, a[j].dh_fin, a[j].dc_fin, l.Gt.as<float>(), l.Cs.as<float>(), a[j].c0,
-                                  l.Z.as<float>(), l.dRec.as<float>(), a[j].dc, l.len, l.reverse ? 1 : 0};
-        }
-        ra.counters = slot;
-        const int grid = plain ? train_recurrence_bwd_grid(ra, m->ncu) : 0;
-        if (grid) {
-            hipEvent_t ev{};
-            double flops = 0;
-            for (int j = 0; j < count; ++j) flops += 2.0 * B * 4.0 * W * W * a[j].l->len;
-            m->prof_begin(PC_PERSIST, flops, 0.0, ev);
-            launch_train_recurrence_bwd(ra, grid, m->stream);
-            m->prof_end(PC_PERSIST, ev);
-            persist_launched(ts, slot, train_recurrence_bwd_counter_bytes(B));
-            persistent = true;
-        }
-    }
+    bool persistent = false, plain = true;
+    double flops = 0;
+    for (int j = 0; j < count; ++j) { plain = plain && a[j].l->kr == W; flops += 2.0 * B * 4.0 * W * W * a[j].l->len; }
+    if (int rc = persist_launch(m, persist_site(TRAIN_REC_BWD, {W, m->C, B, maxlen, count}, plain), flops, &persistent, [&](const TrainLaunch& plan, unsigned* counters) {
+            RecBwdArgs ra{};
+            ra.njobs = count; ra.B = B; ra.W = W; ra.counters = counters;
+            for (int j = 0; j < count; ++j) {
+                TLayer& l = *a[j].l;
+                ra.job[j] = RecBwdJob{l.wrT.as<float>(), a[j].dOut, a[j].ld_out, a[j].mask, a[j].dh_fin, a[j].dc_fin, l.Gt.as<float>(), l.Cs.as<float>(), a[j].c0,
+                                      l.Z.as<float>(), l.dRec.as<float>(), a[j].dc, l.len, l.reverse ? 1 : 0};
+            }
+            launch_train_recurrence_bwd(ra, plan.grid, m->stream);
+            return 0;
+        })) return rc;
     if (persistent) {
     } else if (m->fused_backward && !m->deterministic) {
         // one launch per step for both layers: the cells' backward inside the data GEMM (gemm_bwd.hip); dL/dc ping-pongs
@@ -541,30 +566,26 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
     TrainState* ts = m->train;
     const int W = m->W, B = ts->B;
     int maxlen = 0;
-    for (int j = 0; j < count; ++j) maxlen = std::max(maxlen, a[j].l->len);
-    if (unsigned* slot = persist_slot(m, ts)) {
-        RecArgs ra{};
-        ra.njobs = count; ra.B = B; ra.W = W;
-        for (int j = 0; j < count; ++j) {
-            TLayer& l = *a[j].l;
-            ra.job[j] = RecJob{ts->W_(l.iwr), l.Z.as<float>(), l.hs, l.hs_ld, l.Cs.as<float>(), l.Gt.as<float>(), a[j].h0, a[j].c0, l.len,
-                               l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr,        // (a scoring state has no dRec: nullptr, nothing to clear)
-                               l.rows == B ? 0 : l.rows};                           // (the encoder's job of a candidates call: Be < B rows)
-        }
-        ra.counters = slot;
-        ra.fault = m->persist_mode == 2;       // (test of the give-up path)
-        if (const int grid = train_recurrence_grid(ra, m->ncu)) {
-            hipEvent_t ev{};
-            double flops = 0;
-            for (int j = 0; j < count; ++j) flops += 2.0 * a[j].l->rows * 4.0 * W * W * a[j].l->len;
-            m->prof_begin(PC_PERSIST, flops, 0.0, ev);
-            launch_train_recurrence(ra, grid, m->stream);
-            m->prof_end(PC_PERSIST, ev);
-            persist_launched(ts, slot, train_recurrence_counter_bytes(B));
-            if (masked) *masked = true;
-            for (int j = 0; j < count; ++j) a[j].l->drec_cleared = a[j].l->kr == W;
+    double flops = 0;
+    for (int j = 0; j < count; ++j) { maxlen = std::max(maxlen, a[j].l->len); flops += 2.0 * a[j].l->rows * 4.0 * W * W * a[j].l->len; }
+    bool persistent = false;
+    if (int rc = persist_launch(m, persist_site(TRAIN_REC, {W, m->C, B, maxlen, count}), flops, &persistent, [&](const TrainLaunch& plan, unsigned* counters) {
+            RecArgs ra{};
+            ra.njobs = count; ra.B = B; ra.W = W; ra.counters = counters;
+            ra.fault = m->persist_mode == 2;       // (test of the give-up path)
+            for (int j = 0; j < count; ++j) {
+                TLayer& l = *a[j].l;
+                ra.job[j] = RecJob{ts->W_(l.iwr), l.Z.as<float>(), l.hs, l.hs_ld, l.Cs.as<float>(), l.Gt.as<float>(), a[j].h0, a[j].c0, l.len,
+                                   l.reverse ? 1 : 0, masked ? a[j].om : nullptr, a[j].om_ld, a[j].omask, l.kr == W ? l.dRec.as<float>() : nullptr,        // (a scoring state has no dRec: nullptr, nothing to clear)
+                                   l.rows == B ? 0 : l.rows};                           // (the encoder's job of a candidates call: Be < B rows)
+                l.drec_cleared = l.kr == W;
+            }
+            launch_train_recurrence(ra, plan.grid, m->stream);
             return 0;
-        }
+        })) return rc;
+    if (persistent) {
+        if (masked) *masked = true;
+        return 0;
     }
     for (int k = 0; k < maxlen; ++k) {
         GemmBatch b{};
@@ -644,7 +665,7 @@ static int plan_buffers(Step& s) {
         else if (deep && enc) { l.hs = (&l - 1)->hs + W; l.hs_ld = 2 * W; }        // (a backward direction: the second half of its forward partner's rows)
         else { ENS(l.Hown, rows * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = W; }
     }
-    ENS(ts->rec_cnt, REC_LAUNCH_CAP * persist_slot_bytes(B)) BWD(ts->dcalt, (size_t)2 * B * W * 4)
+    ENS(ts->rec_cnt, TRAIN_LAUNCH_CAP * train_slot_bytes(B)) BWD(ts->dcalt, (size_t)2 * B * W * 4)
     if (s.det) {
         ENS(ts->sum_parts, (size_t)std::max(MULTI_MAX * 64, (W + 63) / 64 + V) * 8)
         ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
@@ -710,8 +731,8 @@ static int stage_inputs(Step& s) {
     s.inv_count = 1.0f / (float)std::max(cnt, 1L);
     HIPCHK(hipMemsetAsync(ts->loss.p, 0, 16, st));
     HIPCHK(hipMemsetAsync(ts->normsq.p, 0, 16, st));
-    HIPCHK(hipMemsetAsync(ts->rec_cnt.p, 0, REC_LAUNCH_CAP * persist_slot_bytes(B), st));
-    ts->rec_launches = ts->rec_checked = 0; ts->split_launch = -1; ts->tn_ws_rc = 0;
+    HIPCHK(hipMemsetAsync(ts->rec_cnt.p, 0, TRAIN_LAUNCH_CAP * train_slot_bytes(B), st));
+    ts->plan = TrainStepPlan{}; ts->rec_checked = 0; ts->split_launch = -1; ts->tn_ws_rc = 0;
     for (auto& l : ts->layers) l.drec_cleared = false;
     if (ts->rec_skip > 0) --ts->rec_skip;
     if (s.training) for (auto& t : ts->tens) HIPCHK(hipMemsetAsync(t.g.p, 0, t.n * 4, st));
@@ -858,22 +879,16 @@ static int forward_cell(Step& s) {
     att.apos = nullptr; att.amax1 = nullptr; att.nrows = nullptr;
     att.u_line = W; att.u_time = (long long)s.Be * W; att.enc_line = C; att.enc_time = (long long)s.Be * C;
     bool top_persistent = false;
-    if (unsigned* slot = persist_slot(m, ts)) {
-        // ONE launch for the whole recurrence of the cell (train_persist_top.hip)
-        TopRecArgs ra{};
-        ra.Wr = ts->W_(top.iwr); ra.WaT = ts->W_(ts->iWaT); ra.bUW = ts->W_(ts->ibUW); ra.Z = top.Z.as<float>();
-        ra.RecIn = ts->RecIn.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.hs = top.hs; ra.Cs = top.Cs.as<float>(); ra.Gt = top.Gt.as<float>();
-        ra.c0 = c0t; ra.WIN = ts->WIN.as<int>(); ra.att = att; ra.B = B; ra.U = U; ra.W = W; ra.C = C;
-        ra.counters = slot;
-        if (const int grid = top.hs_ld == W ? train_attention_cell_grid(ra, m->ncu) : 0) {
-            hipEvent_t ev{};
-            m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
-            launch_train_attention_cell(ra, grid, st);
-            m->prof_end(PC_PERSIST, ev);
-            persist_launched(ts, slot, train_attention_cell_counter_bytes(B));
-            top_persistent = true;
-        }
-    }
+    // ONE launch for the whole recurrence of the cell (train_persist_top.hip)
+    if (int rc = persist_launch(m, persist_site(TRAIN_CELL, {W, C, B, U, 1}, top.hs_ld == W), 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W),
+                                &top_persistent, [&](const TrainLaunch& plan, unsigned* counters) {
+            TopRecArgs ra{};
+            ra.Wr = ts->W_(top.iwr); ra.WaT = ts->W_(ts->iWaT); ra.bUW = ts->W_(ts->ibUW); ra.Z = top.Z.as<float>();
+            ra.RecIn = ts->RecIn.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.hs = top.hs; ra.Cs = top.Cs.as<float>(); ra.Gt = top.Gt.as<float>();
+            ra.c0 = c0t; ra.WIN = ts->WIN.as<int>(); ra.att = att; ra.B = B; ra.U = U; ra.W = W; ra.C = C; ra.counters = counters;
+            launch_train_attention_cell(ra, plan.grid, st);
+            return 0;
+        })) return rc;
     if (!top_persistent) HIPCHK(hipMemsetAsync(ts->WQ.p, 0, UB * W * 4, st));      // (the per-step launches' split-K partial sums land here; the persistent kernel stores its queries)
     for (int t = 0; t < U && !top_persistent; ++t) {
         const float* hprev = t == 0 ? h0t : top.hs + (long long)(t - 1) * B * W;
@@ -924,12 +939,12 @@ static int loss_head(Step& s) {
 static int recurrences_gave_up(casv_model* m, bool& any) {
     TrainState* ts = m->train; hipStream_t st = m->stream;
     any = false;
-    if (ts->rec_launches == ts->rec_checked) return 0;
-    unsigned gave_up[REC_LAUNCH_CAP] = {0};
-    for (int i = ts->rec_checked; i < ts->rec_launches; ++i)
+    if (ts->plan.launches == ts->rec_checked) return 0;
+    unsigned gave_up[TRAIN_LAUNCH_CAP] = {0};
+    for (int i = ts->rec_checked; i < ts->plan.launches; ++i)
         HIPCHK(hipMemcpyAsync(&gave_up[i], ts->rec_abort[i], 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int i = ts->rec_checked; i < ts->rec_launches; ++i) {
+    for (int i = ts->rec_checked; i < ts->plan.launches; ++i) {
         any |= gave_up[i] != 0;
         if (gave_up[i] && i == ts->split_launch && !ts->split_off) {        // (the two launches were not resident together: one launch from now on)
             ts->split_off = true;
@@ -937,7 +952,7 @@ static int recurrences_gave_up(casv_model* m, bool& any) {
                             "dispatch, or the GPU is shared): ONE launch from now on\n");
         }
     }
-    ts->rec_checked = ts->rec_launches;
+    ts->rec_checked = ts->plan.launches;
     if (any) {
         ++m->stat_train_give_ups;           // (statistic "train_give_ups": the caller redoes the step)
         ts->rec_penalty = ts->rec_penalty ? std::min(2 * ts->rec_penalty, 1 << 20) : 16;
@@ -948,36 +963,6 @@ static int recurrences_gave_up(casv_model* m, bool& any) {
     return 0;
 }
 
-// CASV_ATTN_DEFER, read once: d_enc / du summed behind the cell's backward recurrence instead of by float atomics inside it
-// (attn_bwd.h, DEFER; the recurrence has forms 0, 1 and 3 only)
-static int attn_defer_option() {
-    static const int opt = [] { const char* e = getenv("CASV_ATTN_DEFER"); const int v = e ? atoi(e) : 1; return v == 3 ? 3 : v == 0 ? 0 : 1; }();
-    return opt;
-}
-
-// CASV_TOPB_SPLIT, read once: the attention backward of the samples as a launch of its own on a second stream, resident beside the
-// big one: it then runs under the h tiles instead of behind them (CASV_TOPB_SPLIT=0: one launch).
-// Two launches that hand rows to each other must be resident TOGETHER: where the runtime serialises kernel dispatch
-// (rocprofv3 --pmc sets ROCPROF_COUNTERS; AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING) the side launch would never see
-// the main one's counters -- one launch there, said once on stderr (profiles taken that way describe that form).
-static bool read_cell_bwd_split_option() {
-    const char* e = getenv("CASV_TOPB_SPLIT");
-    if (e && e[0] == '0') return false;
-    auto on = [](const char* name) { const char* v = getenv(name); return v && v[0] && !(v[0] == '0' && !v[1]); };
-    const char* why = getenv("ROCPROF_COUNTERS") ? "ROCPROF_COUNTERS (counter collection)" : on("AMD_SERIALIZE_KERNEL") ? "AMD_SERIALIZE_KERNEL" :
-                      on("HIP_LAUNCH_BLOCKING") ? "HIP_LAUNCH_BLOCKING" : nullptr;
-    if (why && !(e && e[0] == '1')) {       // (CASV_TOPB_SPLIT=1 insists)
-        fprintf(stderr, "cor_asv_ann_hip: kernel dispatch is serialised (%s): the attention cell's backward runs as ONE launch "
-                        "(the two-launch form needs both resident together)\n", why);
-        return false;
-    }
-    return true;
-}
-static bool cell_bwd_split_option() {
-    static const bool opt = read_cell_bwd_split_option();
-    return opt;
-}
-
 // The cell's backward recurrence as ONE launch (train_persist_topb.hip; two side by side in the split form) where the step may
 // take a persistent launch and the shape has one; *done says whether it did.  dc: dL/dc, cleared; dL/dc0 at the end.
 static int cell_backward_persistent(Step& s, float* dc, bool* done) {
@@ -985,59 +970,48 @@ static int cell_backward_persistent(Step& s, float* dc, bool* done) {
     const int B = s.B, T = s.T, U = s.U, W = s.W, C = s.C;
     const int kr = C + W;
     TLayer& top = s.top();
-    *done = false;
-    unsigned* slot = persist_slot(m, ts);
-    if (!slot) return 0;
-    TopBwdArgs ra{};
-    ra.WrT = top.wrT.as<float>(); ra.WaN = ts->WaN.as<float>(); ra.dG = ts->dG.as<float>();
-    ra.Gt = top.Gt.as<float>(); ra.Cs = top.Cs.as<float>(); ra.c0 = s.dec_c0(s.D); ra.dZ = top.Z.as<float>(); ra.dRec = top.dRec.as<float>();
-    ra.dhatt = ts->dhatt.as<float>(); ra.DWQ = ts->DWQ.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.Ast = ts->Ast.as<float>();
-    ra.WIN = ts->WIN.as<int>(); ra.dc_out = dc; ra.B = B; ra.U = U; ra.W = W; ra.C = C;
-    AttnBwdArgs& ab = ra.ab;
-    ab.mcell = s.mcell; ab.ld_mcell = W + C; ab.mc_off = W; ab.va = ts->W_(ts->iva);
-    ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
-    ab.enc = s.enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
-    ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>();
-    ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
-    ra.counters = slot;
-    const int defer_opt = attn_defer_option();
-    const int defer = (T <= ATTN_DEFER_MAX_T && W % 64 == 0 && C % 64 == 0) ? defer_opt : 0;
-    ra.DS = defer ? ts->DSrows.as<float>() : nullptr; ra.defer = defer;
-    const int grid = train_attention_cell_bwd_grid(ra, m->ncu);
-    if (!grid) return 0;
-    hipEvent_t ev{};
-    m->prof_begin(PC_PERSIST, 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), 0.0, ev);
-    const bool split_opt = cell_bwd_split_option();
-    ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;
-    if (ra.split_a && !ts->side) {          // (no second stream to be had: one launch, as before)
-        if (hipStreamCreateWithFlags(&ts->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ts->side = nullptr; }
-        else if (hipEventCreateWithFlags(&ts->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                 hipEventCreateWithFlags(&ts->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamDestroy(ts->side); ts->side = nullptr;
+    return persist_launch(m, persist_site(TRAIN_CELL_BWD, {W, C, B, U, 1}, true, T), 2.0 * B * U * ((double)4 * W * (C + W) + (double)W * W), done,
+                          [&](const TrainLaunch& plan, unsigned* counters) {
+        TopBwdArgs ra{};
+        ra.WrT = top.wrT.as<float>(); ra.WaN = ts->WaN.as<float>(); ra.dG = ts->dG.as<float>();
+        ra.Gt = top.Gt.as<float>(); ra.Cs = top.Cs.as<float>(); ra.c0 = s.dec_c0(s.D); ra.dZ = top.Z.as<float>(); ra.dRec = top.dRec.as<float>();
+        ra.dhatt = ts->dhatt.as<float>(); ra.DWQ = ts->DWQ.as<float>(); ra.WQ = ts->WQ.as<float>(); ra.Ast = ts->Ast.as<float>();
+        ra.WIN = ts->WIN.as<int>(); ra.dc_out = dc; ra.B = B; ra.U = U; ra.W = W; ra.C = C; ra.counters = counters;
+        AttnBwdArgs& ab = ra.ab;
+        ab.mcell = s.mcell; ab.ld_mcell = W + C; ab.mc_off = W; ab.va = ts->W_(ts->iva);
+        ab.u = ts->u.as<float>(); ab.u_line = W; ab.u_time = (long long)B * W;
+        ab.enc = s.enc_out; ab.enc_line = C; ab.enc_time = (long long)B * C;
+        ab.d_enc = ts->d_enc.as<float>(); ab.du = ts->du.as<float>();
+        ab.dva_part = ts->dvaP.as<float>(); ab.dbv_part = ts->dbvP.as<float>(); ab.B = B; ab.T = T; ab.W = W; ab.C = C;
+        ra.DS = plan.defer ? ts->DSrows.as<float>() : nullptr; ra.defer = plan.defer;
+        ra.split_a = plan.split_a;
+        if (ra.split_a && !ts->side) {          // (no second stream to be had: one launch, as before)
+            if (hipStreamCreateWithFlags(&ts->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ts->side = nullptr; }
+            else if (hipEventCreateWithFlags(&ts->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                     hipEventCreateWithFlags(&ts->ev_join, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipStreamDestroy(ts->side); ts->side = nullptr;
+            }
+            if (!ts->side) { ts->split_off = true; ra.split_a = 0; }
         }
-        if (!ts->side) { ts->split_off = true; ra.split_a = 0; }
-    }
-    if (ra.split_a) {
-        HIPCHK(hipEventRecord(ts->ev_fork, st));
-        HIPCHK(hipStreamWaitEvent(ts->side, ts->ev_fork, 0));
-        launch_train_attention_cell_bwd_rows(ra, grid, ts->side);
-        HIPCHK(hipEventRecord(ts->ev_join, ts->side));
-        ts->split_launch = ts->rec_launches;
-    }
-    launch_train_attention_cell_bwd(ra, grid, st);
-    if (ra.split_a) HIPCHK(hipStreamWaitEvent(st, ts->ev_join, 0));
-    if (defer) {
-        AttnDeferArgs da{};
-        da.dRec = ra.dRec; da.ld_drec = kr; da.mcell = s.mcell; da.ld_mcell = W + C; da.mc_off = W;
-        da.Ast = ra.Ast; da.WIN = ra.WIN; da.DS = ra.DS; da.WQ = ra.WQ; da.va = ab.va; da.u = ab.u;
-        da.d_enc = ab.d_enc; da.du = ab.du; da.B = B; da.U = U; da.T = T; da.W = W; da.C = C; da.what = defer;
-        launch_attention_deferred(da, st);
-    }
-    m->prof_end(PC_PERSIST, ev);
-    persist_launched(ts, slot, train_attention_cell_bwd_counter_bytes(B));
-    *done = true;
-    return 0;
+        if (ra.split_a) {
+            HIPCHK(hipEventRecord(ts->ev_fork, st));
+            HIPCHK(hipStreamWaitEvent(ts->side, ts->ev_fork, 0));
+            launch_train_attention_cell_bwd_rows(ra, plan.grid, ts->side);
+            HIPCHK(hipEventRecord(ts->ev_join, ts->side));
+            ts->split_launch = plan.slot;
+        }
+        launch_train_attention_cell_bwd(ra, plan.grid, st);
+        if (ra.split_a) HIPCHK(hipStreamWaitEvent(st, ts->ev_join, 0));
+        if (plan.defer) {
+            AttnDeferArgs da{};
+            da.dRec = ra.dRec; da.ld_drec = kr; da.mcell = s.mcell; da.ld_mcell = W + C; da.mc_off = W;
+            da.Ast = ra.Ast; da.WIN = ra.WIN; da.DS = ra.DS; da.WQ = ra.WQ; da.va = ab.va; da.u = ab.u;
+            da.d_enc = ab.d_enc; da.du = ab.du; da.B = B; da.U = U; da.T = T; da.W = W; da.C = C; da.what = plan.defer;
+            launch_attention_deferred(da, st);
+        }
+        return 0;
+    });
 }
 
 // ... and as three launches per time step (two with the fused backward step): cell backward + data GEMM, attention backward, query GEMM
@@ -1297,20 +1271,20 @@ static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo)
         HIPCHK(hipMemcpyAsync(loss_out, ts->loss.p, 8, hipMemcpyDeviceToHost, s.st));
         HIPCHK(hipStreamSynchronize(s.st));
         if (norm_out) *norm_out = 0.0;
-        m->stat_train_launches = ts->rec_launches;
+        m->stat_train_launches = ts->plan.launches;
         return CASV_OK;
     }
     if (int rc = backward_cell(s)) return rc;
     if (int rc = backward_layers(s)) return rc;
     if (int rc = recurrences_gave_up(m, *redo)) return rc;
     if (*redo) return CASV_OK;
-    if (ts->rec_launches) ts->rec_penalty = 0;
+    if (ts->plan.launches) ts->rec_penalty = 0;
     if (ts->tn_ws_rc) {                    // (a weight gradient was not computed: no update, the step fails with the allocation's error)
         (void)hipStreamSynchronize(s.st);
         return ts->tn_ws_rc;
     }
     if (int rc = update(s, loss_out, norm_out)) return rc;
-    m->stat_train_launches = ts->rec_launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
+    m->stat_train_launches = ts->plan.launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
     return CASV_OK;
 }
 
@@ -1395,7 +1369,7 @@ static int score_attempt(Step s, const ScoreOut& out, bool* redo) {
         for (int u = 0; u < U; ++u)
             memcpy(out.align + ((size_t)b * U + u) * T, rows.data() + ((size_t)u * B + b) * T, (size_t)T * 4);
     ts->score_B = B; ts->score_U = U; ts->score_T = T;
-    m->stat_train_launches = ts->rec_launches;      // (statistic "train_persistent_launches", as a mode-0 step reports it)
+    m->stat_train_launches = ts->plan.launches;      // (statistic "train_persistent_launches", as a mode-0 step reports it)
     if (m->prof.on) m->prof.collect();
     return CASV_OK;
 }
@@ -1446,7 +1420,7 @@ static int score_call(casv_model* m, int32_t Be, int32_t N, int32_t T, int32_t U
     s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
     s.TB = (long long)T * Be; s.UB = UB;
     // (no masks, no regulariser; det / fused govern the backward pass and the ordered sums of the loss: the head has neither, and
-    // persist_slot and the launchers read the "deterministic" option from the handle)
+    // persist_launch and the launchers read the "deterministic" option from the handle)
     s.training = false; s.det = false; s.fused = false;
     s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
     s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;

@@ -1,6 +1,7 @@
 // Kernels of the train step that are not contractions (train_kernels.hip).
 #pragma once
 #include "common.h"
+#include "train_plan.h"
 #include <algorithm>
 
 namespace casv {
@@ -50,8 +51,9 @@ struct RecJob {
                                      // count; the grid, the counters and the give-up word stay those of B, the row blocks beyond leave at once
 };
 struct RecArgs { RecJob job[2]; int njobs, B, W; unsigned* counters; int fault; };   // fault: test of the give-up path (one workgroup leaves early)
-size_t train_recurrence_counter_bytes(int B);
-int train_recurrence_grid(const RecArgs& ra, int ncu);      // 0: no persistent form for this shape on this device
+// What each of the four persistent kernel files exports: the runtime's workgroups per CU for the width's instantiation, at most
+// train_plan.h's figure for the kind (0: no instantiation, or the query failed), and the launcher of a grid train_plan.h planned.
+int train_recurrence_blocks_per_cu(int W);
 void launch_train_recurrence(const RecArgs& ra, int grid, hipStream_t stream);
 
 // ... and the backward recurrence of up to two plain layers (train_persist_bwd.hip): cell backward + data GEMM of every step.
@@ -66,8 +68,7 @@ struct RecBwdJob {
     int len, reverse;
 };
 struct RecBwdArgs { RecBwdJob job[2]; int njobs, B, W; unsigned* counters; };
-size_t train_recurrence_bwd_counter_bytes(int B);
-int train_recurrence_bwd_grid(const RecBwdArgs& ra, int ncu);
+int train_recurrence_bwd_blocks_per_cu(int W);
 void launch_train_recurrence_bwd(const RecBwdArgs& ra, int grid, hipStream_t stream);
 
 // ... and the attention cell's forward recurrence (train_persist_top.hip): query, attention rows, cell input rows and LSTM step of
@@ -86,8 +87,7 @@ struct TopRecArgs {
     int B, U, W, C;
     unsigned* counters;
 };
-size_t train_attention_cell_counter_bytes(int B);
-int train_attention_cell_grid(const TopRecArgs& ra, int ncu);
+int train_attention_cell_blocks_per_cu(int W);
 void launch_train_attention_cell(const TopRecArgs& ra, int grid, hipStream_t stream);
 
 struct LstmBwdArgs {
@@ -124,8 +124,7 @@ struct AttnBwdArgs {
 };
 void launch_attention_bwd(const AttnBwdArgs& p, hipStream_t st, bool ordered = false);
 // The deferred sums of the persistent attention-cell backward: d_enc += sum_t a_t (x) dctx_t, du += sum_t dpre_t, per sample in LDS
-// (T <= ATTN_DEFER_MAX_T positions).  dctx_t = dRec[t][b][0:C] (row stride ld_drec) x the sample's input mask.
-constexpr int ATTN_DEFER_MAX_T = 288;
+// (T <= ATTN_DEFER_MAX_T positions, train_plan.h).  dctx_t = dRec[t][b][0:C] (row stride ld_drec) x the sample's input mask.
 struct AttnDeferArgs {
     const float* dRec; long long ld_drec;                    // [U][B][ld_drec]
     const float* mcell; long long ld_mcell; int mc_off;
@@ -157,12 +156,11 @@ struct TopBwdArgs {
     unsigned* counters;
     int split_a;                 // part A (the attention backward of the row block's samples) runs as a launch of its own beside this one
 };
-size_t train_attention_cell_bwd_counter_bytes(int B);
-int train_attention_cell_bwd_grid(const TopBwdArgs& ra, int ncu);
+int train_attention_cell_bwd_blocks_per_cu(int W);
 void launch_train_attention_cell_bwd(const TopBwdArgs& ra, int grid, hipStream_t stream);
 // ... part A as its own launch (same grid, same counters), to be resident TOGETHER with the launch above (split_a = 1) on another
 // stream: the two hand rows to each other as the parts of one launch do.  _fits: both fit a CU at once on this device.
-bool train_attention_cell_bwd_rows_fit(const TopBwdArgs& ra);
+bool train_attention_cell_bwd_rows_fit(int W);
 void launch_train_attention_cell_bwd_rows(const TopBwdArgs& ra, int grid, hipStream_t stream);
 
 void launch_axpy(float* y, const float* x, long long n, hipStream_t st);

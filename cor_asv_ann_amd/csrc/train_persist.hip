@@ -207,33 +207,24 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
     }
 }
 
-size_t train_recurrence_counter_bytes(int B) { return persist_counters_bytes((size_t)2 * ((B + RBM - 1) / RBM)); }
+static_assert(RBM == TRAIN_ROW_BLOCK, "train_plan.h plans for this row block");
 
-// Workgroups of the launch if this shape has a persistent form on a device of `ncu` CUs whose every workgroup is resident at
-// once, else 0 (the caller runs the per-step launches).
-template <int NT> static int rec_grid(const RecArgs& ra, int ncu) {
-    const int grid = ra.njobs * ((ra.B + RBM - 1) / RBM) * NT;
-    return grid <= persist_blocks_per_cu(train_recurrence_kernel<NT>, 0, 2) * ncu ? grid : 0;
-}
-#define CASV_REC_WIDTHS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-int train_recurrence_grid(const RecArgs& ra, int ncu) {
-    if (ra.W % 32 || ra.njobs < 1 || ra.njobs > 2 || ra.B < 1) return 0;
-    switch (ra.W / 32) {
-#define CASV_REC_CASE(NT_) case NT_: return rec_grid<NT_>(ra, ncu);
-        CASV_REC_WIDTHS(CASV_REC_CASE)
+// The instantiation of a width, from train_plan.h's list (nullptr: the width has none, and no plan)
+typedef void (*RecKernel)(const RecArgs);
+static RecKernel rec_kernel(int W) {
+    switch (train_width_nt(W)) {
+#define CASV_REC_CASE(NT_) case NT_: return train_recurrence_kernel<NT_>;
+        CASV_TRAIN_REC_WIDTHS(CASV_REC_CASE)
 #undef CASV_REC_CASE
-        default: return 0;          // wider layers: the rows of h no longer fit a thread's registers
+        default: return nullptr;
     }
 }
-
+int train_recurrence_blocks_per_cu(int W) {
+    const RecKernel k = rec_kernel(W);
+    return k ? persist_blocks_per_cu(k, 0, TRAIN_BLOCKS_PER_CU[TRAIN_REC]) : 0;
+}
 void launch_train_recurrence(const RecArgs& ra, int grid, hipStream_t stream) {
-    switch (ra.W / 32) {
-#define CASV_REC_CASE(NT_) case NT_: hipLaunchKernelGGL((train_recurrence_kernel<NT_>), dim3(grid), dim3(256), 0, stream, ra); break;
-        CASV_REC_WIDTHS(CASV_REC_CASE)
-#undef CASV_REC_CASE
-        default: break;
-    }
+    if (const RecKernel k = rec_kernel(ra.W)) hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, ra);
 }
-#undef CASV_REC_WIDTHS
 
 }  // namespace casv

@@ -231,31 +231,24 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_bwd_kernel(const RecB
     if (row_ok) *reinterpret_cast<f32x4*>(job.dc_out + (long long)mrow * W + u0) = dc;
 }
 
-size_t train_recurrence_bwd_counter_bytes(int B) { return persist_counters_bytes((size_t)2 * ((B + QBM - 1) / QBM) * 8); }
+static_assert(QBM == TRAIN_ROW_BLOCK, "train_plan.h plans for this row block");
 
-template <int NT> static int recb_grid(const RecBwdArgs& ra, int ncu) {
-    const int grid = ra.njobs * ((ra.B + QBM - 1) / QBM) * NT;
-    return grid <= persist_blocks_per_cu(train_recurrence_bwd_kernel<NT>, 0, 2) * ncu ? grid : 0;
-}
-// Workgroups of the launch, or 0: no persistent form for this shape on this device (whole column tiles of 128 units only)
-int train_recurrence_bwd_grid(const RecBwdArgs& ra, int ncu) {
-    if (ra.W % 128 || ra.njobs < 1 || ra.njobs > 2 || ra.B < 1) return 0;
-    switch (ra.W / 32) {
-        case 4: return recb_grid<4>(ra, ncu);
-        case 8: return recb_grid<8>(ra, ncu);
-        case 12: return recb_grid<12>(ra, ncu);
-        case 16: return recb_grid<16>(ra, ncu);
-        default: return 0;
+// The instantiation of a width, from train_plan.h's list (nullptr: the width has none, and no plan)
+typedef void (*RecBwdKernel)(const RecBwdArgs);
+static RecBwdKernel recb_kernel(int W) {
+    switch (train_width_nt(W)) {
+#define CASV_RECB_CASE(NT_) case NT_: return train_recurrence_bwd_kernel<NT_>;
+        CASV_TRAIN_REC_BWD_WIDTHS(CASV_RECB_CASE)
+#undef CASV_RECB_CASE
+        default: return nullptr;
     }
+}
+int train_recurrence_bwd_blocks_per_cu(int W) {
+    const RecBwdKernel k = recb_kernel(W);
+    return k ? persist_blocks_per_cu(k, 0, TRAIN_BLOCKS_PER_CU[TRAIN_REC_BWD]) : 0;
 }
 void launch_train_recurrence_bwd(const RecBwdArgs& ra, int grid, hipStream_t stream) {
-    switch (ra.W / 32) {
-        case 4: hipLaunchKernelGGL((train_recurrence_bwd_kernel<4>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 8: hipLaunchKernelGGL((train_recurrence_bwd_kernel<8>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 12: hipLaunchKernelGGL((train_recurrence_bwd_kernel<12>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 16: hipLaunchKernelGGL((train_recurrence_bwd_kernel<16>), dim3(grid), dim3(256), 0, stream, ra); break;
-        default: break;
-    }
+    if (const RecBwdKernel k = recb_kernel(ra.W)) hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, ra);
 }
 
 }  // namespace casv

@@ -362,31 +362,24 @@ __global__ __launch_bounds__(256, 1) void train_attention_cell_kernel(const TopR
 #undef CASV_LOAD_BH
 }
 
-size_t train_attention_cell_counter_bytes(int B) { return persist_counters_bytes((size_t)((B + TBM - 1) / TBM) * 3); }
+static_assert(TBM == TRAIN_ROW_BLOCK, "train_plan.h plans for this row block");
 
-template <int NT> static int top_grid(const TopRecArgs& ra, int ncu) {
-    const int grid = ((ra.B + TBM - 1) / TBM) * NT;
-    // (planned for one workgroup per CU: its two idle waves in part A leave room)
-    return grid <= persist_blocks_per_cu(train_attention_cell_kernel<NT>, 0, 1) * ncu ? grid : 0;
-}
-// Workgroups of the launch, or 0: no persistent form for this shape on this device (context as wide as the layer, i.e. depth >= 2;
-// widths whose unit groups divide the 32 rows of a row block)
-int train_attention_cell_grid(const TopRecArgs& ra, int ncu) {
-    if (ra.W != ra.C || ra.B < 1 || ra.U < 1) return 0;
-    switch (ra.W / 32 * (ra.W % 32 == 0)) {
-        case 4: return top_grid<4>(ra, ncu);
-        case 8: return top_grid<8>(ra, ncu);
-        case 16: return top_grid<16>(ra, ncu);
-        default: return 0;
+// The instantiation of a width, from train_plan.h's list (nullptr: the width has none, and no plan)
+typedef void (*TopKernel)(const TopRecArgs);
+static TopKernel top_kernel(int W) {
+    switch (train_width_nt(W)) {
+#define CASV_TOP_CASE(NT_) case NT_: return train_attention_cell_kernel<NT_>;
+        CASV_TRAIN_CELL_WIDTHS(CASV_TOP_CASE)
+#undef CASV_TOP_CASE
+        default: return nullptr;
     }
+}
+int train_attention_cell_blocks_per_cu(int W) {
+    const TopKernel k = top_kernel(W);
+    return k ? persist_blocks_per_cu(k, 0, TRAIN_BLOCKS_PER_CU[TRAIN_CELL]) : 0;
 }
 void launch_train_attention_cell(const TopRecArgs& ra, int grid, hipStream_t stream) {
-    switch (ra.W / 32) {
-        case 4: hipLaunchKernelGGL((train_attention_cell_kernel<4>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 8: hipLaunchKernelGGL((train_attention_cell_kernel<8>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 16: hipLaunchKernelGGL((train_attention_cell_kernel<16>), dim3(grid), dim3(256), 0, stream, ra); break;
-        default: break;
-    }
+    if (const TopKernel k = top_kernel(ra.W)) hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, ra);
 }
 
 }  // namespace casv

@@ -502,31 +502,7 @@ __global__ __launch_bounds__(256, 3) void train_attention_cell_bwd_rows_kernel(c
     }
 }
 
-size_t train_attention_cell_bwd_counter_bytes(int B) { return persist_counters_bytes((size_t)((B + VBM - 1) / VBM) * 12); }
-
-template <int NT> static int topb_grid(const TopBwdArgs& ra, int ncu) {
-    const int grid = ((ra.B + VBM - 1) / VBM) * NT;
-    return grid <= persist_blocks_per_cu(train_attention_cell_bwd_kernel<NT>, 0, 1) * ncu ? grid : 0;
-}
-// Workgroups of the launch, or 0: no persistent form for this shape on this device (context as wide as the layer; whole column
-// tiles of 128 units; unit groups that divide the 32 rows of a row block)
-int train_attention_cell_bwd_grid(const TopBwdArgs& ra, int ncu) {
-    if (ra.W != ra.C || ra.W % 128 || ra.B < 1 || ra.U < 1 || ra.ab.C > 1024) return 0;
-    switch (ra.W / 32) {
-        case 4: return topb_grid<4>(ra, ncu);
-        case 8: return topb_grid<8>(ra, ncu);
-        case 16: return topb_grid<16>(ra, ncu);
-        default: return 0;
-    }
-}
-void launch_train_attention_cell_bwd(const TopBwdArgs& ra, int grid, hipStream_t stream) {
-    switch (ra.W / 32) {
-        case 4: hipLaunchKernelGGL((train_attention_cell_bwd_kernel<4>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 8: hipLaunchKernelGGL((train_attention_cell_bwd_kernel<8>), dim3(grid), dim3(256), 0, stream, ra); break;
-        case 16: hipLaunchKernelGGL((train_attention_cell_bwd_kernel<16>), dim3(grid), dim3(256), 0, stream, ra); break;
-        default: break;
-    }
-}
+static_assert(VBM == TRAIN_ROW_BLOCK, "train_plan.h plans for this row block");
 
 // Both launches resident at once, a workgroup of each on every CU, in whatever order the hardware takes them from their streams:
 // the big kernel's registers admit one of its workgroups per CU; the small kernel asks for ROWS_LDS_PAD bytes of LDS it never touches,
@@ -549,21 +525,40 @@ template <int NT> static bool topb_rows_fit() {
     }();
     return ok;
 }
-bool train_attention_cell_bwd_rows_fit(const TopBwdArgs& ra) {
-    switch (ra.W / 32) {
-        case 4: return topb_rows_fit<4>();
-        case 8: return topb_rows_fit<8>();
-        case 16: return topb_rows_fit<16>();
-        default: return false;
+
+// The instantiations of a width, from train_plan.h's list (null: the width has none, and no plan): the recurrence; part A as
+// its own launch, with whether the two fit a CU together
+typedef void (*TopBwdKernel)(const TopBwdArgs);
+static TopBwdKernel topb_kernel(int W) {
+    switch (train_width_nt(W)) {
+#define CASV_TOPB_CASE(NT_) case NT_: return train_attention_cell_bwd_kernel<NT_>;
+        CASV_TRAIN_CELL_BWD_WIDTHS(CASV_TOPB_CASE)
+#undef CASV_TOPB_CASE
+        default: return nullptr;
     }
 }
-void launch_train_attention_cell_bwd_rows(const TopBwdArgs& ra, int grid, hipStream_t stream) {
-    switch (ra.W / 32) {
-        case 4: hipLaunchKernelGGL((train_attention_cell_bwd_rows_kernel<4>), dim3(grid), dim3(256), ROWS_LDS_PAD, stream, ra); break;
-        case 8: hipLaunchKernelGGL((train_attention_cell_bwd_rows_kernel<8>), dim3(grid), dim3(256), ROWS_LDS_PAD, stream, ra); break;
-        case 16: hipLaunchKernelGGL((train_attention_cell_bwd_rows_kernel<16>), dim3(grid), dim3(256), ROWS_LDS_PAD, stream, ra); break;
-        default: break;
+struct TopBwdRows { TopBwdKernel kernel; bool (*fit)(); };
+static TopBwdRows topb_rows(int W) {
+    switch (train_width_nt(W)) {
+#define CASV_TOPB_ROWS_CASE(NT_) case NT_: return {train_attention_cell_bwd_rows_kernel<NT_>, topb_rows_fit<NT_>};
+        CASV_TRAIN_CELL_BWD_WIDTHS(CASV_TOPB_ROWS_CASE)
+#undef CASV_TOPB_ROWS_CASE
+        default: return {nullptr, nullptr};
     }
+}
+int train_attention_cell_bwd_blocks_per_cu(int W) {
+    const TopBwdKernel k = topb_kernel(W);
+    return k ? persist_blocks_per_cu(k, 0, TRAIN_BLOCKS_PER_CU[TRAIN_CELL_BWD]) : 0;
+}
+void launch_train_attention_cell_bwd(const TopBwdArgs& ra, int grid, hipStream_t stream) {
+    if (const TopBwdKernel k = topb_kernel(ra.W)) hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, stream, ra);
+}
+bool train_attention_cell_bwd_rows_fit(int W) {
+    const TopBwdRows r = topb_rows(W);
+    return r.fit && r.fit();
+}
+void launch_train_attention_cell_bwd_rows(const TopBwdArgs& ra, int grid, hipStream_t stream) {
+    if (const TopBwdKernel k = topb_rows(ra.W).kernel) hipLaunchKernelGGL(k, dim3(grid), dim3(256), ROWS_LDS_PAD, stream, ra);
 }
 
 }  // namespace casv

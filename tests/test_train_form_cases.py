@@ -1,8 +1,34 @@
 """Without a GPU: the case table of tests/train_form_cases.py reaches every instantiation the train step's dispatchers name, its
-restated form decision (train_form) uses the constants and conditions the .hip sources hold, the noise bounds would see a
-persistent kernel that gets a row-block edge or a job's last step wrong, and no case measures against a degenerate noise unit."""
+restated form decision (train_form) is what csrc/train_plan.h decides, the noise bounds would see a persistent kernel that gets a
+row-block edge or a job's last step wrong, and no case measures against a degenerate noise unit.
+
+The plan is held by behaviour: a stand-alone driver (tests/train_plan_driver.cpp: train_plan.h and the standard library, built
+with the host compiler, -Wall -Werror, and once more under the address and undefined-behaviour sanitizers) plans what train_form
+plans, and every record must be equal.  Which means holds which fact of the form:
+  row block 32, workgroups per CU 2 / 2 / 1 / 1, counters 2 / 16 / 3 / 12, cap 16 as one constant, 64 CUs, T <= 288
+        the driver's constants (test_the_constants_and_the_widths_with_a_form); their effect, by the records of every case on six
+        CU counts and six residency figures (test_the_plan_equals_the_restatement_...: grids, counter bytes, the capped sites of
+        depth 8, nothing below 64 CUs); the kernel files' own row blocks by their static_assert against the header's
+  the four shape conditions and their labels
+        the sweep of test_the_constants_and_the_widths_with_a_form: which NT have a form per kind, beside multiples of 32, at W != C,
+        C = 1056, no rows, no steps, 0 and 3 jobs -- equal to train_form_cases.grid and NT
+  the same labels in the grid and in the launcher
+        there is one list per kind (the driver prints it); that every instantiation comes from it is structure:
+        test_the_plan_is_pure_and_the_sources_only_run_it, and tests/test_gpu_train_forms.py runs every one of them
+  one deciding place and one counting place, used by exactly four sites
+        the plan counts (the records' slots and the step's count); that train.hip asks it in one function, called by the four
+        sites and by nothing else, and never counts itself is structure (same test)
+  one slot size, the maximum, for addresses, allocation and clear
+        the records' offsets and slot_bytes (equal to the largest kind's counters); that allocation and clear use the same function
+        is structure (same test)
+  the cell's, the backward's and the split's own conditions, the defer rule
+        test_the_site_conditions_each_decide: each flag off, T = 288 / 289, W = 96, CASV_ATTN_DEFER 0 / 1 / 3
+  the gate (option, deterministic, back-off)
+        every case under each of them (test_the_plan_equals_the_restatement_...)."""
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -89,72 +115,198 @@ def test_every_case_has_ragged_sources_and_targets_where_its_shape_allows():
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. the restatement
-def test_restated_constants_and_conditions_are_the_sources():
-    rec, bwd, top, topb, train = (_src(n) for n in ('train_persist.hip', 'train_persist_bwd.hip', 'train_persist_top.hip',
-                                                     'train_persist_topb.hip', 'train.hip'))
-    # row blocks
-    for text, name in ((rec, 'RBM'), (bwd, 'QBM'), (top, 'TBM'), (topb, 'VBM')):
-        assert int(re.search(r'constexpr int %s = (\d+)' % name, text).group(1)) == tf.ROW_BLOCK
-    # workgroups of a launch and the workgroups per CU the residency query is capped at
-    grids = {'rec': (rec, 'rec_grid', 'RBM', 'ra.njobs * '), 'rec_bwd': (bwd, 'recb_grid', 'QBM', 'ra.njobs * '),
-             'cell': (top, 'top_grid', 'TBM', ''), 'cell_bwd': (topb, 'topb_grid', 'VBM', '')}
-    for kind, (text, fn, bm, jobs) in grids.items():
-        body = _function(text, 'template <int NT> static int %s(' % fn)
-        assert 'const int grid = %s((ra.B + %s - 1) / %s) * NT;' % (jobs, bm, bm) in body, kind
-        m = re.search(r'return grid <= persist_blocks_per_cu\((\w+)<NT>, 0, (\d+)\) \* ncu \? grid : 0;', body)
-        assert m and m.group(1) == tf.KERNEL[kind] and int(m.group(2)) == tf.BLOCKS_PER_CU[kind], kind
-    # the conditions and the switch labels of the four dispatchers (and of the launchers: the same labels)
-    labels = lambda body: tuple(int(x) for x in re.findall(r'case (\d+):', body))
-    body = _function(rec, 'int train_recurrence_grid(')
-    assert 'if (ra.W % 32 || ra.njobs < 1 || ra.njobs > 2 || ra.B < 1) return 0;' in body and 'switch (ra.W / 32)' in body
-    widths = re.search(r'#define CASV_REC_WIDTHS\(X\)((?: X\(\d+\))+)', rec).group(1)
-    assert tuple(int(x) for x in re.findall(r'X\((\d+)\)', widths)) == tf.NT['rec']
-    assert 'CASV_REC_WIDTHS(CASV_REC_CASE)' in body and 'CASV_REC_WIDTHS(CASV_REC_CASE)' in _function(rec, 'void launch_train_recurrence(')
-    assert len(re.findall(r'train_recurrence_kernel<', rec)) == 2        # (the grid and the launcher: no instantiation beside the list)
-    body = _function(bwd, 'int train_recurrence_bwd_grid(')
-    assert 'if (ra.W % 128 || ra.njobs < 1 || ra.njobs > 2 || ra.B < 1) return 0;' in body and 'switch (ra.W / 32)' in body
-    assert labels(body) == labels(_function(bwd, 'void launch_train_recurrence_bwd(')) == tf.NT['rec_bwd']
-    body = _function(top, 'int train_attention_cell_grid(')
-    assert 'if (ra.W != ra.C || ra.B < 1 || ra.U < 1) return 0;' in body and 'switch (ra.W / 32 * (ra.W % 32 == 0))' in body
-    assert labels(body) == labels(_function(top, 'void launch_train_attention_cell(')) == tf.NT['cell']
-    body = _function(topb, 'int train_attention_cell_bwd_grid(')
-    assert 'if (ra.W != ra.C || ra.W % 128 || ra.B < 1 || ra.U < 1 || ra.ab.C > 1024) return 0;' in body
-    assert labels(body) == labels(_function(topb, 'void launch_train_attention_cell_bwd(')) == tf.NT['cell_bwd']
-    assert labels(_function(topb, 'bool train_attention_cell_bwd_rows_fit(')) == tf.NT['cell_bwd']
-    assert labels(_function(topb, 'void launch_train_attention_cell_bwd_rows(')) == tf.NT['cell_bwd']
-    assert tf.SPLIT_KERNEL + '<' in topb
-    # every instantiation of the five kernels goes through those switches
-    for text, kernel in ((bwd, tf.KERNEL['rec_bwd']), (top, tf.KERNEL['cell']), (topb, tf.KERNEL['cell_bwd']), (topb, tf.SPLIT_KERNEL)):
-        assert set(int(x) for x in re.findall(r'%s<(\d+)>' % kernel, text)) <= set(tf.NT['rec']), kernel
-    # train.hip: ONE place that decides (persist_slot) and ONE that counts (persist_launched), called from the four sites; the cap as
-    # one named constant; the cell's and the backward's own conditions
-    cap = 'REC_LAUNCH_CAP'
-    assert len(re.findall(r'constexpr int %s = (\d+);' % cap, train)) == 1
-    assert int(re.search(r'constexpr int %s = (\d+);' % cap, train).group(1)) == tf.CAP
-    cond = 'if (m->persist_mode != 0 && !m->deterministic && ts->rec_skip == 0 && ts->rec_launches < %s && m->ncu >= %d) {' % (cap, tf.MIN_CUS)
-    assert train.count(cond) == 1 and cond in _function(train, 'static unsigned* persist_slot(casv_model* m, TrainState* ts) {')
-    assert re.findall(r'rec_launches < \w+', train) == ['rec_launches < ' + cap] and train.count('persist_mode != 0') == 1
-    assert 'const unsigned* rec_abort[%s]' % cap in train and len(re.findall(r'rec_launches\+\+', train)) == 1
-    assert 'rec_launches++' in _function(train, 'static void persist_launched(TrainState* ts, unsigned* slot, size_t counter_bytes) {')
-    sites = {'layers_backward': 'static int layers_backward(', 'layers_forward': 'static int layers_forward(',
-             'forward_cell': 'static int forward_cell(', 'cell_backward_persistent': 'static int cell_backward_persistent('}
-    for name, head in sites.items():
-        body = _function(train, head)
-        assert len(re.findall(r'unsigned\* slot = persist_slot\(m, ts\)', body)) == 1 and body.count('ra.counters = slot;') == 1, name
-        assert len(re.findall(r'persist_launched\(ts, slot, %s\(B\)\);' % tf.COUNTER_BYTES[name], body)) == 1, name
-    assert len(re.findall(r'persist_slot\(m, ts\)', train)) == 4 and len(re.findall(r'persist_launched\(ts, slot, ', train)) == 4
-    # one slot size: the largest of the four kinds' counters, for the addresses, the allocation and the clear
-    body = _function(train, 'static size_t persist_slot_bytes(int B) {')
-    assert all(body.count(fn + '(B)') == 1 for fn in tf.COUNTER_BYTES.values()) and body.count('std::max(') == 3
-    assert 'persist_slot_bytes(ts->B) * ts->rec_launches' in _function(train, 'static unsigned* persist_slot(')
-    assert 'ENS(ts->rec_cnt, %s * persist_slot_bytes(B))' % cap in _function(train, 'static int plan_buffers(Step& s) {')
-    assert 'hipMemsetAsync(ts->rec_cnt.p, 0, %s * persist_slot_bytes(B), st)' % cap in _function(train, 'static int stage_inputs(Step& s) {')
-    assert train.count('persist_slot_bytes(') == 4
-    assert 'const int grid = top.hs_ld == W ? train_attention_cell_grid(ra, m->ncu) : 0' in _function(train, sites['forward_cell'])
-    body = _function(train, sites['layers_backward'])
-    assert 'plain = plain && l.kr == W;' in body and 'const int grid = plain ? train_recurrence_bwd_grid(ra, m->ncu) : 0;' in body
-    assert ('ra.split_a = split_opt && !ts->split_off && train_attention_cell_bwd_rows_fit(ra) ? 1 : 0;'
-            in _function(train, sites['cell_backward_persistent']))
+DRIVER = os.path.join(ROOT, 'tests', 'train_plan_driver.cpp')
+CUS = (256, 304, 264, 128, 64, 63)              # the MI355X, larger parts (264: one more row block fits), smaller ones, one below MIN_CUS
+PER_CU = ((2, 2, 1, 1), (1, 1, 1, 1), (0, 2, 1, 1), (2, 0, 1, 1), (2, 2, 0, 1), (2, 2, 1, 0))     # as planned for, one each, a failed query per kind
+GATES = (dict(), dict(deterministic=True), dict(backoff=True))
+
+
+def _cxx():
+    cxx = os.environ.get('CXX') or next((c for c in ('c++', 'g++', 'clang++') if shutil.which(c)), None)
+    if not cxx or not shutil.which(cxx):
+        pytest.skip('no host compiler')
+    return cxx
+
+
+def _site_condition_steps():
+    """[(key, train_form)] beside the table: every site condition with its flag off, the switches' values, the defer rule's edges."""
+    from oracle import ModelConfig
+    cfg = ModelConfig(depth=2, width=128, voc_size=40)
+    out = [('all_on', tf.train_form(cfg, 33, 5, 11))]
+    out += [('kr_off', tf.train_form(cfg, 33, 5, 11, not_plain=('rec_bwd',))), ('hs_ld_off', tf.train_form(cfg, 33, 5, 11, not_plain=('cell',)))]
+    out += [('split_opt_off', tf.train_form(cfg, 33, 5, 11, split=False)), ('split_gave_up', tf.train_form(cfg, 33, 5, 11, split_off=True)),
+            ('rows_do_not_fit', tf.train_form(cfg, 33, 5, 11, rows_fit=False))]
+    out += [('defer%d_t%d' % (d, T), tf.train_form(cfg, 33, T, 11, defer=d)) for d in (0, 1, 3) for T in (288, 289)]
+    out += [('defer%d_w96' % d, tf.train_form(ModelConfig(depth=2, width=96, voc_size=40), 33, 5, 11, defer=d)) for d in (1, 3)]
+    return out
+
+
+def _steps():
+    """[(key, train_form)] of every case of the table on every CU count, option value and residency, under every gate."""
+    out = []
+    for gate in GATES:
+        for fc in tf.ALL:
+            for cus in CUS:
+                for on in (True, False):
+                    for per_cu in PER_CU:
+                        key = '%s|%d|%d|%s|%s' % (fc[0][0], cus, on, '%d%d%d%d' % per_cu, ''.join(gate))
+                        out.append((key, tf.form(fc, cus=cus, persistent=on, blocks_per_cu=per_cu, **gate)))
+    return out + _site_condition_steps()
+
+
+def _run(exe, lines):
+    out = subprocess.run([exe], input=''.join(line + '\n' for line in lines), capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return out.stdout.splitlines()
+
+
+def _plan_steps(exe, steps):
+    """The driver's records of the steps, per step: the sites' records and the step's count."""
+    got = _run(exe, [line for key, f in steps for line in tf.driver_lines(key, f)])
+    out, at = [], 0
+    for key, f in steps:
+        n = len(f['launches']) + 2
+        assert got[at] == 'case ' + key
+        out.append(got[at + 1:at + n])
+        at += n
+    assert at == len(got)
+    return out
+
+
+@pytest.fixture(scope='module')
+def steps():
+    return _steps()
+
+
+@pytest.fixture(scope='module')
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp('train_plan') / 'driver')
+    subprocess.run([_cxx(), '-std=c++17', '-O1', '-Wall', '-Werror', DRIVER, '-o', exe], check=True)
+    return exe
+
+
+def test_the_plan_equals_the_restatement_on_every_case_cu_count_and_gate(driver, steps):
+    """train_plan.h (through tests/train_plan_driver.cpp) against train_form: every site's record -- persistent, capped, grid, NT, slot,
+    slot offset, the kind's counter bytes, defer, split -- and every step's count and slot size, in sites()'s order."""
+    assert len(set(k for k, _ in steps)) == len(steps) == len(GATES) * len(tf.ALL) * len(CUS) * 2 * len(PER_CU) + 14
+    got = _plan_steps(driver, steps)
+    wrong = [(k, g, tf.records(f)) for (k, f), g in zip(steps, got) if g != tf.records(f)]
+    assert not wrong, 'first of %d: %r' % (len(wrong), wrong[0])
+    by_key = {k: f for k, f in steps}
+    # the inputs decide: the gate's four, the CU count and the residency figure each change a count
+    plain = '|256|1|2211|'
+    assert by_key['w256_b1024' + plain]['count'] == 6 and by_key['w256_b1025' + plain]['count'] == 0
+    assert by_key['w256_b1025|264|1|2211|']['count'] == 6 and by_key['w256_b1024|256|1|1111|']['count'] == 2
+    assert by_key['w128_b33|256|1|0211|']['count'] == 4 and by_key['w128_b33|256|1|2210|']['count'] == 5
+    assert all(f['count'] == 0 for k, f in steps if '|63|' in k or re.search(r'\|0\|\d{4}\|', k) or 'deterministic' in k or 'backoff' in k)
+    assert all(f['count'] == fc[2] for fc in tf.ALL for f in [by_key[fc[0][0] + plain]])
+    # the slots: one size per step, the backward recurrence's counters; consecutive; the give-up word behind the kind's own counters
+    f = by_key['d8_plain' + plain]
+    assert f['slot_bytes'] == tf.counter_bytes('rec_bwd', 5) == (16 * 32 + 32) * 4
+    assert [ln['offset'] for ln in f['launches']] == [i * f['slot_bytes'] for i in range(16)] + [0, 0]
+    assert {ln['kind']: ln['counters'] for ln in f['launches'] if ln['persistent']} == {k: (tf.COUNTERS[k] * 32 + 32) * 4 for k in tf.KINDS}
+    assert by_key['w128_b33' + plain]['slot_bytes'] == (2 * 16 * 32 + 32) * 4
+
+
+def test_the_site_conditions_each_decide(driver):
+    """The sites' own conditions, each with its flag off: one job's kr != W, hs_ld != W, the split's three inputs, the defer rule."""
+    steps = _site_condition_steps()
+    got = _plan_steps(driver, steps)
+    assert [tf.records(f) for _, f in steps] == got
+    f = dict(steps)
+    kinds = lambda name: [(ln['kind'], ln['persistent']) for ln in f[name]['launches']]
+    assert f['all_on']['count'] == 6 and kinds('all_on') == [(k, True) for k in ('rec', 'rec', 'cell', 'cell_bwd', 'rec_bwd', 'rec_bwd')]
+    assert f['kr_off']['count'] == 4 and [k for k, on in kinds('kr_off') if not on] == ['rec_bwd', 'rec_bwd']
+    assert f['hs_ld_off']['count'] == 5 and [k for k, on in kinds('hs_ld_off') if not on] == ['cell']
+    cell_bwd = lambda name: [ln for ln in f[name]['launches'] if ln['kind'] == 'cell_bwd'][0]
+    assert cell_bwd('all_on')['split'] and (cell_bwd('all_on')['defer'], cell_bwd('all_on')['slot']) == (1, 3)
+    for name in ('split_opt_off', 'split_gave_up', 'rows_do_not_fit'):
+        assert f[name]['count'] == 6 and not cell_bwd(name)['split'] and cell_bwd(name)['persistent'], name
+    assert [cell_bwd('defer%d_t%d' % (d, T))['defer'] for d in (0, 1, 3) for T in (288, 289)] == [0, 0, 1, 0, 3, 0]
+    assert all(cell_bwd('defer%d_t289' % d)['persistent'] and cell_bwd('defer%d_t289' % d)['split'] for d in (0, 1, 3))
+    assert not cell_bwd('defer3_w96')['persistent'] and cell_bwd('defer3_w96')['defer'] == 0 and f['defer3_w96']['count'] == 2
+
+
+def test_the_constants_and_the_widths_with_a_form(driver):
+    """The header's numbers, and which NT have a form: every kind at W = 32 ... 640, beside multiples of 32, at W != C and C = 1056."""
+    got = _run(driver, ['K'])
+    assert got[0] == 'constants row_block=%d cap=%d min_cus=%d defer_max_t=%d' % (tf.ROW_BLOCK, tf.CAP, tf.MIN_CUS, tf.DEFER_MAX_T)
+    assert (tf.ROW_BLOCK, tf.CAP, tf.MIN_CUS, tf.DEFER_MAX_T) == (32, 16, 64, 288)
+    assert got[1:] == ['kind %s per_cu=%d counters=%d widths=%s' % (k, tf.BLOCKS_PER_CU[k], tf.COUNTERS[k], ''.join('%d,' % n for n in tf.NT[k]))
+                       for k in tf.KINDS]
+    assert [(tf.BLOCKS_PER_CU[k], tf.COUNTERS[k]) for k in tf.KINDS] == [(2, 2), (2, 16), (1, 3), (1, 12)]
+    shapes = [(W, W) for W in range(32, 641, 32)] + [(136, 136), (100, 100), (128, 256), (256, 128), (1056, 1056)]
+    rows = [(k, W, C, 33, 3, jobs) for k in tf.KINDS for W, C in shapes for jobs in (1, 2)]
+    rows += [(k, 128, 128, B, U, jobs) for k in tf.KINDS for B, U, jobs in ((0, 3, 1), (1, 0, 1), (1, 3, 0), (1, 3, 3))]
+    got = _run(driver, ['G %s %d %d %d %d %d 256 %d' % (r + (tf.BLOCKS_PER_CU[r[0]],)) for r in rows])
+    assert got == ['grid=%d' % tf.grid(k, W, C, B, jobs, 256, tf.BLOCKS_PER_CU[k], U) for k, W, C, B, U, jobs in rows]
+    have = {k: tuple(sorted({W // 32 for (kk, W, C, *_), g in zip(rows, got) if kk == k and g != 'grid=0'})) for k in tf.KINDS}
+    assert have == tf.NT
+    grid_of = {r: int(g[5:]) for r, g in zip(rows, got)}
+    assert grid_of[('rec', 128, 256, 33, 3, 2)] == 16 and grid_of[('rec_bwd', 128, 256, 33, 3, 2)] == 16      # (the recurrences do not look at C)
+    assert grid_of[('cell', 128, 256, 33, 3, 1)] == grid_of[('cell_bwd', 256, 128, 33, 3, 1)] == 0 and grid_of[('cell', 128, 128, 33, 3, 2)] == 8
+    assert all(grid_of[(k, 128, 128, 0, 3, 1)] == 0 for k in tf.KINDS)
+    assert [grid_of[(k, 128, 128, 1, 0, 1)] for k in tf.KINDS] == [4, 4, 0, 0]
+    assert [grid_of[(k, 128, 128, 1, 3, j)] for k in tf.KINDS for j in (0, 3)] == [0, 0, 0, 0, 4, 4, 4, 4]
+
+
+def test_the_driver_is_clean_under_the_host_sanitizers(tmp_path, driver, steps):
+    cxx = _cxx()
+    probe = tmp_path / 'probe.cpp'
+    probe.write_text('int main() { return 0; }\n')
+    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-fno-omit-frame-pointer']
+    if subprocess.run([cxx] + flags + [str(probe), '-o', str(tmp_path / 'probe')], capture_output=True).returncode != 0:
+        pytest.skip('the host compiler has no sanitizer runtime')
+    exe = str(tmp_path / 'driver_san')
+    subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-Wall', '-Werror'] + flags + [DRIVER, '-o', exe], check=True)
+    lines = ['K'] + [line for key, f in steps for line in tf.driver_lines(key, f)]
+    assert _run(exe, lines) == _run(driver, lines)
+
+
+def _code(text):
+    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+
+
+def test_the_plan_is_pure_and_the_sources_only_run_it():
+    """What behaviour cannot show: train_plan.h knows no device and no environment; every instantiation of the five kernels comes
+    from its lists; train.hip asks it in one place, which the four sites call; one slot size serves addresses, allocation and clear."""
+    plan = _src('train_plan.h')
+    assert not re.search(r'\bhip|getenv', _code(plan), re.I)
+    assert re.findall(r'#include [<"]([^>"]+)[>"]', plan) == ['algorithm', 'cstddef']
+    assert re.findall(r'#include [<"]([^>"]+)[>"]', open(DRIVER).read())[0] == '../cor_asv_ann_amd/csrc/train_plan.h'
+    files = {'train_persist.hip': ('RBM', 'REC', [tf.KERNEL['rec']]), 'train_persist_bwd.hip': ('QBM', 'REC_BWD', [tf.KERNEL['rec_bwd']]),
+             'train_persist_top.hip': ('TBM', 'CELL', [tf.KERNEL['cell']]), 'train_persist_topb.hip': ('VBM', 'CELL_BWD', [tf.KERNEL['cell_bwd'], tf.SPLIT_KERNEL])}
+    csrc = {n: _code(_src(n)) for n in os.listdir(CSRC) if n.endswith(('.hip', '.h'))}
+    for name, (bm, widths, kernels) in files.items():
+        code = csrc[name]
+        assert 'static_assert(%s == TRAIN_ROW_BLOCK' % bm in code, name
+        assert 'switch (train_width_nt(' in code and not re.search(r'case \d+:', code), name           # (no hand-written width switch)
+        for kernel in kernels:
+            # a width's instantiation is named in ONE place, a case generated from the kind's list; elsewhere only as a template of NT
+            uses = re.findall(r'%s<(\w+)>' % kernel, code)
+            assert sorted(set(uses)) == ['NT', 'NT_'] or uses == ['NT_'], (kernel, uses)
+            assert uses.count('NT_') == 1, (kernel, uses)
+            line = [ln for ln in code.splitlines() if kernel + '<NT_>' in ln][0]
+            macro = re.match(r'#define (\w+)\(NT_\) case NT_: return ', line).group(1)
+            assert code.count('CASV_TRAIN_%s_WIDTHS(%s)' % (widths, macro)) == 1, kernel
+            assert all(kernel + '<' not in other for n, other in csrc.items() if n != name), kernel
+        assert 'TRAIN_BLOCKS_PER_CU[TRAIN_%s]' % widths in code and not re.search(r'persist_blocks_per_cu\([^;]*, \d+\)', code), name
+    train = _code(_src('train.hip'))
+    # one asking place, called by exactly the four sites; nothing else in the sources plans, counts or sizes
+    assert train.count('.next(') == 1 and '.next(gate, site)' in _function(train, 'static int persist_launch(')
+    callers = [name for head, name in re.findall(r'^(static \w+ (\w+)\()', train, re.M)
+               if name != 'persist_launch' and 'persist_launch(' in _function(train, head)]
+    assert sorted(callers) == ['cell_backward_persistent', 'forward_cell', 'layers_backward', 'layers_forward']
+    assert train.count('persist_launch(m, ') == 4 and train.count('PC_PERSIST') == 2 and train.count('persist_give_up_word(') == 1
+    assert not re.search(r'plan\.launches\s*(\+\+|--|[-+]?=[^=])|(\+\+|--)\s*\w*(->|\.)?plan\.launches', train)      # (only the plan counts)
+    assert 'ts->plan = TrainStepPlan{}' in _function(train, 'static int stage_inputs(Step& s) {')
+    assert train.count('train_slot_bytes(') == 2 and train.count('slot_offset') == 1
+    assert 'TRAIN_LAUNCH_CAP * train_slot_bytes(B)' in _function(train, 'static int plan_buffers(Step& s) {')
+    assert 'TRAIN_LAUNCH_CAP * train_slot_bytes(B)' in _function(train, 'static int stage_inputs(Step& s) {')
+    assert 'rec_abort[TRAIN_LAUNCH_CAP]' in train and train.count('getenv("CASV_') == 2 == _function(train, 'static TrainSwitches read_train_switches(').count('getenv("CASV_')
+    for n, code in csrc.items():
+        if n != 'train_plan.h':
+            assert not re.search(r'TRAIN_LAUNCH_CAP\s*=|TRAIN_MIN_CUS\s*=|ATTN_DEFER_MAX_T\s*=|_counter_bytes\(int B\)', code), n
 
 
 _LAUNCH_SITE = r'layers_forward\(m, f, \d|launch_train_attention_cell\(|launch_train_attention_cell_bwd\(|layers_backward\(m, \w+, \d'

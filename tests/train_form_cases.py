@@ -1,5 +1,5 @@
-"""The forms of the train step's persistent recurrences (csrc/train.hip, csrc/train_persist*.hip): a case table that reaches every
-instantiation the dispatchers name, the form decision restated (train_form), and the two input-level mistakes a persistent
+"""The forms of the train step's persistent recurrences (csrc/train_plan.h, csrc/train.hip, csrc/train_persist*.hip): a case table that
+reaches every instantiation the dispatchers name, the plan restated (grid, train_form), and the two input-level mistakes a persistent
 kernel could make that tests/grad_noise_cases.py's mutations do not model.  Loss, norm and every gradient of a case are held to
 the float64 oracle by the method and the constants of tests/grad_noise_cases.py (tests/test_gpu_train_forms.py on the device,
 tests/test_train_form_cases.py without one).
@@ -14,34 +14,48 @@ from oracle.train import forward_backward
 from tests import grad_noise_cases as gn
 
 # ------------------------------------------------------------------------------------------------------------------ the form
-ROW_BLOCK = 32                      # rows of a row block: RBM, QBM, TBM, VBM
-CAP = 16                            # persistent launches of one step (train.hip: REC_LAUNCH_CAP -- persist_slot's gate, rec_abort[], rec_cnt's slots)
-MIN_CUS = 64                        # train.hip, persist_slot: m->ncu >= 64
-# the switch labels of the four *_grid functions (NT = W / 32) and the workgroups per CU their persist_blocks_per_cu calls request
+# csrc/train_plan.h restated: the C++ is held to this file by tests/test_train_form_cases.py through tests/train_plan_driver.cpp
+KINDS = ('rec', 'rec_bwd', 'cell', 'cell_bwd')
+ROW_BLOCK = 32                      # rows of a row block: TRAIN_ROW_BLOCK = RBM, QBM, TBM, VBM
+CAP = 16                            # persistent launches of one step: TRAIN_LAUNCH_CAP (the gate, rec_abort[], rec_cnt's slots)
+MIN_CUS = 64                        # TRAIN_MIN_CUS
+# the widths NT = W / 32 with an instantiation (CASV_TRAIN_*_WIDTHS), the workgroups per CU a form plans for, the hand-off counters
+# per row block, and the longest source the cell's backward can defer its sums for
 NT = {'rec': tuple(range(1, 17)), 'rec_bwd': (4, 8, 12, 16), 'cell': (4, 8, 16), 'cell_bwd': (4, 8, 16)}
 BLOCKS_PER_CU = {'rec': 2, 'rec_bwd': 2, 'cell': 1, 'cell_bwd': 1}
+COUNTERS = {'rec': 2, 'rec_bwd': 16, 'cell': 3, 'cell_bwd': 12}
+DEFER_MAX_T = 288
 KERNEL = {'rec': 'train_recurrence_kernel', 'rec_bwd': 'train_recurrence_bwd_kernel', 'cell': 'train_attention_cell_kernel',
           'cell_bwd': 'train_attention_cell_bwd_kernel'}
 SPLIT_KERNEL = 'train_attention_cell_bwd_rows_kernel'       # the cell's backward split: a second launch beside the first (same NT)
-# the four functions of train.hip that ask persist_slot for a launch, and whose counters each one's give-up word sits behind
-COUNTER_BYTES = {'layers_forward': 'train_recurrence_counter_bytes', 'layers_backward': 'train_recurrence_bwd_counter_bytes',
-                 'forward_cell': 'train_attention_cell_counter_bytes', 'cell_backward_persistent': 'train_attention_cell_bwd_counter_bytes'}
 
 
-def grid(kind, W, C, B, jobs, cus, per_cu):
-    """The workgroups of a launch, or 0 where the shape has no persistent form on `cus` CUs: train_recurrence_grid,
-    train_recurrence_bwd_grid, train_attention_cell_grid and train_attention_cell_bwd_grid."""
-    if B < 1 or W % 32:
+def counter_bytes(kind, B):
+    """A launch's hand-off counters: 32 words each, then 32 words the first of which is the give-up word."""
+    return (COUNTERS[kind] * ((B + ROW_BLOCK - 1) // ROW_BLOCK) * 32 + 32) * 4
+
+
+def slot_bytes(B):
+    """The slot a launch takes, whatever its kind: the largest kind's counters."""
+    return max(counter_bytes(kind, B) for kind in KINDS)
+
+
+def grid(kind, W, C, B, jobs, cus, per_cu, U=1):
+    """The workgroups of a launch, or 0 where the shape has no persistent form on `cus` CUs: train_plan.h's train_form_grid."""
+    cell = kind in ('cell', 'cell_bwd')
+    if B < 1 or W < 32 or W % 32:
         return 0
-    if kind == 'rec_bwd' and W % 128:
+    if kind in ('rec_bwd', 'cell_bwd') and W % 128:
         return 0
-    if kind in ('cell', 'cell_bwd') and W != C:
+    if cell and (W != C or U < 1):
         return 0
-    if kind == 'cell_bwd' and (W % 128 or C > 1024):
+    if not cell and jobs not in (1, 2):
+        return 0
+    if kind == 'cell_bwd' and C > 1024:
         return 0
     if W // 32 not in NT[kind]:
         return 0
-    n = (jobs if kind in ('rec', 'rec_bwd') else 1) * ((B + ROW_BLOCK - 1) // ROW_BLOCK) * (W // 32)
+    n = (1 if cell else jobs) * ((B + ROW_BLOCK - 1) // ROW_BLOCK) * (W // 32)
     return n if n <= per_cu * cus else 0
 
 
@@ -65,28 +79,54 @@ def sites(cfg, T, U):
     return out + [('rec_bwd',) + pair1]
 
 
-def train_form(cfg, B, T, U, cus=256, blocks_per_cu=(2, 2, 1, 1), persistent=True):
-    """The form of one mode-1 / mode-2 step (option "persistent" != 0, "deterministic" off, no back-off pending), restated from
-    train.hip's persist_slot and its four callers (layers_forward, layers_backward, forward_cell, cell_backward_persistent) and the four
-    *_grid functions.
-    -> dict(launches = per site dict(kind, kernel, NT, jobs, layers, lengths, persistent, split, capped), count = the persistent
-    launches of the step after the cap CAP (the statistic "train_persistent_launches"), capped = the layers of the sites whose
-    shape has a persistent form but which come behind the CAP-th launch and run per step).
-    split: the attention cell's backward takes its two-launch form (SPLIT_KERNEL beside the main kernel: one launch of the count) --
-    predicted wherever that launch is persistent; a device on which the two do not fit together, CASV_TOPB_SPLIT=0 or a serialised
-    dispatch take one launch instead."""
+def train_form(cfg, B, T, U, cus=256, blocks_per_cu=(2, 2, 1, 1), persistent=True, deterministic=False, backoff=False,
+               not_plain=(), defer=1, split=True, split_off=False, rows_fit=True):
+    """The form of one mode-1 / mode-2 step, restated from train_plan.h's TrainStepPlan asked at the sites of train.hip
+    (layers_forward, layers_backward, forward_cell, cell_backward_persistent) in the step's order.
+    The gate: option "persistent" != 0, "deterministic" off, no back-off pending, MIN_CUS CUs.  not_plain: the kinds whose sites' own
+    condition fails (rec_bwd: a job's kr != W; cell: hs_ld != W).  defer / split: CASV_ATTN_DEFER and CASV_TOPB_SPLIT (after the
+    serialised-dispatch rule); split_off: a step gave up in the two-launch form; rows_fit: both launches fit a CU.
+    -> dict(launches = per site dict(kind, kernel, NT, jobs, layers, lengths, grid, persistent, split, capped, slot, offset, counters,
+    defer, site), count = the persistent launches of the step after the cap CAP (the statistic "train_persistent_launches"),
+    capped = the layers of the sites whose shape has a persistent form but which come behind the CAP-th launch and run per step).
+    split: the attention cell's backward takes its two-launch form (SPLIT_KERNEL beside the main kernel: one launch of the count).
+    slot / offset / counters: the launch's slot of the counter buffer, its byte offset, and its kind's counter bytes, behind which its
+    give-up word sits.  site: the plan's inputs for the site, as tests/train_plan_driver.cpp reads them."""
     W, C = cfg.width, cfg.ctx_width
-    per_cu = dict(zip(('rec', 'rec_bwd', 'cell', 'cell_bwd'), blocks_per_cu))
+    per_cu = dict(zip(KINDS, blocks_per_cu))
+    gate = bool(persistent) and not deterministic and not backoff and cus >= MIN_CUS
     launches, count, capped = [], 0, []
     for kind, layers, lengths in sites(cfg, T, U):
-        g = grid(kind, W, C, B, len(layers), cus, per_cu[kind]) if persistent and cus >= MIN_CUS else 0
+        plain = kind not in not_plain
+        steps = max(lengths)
+        g = grid(kind, W, C, B, len(layers), cus, per_cu[kind], steps) if gate and plain else 0
         on = g > 0 and count < CAP
         if g > 0 and not on:
             capped.append(layers)
+        ln = dict(kind=kind, kernel=KERNEL[kind], NT=W // 32, jobs=len(layers), layers=layers, lengths=lengths, grid=g,
+                  persistent=on, split=False, capped=g > 0 and not on, slot=0, offset=0, counters=0, defer=0,
+                  site=(kind, W, C, B, steps, len(layers), per_cu[kind], int(plain), T, defer, int(split), int(split_off), int(rows_fit)))
+        if on:
+            ln.update(slot=count, offset=count * slot_bytes(B), counters=counter_bytes(kind, B))
+            if kind == 'cell_bwd':
+                ln.update(defer=defer if T <= DEFER_MAX_T and W % 64 == 0 and C % 64 == 0 else 0, split=bool(split and not split_off and rows_fit))
         count += on
-        launches.append(dict(kind=kind, kernel=KERNEL[kind], NT=W // 32, jobs=len(layers), layers=layers, lengths=lengths, grid=g,
-                             persistent=on, split=on and kind == 'cell_bwd', capped=g > 0 and not on))
-    return dict(launches=launches, count=count, capped=capped)
+        launches.append(ln)
+    return dict(launches=launches, count=count, capped=capped, slot_bytes=slot_bytes(B),
+                gate=(int(bool(persistent)), int(deterministic), int(backoff), cus))
+
+
+def driver_lines(name, f):
+    """A step of train_form as tests/train_plan_driver.cpp reads it ..."""
+    return ['S %s %d %d %d %d %d' % ((name,) + f['gate'] + (len(f['launches']),))] + \
+           ['%s %d %d %d %d %d %d %d %d %d %d %d %d' % ln['site'] for ln in f['launches']]
+
+
+def records(f):
+    """... and as it prints it: one record per site, then the step's count."""
+    return ['site kind=%s persistent=%d capped=%d grid=%d nt=%d slot=%d offset=%d counters=%d defer=%d split=%d'
+            % (ln['kind'], ln['persistent'], ln['capped'], ln['grid'], ln['NT'] if ln['grid'] else 0, ln['slot'], ln['offset'], ln['counters'],
+               ln['defer'], ln['split']) for ln in f['launches']] + ['step count=%d slot_bytes=%d' % (f['count'], f['slot_bytes'])]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the cases
@@ -135,11 +175,11 @@ def build(fc):
     return gn.build(fc[0], source=fc[1])
 
 
-def form(fc, cus=256, persistent=True):
+def form(fc, cus=256, persistent=True, **inputs):
     """train_form of a case's step."""
     (name, d, W, V, B, L, es, mk, flags, A, frozen), S, _ = fc
     from oracle import ModelConfig
-    return train_form(ModelConfig(depth=d, width=W, voc_size=V, **flags), B, S + 1, L + 2, cus=cus, persistent=persistent)
+    return train_form(ModelConfig(depth=d, width=W, voc_size=V, **flags), B, S + 1, L + 2, cus=cus, persistent=persistent, **inputs)
 
 
 _ORACLES, _EVALS = {}, {}
