@@ -84,8 +84,10 @@ SIGNATURES = {
     'casv_score_targets': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 10),
     'casv_score_candidates': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 10),
     'casv_score_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    'casv_score_get_alternatives': (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'casv_score_release': (c_int, [c_void_p]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    'casv_debug_alternatives_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'casv_profile': (c_int, [c_void_p, c_int32]),
     'casv_profile_read': (c_int, [c_void_p, c_char_p, POINTER(c_int64), POINTER(c_double), POINTER(c_double),
                                   POINTER(c_double)]),

@@ -82,6 +82,7 @@ struct TrainState {
     // forward_only: the state of a scoring call outside a session (m->score) -- weights in the train layout, the derived transposes,
     // the forward buffers; no gradient, no Adam moment, no backward buffer.  commit_gen: the commit of the handle's weights it holds.
     DevBuf s_logp, s_best, s_rank, s_nll, s_count, s_lo, s_w;
+    DevBuf s_alt_idx, s_alt_logp, s_entropy;     // casv_score_get_alternatives: [B][U][K], [B][U] of the last retrieval
     int score_B = 0, score_U = 0, score_T = 0;
     bool forward_only = false; unsigned long long commit_gen = 0;
     int find(const std::string& n) const { for (size_t i = 0; i < tens.size(); ++i) if (tens[i].name == n) return (int)i; return -1; }
@@ -214,7 +215,8 @@ static void release_state(casv_model* m, TrainState* ts) {
         &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn,
         &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
         &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
-        &ts->seg_dec_pos, &ts->s_logp, &ts->s_best, &ts->s_rank, &ts->s_nll, &ts->s_count, &ts->s_lo, &ts->s_w};
+        &ts->seg_dec_pos, &ts->s_logp, &ts->s_best, &ts->s_rank, &ts->s_nll, &ts->s_count, &ts->s_lo, &ts->s_w,
+        &ts->s_alt_idx, &ts->s_alt_logp, &ts->s_entropy};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : ts->O) b.release();
     for (auto& b : ts->DO) b.release();
@@ -1465,6 +1467,29 @@ extern "C" int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_
     return CASV_OK;
 }
 
+// The K likeliest characters and the entropy of every position of the LAST scoring call: the logits of its B * U rows still lie in
+// the state's buffer (the head writes nothing back into them), one launch reads them; nothing a later call reads is changed.
+extern "C" int casv_score_get_alternatives(casv_model* m, int32_t K, int32_t* alt_idx, float* alt_logp, float* entropy) {
+    if (!m) return fail(CASV_ERR_ARG, "null argument");
+    if (K < 1 || K > m->V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, m->V < 64 ? m->V : 64);
+    TrainState* ts = m->train ? m->train : m->score;
+    if (!ts || !ts->score_B) return fail(CASV_ERR_STATE, "no scoring call to take alternatives from");
+    if (!alt_idx || !alt_logp) return fail(CASV_ERR_ARG, "null argument");      // (after the state: a caller without a shape learns why)
+    HIPCHK(hipSetDevice(m->device));
+    const size_t n = (size_t)ts->score_B * ts->score_U;
+    if (int rc = ts->s_alt_idx.ensure(n * K * 4)) return rc;
+    if (int rc = ts->s_alt_logp.ensure(n * K * 4)) return rc;
+    if (int rc = ts->s_entropy.ensure(n * 4)) return rc;
+    launch_score_alternatives(ts->logits.as<float>(), ts->score_B, ts->score_U, m->V, m->Vp, K, ts->s_alt_idx.as<int>(),
+                              ts->s_alt_logp.as<float>(), entropy ? ts->s_entropy.as<float>() : nullptr, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(alt_idx, ts->s_alt_idx.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(alt_logp, ts->s_alt_logp.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
+    if (entropy) HIPCHK(hipMemcpyAsync(entropy, ts->s_entropy.p, n * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
+}
+
 // Test support: the head alone on the caller's logits (R,V), laid out with the library's row stride and the padding filled.
 extern "C" int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
                                      float* logp, int32_t* best, int32_t* rank) {
@@ -1486,6 +1511,33 @@ extern "C" int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const 
     HIPCHK(hipMemcpyAsync(logp, dl.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(best, db.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(rank, dr.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return CASV_OK;
+}
+
+// Test support: score_alternatives_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out.
+extern "C" int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, float pad_value,
+                                            int32_t* alt_idx, float* alt_logp, float* entropy) {
+    if (!m || !logits || !alt_idx || !alt_logp) return fail(CASV_ERR_ARG, "null argument");
+    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
+    if (K < 1 || K > V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, V < 64 ? V : 64);
+    HIPCHK(hipSetDevice(m->device));
+    const int Vp = (V + 31) & ~31;
+    std::vector<float> x((size_t)R * Vp, pad_value);
+    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
+    DevBuf dx, di, dl, de;
+    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
+        release_on_exit{{&dx, &di, &dl, &de}, m->stream};
+    if (int rc = dx.ensure(x.size() * 4)) return rc;
+    if (int rc = di.ensure((size_t)R * K * 4)) return rc;
+    if (int rc = dl.ensure((size_t)R * K * 4)) return rc;
+    if (int rc = de.ensure((size_t)R * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
+    launch_score_alternatives(dx.as<float>(), R, 1, V, Vp, K, di.as<int>(), dl.as<float>(), entropy ? de.as<float>() : nullptr, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(alt_idx, di.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(alt_logp, dl.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
+    if (entropy) HIPCHK(hipMemcpyAsync(entropy, de.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return CASV_OK;
 }

@@ -36,6 +36,13 @@ void launch_score_rows(const float* logits, const int* target, int B, int U, int
 void launch_score_lines(const float* logp, const int* target, int B, int U, int V, double* nll, int* count, hipStream_t st);
 // ... the cell's attention rows Ast [U+1][B][T] / windows WIN [U][B] in window form, (B,U) order: lo, w [K] per step
 void launch_score_extract_sparse(const float* Ast, const int* WIN, int B, int U, int T, int K, int* lo, float* w, hipStream_t st);
+// The K likeliest entries of every row (casv_score_get_alternatives), rows and (B,U) order as launch_score_rows, 1 <= K <=
+// min(V, 64), Vp <= 4096: alt_idx / alt_logp [B][U][K] in the order "x descending, the two zeros equal, the lower index first"
+// (-inf entries are members: last, in index order, logp -inf); alt_logp[j] has the bits of launch_score_rows' logp for target
+// alt_idx[j]; entropy [B][U] (or nullptr) = log(sum) - sum(exp(x - m) (x - m)) / sum over the entries above -inf.  A row that
+// launch_score_rows calls invalid gives -1 / NaN / NaN.  Columns [V, Vp) are never read; the logits are not written.
+void launch_score_alternatives(const float* logits, int B, int U, int V, int Vp, int K, int* alt_idx, float* alt_logp, float* entropy,
+                               hipStream_t st);
 
 // The forward recurrence of up to two independent plain LSTM layers over all their time steps as ONE launch (train_persist.hip).
 struct RecJob {

@@ -277,6 +277,82 @@ void launch_score_rows(const float* logits, const int* target, int B, int U, int
     hipLaunchKernelGGL(score_rows_kernel, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, rows, B, U, V, Vp, logp, best, rank);
 }
 
+// ---- the K likeliest entries and the entropy of every row (casv_score_get_alternatives) ----
+// The order is total: x descending as floats (the two zeros equal), the lower index first among equals.  One 64-bit key holds it:
+// the float's bits made monotone (sign bit set for the positives, all bits flipped for the negatives; -0.0 taken as +0.0) above
+// ~index, so a larger key is an earlier place.  No key of a valid row is 0 or all ones (those are NaN bit patterns).
+__device__ __forceinline__ unsigned long long alt_key(float x, int v) {
+    unsigned b = __float_as_uint(x);
+    if (b == 0x80000000u) b = 0u;
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((unsigned long long)b << 32) | (0xffffffffu - (unsigned)v);
+}
+template <int MASK> __device__ __forceinline__ unsigned long long max_across(unsigned long long v) {
+    const unsigned lo = (unsigned)lane_xor<MASK>((int)(unsigned)v), hi = (unsigned)lane_xor<MASK>((int)(unsigned)(v >> 32));
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    return o > v ? o : v;
+}
+// One wave per row, as score_rows_kernel, and its m, sum and validity formed by the same two loops (lane-strided, then the wave
+// butterfly): logp has the bits of the head's logp for that index as target.  The row is read from memory once, into the wave's
+// own Vp floats of LDS (no other wave touches them: no barrier); every later pass reads the entries the lane itself wrote.
+// Selection: K rounds of a wave-wide maximum over the keys strictly below the previous winner's -- V/64 compares per lane and
+// round, no scratch, no atomics, the same result whatever the launch shape.  Lane j keeps place j; the K places go out in one store.
+__global__ __launch_bounds__(256) void score_alternatives_kernel(const float* __restrict__ logits, long long rows, int B, int U, int V,
+                                                                 int Vp, int K, int* __restrict__ alt_idx, float* __restrict__ alt_logp,
+                                                                 float* __restrict__ entropy) {
+    extern __shared__ float alt_rows[];             // [4][Vp]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* s = alt_rows + wave * Vp;
+    for (long long r = blockIdx.x * 4LL + wave; r < rows; r += 4LL * gridDim.x) {
+        const float* x = logits + r * Vp;
+        float m = -INFINITY;
+        int nan = 0;
+        for (int v = lane; v < V; v += 64) { const float xv = x[v]; s[v] = xv; nan |= xv != xv; m = fmaxf(m, xv); }
+        m = wave_butterfly(m, [](float a, float b) { return fmaxf(a, b); });
+        nan = wave_butterfly(nan, [](int a, int b) { return a | b; });
+        const bool valid = !nan && m > -INFINITY && m < INFINITY;        // (the same in every lane)
+        const long long src = (r % B) * U + r / B;
+        int place = -1;
+        float lp = __builtin_nanf(""), h = __builtin_nanf("");
+        if (valid) {
+            float sum = 0.f, dot = 0.f;
+            for (int v = lane; v < V; v += 64) {
+                const float xv = s[v], d = xv - m, e = expf(d);
+                sum += e;
+                if (xv > -INFINITY) dot += e * d;                        // (an -inf entry adds 0, not 0 * inf)
+            }
+            sum = wsum(sum);
+            dot = wsum(dot);
+            const float ls = logf(sum);
+            h = ls - dot / sum;
+            unsigned long long prev = ~0ull;
+            for (int j = 0; j < K; ++j) {
+                unsigned long long top = 0ull;
+                for (int v = lane; v < V; v += 64) {
+                    const unsigned long long key = alt_key(s[v], v);
+                    if (key < prev && key > top) top = key;
+                }
+                top = max_across<32>(top); top = max_across<16>(top); top = max_across<8>(top);
+                top = max_across<4>(top); top = max_across<2>(top); top = max_across<1>(top);
+                const int idx = (int)(0xffffffffu - (unsigned)top);      // (K <= V: every round finds one)
+                const int own = (idx & ~63) | lane;                      // the winner's pass: its lane reads it, the wave gets it
+                const float xw = __shfl(own < V ? s[own] : 0.f, idx & 63, 64);
+                if (lane == j) { place = idx; lp = (xw - m) - ls; }
+                prev = top;
+            }
+        }
+        if (lane < K) { alt_idx[src * K + lane] = place; alt_logp[src * K + lane] = lp; }
+        if (lane == 0 && entropy) entropy[src] = h;
+    }
+}
+void launch_score_alternatives(const float* logits, int B, int U, int V, int Vp, int K, int* alt_idx, float* alt_logp, float* entropy,
+                               hipStream_t st) {
+    const long long rows = (long long)B * U;
+    const long long wgs = std::min<long long>((rows + 3) / 4, 2048);
+    hipLaunchKernelGGL(score_alternatives_kernel, dim3((unsigned)wgs), dim3(256), (size_t)4 * Vp * sizeof(float), st, logits, rows, B, U,
+                       V, Vp, K, alt_idx, alt_logp, entropy);
+}
+
 // ... and the lines' sums: nll[b] = sum over the scored positions of -(double)logp[b][u], one thread per line adding in the order
 // of u (one accumulator, no atomics: the same bits whatever the launch shape); count[b] = scored positions.
 __global__ __launch_bounds__(64) void score_lines_kernel(const float* __restrict__ logp, const int* __restrict__ target, int B, int U,

@@ -139,6 +139,7 @@ class HipEngine(object):
         self.shapes = weight_shapes(self.depth, self.width, self.voc_size, self.bridge_dense, self.deep)
         self.pshapes = weight_shapes(self.depth, self.pwidth, self.voc_size, self.bridge_dense, self.deep)
         self.B = self.T = 0
+        self._score_shape = None            # (rows, U) of this object's last scoring call (score_alternatives)
 
     # -- dead-unit padding (class docstring) ---------------------------------------------------
     def _pad_weight(self, name, a):
@@ -408,6 +409,7 @@ class HipEngine(object):
         align = np.empty((B, U, T), np.float32) if want_align and not sparse else None
         nv.check(self.lib.casv_score_targets(self.handle, B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), nv.ptr(dec_out),
                                              nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count), nv.ptr(align)))
+        self._score_shape = (B, U)          # (score_alternatives: the rows the library now holds)
         if sparse:
             K = 2 * self.window_width + 1
             lo = np.empty((B, U), np.int32)
@@ -442,6 +444,7 @@ class HipEngine(object):
         nv.check(self.lib.casv_score_candidates(self.handle, B, N, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
                                                 nv.ptr(dec_out), nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count),
                                                 nv.ptr(align)))
+        self._score_shape = (B * N, U)
         if sparse:
             K = 2 * self.window_width + 1
             lo = np.empty((B, N, U), np.int32)
@@ -449,6 +452,26 @@ class HipEngine(object):
             nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(lo), nv.ptr(w)))
             align = (lo, w)
         return logp, best, rank, nll, count, align
+
+    def score_alternatives(self, K, want_entropy=True):
+        """The K likeliest characters and the entropy of every position of the LAST score_targets / score_candidates call
+        (casv_score_get_alternatives), unscored positions included.  Returns (alt_idx int32 (rows,U,K), alt_logp float32 (rows,U,K),
+        entropy float32 (rows,U) or None), rows = B, or B*N after score_candidates (row b * N + n); most probable first, ties to the
+        lower index, alt_logp the bits score_targets returns for that index as target; -1 / NaN / NaN on an invalid row.  May be
+        repeated with another K; NativeError (CASV_ERR_STATE) without a scoring call to read, CASV_ERR_ARG for K outside
+        [1, min(V, 64)]."""
+        K = int(K)
+        # the shape is that of this object's last scoring call; without one no buffer is handed over, and the library -- which
+        # checks K, then its state, then the pointers -- gives the error
+        shape = self._score_shape
+        alt_idx = alt_logp = entropy = None
+        if shape is not None:
+            width = min(max(K, 1), 64)      # (a K out of range is refused before anything is written)
+            alt_idx = np.empty(shape + (width,), np.int32)
+            alt_logp = np.empty(shape + (width,), np.float32)
+            entropy = np.empty(shape, np.float32) if want_entropy else None
+        nv.check(self.lib.casv_score_get_alternatives(self.handle, K, nv.ptr(alt_idx), nv.ptr(alt_logp), nv.ptr(entropy)))
+        return alt_idx, alt_logp, entropy
 
     def score_release(self):
         """Drop the forward-only state score_targets keeps outside a training session (allowed when there is none)."""
@@ -467,6 +490,20 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_score_rows(self.handle, R, V, nv.ptr(logits), nv.ptr(target), float(pad_value), nv.ptr(logp),
                                                 nv.ptr(best), nv.ptr(rank)))
         return logp, best, rank
+
+    def debug_alternatives_rows(self, logits, K, pad_value=0.0):
+        """Test support (casv_debug_alternatives_rows): score_alternatives' kernel alone on logits (R,V); the padding columns of the
+        device rows hold pad_value.  Returns (alt_idx (R,K), alt_logp (R,K), entropy (R))."""
+        logits = nv.carray(logits, np.float32)
+        R, V = logits.shape
+        K = int(K)
+        width = min(max(K, 1), 64)
+        alt_idx = np.empty((R, width), np.int32)
+        alt_logp = np.empty((R, width), np.float32)
+        entropy = np.empty((R,), np.float32)
+        nv.check(self.lib.casv_debug_alternatives_rows(self.handle, R, V, K, nv.ptr(logits), float(pad_value), nv.ptr(alt_idx),
+                                                       nv.ptr(alt_logp), nv.ptr(entropy)))
+        return alt_idx, alt_logp, entropy
 
     # -- measurement ---------------------------------------------------------------------------
     def profile(self, enable=True):

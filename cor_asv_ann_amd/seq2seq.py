@@ -26,6 +26,20 @@ from .realign import SparseAlignment
 _UNSUPPORTED = ('lm_loss', 'lm_predict', 'scheduled_sampling', 'stateful')
 
 
+def alternatives_to_confmat(alternatives_of_a_line, floor=0.0):
+    """One line's alternatives, as `Sequence2Sequence.score_alternatives` returns them, in the confusion-network form that
+    `correct_lines(conf=...)` reads: one chunk per position, each a list of (char, p) with p = exp(logp).  Alternatives with
+    p < `floor` are dropped, except the first of a position, which is never dropped; a position without alternatives (an
+    invalid row) is left out."""
+    line = []
+    for position in alternatives_of_a_line:
+        chunk = [(char, math.exp(logp)) for char, logp in position]
+        chunk = chunk[:1] + [(char, p) for char, p in chunk[1:] if p >= floor]
+        if chunk:
+            line.append(chunk)
+    return line
+
+
 class _ShortSwitchInterval(object):
     """The interpreter's thread switch interval is process-wide: a counted guard, so that overlapping pipelines (two
     `correct_batches` generators, or one that is never exhausted) neither restore each other's saved value in the wrong
@@ -678,6 +692,40 @@ class Sequence2Sequence(object):
                 ranks[j] = rank[i, :k].tolist()
                 aligns[j] = self._alignment_rows(align, i, k, idx.shape[1])
         return logprobs, scores, predictions, ranks, aligns
+
+    def score_alternatives(self, sources, targets, conf=None, k=4):
+        """What else the model would have written at each position of the given targets: the `k` most probable characters of
+        every target position with their log-probabilities, and the entropy of the position's distribution -- the rest of the
+        distribution whose target entry `score_lines` returns (`HipEngine.score_alternatives` behind `HipEngine.score_targets`;
+        the same skipping rule and the same chunks of `batch_size` as `score_lines`, so the two see identical batches).  Returns
+        (alternatives, entropies), one entry per pair:
+        alternatives -- list over the scored positions of the target, newline included; each position a list of up to `k`
+        (char, logp) tuples, most probable first (natural log, ties to the lower vocabulary index).  Vocabulary index 0, the
+        unmapped / padding entry whose character is '', is left out of the lists (the engine method's raw arrays keep it);
+        entropies -- list of floats (nats) per scored position.
+        A skipped pair gives [], [].  With `k` > `voc_size` the call uses `voc_size`; the engine takes at most 64.
+        `alternatives_to_confmat` turns a line's alternatives into the `conf` input of `correct_lines`."""
+        assert self.status == 2
+        assert len(sources) == len(targets) and (conf is None or len(conf) == len(sources))
+        from .training import batch_to_indices
+        eng = self._require_engine()
+        n = len(sources)
+        K = min(int(k), self.voc_size)
+        chars = self.mapping[1]
+        alternatives, entropies = [[] for _ in range(n)], [[] for _ in range(n)]
+        live = [j for j in range(n) if sources[j] and targets[j]]
+        for start in range(0, len(live), self.batch_size):
+            chunk = live[start:start + self.batch_size]
+            idx, val, dec_in, dec_out, _ = batch_to_indices(self, [sources[j] for j in chunk], [targets[j] for j in chunk],
+                                                            None if conf is None else [conf[j] for j in chunk])
+            count = eng.score_targets(idx, val, dec_in, dec_out, want_align=False)[4]
+            alt_idx, alt_logp, entropy = eng.score_alternatives(K)
+            for i, j in enumerate(chunk):
+                c = int(count[i])               # (the scored positions are the first c: the target's characters)
+                alternatives[j] = [[(chars[v], lp) for v, lp in zip(alt_idx[i, u].tolist(), alt_logp[i, u].tolist()) if chars.get(v)]
+                                   for u in range(c)]           # (0: no character; -1, an invalid row: none either)
+                entropies[j] = entropy[i, :c].tolist()
+        return alternatives, entropies
 
     def score_candidates(self, sources, candidates, conf=None, alignments=False):
         """`score_lines` for several candidate targets per source -- rescoring an n-best list -- with ONE encoder pass per source

@@ -250,6 +250,20 @@ int casv_score_candidates(casv_model* m, int32_t B, int32_t N, int32_t T, int32_
  * from there (zeros beyond the window), K >= 2*window_width+1; after casv_score_candidates B is its B*N rows.  CASV_ERR_STATE once
  * a train step or casv_score_release has run since. */
 int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w);
+/* The K likeliest characters and the entropy of every position of the LAST casv_score_targets / casv_score_candidates call (kt:407
+ * / s2s:491-497: the rest of the distribution whose target entry the call returned), read from the logits the call left on the
+ * device.  alt_idx / alt_logp (rows,U,K), entropy (rows,U) or NULL; rows = B, or B*N after casv_score_candidates (decoder row
+ * b*N + n).  Per position, over the V logits x of the row, in a total order -- x descending, compared as floats (-0.0 == +0.0),
+ * ties to the lower index first -- alt_idx holds the first K entries; entries equal to -inf are ordinary members (last, in index
+ * order, alt_logp -inf).  alt_logp[j] = (x[alt_idx[j]] - m) - logf(sum) with the head's m and sum: the bits of the logp that
+ * casv_score_targets returns for target alt_idx[j] on the same row.  entropy = logf(sum) - (sum of expf(x - m) (x - m)) / sum in
+ * float32 over the entries above -inf (an -inf entry adds 0).  A row with a NaN entry or a maximum that is not finite gives
+ * alt_idx -1, alt_logp NaN, entropy NaN.  Unscored positions (dec_out = -1) are filled like any other: the distribution exists
+ * whether or not a target was given.  K outside [1, min(V, 64)] is CASV_ERR_ARG, found before any launch.  State rules of
+ * casv_score_get_alignments_sparse: CASV_ERR_STATE when there is no scoring call to read, and once a train step or
+ * casv_score_release has run since; inside and outside a training session; the call changes nothing a later call reads and may be
+ * repeated, with different K, after one scoring call. */
+int casv_score_get_alternatives(casv_model* m, int32_t K, int32_t* alt_idx, float* alt_logp, float* entropy);
 /* Drop the forward-only state of casv_score_targets (kt:407 / s2s:491-497); allowed when there is none. */
 int casv_score_release(casv_model* m);
 /* Test support, like casv_debug_activation: the scoring head (kt:407 / s2s:491-497) alone on the caller's logits (R,V) and targets
@@ -257,6 +271,12 @@ int casv_score_release(casv_model* m);
  * no output may depend on.  tests/test_gpu_score.py compares the results with float64. */
 int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
                           float* logp, int32_t* best, int32_t* rank);
+/* Test support, the counterpart of casv_debug_score_rows for casv_score_get_alternatives (kt:407 / s2s:491-497): its kernel alone on
+ * the caller's logits (R,V), 1 <= K <= min(V, 64); alt_idx / alt_logp (R,K), entropy (R) or NULL.  The entry lays the rows out with
+ * the row stride Vp = (V+31)&~31 and fills the columns [V, Vp) with pad_value, which no output may depend on.
+ * tests/test_gpu_score_alternatives.py compares the results with float64 and with casv_debug_score_rows. */
+int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, float pad_value,
+                                 int32_t* alt_idx, float* alt_logp, float* entropy);
 
 /* Multi-GPU: lines are independent (seq2seq.py:113 stateful=False), so one process per GPU decodes a
  * contiguous shard of the lines with its own handle and NO data-path collective; what crosses the GPUs is one all-gather
