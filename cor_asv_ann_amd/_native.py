@@ -86,6 +86,10 @@ SIGNATURES = {
     'casv_score_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_score_get_alternatives': (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'casv_score_release': (c_int, [c_void_p]),
+    'casv_train_step_soft': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32]
+                             + [c_void_p] * 6 + [POINTER(c_double), POINTER(c_double)]),
+    'casv_debug_soft_ce_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                        c_int32, POINTER(c_double), c_void_p, c_int32]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'casv_debug_alternatives_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'casv_profile': (c_int, [c_void_p, c_int32]),

@@ -20,6 +20,8 @@
 //   7 backward_layers  decoder / encoder pairs downwards, embedding                    -- give-up check
 //   8 update           regulariser, norm, clipped Adam, results
 // train_plan.h decides and counts the persistent launches of a step; persist_launch is the one place that asks it and launches.
+// casv_train_step_soft is the same step on soft targets: K (index, mass) slots per position (Step::K / soft_idx / soft_q) staged in
+// place of the target indices in phase 2, the soft head's launcher in phase 5; every other phase does not know the difference.
 // casv_score_targets (teacher-forced log-probabilities of given targets) makes the same two attempts (score_attempt): phases 1-4 as
 // they are, then the projection and the scoring head in place of the loss -- give-up check; on a forward-only state outside a session.
 // casv_score_candidates is the same call with N targets per source: the encoder side of the forward phases works on the Be sources,
@@ -62,6 +64,7 @@ struct TrainState {
     int B = 0, T = 0, U = 0, A = 0;        // B: the step's batch = the decoder's rows
     int Be = 0, N = 1;                     // the encoder's lines and the decoder rows per line, Be * N == B (N > 1: casv_score_candidates only)
     DevBuf e_idx, e_val, d_in, d_out, d_w, m_enc, m_dec, m_cell;
+    DevBuf d_sidx, d_sq;                   // casv_train_step_soft: the soft targets' slots [B][U][K] (index, mass) in place of d_out
     DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
     std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])
     std::vector<DevBuf> XD;                // deep_bidirectional_encoder: layer n's input = the cross sum of O[n-1] (seq2seq.py:246-259)
@@ -216,7 +219,7 @@ static void release_state(casv_model* m, TrainState* ts) {
         &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
         &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
         &ts->seg_dec_pos, &ts->s_logp, &ts->s_best, &ts->s_rank, &ts->s_nll, &ts->s_count, &ts->s_lo, &ts->s_w,
-        &ts->s_alt_idx, &ts->s_alt_logp, &ts->s_entropy};
+        &ts->s_alt_idx, &ts->s_alt_logp, &ts->s_entropy, &ts->d_sidx, &ts->d_sq};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : ts->O) b.release();
     for (auto& b : ts->DO) b.release();
@@ -606,6 +609,7 @@ struct Step {
     int Be, N;                      // the encoder's lines, decoder rows per line: Be * N == B (casv_train_step: Be = B, N = 1)
     const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
     const float* mask_enc; const float* mask_dec; const float* mask_cell;
+    int K; const int32_t* soft_idx; const float* soft_q;      // casv_train_step_soft: K > 0, (B,U,K) slots in place of dec_out (nullptr)
     int W, V, Vp, C, D;
     long long TB, UB;
     // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent
@@ -673,6 +677,7 @@ static int plan_buffers(Step& s) {
         ENS(ts->seg_enc_off, (size_t)(V + 1) * 4) ENS(ts->seg_enc_pos, (size_t)TB * A * 4) ENS(ts->seg_dec_off, (size_t)(V + 1) * 4) ENS(ts->seg_dec_pos, (size_t)UB * 4)
     }
     if (s.bridged) { ENS(ts->hbr, (size_t)D * Be * W * 4) ENS(ts->cbr, (size_t)D * Be * W * 4) ENS(ts->brtmp, (size_t)Be * W * 4) }
+    if (s.K > 0) { ENS(ts->d_sidx, UB * s.K * 4) ENS(ts->d_sq, UB * s.K * 4) }
     if (s.N > 1) { ENS(ts->h0rep, (size_t)D * B * W * 4) ENS(ts->c0rep, (size_t)D * B * W * 4) }
     if (s.residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
     for (int n = 1; n <= D; ++n) ENS(ts->O[n], TB * ((n == 1 || deep) ? 2 * W : W) * 4)
@@ -714,7 +719,10 @@ static int stage_inputs(Step& s) {
     HIPCHK(hipMemcpyAsync(ts->e_idx.p, s.enc_idx, TB * A * 4, hipMemcpyHostToDevice, st));
     if (s.enc_val) HIPCHK(hipMemcpyAsync(ts->e_val.p, s.enc_val, TB * A * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_in.p, s.dec_in, UB * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ts->d_out.p, s.dec_out, UB * 4, hipMemcpyHostToDevice, st));
+    if (s.K > 0) {
+        HIPCHK(hipMemcpyAsync(ts->d_sidx.p, s.soft_idx, UB * s.K * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ts->d_sq.p, s.soft_q, UB * s.K * 4, hipMemcpyHostToDevice, st));
+    } else HIPCHK(hipMemcpyAsync(ts->d_out.p, s.dec_out, UB * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_w.p, s.weights, UB * 4, hipMemcpyHostToDevice, st));
     if (s.det) {
         char_segments(s.enc_idx, s.Be, T, A, V, ts->h_seg_enc_off, ts->h_seg_enc_pos);
@@ -930,8 +938,15 @@ static int loss_head(Step& s) {
     TrainState* ts = s.ts; hipStream_t st = s.st;
     const int B = s.B, U = s.U, V = s.V, Vp = s.Vp;
     if (int rc = projection(s)) return rc;
-    launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, s.inv_count, ts->loss.as<double>(),
-                      s.training ? 1 : 0, st, s.parts);
+    hipEvent_t ev{};            // (casv_profile, class "softmax": the head reads the logits once and, training, writes them once)
+    s.m->prof_begin(PC_SOFTMAX, 0.0, 4.0 * (double)s.UB * (V + (s.training ? Vp : 0)) + 8.0 * (double)s.UB * s.K, ev);
+    if (s.K > 0)
+        launch_soft_ce(ts->logits.as<float>(), ts->d_sidx.as<int>(), ts->d_sq.as<float>(), ts->d_w.as<float>(), B, U, V, Vp, s.K, s.inv_count,
+                       ts->loss.as<double>(), s.training ? 1 : 0, st, s.parts);
+    else
+        launch_softmax_ce(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), B, U, V, Vp, s.inv_count, ts->loss.as<double>(),
+                          s.training ? 1 : 0, st, s.parts);
+    s.m->prof_end(PC_SOFTMAX, ev);
     return 0;
 }
 
@@ -1318,6 +1333,94 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
         if (!redo) return CASV_OK;
     }
     return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
+}
+
+// The soft targets' rules (include/cor_asv_ann_hip.h), checked on the host before anything is launched or cleared: O(B*U*K).
+static int check_soft_targets(long long positions, int K, int V, const int32_t* soft_idx, const float* soft_q) {
+    if (K < 1 || K > V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, V < 64 ? V : 64);
+    for (long long p = 0; p < positions; ++p) {
+        const int32_t* ix = soft_idx + p * K; const float* q = soft_q + p * K;
+        for (int k = 0; k < K; ++k) {
+            if (ix[k] < -1 || ix[k] >= V) return fail(CASV_ERR_ARG, "soft_idx[%lld][%d] = %d outside [-1, %d)", p, k, ix[k], V);
+            if (ix[k] < 0) continue;
+            if (!(q[k] >= 0.f) || q[k] == INFINITY) return fail(CASV_ERR_ARG, "soft_q[%lld][%d] = %g: a mass is finite and >= 0", p, k, (double)q[k]);
+            for (int j = 0; j < k; ++j)
+                if (ix[j] == ix[k]) return fail(CASV_ERR_ARG, "soft_idx[%lld]: index %d in slots %d and %d", p, ix[k], j, k);
+        }
+    }
+    return CASV_OK;
+}
+
+// casv_train_step with the target array replaced by K (index, mass) slots per position: the same view, the same attempts.
+extern "C" int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                                    const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, int32_t K,
+                                    const int32_t* soft_idx, const float* soft_q, const float* weights, const float* mask_enc,
+                                    const float* mask_dec, const float* mask_cell, double* loss_out, double* norm_out) {
+    if (!m || !enc_idx || !dec_in || !soft_idx || !soft_q || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
+    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
+    if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
+    if (int rc = check_soft_targets((long long)B * U, K, m->V, soft_idx, soft_q)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
+    OrderedScope ordered(m, m->deterministic);
+    Step s{};
+    s.m = m; s.ts = m->train; s.st = m->stream;
+    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
+    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = nullptr; s.weights = weights;
+    s.K = K; s.soft_idx = soft_idx; s.soft_q = soft_q;
+    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
+    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
+    s.TB = (long long)T * B; s.UB = (long long)U * B;
+    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
+    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
+    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool redo = false;
+        if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
+        if (!redo) return CASV_OK;
+    }
+    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
+}
+
+// Test support: soft_ce_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out (B = R, U = 1).
+extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, const int32_t* soft_idx,
+                                       const float* soft_q, const float* weight, float inv_count, float pad_value, int32_t want_grad,
+                                       double* loss, float* dlogits, int32_t ordered) {
+    if (!m || !logits || !soft_idx || !soft_q || !weight || !loss || (want_grad && !dlogits)) return fail(CASV_ERR_ARG, "null argument");
+    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
+    if (int rc = check_soft_targets(R, K, V, soft_idx, soft_q)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    const int Vp = (V + 31) & ~31;
+    std::vector<float> x((size_t)R * Vp, pad_value);
+    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
+    DevBuf dx, di, dq, dw, dl, dp;
+    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
+        release_on_exit{{&dx, &di, &dq, &dw, &dl, &dp}, m->stream};
+    if (int rc = dx.ensure(x.size() * 4)) return rc;
+    if (int rc = di.ensure((size_t)R * K * 4)) return rc;
+    if (int rc = dq.ensure((size_t)R * K * 4)) return rc;
+    if (int rc = dw.ensure((size_t)R * 4)) return rc;
+    if (int rc = dl.ensure(16)) return rc;
+    if (int rc = dp.ensure((size_t)2048 * 8)) return rc;         // (launch_soft_ce: at most 2048 workgroups)
+    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(di.p, soft_idx, (size_t)R * K * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dq.p, soft_q, (size_t)R * K * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dw.p, weight, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemsetAsync(dl.p, 0, 16, m->stream));
+    launch_soft_ce(dx.as<float>(), di.as<int>(), dq.as<float>(), dw.as<float>(), R, 1, V, Vp, K, inv_count, dl.as<double>(),
+                   want_grad ? 1 : 0, m->stream, ordered ? dp.as<double>() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(loss, dl.p, 8, hipMemcpyDeviceToHost, m->stream));
+    if (want_grad) HIPCHK(hipMemcpyAsync(x.data(), dx.p, x.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (want_grad)
+        for (int r = 0; r < R; ++r) {
+            for (int v = V; v < Vp; ++v)
+                if (x[(size_t)r * Vp + v] != 0.f) return fail(CASV_ERR_HIP, "soft head: padding column %d of row %d is %g, not zero", v, r, (double)x[(size_t)r * Vp + v]);
+            memcpy(dlogits + (size_t)r * V, &x[(size_t)r * Vp], (size_t)V * 4);
+        }
+    return CASV_OK;
 }
 
 // ---- scoring: teacher-forced log-probabilities of given targets (kt:407 / s2s:491-497, the forward pass of a mode-0 step) ----

@@ -26,6 +26,12 @@ void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, lon
 // parts (ordered form, "deterministic" train step): [min(ceil(B*U/4), 2048)] doubles of workspace, or nullptr
 void launch_softmax_ce(float* logits, const int* target, const float* weight, int B, int U, int V, int Vp, float inv_count,
                        double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
+// The same head on soft targets (casv_train_step_soft): soft_idx / soft_q [B][U][K], 1 <= K <= 64, slot k of a position = (index,
+// mass), index -1 = empty; per row loss += w * inv_count * sum_k q_k * -log(clip(p[i_k])), dlogit[v] = (p_v * S - q_k ok_k of the
+// slot with i_k == v) * w * inv_count with ok_k = 1e-7 < p[i_k] < 1 - 1e-7 and S = sum_k q_k ok_k.  The indices of a position are
+// distinct (the caller checks).  One slot (i, 1.0) gives launch_softmax_ce's bits for target i.  parts as launch_softmax_ce.
+void launch_soft_ce(float* logits, const int* soft_idx, const float* soft_q, const float* weight, int B, int U, int V, int Vp, int K,
+                    float inv_count, double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
 // Scoring head (casv_score_targets): per row r = u * B + b of the logits [U*B][Vp] and target t = target[b][u], in the caller's
 // (B,U) order -- logp = log softmax(x)[t] in the log domain, unclipped (0 where t = -1); best = lowest index of the row's maximum;
 // rank = entries strictly above x[t] (-1 where unscored).  A row with a NaN among its V entries or a maximum that is not finite

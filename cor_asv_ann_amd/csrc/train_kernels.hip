@@ -231,6 +231,83 @@ void launch_softmax_ce(float* logits, const int* target, const float* weight, in
                        Vp, inv_count, loss, want_grad);
 }
 
+// ---- the same head on soft targets (casv_train_step_soft): K (index, mass) slots per row instead of one index ----
+// One wave per row and m, sum and p_v formed as softmax_ce_kernel forms them.  Lane k holds slot k (K <= 64; index -1 = empty): its
+// p[i_k], its loss term q_k * -log(clip(p)) and q_k * ok_k, ok_k the hard head's strict rule for that entry; the terms and
+// S = sum q_k ok_k are summed across the wave by the butterfly (one order whatever the launch shape).  With one slot (i, 1.0) every
+// value has the bits of softmax_ce_kernel's for target i.  dlogit[v] = (p_v * S - q ok of the slot with i_k == v) * w * inv_count:
+// the dense pass looks the slots up, lane k's pair broadcast to the wave in the order of k (the indices of a row are distinct, so
+// at most one matches), outside every divergent branch -- one store per element, by the lane that owns it; no LDS, no atomics.
+// Columns [V, Vp) are never read and written as zeros.
+template <bool ORDERED>
+__global__ __launch_bounds__(256) void soft_ce_kernel(float* __restrict__ logits, const int* __restrict__ soft_idx,
+                                                      const float* __restrict__ soft_q, const float* __restrict__ weight, long long rows,
+                                                      int B, int U, int V, int Vp, int K, float inv_count, double* __restrict__ loss,
+                                                      int want_grad) {
+    __shared__ double part[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double mine = 0.0;
+    for (long long r = blockIdx.x * 4LL + wave; r < rows; r += 4LL * gridDim.x) {
+        float* x = logits + r * Vp;
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+        m = wave_butterfly(m, [](float a, float b) { return fmaxf(a, b); });
+        float sum = 0.f;
+        for (int v = lane; v < V; v += 64) sum += expf(x[v] - m);
+        sum = wsum(sum);
+        const long long src = (r % B) * U + r / B;        // row r = t*B + b  <-  (b, t) of the caller's (B,U,K) arrays
+        const float wgt = weight[src];
+        int ik = -1;
+        float qk = 0.f;
+        if (lane < K) { ik = soft_idx[src * K + lane]; qk = soft_q[src * K + lane]; }
+        const bool slot = ik >= 0 && ik < V;
+        if (!slot) ik = -1;
+        float term = 0.f, qok = 0.f;
+        if (slot) {
+            const float pk = expf(x[ik] - m) / sum;
+            term = qk * -logf(fminf(fmaxf(pk, 1e-7f), 1.0f - 1e-7f));
+            if (pk > 1e-7f && pk < 1.0f - 1e-7f) qok = qk;               // tf.clip_by_value passes gradient inside only
+        }
+        const float terms = wsum(term), S = wsum(qok);
+        if (__ballot(slot) != 0ull) mine += (double)(terms * wgt * inv_count);      // (the same value in every lane)
+        if (want_grad) {
+            const float sc = wgt * inv_count;
+            for (int v0 = 0; v0 < Vp; v0 += 64) {
+                const int v = v0 + lane;
+                float sub = 0.f;
+                for (int k = 0; k < K; ++k) {
+                    const int i = __builtin_amdgcn_readlane(ik, k);
+                    const float q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qok), k));
+                    sub = i == v ? q : sub;
+                }
+                float gvl = 0.f;
+                if (v < V) gvl = (expf(x[v] - m) / sum * S - sub) * sc;
+                if (v < Vp) x[v] = gvl;
+            }
+        }
+    }
+    if (lane == 0) part[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s4 = part[0] + part[1] + part[2] + part[3];
+        if (ORDERED) loss[blockIdx.x] = s4;
+        else if (s4 != 0.0) atomicAdd(loss, s4);
+    }
+}
+void launch_soft_ce(float* logits, const int* soft_idx, const float* soft_q, const float* weight, int B, int U, int V, int Vp, int K,
+                    float inv_count, double* loss, int want_grad, hipStream_t st, double* parts) {
+    const long long rows = (long long)B * U;
+    const long long wgs = std::min<long long>((rows + 3) / 4, 2048);
+    if (parts) {
+        hipLaunchKernelGGL(soft_ce_kernel<true>, dim3((unsigned)wgs), dim3(256), 0, st, logits, soft_idx, soft_q, weight, rows, B, U, V,
+                           Vp, K, inv_count, parts, want_grad);
+        ordered_sum(parts, (int)wgs, loss, st);
+        return;
+    }
+    hipLaunchKernelGGL(soft_ce_kernel<false>, dim3((unsigned)wgs), dim3(256), 0, st, logits, soft_idx, soft_q, weight, rows, B, U, V,
+                       Vp, K, inv_count, loss, want_grad);
+}
+
 // ---- scoring head (casv_score_targets, kt:407 / s2s:491-497 without the clip): log-probability, argmax and rank per row ----
 // One wave per row, as softmax_ce_kernel; two passes over the row's first V columns (the padding columns [V, Vp) are never read):
 // the maximum and the NaN test, then the exponentials' sum, the lowest index of the maximum and the count of entries above the

@@ -320,6 +320,19 @@ class HipEngine(object):
         self._frozen = tuple(frozen)
         nv.check(self.lib.casv_train_begin(self.handle, byref(p), csv))
 
+    def _step_masks(self, masks):
+        """The train step's three mask arrays (enc, dec, cell) in the device's padded widths, or None each without masks."""
+        if masks is None:
+            return None, None, None
+        # (dead units are multiplied by zero whatever their mask says)
+        m_enc = nv.carray(np.concatenate([self._padw(np.asarray(x, np.float32).ravel(), 2 if (n == 0 or self.deep) else 1)
+                                          for n, x in enumerate(masks['enc'])]), np.float32)
+        m_dec = None
+        if self.depth > 1:
+            m_dec = nv.carray(np.concatenate([self._padw(np.asarray(x, np.float32).ravel()) for x in masks['dec']]), np.float32)
+        m_cell = nv.carray(self._padw(np.asarray(masks['cell'], np.float32), 1 + self.cblocks), np.float32)
+        return m_enc, m_dec, m_cell
+
     def train_step(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1):
         """One train_on_batch (mode 1), test_on_batch (mode 0) or loss+gradients (mode 2).
         enc_idx (B,T[,A]) int32, dec_in/dec_out (B,U) int32 (-1 = zero row), weights (B,U).
@@ -333,18 +346,35 @@ class HipEngine(object):
         dec_out = nv.carray(dec_out, np.int32)
         weights = nv.carray(weights, np.float32)
         U = dec_in.shape[1]
-        m_enc = m_dec = m_cell = None
-        if masks is not None:
-            # (dead units are multiplied by zero whatever their mask says)
-            m_enc = nv.carray(np.concatenate([self._padw(np.asarray(x, np.float32).ravel(), 2 if (n == 0 or self.deep) else 1)
-                                              for n, x in enumerate(masks['enc'])]), np.float32)
-            if self.depth > 1:
-                m_dec = nv.carray(np.concatenate([self._padw(np.asarray(x, np.float32).ravel()) for x in masks['dec']]), np.float32)
-            m_cell = nv.carray(self._padw(np.asarray(masks['cell'], np.float32), 1 + self.cblocks), np.float32)
+        m_enc, m_dec, m_cell = self._step_masks(masks)
         loss, norm = c_double(), c_double()
         nv.check(self.lib.casv_train_step(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
                                           nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
                                           byref(loss), byref(norm)))
+        return loss.value, norm.value
+
+    def train_step_soft(self, enc_idx, enc_val, dec_in, soft_idx, soft_q, weights, masks=None, mode=1):
+        """train_step on soft targets (casv_train_step_soft): soft_idx int32 / soft_q float32 (B,U,K) hold K (index, mass) slots
+        per position in place of dec_out -- index -1 = empty slot, all empty = zero row, masses finite and >= 0, a position's indices
+        distinct, 1 <= K <= min(V, 64) (NativeError CASV_ERR_ARG otherwise, nothing touched).  One slot (dec_out, 1.0) is the hard
+        step.  Everything else as train_step; returns (loss, grad_norm)."""
+        enc_idx = nv.carray(enc_idx, np.int32)
+        if enc_idx.ndim == 2:
+            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
+        B, T, A = enc_idx.shape
+        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        dec_in = nv.carray(dec_in, np.int32)
+        soft_idx = nv.carray(soft_idx, np.int32)
+        soft_q = nv.carray(soft_q, np.float32)
+        weights = nv.carray(weights, np.float32)
+        U = dec_in.shape[1]
+        assert soft_idx.ndim == 3 and soft_idx.shape[:2] == (B, U) and soft_q.shape == soft_idx.shape and weights.shape == (B, U)
+        K = soft_idx.shape[2]
+        m_enc, m_dec, m_cell = self._step_masks(masks)
+        loss, norm = c_double(), c_double()
+        nv.check(self.lib.casv_train_step_soft(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
+                                               K, nv.ptr(soft_idx), nv.ptr(soft_q), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec),
+                                               nv.ptr(m_cell), byref(loss), byref(norm)))
         return loss.value, norm.value
 
     def train_gradients(self):
@@ -504,6 +534,24 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_alternatives_rows(self.handle, R, V, K, nv.ptr(logits), float(pad_value), nv.ptr(alt_idx),
                                                        nv.ptr(alt_logp), nv.ptr(entropy)))
         return alt_idx, alt_logp, entropy
+
+    def debug_soft_ce_rows(self, logits, soft_idx, soft_q, weight, inv_count, pad_value=0.0, want_grad=True, ordered=False):
+        """Test support (casv_debug_soft_ce_rows): the soft-target loss head alone on logits (R,V), slots soft_idx / soft_q (R,K) and
+        weights (R); the padding columns of the device rows hold pad_value and are checked to come back as zeros.  Returns (loss
+        float64, dlogits (R,V) or None)."""
+        logits = nv.carray(logits, np.float32)
+        soft_idx = nv.carray(soft_idx, np.int32)
+        soft_q = nv.carray(soft_q, np.float32)
+        weight = nv.carray(weight, np.float32)
+        R, V = logits.shape
+        assert soft_idx.ndim == 2 and soft_idx.shape[0] == R and soft_q.shape == soft_idx.shape and weight.shape == (R,)
+        K = soft_idx.shape[1]
+        loss = c_double()
+        dlogits = np.empty((R, V), np.float32) if want_grad else None
+        nv.check(self.lib.casv_debug_soft_ce_rows(self.handle, R, V, K, nv.ptr(logits), nv.ptr(soft_idx), nv.ptr(soft_q), nv.ptr(weight),
+                                                  float(inv_count), float(pad_value), int(bool(want_grad)), byref(loss), nv.ptr(dlogits),
+                                                  int(bool(ordered))))
+        return loss.value, dlogits
 
     # -- measurement ---------------------------------------------------------------------------
     def profile(self, enable=True):

@@ -25,6 +25,7 @@ layers that is not named in `layer_names`, so that keras' `load_weights` and thi
     /training_state/best_val_loss               float64 scalar (inf: none yet)
     /training_state/adam                        float64[5]: lr, beta1, beta2, epsilon, clipnorm
     /training_state/frozen                      bytes: the frozen tensor-name prefixes, comma-separated
+    /training_state/{distill_k,distill_alpha}   int64 / float64 scalars: a distilled run's K and alpha (absent: no teacher)
     /training_state/rng                         bytes: JSON of the numpy bit generator's state
     /training_state/split_rand                  float64[lines]: the validation split (absent: validation files were given)
     /training_state/history_{loss,val_loss}     float64[epochs]
@@ -253,6 +254,9 @@ def _write_state(w, st):
     w.create_dataset(g + 'adam', np.asarray(st['adam'], np.float64).reshape(5))
     w.create_dataset(g + 'frozen', np.bytes_(','.join(st['frozen']).encode('utf-8') or b','))
     w.create_dataset(g + 'rng', np.bytes_(json.dumps(st['rng']).encode('utf-8')))
+    if st.get('distill') is not None:
+        w.create_dataset(g + 'distill_k', np.asarray(int(st['distill'][0]), np.int64))
+        w.create_dataset(g + 'distill_alpha', np.asarray(float(st['distill'][1]), np.float64))
     if st.get('split_rand') is not None:
         w.create_dataset(g + 'split_rand', np.asarray(st['split_rand'], np.float64))
     hist = st.get('history') or []
@@ -283,6 +287,8 @@ def read_training_state(filename):
         st['frozen'] = [p for p in text('frozen').split(',') if p]
         st['rng'] = json.loads(text('rng'))
         st['split_rand'] = np.asarray(g['split_rand'].read(), np.float64) if 'split_rand' in g else None
+        if 'distill_k' in g:           # (a distilled run only: a plain run's state has the keys it always had)
+            st['distill'] = (int(np.asarray(g['distill_k'].read())), float(np.asarray(g['distill_alpha'].read())))
         st['history'] = []
         if 'history_loss' in g:
             st['history'] = [{'loss': float(a), 'val_loss': float(b)} for a, b in

@@ -40,6 +40,53 @@ def alternatives_to_confmat(alternatives_of_a_line, floor=0.0):
     return line
 
 
+def alternatives_to_soft_targets(alt_idx, alt_logp, dec_out, alpha=0.5, renormalise=True):
+    """Soft targets for `HipEngine.train_step_soft` from a teacher's alternatives: `alt_idx` / `alt_logp` (rows,U,K) as
+    `HipEngine.score_alternatives` returns them for the batch, `dec_out` (rows,U) the hard targets (-1 = unscored).  Returns
+    (soft_idx int32, soft_q float32), both (rows,U,K+1).  Per scored position the teacher's mass of alternative k is
+    exp(alt_logp[k]) in float32 -- divided by the sum over the K entries when `renormalise` -- times 1 - `alpha`; the hard target
+    gets `alpha`, added to its own slot when it is among the K, put into the spare slot K otherwise (which stays empty, index -1,
+    in the first case).  A position with dec_out = -1 gets all-empty slots (a true-zero target row); a position the teacher calls
+    invalid (alt_idx = -1) falls back to the one-hot row, one slot (target, 1.0), and so does every scored position at alpha = 1.
+    Temperature scaling is the caller's: apply it to `alt_logp` first."""
+    alt_idx = np.asarray(alt_idx, np.int32)
+    alt_logp = np.asarray(alt_logp, np.float32)
+    dec_out = np.asarray(dec_out, np.int32)
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError('alpha must be in [0, 1], got %r' % alpha)
+    if alt_idx.ndim != 3 or alt_logp.shape != alt_idx.shape or dec_out.shape != alt_idx.shape[:2]:
+        raise ValueError('alt_idx / alt_logp must be (rows,U,K) and dec_out (rows,U), got %s, %s and %s'
+                         % (alt_idx.shape, alt_logp.shape, dec_out.shape))
+    K = alt_idx.shape[2]
+    soft_idx = np.full(dec_out.shape + (K + 1,), -1, np.int32)
+    soft_q = np.zeros(dec_out.shape + (K + 1,), np.float32)
+    scored = dec_out >= 0
+    taught = scored & (alt_idx >= 0).all(axis=2) & ~np.isnan(alt_logp).any(axis=2) & (alpha < 1.0)
+    onehot = scored & ~taught
+    soft_idx[onehot, 0] = dec_out[onehot]
+    soft_q[onehot, 0] = 1.0
+    if taught.any():
+        with np.errstate(under='ignore'):
+            mass = np.exp(alt_logp[taught])                              # (n,K) float32
+        if renormalise:
+            mass = mass / mass.sum(axis=1, dtype=np.float32, keepdims=True)
+        q = np.zeros((mass.shape[0], K + 1), np.float32)
+        q[:, :K] = np.float32(1.0 - alpha) * mass
+        idx = np.full((mass.shape[0], K + 1), -1, np.int32)
+        idx[:, :K] = alt_idx[taught]
+        target = dec_out[taught]
+        hit = idx[:, :K] == target[:, None]
+        inside = hit.any(axis=1)
+        slot = np.where(inside, hit.argmax(axis=1), K)
+        rows = np.arange(mass.shape[0])
+        idx[rows, slot] = target
+        q[rows, slot] += np.float32(alpha)
+        soft_idx[taught] = idx
+        soft_q[taught] = q
+    return soft_idx, soft_q
+
+
 class _ShortSwitchInterval(object):
     """The interpreter's thread switch interval is process-wide: a counted guard, so that overlapping pipelines (two
     `correct_batches` generators, or one that is never exhausted) neither restore each other's saved value in the wrong
@@ -1141,12 +1188,20 @@ class Sequence2Sequence(object):
             for k in names:
                 self.logger.info('%s %-7s %.3f±%.3f', what, labels[k].strip() + ':', counts[k].mean, math.sqrt(counts[k].varia))
 
-    def train(self, filenames, val_filenames=None, resume=None):
+    def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5):
         """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
         from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
-        restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint)."""
+        restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint).
+        teacher: a second configured and loaded `Sequence2Sequence` to distil from -- every training batch is scored by the teacher
+        (`HipEngine.score_targets` on the batch as the student sees it), its `distill_k` likeliest characters per target position
+        become soft targets (`alternatives_to_soft_targets` with alpha = `distill_alpha`, the hard target's share) and the step
+        is `HipEngine.train_step_soft`.  The teacher must have this model's `voc_size` and character mapping once the files'
+        characters are mapped (ValueError otherwise, before anything runs); validation stays the hard loss, so `val_loss`, early
+        stopping and the checkpoints' names mean what they mean without a teacher.  A distilled run's state checkpoints record
+        `distill_k` and `distill_alpha`; `resume` refuses a mismatch or a missing teacher.  distill_alpha = 1 is plain training."""
         from .training import train_files
-        return train_files(self, filenames, val_filenames, resume=resume)
+        return train_files(self, filenames, val_filenames, resume=resume, teacher=teacher, distill_k=distill_k,
+                           distill_alpha=distill_alpha)
 
 
 class _EncoderModel(object):

@@ -1,6 +1,7 @@
 """Host side of `Sequence2Sequence.train()` (seq2seq.py:590-649 + lib/keras_train.py:27-438): epochs over the
 generator, validation, early stopping / NaN termination / per-epoch checkpoints.  Each batch is ONE call into
-the C ABI (`casv_train_step`), which runs forward, backward, clipping and Adam on the device."""
+the C ABI (`casv_train_step`), which runs forward, backward, clipping and Adam on the device.  With a teacher
+(distillation) a batch is the teacher's scoring call, its K alternatives per position and `casv_train_step_soft`."""
 import queue
 import signal
 import threading
@@ -164,14 +165,66 @@ def resume_state(s2s, filename):
     return state
 
 
-def train_files(s2s, filenames, val_filenames=None, resume=None):
+def check_teacher(s2s, teacher, distill_k, distill_alpha):
+    """What distillation asks of the pair, checked on the host before anything runs: the teacher is another, loaded model with the
+    student's vocabulary size and character mapping (the soft targets are the teacher's indices), K + 1 slots fit the loss head,
+    alpha is a share.  Raises ValueError with the first difference."""
+    if teacher is s2s:
+        raise ValueError('cannot distil a model from itself')
+    if getattr(teacher, 'status', 0) != 2:
+        raise ValueError('the teacher must be a configured and loaded model (status 2), its status is %r' % getattr(teacher, 'status', None))
+    if teacher.voc_size != s2s.voc_size:
+        raise ValueError('teacher and student differ in voc_size (teacher %d, student %d)' % (teacher.voc_size, s2s.voc_size))
+    if teacher.mapping[0] != s2s.mapping[0]:
+        theirs, mine = teacher.mapping[0], s2s.mapping[0]
+        char = next(c for c in sorted(set(theirs) | set(mine)) if theirs.get(c) != mine.get(c))
+        raise ValueError('teacher and student differ in their character mapping (%r: teacher %r, student %r)'
+                         % (char, theirs.get(char), mine.get(char)))
+    most = min(s2s.voc_size, 64) - 1
+    if int(distill_k) != distill_k or not 1 <= distill_k <= most:
+        raise ValueError('distill_k must be in [1, min(voc_size, 64) - 1] = [1, %d], got %r' % (most, distill_k))
+    if not 0.0 <= float(distill_alpha) <= 1.0:
+        raise ValueError('distill_alpha must be in [0, 1], got %r' % (distill_alpha,))
+
+
+def check_distill_resume(state, filename, teacher, distill_k, distill_alpha):
+    """A distilled run resumes as a distilled run with the same K and alpha, a plain run as a plain run: ValueError otherwise."""
+    theirs = state.get('distill')
+    if theirs is None and teacher is None:
+        return
+    if theirs is None:
+        raise ValueError('cannot resume from "%s": it was trained without a teacher' % filename)
+    if teacher is None:
+        raise ValueError('cannot resume from "%s": it was distilled (distill_k %d, distill_alpha %r), the teacher is missing'
+                         % (filename, theirs[0], theirs[1]))
+    if (int(theirs[0]), float(theirs[1])) != (int(distill_k), float(distill_alpha)):
+        raise ValueError('cannot resume from "%s": distillation differs (file distill_k %d, distill_alpha %r; now %d, %r)'
+                         % (filename, theirs[0], theirs[1], distill_k, distill_alpha))
+
+
+def distill_step(engine, teacher_engine, batch, distill_k, distill_alpha):
+    """One training batch with a teacher: the teacher scores the batch as the student sees it, its K likeliest characters per
+    position become the soft targets, the student takes the soft step."""
+    from .seq2seq import alternatives_to_soft_targets
+    idx, val, dec_in, dec_out, w, masks = batch
+    teacher_engine.score_targets(idx, val, dec_in, dec_out)
+    alt_idx, alt_logp, _ = teacher_engine.score_alternatives(distill_k, want_entropy=False)
+    soft_idx, soft_q = alternatives_to_soft_targets(alt_idx, alt_logp, dec_out, alpha=distill_alpha)
+    return engine.train_step_soft(idx, val, dec_in, soft_idx, soft_q, w, masks, mode=1)
+
+
+def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5):
     num_lines = s2s.map_files(filenames)
     s2s.logger.info('Training on "%d" files with %d lines', len(filenames), num_lines)
     if val_filenames:
         num_lines = s2s.map_files(val_filenames)
         s2s.logger.info('Validating on "%d" files with %d lines', len(val_filenames), num_lines)
         split_rand = None
+    if teacher is not None:
+        check_teacher(s2s, teacher, distill_k, distill_alpha)    # (after map_files: the student's mapping is final only now)
     state = resume_state(s2s, resume) if resume else None        # (after map_files: the mapping is part of what must match)
+    if state is not None:
+        check_distill_resume(state, resume, teacher, distill_k, distill_alpha)
     if val_filenames:
         if state is not None and state['split_rand'] is not None:
             raise ValueError('cannot resume from "%s": it was trained without validation files' % resume)
@@ -188,6 +241,10 @@ def train_files(s2s, filenames, val_filenames=None, resume=None):
     rng = s2s._rng
     engine = s2s._require_engine()
     engine.set_option('deterministic', 1 if s2s.deterministic else 0)
+    teacher_engine = None
+    if teacher is not None:
+        teacher_engine = teacher._require_engine()
+        teacher_engine.set_option('deterministic', 1 if s2s.deterministic else 0)      # (governs the scoring pass as it governs a step)
     adam = tuple(state['adam']) if state is not None else ADAM
     engine.train_begin(*adam, frozen=tuple(s2s.frozen_prefixes))
     if state is not None:
@@ -216,7 +273,10 @@ def train_files(s2s, filenames, val_filenames=None, resume=None):
             nan = cut = False
             # the next batches are vectorised by a worker thread while the device runs this one (kt:133-145)
             for idx, val, dec_in, dec_out, w, masks in prefetch(train_batches(s2s, filenames, split_rand, rng)):
-                loss, _ = engine.train_step(idx, val, dec_in, dec_out, w, masks, mode=1)
+                if teacher_engine is not None:
+                    loss, _ = distill_step(engine, teacher_engine, (idx, val, dec_in, dec_out, w, masks), distill_k, distill_alpha)
+                else:
+                    loss, _ = engine.train_step(idx, val, dec_in, dec_out, w, masks, mode=1)
                 if not np.isfinite(loss):
                     s2s.logger.warning('Batch %d: Invalid loss, terminating training', nb)   # TerminateOnNaN
                     nan = True
@@ -249,6 +309,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None):
                 ckpt_state = {'epoch': epoch + 1, 'step': step, 'wait': wait, 'best_epoch': best_epoch, 'best_val_loss': best,
                               'adam': adam, 'frozen': list(s2s.frozen_prefixes), 'rng': rng.bit_generator.state,
                               'split_rand': split_rand, 'history': history, 'm': m, 'v': v, 'best': best_weights or {}}
+                if teacher is not None:
+                    ckpt_state['distill'] = (int(distill_k), float(distill_alpha))
             keras_h5.write_model('model.ckpt.weights-%02d-%.2f.h5' % (epoch + 1, val_loss), s2s._config_dict(), weights, ckpt_state)
             if wait >= 3:                              # EarlyStopping(patience=3, restore_best_weights)
                 s2s.logger.info('Epoch %05d: early stopping', epoch + 1)
@@ -259,6 +321,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None):
         if old_handler is not None:
             signal.signal(signal.SIGINT, old_handler)
         engine.train_end()
+        if teacher_engine is not None:
+            teacher_engine.score_release()             # (the teacher's forward-only scoring state)
     s2s.history = history
     if best_weights is not None:
         s2s.logger.info('training finished with val_loss %f', best)

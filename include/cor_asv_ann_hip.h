@@ -194,6 +194,36 @@ int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U
                     const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
                     const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
                     double* loss, double* grad_norm);
+/* casv_train_step on soft targets: the target array dec_out (B,U) replaced by K (index, mass) slots per position, soft_idx /
+ * soft_q (B,U,K), 1 <= K <= min(V, 64) -- the sparse form of the dense float y_true (B,U,V) that the reference's graph takes
+ * (seq2seq.py:491-497; Keras' categorical_crossentropy is defined for any such row), and what casv_score_get_alternatives emits.
+ * Slot k of a position is (i_k, q_k): i_k = -1 marks an empty slot (its q_k is ignored); a position whose slots are all empty is
+ * a true-zero target row (no loss, a zero gradient row, like dec_out = -1); q_k is a finite float >= 0; the indices of one
+ * position are distinct; the masses need not sum to 1.  With x the row's V logits, m, sum and p_v = expf(x_v - m) / sum as the hard
+ * head forms them, w the position's weight and inv_count = 1 / max(number of nonzero weights, 1):
+ *   ok_k      = 1e-7 < p[i_k] < 1 - 1e-7                       (tf.clip_by_value passes gradient inside only, per entry)
+ *   loss     += w * inv_count * sum_k q_k * -logf(clip(p[i_k], 1e-7, 1 - 1e-7))
+ *   S         = sum_k q_k * ok_k
+ *   dlogit[v] = (p_v * S - sum_{k: i_k == v} q_k * ok_k) * w * inv_count
+ * the sums over k in one fixed order (a wave butterfly over the slots) whatever the launch shape.  One slot (dec_out, 1.0) per
+ * position gives casv_train_step's loss and gradients bit for bit with "deterministic".  Modes, masks, weights, the options
+ * ("deterministic", "persistent", "fused_backward", the arithmetic), the give-up path and everything behind dL/dlogits are
+ * casv_train_step's.  Checked on the host before anything is launched or cleared, each CASV_ERR_ARG with the session's step
+ * count, moments and gradients untouched: K outside [1, min(V, 64)]; an index outside [-1, V); a mass that is negative, NaN or
+ * infinite in a non-empty slot; an index repeated within a position. */
+int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                         const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, int32_t K,
+                         const int32_t* soft_idx, const float* soft_q, const float* weights, const float* mask_enc,
+                         const float* mask_dec, const float* mask_cell, double* loss, double* grad_norm);
+/* Test support, like casv_debug_score_rows: the soft-target loss head alone on the caller's logits (R,V), slots soft_idx / soft_q
+ * (R,K) and weights (R), with the caller's inv_count; the slots are checked as casv_train_step_soft checks them.  The entry lays
+ * the rows out with the row stride Vp = (V+31)&~31 and fills the columns [V, Vp) with pad_value, which no output may depend on.
+ * *loss = the rows' loss (ordered != 0: summed as the "deterministic" step sums it); want_grad != 0: dlogits (R,V) = the first V
+ * columns after the launch, and the entry checks that the padding columns came back as zeros (CASV_ERR_HIP with a message
+ * otherwise); want_grad = 0: the logits are not written and dlogits may be NULL. */
+int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, const int32_t* soft_idx,
+                            const float* soft_q, const float* weight, float inv_count, float pad_value, int32_t want_grad,
+                            double* loss, float* dlogits, int32_t ordered);
 /* Gradient of the last step for one tensor, in Keras layout (parity tests). */
 int casv_train_get_gradient(casv_model* m, const char* name, float* out, int64_t capacity);
 /* Adam's optimizer state of one trained tensor in Keras layout, like casv_train_get_gradient: which = 0 the first moment m,
