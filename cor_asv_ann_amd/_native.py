@@ -55,6 +55,14 @@ class DebugJob(Structure):
                 ('b_static', c_int32), ('epi_plain', c_int32)]
 
 
+class DebugBwdJob(Structure):
+    """casv_debug_bwd_job: one layer's backward time step (casv_debug_bwd_step)"""
+    _fields_ = [('rows', c_int32), ('W', c_int32), ('N', c_int32), ('Bt', c_void_p), ('a', c_void_p), ('lda', c_int64), ('mask_a', c_void_p),
+                ('b', c_void_p), ('ldb', c_int64), ('c', c_void_p), ('ldc', c_int64), ('c_prev', c_void_p), ('ld_cprev', c_int64),
+                ('gates', c_void_p), ('cell', c_void_p), ('dc_in', c_void_p), ('dz', c_void_p), ('dc', c_void_p), ('out', c_void_p),
+                ('ld_out', c_int64)]
+
+
 # name -> (restype, argtypes); every symbol declared in the header is listed here and checked at load
 SIGNATURES = {
     'casv_last_error': (c_char_p, []),
@@ -101,6 +109,7 @@ SIGNATURES = {
                                        c_void_p, c_int64, c_void_p]),
     'casv_debug_activation': (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     'casv_debug_gemm_jobs': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), c_int32, c_int32]),
+    'casv_debug_bwd_step': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugBwdJob)]),
     'casv_set_option': (c_int, [c_void_p, c_char_p, c_int64]),
     'casv_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_comm_unique_id': (c_int, [c_void_p]),

@@ -336,6 +336,8 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "train_give_ups")) { *value = m->stat_train_give_ups; return CASV_OK; }
     if (!strcmp(key, "gemm_jobs_forms")) { *value = m->stat_jobs[0]; return CASV_OK; }
     if (!strcmp(key, "gemm_jobs_launches")) { *value = m->stat_jobs[1]; return CASV_OK; }
+    if (!strcmp(key, "bwd_step_shares")) { *value = m->stat_bwd_step[0]; return CASV_OK; }
+    if (!strcmp(key, "bwd_step_groups")) { *value = m->stat_bwd_step[1]; return CASV_OK; }
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }

@@ -253,23 +253,18 @@ __global__ __launch_bounds__(256, 2) void lstm_bwd_gemm_kernel(const BwdStepBatc
     }
 }
 
-// K shares: as many as keep ~2 workgroups per CU busy, whole unit groups each
-void launch_lstm_bwd_gemm(const BwdStepBatch& b, hipStream_t stream) {
-    if (b.count < 1) return;
-    int blocks = 0;
-    for (int j = 0; j < b.count; ++j) {
-        const int nb = ((b.j[j].p.rows + FBM - 1) / FBM) * ((b.j[j].N + FBN - 1) / FBN);
-        blocks = nb > blocks ? nb : blocks;
-    }
-    const int groups = b.j[0].p.W / 32;
-    int ksplit = 1;
-    for (int s = 2; s <= groups && s <= 8; ++s)
-        if (groups % s == 0 && (long long)blocks * b.count * s <= 640) ksplit = s;
+// K shares: as many as keep ~2 workgroups per CU busy, whole unit groups each (train_plan.h, bwd_step_plan: the rule and its numbers)
+static_assert(FBM == BWD_STEP_ROWS && FBN == BWD_STEP_COLS, "train_plan.h plans this kernel's tiles");
+BwdStepPlan launch_lstm_bwd_gemm(const BwdStepBatch& b, hipStream_t stream) {
+    if (b.count < 1) return BwdStepPlan{0, 0, 0};
+    const int rows[2] = {b.j[0].p.rows, b.j[1].p.rows}, N[2] = {b.j[0].N, b.j[1].N};
+    const BwdStepPlan plan = bwd_step_plan(rows, N, b.count, b.j[0].p.W);
     constexpr size_t lds = (size_t)(2 * FA_GROUP + 2 * FB_STAGE) * sizeof(float);
     static const hipError_t lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_gemm_kernel),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)lds_ok;          // (a refusal surfaces as the launch error the caller checks)
-    hipLaunchKernelGGL(lstm_bwd_gemm_kernel, dim3(blocks, b.count, ksplit), dim3(256), lds, stream, b);
+    hipLaunchKernelGGL(lstm_bwd_gemm_kernel, dim3(plan.blocks, b.count, plan.ksplit), dim3(256), lds, stream, b);
+    return plan;
 }
 
 }  // namespace casv

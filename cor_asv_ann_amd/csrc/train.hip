@@ -1423,6 +1423,115 @@ extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int3
     return CASV_OK;
 }
 
+// Test support: one backward time step of 1 or 2 layers on host data (casv_debug_bwd_step), in the fused form or as the two
+// launches layers_backward and cell_backward_steps build.  Nothing is launched unless every address the kernels form lies inside
+// a buffer allocated here: they clamp rows to rows - 1 and columns to N - 1, read W floats of every input row ([rows][ld], the
+// last row W floats long) and of the mask, 4W of a gates row and of a Bt row; they store rows < rows only.
+namespace {
+struct DebugBwdBuffers {
+    std::vector<DevBuf*> owned; hipStream_t stream;
+    ~DebugBwdBuffers() { (void)hipStreamSynchronize(stream); for (DevBuf* b : owned) { b->release(); delete b; } }
+    // n floats on the device: a copy of src, or (src == nullptr) 0xFF bytes
+    float* put(const float* src, size_t n, int& rc) {
+        DevBuf* b = new DevBuf();
+        owned.push_back(b);
+        if ((rc = b->ensure(n * 4))) return nullptr;
+        const hipError_t e = src ? hipMemcpyAsync(b->p, src, n * 4, hipMemcpyHostToDevice, stream) : hipMemsetAsync(b->p, 0xff, n * 4, stream);
+        if (e != hipSuccess) { rc = fail(CASV_ERR_HIP, "copy of a debug operand failed: %s", hipGetErrorString(e)); return nullptr; }
+        return b->as<float>();
+    }
+};
+int check_debug_bwd_job(const casv_debug_bwd_job& d, int j, int W0) {
+    if (d.rows < 1 || d.rows > (1 << 16) || d.N < 1 || d.N > (1 << 14)) return fail(CASV_ERR_ARG, "job %d: rows in [1, 65536], N in [1, 16384]", j);
+    if (d.W < 32 || d.W > 1024 || d.W % 32 || d.W != W0) return fail(CASV_ERR_ARG, "job %d: W a multiple of 32 in [32, 1024], the same in every job", j);
+    if (!d.Bt || !d.gates || !d.cell || !d.dc_in || !d.dz || !d.dc || !d.out) return fail(CASV_ERR_ARG, "job %d: Bt, gates, cell, dc_in, dz, dc and out are required", j);
+    if (d.mask_a && !d.a) return fail(CASV_ERR_ARG, "job %d: mask_a without a", j);
+    const struct { const float* p; int64_t ld; int width; const char* name; } lds[5] = {
+        {d.a, d.lda, d.W, "lda"}, {d.b, d.ldb, d.W, "ldb"}, {d.c, d.ldc, d.W, "ldc"}, {d.c_prev, d.ld_cprev, d.W, "ld_cprev"}, {d.out, d.ld_out, d.N, "ld_out"}};
+    for (const auto& l : lds)
+        if (l.p && (l.ld < l.width || l.ld % 4 || l.ld > (1 << 16))) return fail(CASV_ERR_ARG, "job %d: %s must be >= %d, a multiple of 4 and <= 65536", j, l.name, l.width);
+    return CASV_OK;
+}
+}  // namespace
+
+extern "C" int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, const casv_debug_bwd_job* jobs) {
+    if (!m || !jobs) return fail(CASV_ERR_ARG, "null argument");
+    if ((form != 0 && form != 1) || count < 1 || count > 2) return fail(CASV_ERR_ARG, "form 0 (fused) / 1 (two launches), 1 or 2 jobs");
+    for (int j = 0; j < count; ++j) if (int rc = check_debug_bwd_job(jobs[j], j, jobs[0].W)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
+    OrderedScope ordered(m, m->deterministic);          // (as casv_train_step: form 1's GEMM then sums in a fixed order)
+    DebugBwdBuffers dev{{}, m->stream};
+    int rc = CASV_OK;
+    BwdStepBatch fb{};
+    LstmBwdBatch pw{};
+    GemmBatch gb{};
+    fb.count = pw.count = gb.count = count;
+    for (int j = 0; j < count; ++j) {
+        const casv_debug_bwd_job& d = jobs[j];
+        const size_t rows = (size_t)d.rows, W = (size_t)d.W;
+        auto in = [&](const float* src, int64_t ld) -> const float* { return src ? dev.put(src, (rows - 1) * (size_t)ld + W, rc) : nullptr; };
+        BwdStepJob& q = fb.j[j];
+        LstmBwdArgs& p = q.p;
+        p.a = in(d.a, d.lda); if (rc) return rc;
+        p.lda = d.lda;
+        if (d.mask_a) { p.mask_a = dev.put(d.mask_a, W, rc); if (rc) return rc; }
+        p.b = in(d.b, d.ldb); if (rc) return rc;
+        p.ldb = d.ldb;
+        p.c = in(d.c, d.ldc); if (rc) return rc;
+        p.ldc = d.ldc;
+        p.c_prev = in(d.c_prev, d.ld_cprev); if (rc) return rc;
+        p.ld_cprev = d.ld_cprev;
+        p.gates = dev.put(d.gates, rows * 4 * W, rc); if (rc) return rc;
+        p.cell = dev.put(d.cell, rows * W, rc); if (rc) return rc;
+        q.dc_in = dev.put(d.dc_in, rows * W, rc); if (rc) return rc;
+        q.Bt = dev.put(d.Bt, (size_t)d.N * 4 * W, rc); if (rc) return rc;
+        // outputs: 0xFF bytes and one guard row; out[:rows][:N] cleared (the split-K shares add into it)
+        p.dz = dev.put(nullptr, (rows + 1) * 4 * W, rc); if (rc) return rc;
+        p.dc = dev.put(nullptr, (rows + 1) * W, rc); if (rc) return rc;
+        q.out = dev.put(nullptr, (rows + 1) * (size_t)d.ld_out, rc); if (rc) return rc;
+        q.ld_out = d.ld_out; q.N = d.N; p.rows = d.rows; p.W = d.W;
+        HIPCHK(hipMemset2DAsync(q.out, (size_t)d.ld_out * 4, 0, (size_t)d.N * 4, rows, m->stream));
+        if (form == 1) {            // lstm_bwd_kernel works in place: dL/dc of the step lies where dL/dc of the step before goes
+            HIPCHK(hipMemcpyAsync(p.dc, q.dc_in, rows * W * 4, hipMemcpyDeviceToDevice, m->stream));
+            pw.a[j] = p;
+            gb.g[j] = plain_gemm(p.dz, 4 * d.W, d.rows, 4 * d.W, q.Bt, d.N, nullptr, q.out, d.ld_out);
+            gb.g[j].out_zeroed = 1;
+        }
+    }
+    m->stat_bwd_step[0] = m->stat_bwd_step[1] = 0;
+    if (form == 0) {
+        const BwdStepPlan plan = launch_lstm_bwd_gemm(fb, m->stream);
+        m->stat_bwd_step[0] = plan.ksplit; m->stat_bwd_step[1] = plan.gper;
+    } else {
+        launch_lstm_bwd_batch(pw, m->stream);
+        run_gemm_batch(m, EPI_PLAIN, gb);
+    }
+    HIPCHK(hipGetLastError());
+    for (int j = 0; j < count; ++j) {
+        const casv_debug_bwd_job& d = jobs[j];
+        const size_t rows1 = (size_t)d.rows + 1, W = (size_t)d.W;
+        HIPCHK(hipMemcpyAsync(d.dz, fb.j[j].p.dz, rows1 * 4 * W * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(d.dc, fb.j[j].p.dc, rows1 * W * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(d.out, fb.j[j].out, rows1 * (size_t)d.ld_out * 4, hipMemcpyDeviceToHost, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (int j = 0; j < count; ++j) {
+        const casv_debug_bwd_job& d = jobs[j];
+        const size_t rows = (size_t)d.rows, W = (size_t)d.W, ld = (size_t)d.ld_out;
+        auto untouched = [](const float* p, size_t n) {
+            for (size_t i = 0; i < n; ++i) { uint32_t v; memcpy(&v, p + i, 4); if (v != 0xffffffffu) return false; }
+            return true;
+        };
+        if (!untouched(d.dz + rows * 4 * W, 4 * W)) return fail(CASV_ERR_STATE, "job %d: a launch stored past the last row of dz", j);
+        if (!untouched(d.dc + rows * W, W)) return fail(CASV_ERR_STATE, "job %d: a launch stored past the last row of dc", j);
+        if (!untouched(d.out + rows * ld, ld)) return fail(CASV_ERR_STATE, "job %d: a launch stored past the last row of out", j);
+        for (size_t r = 0; r < rows; ++r)
+            if (!untouched(d.out + r * ld + d.N, ld - d.N)) return fail(CASV_ERR_STATE, "job %d: a launch stored behind column N - 1 of out, row %zu", j, r);
+    }
+    return CASV_OK;
+}
+
 // ---- scoring: teacher-forced log-probabilities of given targets (kt:407 / s2s:491-497, the forward pass of a mode-0 step) ----
 // What a scoring call hands back: (B,U) arrays in the caller's order, (B) sums, the dense alignment rows (B,U,T) or nullptr.
 struct ScoreOut { float* logp; int32_t* best; int32_t* rank; double* nll; int32_t* count; float* align; };

@@ -121,7 +121,7 @@ void launch_lstm_bwd_batch(const LstmBwdBatch& b, hipStream_t st);
 // (gemm_bwd.hip).  p.dc is written (dL/dc of the previous step), dc_in is read: two different buffers.  `out` is zeroed.
 struct BwdStepJob { LstmBwdArgs p; const float* dc_in; const float* Bt; float* out; long long ld_out; int N; };
 struct BwdStepBatch { BwdStepJob j[2]; int count; };
-void launch_lstm_bwd_gemm(const BwdStepBatch& b, hipStream_t st);
+BwdStepPlan launch_lstm_bwd_gemm(const BwdStepBatch& b, hipStream_t st);      // returns what it launched (train_plan.h)
 
 struct AttnBwdArgs {
     const float* dxh; long long ld_dxh; int ctx_off;         // dL/dx of the cell input; context part at ctx_off

@@ -118,4 +118,25 @@ struct TrainStepPlan {
     }
 };
 
+// ---- the fused backward step (gemm_bwd.hip) ----
+// One launch per time step for up to two jobs: workgroups of BWD_STEP_ROWS rows x BWD_STEP_COLS columns, the grid the larger
+// job's.  K = 4W is shared out in whole unit groups of 32 units: the most shares, at most BWD_STEP_MAX_SHARES, that divide W / 32
+// and keep the launch within BWD_STEP_MAX_BLOCKS workgroups (about two per CU and a half).  gper = unit groups per share picks the
+// kernel's pipeline: 1, 2, or >= 3 (a loop of gper - 3 rounds); ksplit == 1 stores plainly, more shares meet in float atomics.
+constexpr int BWD_STEP_ROWS = 32, BWD_STEP_COLS = 128;
+constexpr int BWD_STEP_MAX_SHARES = 8, BWD_STEP_MAX_BLOCKS = 640;
+struct BwdStepPlan { int blocks, ksplit, gper; };
+inline BwdStepPlan bwd_step_plan(const int rows[2], const int N[2], int count, int W) {
+    int blocks = 0;
+    for (int j = 0; j < count; ++j) {
+        const int nb = ((rows[j] + BWD_STEP_ROWS - 1) / BWD_STEP_ROWS) * ((N[j] + BWD_STEP_COLS - 1) / BWD_STEP_COLS);
+        blocks = nb > blocks ? nb : blocks;
+    }
+    const int groups = W / 32;
+    int ksplit = 1;
+    for (int s = 2; s <= groups && s <= BWD_STEP_MAX_SHARES; ++s)
+        if (groups % s == 0 && (long long)blocks * count * s <= BWD_STEP_MAX_BLOCKS) ksplit = s;
+    return BwdStepPlan{blocks, ksplit, groups / ksplit};
+}
+
 }  // namespace casv

@@ -668,6 +668,47 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_gemm_jobs(self.handle, int(epi), len(jobs), cjobs, int(step), int(bool(step_by_ptr))))
         return results, self.stat('gemm_jobs_forms'), self.stat('gemm_jobs_launches')
 
+    def debug_bwd_step(self, form, jobs, outputs=None):
+        """Test support (casv_debug_bwd_step): ONE backward time step of 1 or 2 layers on host data; form 0 the fused launch, 1 the
+        two launches.  A job is an object with the attributes rows, W, N, Bt (N, 4W), gates (rows, 4W), cell, dc_in (rows, W) and the
+        optional inputs a, b, c, c_prev -- None or float32 arrays of `rows` rows whose row stride is the ld (a column window of a wider
+        array: W columns are read) -- mask_a (W,) or None, and ld_out.  Returns per job a dict dz (rows + 1, 4W), dc (rows + 1, W), out
+        (rows + 1, ld_out), every byte the launches did not store to still 0xFF (`outputs`: the arrays to fill instead of fresh ones)."""
+        keep, cjobs, results = [], (nv.DebugBwdJob * len(jobs))(), []
+
+        def dense(a):
+            a = nv.carray(a, np.float32)
+            keep.append(a)
+            return a.ctypes.data
+
+        def window(a, name):
+            if a is None:
+                return None, 0
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0, name
+            keep.append(a)
+            return a.ctypes.data, a.strides[0] // 4 if a.shape[0] > 1 else max(a.strides[0] // 4, a.shape[1])
+
+        for i, (cj, job) in enumerate(zip(cjobs, jobs)):
+            rows, W, N = int(job.rows), int(job.W), int(job.N)
+            assert np.shape(job.Bt) == (N, 4 * W) and np.shape(job.gates) == (rows, 4 * W)
+            assert np.shape(job.cell) == np.shape(job.dc_in) == (rows, W)
+            cj.rows, cj.W, cj.N, cj.ld_out = rows, W, N, int(job.ld_out)
+            cj.Bt, cj.gates, cj.cell, cj.dc_in = dense(job.Bt), dense(job.gates), dense(job.cell), dense(job.dc_in)
+            cj.a, cj.lda = window(job.a, 'a')
+            cj.b, cj.ldb = window(job.b, 'b')
+            cj.c, cj.ldc = window(job.c, 'c')
+            cj.c_prev, cj.ld_cprev = window(job.c_prev, 'c_prev')
+            cj.mask_a = None if job.mask_a is None else dense(job.mask_a)
+            res = outputs[i] if outputs is not None else {
+                'dz': np.empty((rows + 1, 4 * W), np.float32), 'dc': np.empty((rows + 1, W), np.float32),
+                'out': np.empty((rows + 1, max(int(job.ld_out), 1)), np.float32)}
+            for name in ('dz', 'dc', 'out'):
+                assert res[name].dtype == np.float32 and res[name].flags.c_contiguous
+            cj.dz, cj.dc, cj.out = res['dz'].ctypes.data, res['dc'].ctypes.data, res['out'].ctypes.data
+            results.append(res)
+        nv.check(self.lib.casv_debug_bwd_step(self.handle, int(form), len(jobs), cjobs))
+        return results
+
     def alignments_sparse(self, rows, steps, K=None):
         """Window form of the last decode call's soft alignments: (lo int32 (rows, S), w float32 (rows, S, K))."""
         K = int(K or 2 * self.window_width + 1)

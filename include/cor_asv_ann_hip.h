@@ -417,6 +417,32 @@ typedef struct casv_debug_job {
     int32_t epi_plain;
 } casv_debug_job;
 int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr);
+/* Test support: ONE backward time step of 1 or 2 LSTM layers on the caller's host data, as the train step launches it where a
+ * layer has no persistent backward.  form 0 = the fused launch (csrc/gemm_bwd.hip: the cell's pointwise backward inside the data
+ * GEMM out = dz . Bt^T), form 1 = the two launches of the options "deterministic" and "fused_backward" off (lstm_bwd_kernel, then
+ * the plain GEMM batch on a cleared output; with the option "deterministic" on, that GEMM sums in its fixed order).  Per job: dh = a * mask_a + b + c from the optional inputs a [rows][lda] (mask_a [W] or
+ * NULL: ones), b [rows][ldb], c [rows][ldc] (NULL: absent; W columns of each row are read); gates [rows][4W] in the interleaved
+ * order [unit / 32][gate i,f,c,o][unit % 32], cell [rows][W], c_prev [rows][ld_cprev] (NULL: zeros), dc_in [rows][W] = dL/dc of
+ * the step, Bt [N][4W].  Outputs, each with ONE MORE ROW than `rows`: dz [rows + 1][4W], dc [rows + 1][W] = dL/dc of the step
+ * before, out [rows + 1][ld_out].  On the device they start as 0xFF bytes but out[r][0 .. N-1], r < rows, which is zeroed as the
+ * kernels' contract requires (and dc in form 1, which starts as dc_in: that kernel works in place); they come back whole, so
+ * every byte nothing stored to is still 0xFF.  A store to the row behind an output or to columns N .. ld_out-1 of out is
+ * CASV_ERR_STATE.  Checked on the host before anything is launched (CASV_ERR_ARG, nothing is written): form 0 / 1, 1 or 2 jobs,
+ * rows in [1, 65536], N in [1, 16384], W a multiple of 32 in [32, 1024] and the same in both jobs, every ld at least its width
+ * (W; ld_out: N) and a multiple of 4, no required pointer NULL, mask_a only with a.  casv_get_stat then reports
+ * "bwd_step_shares" and "bwd_step_groups": the K shares of the fused launch and the unit groups of 32 per share (csrc/train_plan.h,
+ * bwd_step_plan; both 0 after form 1).  tests/test_gpu_bwd_step.py compares both forms with a float64 reference. */
+typedef struct casv_debug_bwd_job {
+    int32_t rows, W, N;
+    const float* Bt;
+    const float* a; int64_t lda; const float* mask_a;
+    const float* b; int64_t ldb;
+    const float* c; int64_t ldc;
+    const float* c_prev; int64_t ld_cprev;
+    const float* gates; const float* cell; const float* dc_in;
+    float* dz; float* dc; float* out; int64_t ld_out;
+} casv_debug_bwd_job;
+int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, const casv_debug_bwd_job* jobs);
 /* Options: "graph" = replay the decode step through a captured hipGraph (1) or launch kernels eagerly (0);
  * "persistent" = greedy decoding through the persistent decoder (all steps in ONE launch, workgroups hand rows to each
  * other through memory: small batches, where a step is too short for a launch per kernel): -1 by batch size (default:
@@ -482,7 +508,7 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * per role (all 0 where the option, the arithmetic, the device or the depth rule the launch out), "encoder_persist_per_cu" and
  * "encoder_persist_grid" = the same figure and the workgroups of the last encoder pass that was planned (grid 0: no form);
  * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
- * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs;
+ * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
  * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
  * give-up on this handle so far. */

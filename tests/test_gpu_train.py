@@ -21,8 +21,11 @@ def _idx(a):
                                                      (3, 64, 96, 8, 12, 6.0, True), (4, 64, 96, 6, 10, 8.0, False),
                                                      # widths that are no multiple of 32 (dead-unit padding, engine.py)
                                                      (1, 20, 24, 3, 7, 3.0, True), (2, 50, 40, 4, 9, 4.0, True),
-                                                     # three / five unit groups per K share of the fused backward step
+                                                     # three / five K shares of ONE unit group each in the fused backward step
                                                      (2, 96, 40, 5, 8, 4.0, True), (3, 160, 40, 3, 6, 4.0, False),
+                                                     # ... and three / eleven unit groups per K share: its looped pipeline, zero and
+                                                     # eight rounds (which shape takes which path: tests/bwd_step_cases.py, plan)
+                                                     (2, 288, 40, 5, 8, 4.0, True), (2, 352, 40, 3, 6, 4.0, False),
                                                      # whole column tiles of 128 units: the backward recurrences are persistent too
                                                      (3, 128, 40, 37, 7, 4.0, True), (2, 256, 48, 5, 6, 4.0, False)])
 @pytest.mark.parametrize('path', ['fused', 'stepwise'])
@@ -366,8 +369,10 @@ def test_c4_full_size_step_equals_oracle(golden_dir):
 
 def test_fused_backward_step_against_the_host(tmp_path):
     """One fused backward step (cell backward + data GEMM, gemm_bwd.hip) on random data against a double-precision host
-    computation of the same step: every path of the kernel's software pipeline (1, 2, 3 and more unit groups per K share,
-    partial row blocks and column tiles, split-K atomics at the train step's full size)."""
+    computation of the same step: 1, 2 and 4 unit groups per K share of the kernel's software pipeline (the launcher's rule gives
+    these shapes 1 / 1 / 1 / 1 / 1 / 1 / 2 / 4: one group up to W = 256, the loop once at (512, 512, 1024)), partial row blocks and
+    column tiles, split-K atomics at the train step's full size.  Three groups, the loop's further rounds, the plain store beyond one
+    group, absent inputs and the top cell's form: tests/test_gpu_bwd_step.py."""
     import os, re, shutil, subprocess
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,6 +5,7 @@
 //   G <kind> W C B U jobs cus per_cu                              one shape rule (train_form_grid)
 //   S <name> persistent deterministic backoff cus nsites          one step (TrainStepPlan), followed by nsites lines, in the step's order:
 //     <kind> W C B U jobs per_cu plain T defer split split_off rows_fit
+//   B count W rows0 N0 rows1 N1                                   one fused backward step (bwd_step_plan; count 1: rows1 and N1 are ignored)
 #include "../cor_asv_ann_amd/csrc/train_plan.h"
 #include <cstdio>
 #include <iostream>
@@ -68,6 +69,13 @@ int main() {
                 B = v[2];
             }
             printf("step count=%d slot_bytes=%zu\n", plan.launches, train_slot_bytes(B));
+        } else if (what == "B") {
+            int v[6] = {0};
+            for (int& x : v) in >> x;
+            if (!in || v[0] < 1 || v[0] > 2) return bad(line);
+            const int rows[2] = {v[2], v[4]}, N[2] = {v[3], v[5]};
+            const BwdStepPlan p = bwd_step_plan(rows, N, v[0], v[1]);
+            printf("bwd_step blocks=%d ksplit=%d gper=%d\n", p.blocks, p.ksplit, p.gper);
         } else return bad(line);
     }
     return 0;
