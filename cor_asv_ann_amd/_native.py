@@ -109,6 +109,8 @@ SIGNATURES = {
                                        c_void_p, c_int64, c_void_p]),
     'casv_debug_activation': (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     'casv_debug_gemm_jobs': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), c_int32, c_int32]),
+    'casv_debug_gemm_jobs_acc': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), POINTER(DebugRows), c_int32, c_int32]),
+    'casv_debug_get_u': (c_int, [c_void_p, c_void_p]),
     'casv_debug_bwd_step': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugBwdJob)]),
     'casv_set_option': (c_int, [c_void_p, c_char_p, c_int64]),
     'casv_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),

@@ -199,6 +199,11 @@ void launch_lm_softmax(const LmSoftmaxArgs& a, hipStream_t stream);
 
 void launch_embed_sparse(const float* E, const int* idx, const float* val, float* x0,
                          int rows, int A, int V, int W, hipStream_t stream);
+// one-alternative input idx [B][T] -> out [T][B]: the character of (line, position), V where there is none (encoder.hip: rows of
+// layer 1's per-character table, in the order step t reads them)
+void launch_char_rows(const int* idx, int* out, int B, int T, int V, hipStream_t stream);
+// the table's own input, as launch_embed_sparse reads it: idx[v] = v with val[v] = 1 for v < V, idx[V] = -1 (no character)
+void launch_table_input(int* idx, float* val, int V, hipStream_t stream);
 void launch_advance_step(int* step_ptr, hipStream_t stream);
 // elementwise helpers of the optional topologies (seq2seq.py:284-301): dst[i] += src[i]; dst[i] = tanh(src[i]) (n floats, 16-byte aligned)
 void launch_add_inplace(float* dst, const float* src, long long n, hipStream_t stream);

@@ -719,7 +719,14 @@ static int beam_search(casv_model* m, const BeamCall& c, const BeamState& s, boo
         DecodeStep st;
         st.beam = true; st.lm = c.lm; st.softmax = false; st.rows_per_line = N;
         st.step_ptr = step_ptr; st.step_imm = step_imm; st.live = live; st.live_group = N;
-        launch_step(m, st);
+        // Iteration S - 1 creates no node: the beam kernels leave at step + 1 >= S before they read a logit (beam_kernels.hip: the
+        // step kernel only records line_steps, s2s:1398).  What its decoder step would write -- slot S of the state, query,
+        // alignment and window stores, the logits -- is read by nobody: the extraction kernels, casv_get_alignments_sparse and the
+        // records follow n_exp of nodes created at iterations <= S - 2 (slots <= S - 1), the LM jobs feed the same beam kernel.  So
+        // the eager path (the step number is an immediate) launches the beam step alone; a captured body stays whole.
+        // (option "beam_skip_last" = 0: the step is launched all the same -- tests compare the two)
+        const bool unread = !step_ptr && step_imm == S - 1 && m->beam_skip_last;
+        if (!unread) launch_step(m, st);
         hipEvent_t ev{};
         m->prof_begin(PC_BEAM, 0.0, 4.0 * c.R * ((c.lm ? 3.0 : 2.0) * m->Vp), ev);
         BeamState sb = s;

@@ -131,6 +131,27 @@ void launch_embed_sparse(const float* E, const int* idx, const float* val, float
     hipLaunchKernelGGL(embed_sparse_kernel, dim3(rows), dim3(128), 0, stream, E, idx, val, x0, rows, A, V, W);
 }
 
+__global__ void char_rows_kernel(const int* __restrict__ idx, int* __restrict__ out, int B, int T, int V) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // (t, b)
+    if (i >= (long long)B * T) return;
+    const int t = (int)(i / B), b = (int)(i % B);
+    const int c = idx[(long long)b * T + t];
+    out[i] = (c < 0 || c >= V) ? V : c;
+}
+void launch_char_rows(const int* idx, int* out, int B, int T, int V, hipStream_t stream) {
+    const long long n = (long long)B * T;
+    hipLaunchKernelGGL(char_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, idx, out, B, T, V);
+}
+__global__ void table_input_kernel(int* __restrict__ idx, float* __restrict__ val, int V) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v > V) return;
+    idx[v] = v < V ? v : -1;
+    val[v] = 1.0f;
+}
+void launch_table_input(int* idx, float* val, int V, hipStream_t stream) {
+    hipLaunchKernelGGL(table_input_kernel, dim3((V + 1 + 255) / 256), dim3(256), 0, stream, idx, val, V);
+}
+
 // (lo, K weights) of decode step s of line b from the alignment store (slot s+1, row b) -- decode_batch_greedy's
 // per-step alignments (seq2seq.py:1249,1262) without the T-wide rows
 __global__ void greedy_extract_sparse_kernel(const float* a_base, const int* win_store, int B, int S, int T, SparseAlignOut sp) {

@@ -114,14 +114,77 @@ static bool final_h(const casv_model* m, SmallOps& ops, const float* src, long l
 }
 static int too_many_ops() { return fail(CASV_ERR_STATE, "too many set-up operations for one launch"); }
 
+// Layer 1 on plain text from a per-character table (option "encoder_table").  Every x_t row of such an input is one row of E
+// (embed_sparse with one alternative of weight 1) or zeros, so its part of the cell's contraction is one of V + 1 rows -- computed
+// B x T times per direction otherwise.  The table holds those rows as the ACCUMULATORS the split GEMM leaves behind the x columns (its
+// raw plain output); a cell's job takes its row as GemmArgs.acc_in and contracts the h columns only: the same instruction sequence
+// per element as the undivided [x | h] job, the same bits (x comes first in K, its width is whole K tiles, and the 128x128 and
+// 256x256 split tiles contract an element alike).
+// The table of the committed weights: built on first use by the split GEMM itself, on the handle's stream (never under a
+// recording: the encoder pass is not part of the step graph), dropped by casv_commit_weights.
+static int ensure_enc_table(casv_model* m) {
+    if (m->enc_tab_ready) return 0;
+    const int W = m->W, V = m->V;
+    const size_t rows = (size_t)V + 1;
+    for (int dir = 0; dir < 2; ++dir) if (int rc = m->enc_tab[dir].ensure(rows * 4 * W * 4)) return rc;
+    if (int rc = m->enc_tab_x.ensure(rows * W * 4)) return rc;
+    if (int rc = m->enc_tab_idx.ensure(rows * 2 * 4)) return rc;
+    int* idx = m->enc_tab_idx.as<int>(); float* val = reinterpret_cast<float*>(idx + rows);
+    launch_table_input(idx, val, V, m->stream);
+    launch_embed_sparse(m->E.as<float>(), idx, val, m->enc_tab_x.as<float>(), (int)rows, 1, V, W, m->stream);      // (the rows a line's x0 holds; row V: zeros)
+    GemmBatch b{};
+    for (int dir = 0; dir < 2; ++dir) {
+        GemmArgs& g = b.g[dir];
+        g.nseg = 1; g.a[0] = mkseg(m->enc_tab_x.as<float>(), W, W, 0);
+        g.Bt = (dir == 0 ? m->enc_fw : m->enc_bw).wt.as<float>(); g.bias = nullptr;         // (no bias: the raw accumulators)
+        g.M = (int)rows; g.N = 4 * W; g.Ktot = 2 * W;
+        g.out = mkslot(m->enc_tab[dir].as<float>(), 4 * W);
+    }
+    b.count = 2;
+    run_gemm_batch(m, EPI_PLAIN, b);
+    HIPCHK(hipGetLastError());
+    m->enc_tab_ready = true;
+    ++m->stat_enc_table_builds;
+    return 0;
+}
+// a layer-1 job on the table: the h columns alone, on top of the row of the position's character (chars: [T][B], V = none)
+static GemmArgs table_job(const casv_model* m, int dir, int t, const int* chars) {
+    GemmArgs g = bidir_job(m, dir == 0 ? m->enc_fw : m->enc_bw, 1, dir, t, m->x0.as<float>(), m->W, m->H1.as<float>());
+    const int pos = dir == 0 ? t : m->T - 1 - t;
+    g.a[0] = g.a[1]; g.a[1] = Seg{}; g.nseg = 1;            // (koff of the h columns and the weights' row stride Ktot stay)
+    g.acc_in = mkseg(m->enc_tab[dir].as<float>(), 4 * m->W, 0, 0, chars + (size_t)pos * m->B);
+    return g;
+}
+// Whether this pass takes the table: the option, the split arithmetic, plain-text input, no bridge -- and every launch of a step in
+// the one form that honours acc_in (gemm_plan.h)
+static bool layer1_takes_table(casv_model* m) {
+    if (m->enc_table_opt < 1 || m->gemm.arithmetic < 1 || !m->enc_onehot || m->A != 1 || m->cfg.bridge_dense) return false;
+    GemmBatch b{};
+    const int* any = reinterpret_cast<const int*>(m->d_idx.p);
+    for (int dir = 0; dir < 2; ++dir) b.g[dir] = table_job(m, dir, 0, any);
+    b.count = 2;
+    return gemm_plan_takes_acc_in(plan_gemm_launches(m->gemm, gemm_switches(), EPI_LSTM, b));
+}
+
 // layer 1 (seq2seq.py:272-281): the forward step at time t and the backward step at time T-1-t are independent -> one launch of two jobs
-static void run_layer1_steps(casv_model* m) {
+static int run_layer1_steps(casv_model* m, bool table = false) {
+    const int* chars = nullptr;
+    if (table) {
+        if (int rc = ensure_enc_table(m)) return rc;
+        if (int rc = m->enc_cidx.ensure((size_t)m->B * m->T * 4)) return rc;
+        launch_char_rows(m->d_idx.as<int>(), m->enc_cidx.as<int>(), m->B, m->T, m->V, m->stream);
+        chars = m->enc_cidx.as<int>();
+    }
+    m->stat_enc_table = table ? 1 : 0;
     for (int t = 0; t < m->T; ++t) {
         GemmBatch b{};
-        for (int dir = 0; dir < 2; ++dir) b.g[dir] = bidir_job(m, dir == 0 ? m->enc_fw : m->enc_bw, 1, dir, t, m->x0.as<float>(), m->W, m->H1.as<float>());
+        for (int dir = 0; dir < 2; ++dir)
+            b.g[dir] = table ? table_job(m, dir, t, chars)
+                             : bidir_job(m, dir == 0 ? m->enc_fw : m->enc_bw, 1, dir, t, m->x0.as<float>(), m->W, m->H1.as<float>());
         b.count = 2;
         run_gemm_batch(m, EPI_LSTM, b);
     }
+    return 0;
 }
 // layers 2..D (seq2seq.py:283): cell (n, t) needs (n-1, t) and (n, t-1); the cells of one anti-diagonal k = t + (n-2) are
 // independent -> one launch per diagonal (<= GEMM_MAX_JOBS cells, deeper stacks are cut into groups of GEMM_MAX_JOBS layers)
@@ -138,6 +201,39 @@ static void run_wavefront(casv_model* m, float* const* lout) {
             run_gemm_batch(m, EPI_LSTM, b);
         }
     }
+}
+// Option "encoder_table" = 2: the input terms of layers 2..D ahead of their recurrence.  The x part of all T cells of layer n is known
+// once layer n - 1 has finished: ONE plain contraction of M = B * T rows (no bias: the raw accumulators, on whatever split tiles fill
+// the chip) into enc_zx [B][T][4W]; cell t then takes its rows as acc_in and contracts h alone -- the same bits, as for layer 1's table.
+// This gives up the anti-diagonal: the layers run one after the other, each as T launches of ONE job of K = W.
+static GemmArgs ahead_job(const casv_model* m, float* const* lout, int n, int t) {
+    GemmArgs g = layer_job(m, lout, n, t);
+    g.a[0] = g.a[1]; g.a[1] = Seg{}; g.nseg = 1;            // (koff of the h columns and the weights' row stride Ktot stay)
+    g.acc_in = mkseg(m->enc_zx.as<float>(), m->T * 4 * m->W, 0, 0, nullptr, 4 * m->W, 1, 0);
+    return g;
+}
+static bool upper_layers_take_ahead(casv_model* m, float* const* lout) {
+    if (m->enc_table_opt < 2 || m->gemm.arithmetic < 1 || m->cfg.bridge_dense || m->D < 2) return false;
+    GemmBatch b{};
+    b.g[0] = ahead_job(m, lout, 2, 0); b.count = 1;
+    if (!b.g[0].acc_in.base) b.g[0].acc_in.base = m->H1.as<float>();        // (planned before the buffer exists: any non-null address)
+    return gemm_plan_takes_acc_in(plan_gemm_launches(m->gemm, gemm_switches(), EPI_LSTM, b));
+}
+static int run_layers_ahead(casv_model* m, float* const* lout) {
+    const int B = m->B, T = m->T, W = m->W;
+    if (int rc = m->enc_zx.ensure((size_t)B * T * 4 * W * 4)) return rc;
+    for (int n = 2; n <= m->D; ++n) {
+        const int win = n == 2 ? 2 * W : W;
+        GemmArgs x{};
+        x.nseg = 1; x.a[0] = mkseg(lout[n - 1], win, win, 0);
+        x.Bt = m->enc[n].wt.as<float>(); x.bias = nullptr;
+        x.M = B * T; x.N = 4 * W; x.Ktot = win + W;
+        x.out = mkslot(m->enc_zx.as<float>(), 4 * W);
+        run_gemm(m, EPI_PLAIN, x);
+        for (int t = 0; t < T; ++t) { GemmArgs g = ahead_job(m, lout, n, t); run_gemm(m, EPI_LSTM, g); }
+    }
+    m->stat_enc_ahead = 1;
+    return 0;
 }
 // residual_connections (seq2seq.py:284-291): from layer 3 on a layer's output sequence is its LSTM output plus its input sequence
 // -- no wavefront across such layers: they run one after the other, the sum is taken in place over the whole sequence once a
@@ -228,10 +324,15 @@ static int run_encoder(casv_model* m, bool try_persistent) {
     else if (m->cfg.deep_bidirectional_encoder && D >= 2) form = DEEP;
     else if (m->cfg.residual_connections && D >= 3) form = RESIDUAL;       // (the sums live in the unidirectional branch, seq2seq.py:282-291)
 
-    hipEvent_t ev{};
-    m->prof_begin(PC_EMBED, 2.0 * BT * A * W, 4.0 * BT * W * (A + 1), ev);
-    launch_embed_sparse(m->E.as<float>(), m->d_idx.as<int>(), m->d_val.as<float>(), m->x0.as<float>(), (int)BT, A, m->V, W, m->stream);
-    m->prof_end(PC_EMBED, ev);
+    m->stat_enc_table = 0; m->stat_enc_ahead = 0;
+    // (layer 1 from the per-character table reads the characters, not x0: no embedding launch then)
+    const bool table = form == WAVEFRONT && layer1_takes_table(m);
+    if (!table) {
+        hipEvent_t ev{};
+        m->prof_begin(PC_EMBED, 2.0 * BT * A * W, 4.0 * BT * W * (A + 1), ev);
+        launch_embed_sparse(m->E.as<float>(), m->d_idx.as<int>(), m->d_val.as<float>(), m->x0.as<float>(), (int)BT, A, m->V, W, m->stream);
+        m->prof_end(PC_EMBED, ev);
+    }
 
     // outputs of layer n: layers that run strictly one after another alternate between two buffers (depth <= 3), deeper stacks
     // have a slice each of one buffer; the deep form plans its own
@@ -249,9 +350,13 @@ static int run_encoder(casv_model* m, bool try_persistent) {
             if (int rc = launch_persist_enc(m, plan, lout)) return rc;
             give_up = persist_give_up_word(m->p_enc_counters.as<unsigned>(), plan.counter_bytes);
             break;
-        case WAVEFRONT: run_layer1_steps(m); run_wavefront(m, lout); break;
-        case RESIDUAL: run_layer1_steps(m); if (int rc = run_residual_layers(m, lout)) return rc; break;
-        case DEEP: run_layer1_steps(m); if (int rc = run_deep_layers(m, &out)) return rc; break;
+        case WAVEFRONT:
+            if (int rc = run_layer1_steps(m, table)) return rc;
+            if (upper_layers_take_ahead(m, lout)) { if (int rc = run_layers_ahead(m, lout)) return rc; }
+            else run_wavefront(m, lout);
+            break;
+        case RESIDUAL: (void)run_layer1_steps(m); if (int rc = run_residual_layers(m, lout)) return rc; break;
+        case DEEP: (void)run_layer1_steps(m); if (int rc = run_deep_layers(m, &out)) return rc; break;
     }
     {   // final hidden states that no form above has set aside, and the persistent launch's give-up word, in one launch:
         // backward final h of layer 1 = its output at time 0 (seq2seq.py:280); layers n >= 2: the output at the last position
@@ -354,6 +459,10 @@ extern "C" int casv_encode(casv_model* m, int32_t B, int32_t T, int32_t A, const
     HIPCHK(hipEventRecord(m->ev_inputs, m->stream));
     }
     m->B = B; m->T = T; m->A = A;
+    // plain text: one alternative per position, of weight exactly 1 where there is a character (layer 1 may then come from the
+    // per-character table, run_layer1_steps)
+    m->enc_onehot = A == 1 && m->enc_table_opt >= 1;        // (looked at only where the table can be taken at all)
+    for (size_t i = 0; i < BT && m->enc_onehot; ++i) if (idx[i] >= 0 && idx[i] < m->V && val[i] != 1.0f) m->enc_onehot = false;
     m->last_decode = 0; m->has_a0 = false;
     m->enc_check_pending = false;
     // The encoder itself runs for the first entry point that needs its outputs, in that entry point's arithmetic (ensure_encoded):
@@ -413,5 +522,16 @@ extern "C" int casv_get_encoder_outputs(casv_model* m, float* enc_out, float* st
             HIPCHK(hipMemcpy(states + (2 * n) * BW, m->hfin.as<float>() + n * BW, BW * 4, hipMemcpyDeviceToHost));
             HIPCHK(hipMemcpy(states + (2 * n + 1) * BW, m->cfin.as<float>() + n * BW, BW * 4, hipMemcpyDeviceToHost));
         }
+    return CASV_OK;
+}
+
+// Test support: u = attention_dense(enc_out) [B][T][W] as the last encoder pass left it on the device (CASV_ERR_STATE before one has run)
+extern "C" int casv_debug_get_u(casv_model* m, float* u) {
+    if (!m || !u) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->encoded || m->enc_arith < 0) return fail(CASV_ERR_STATE, "no encoder pass has run on this input");
+    HIPCHK(hipSetDevice(m->device));
+    if (int rc = settle_encoder(m); rc < 0) return rc;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(u, m->u.p, (size_t)m->B * m->T * m->W * 4, hipMemcpyDeviceToHost));
     return CASV_OK;
 }

@@ -124,6 +124,16 @@ struct casv_model {
     bool enc_explicit = false;                            // the outputs were handed in (casv_set_encoder_outputs): only u = attention_dense(enc_out) is the library's
     DevBuf d_idx, d_val, d_srcrej, x0, H1, Ha, Hb, Hc, cfin, hfin, u;
     float* enc_out = nullptr;
+    // Layer 1's input contraction per character (encoder.hip, ensure_enc_table; option "encoder_table"): row v of enc_tab[dir]
+    // ([V + 1][4W]) holds the accumulators the split GEMM leaves behind E[v] . K of that direction, row V zeros (no character).
+    // Built on first use from the committed weights, dropped with them.  enc_onehot: every position of the staged input has at most
+    // one alternative, of weight exactly 1 (plain text); enc_cidx [T][B]: its character (V: none) in the order the steps read it.
+    DevBuf enc_tab[2], enc_tab_x, enc_tab_idx, enc_cidx;
+    DevBuf enc_zx; int stat_enc_ahead = 0;                // value 2: a layer's input terms of all positions [B][T][4W] (run_layers_ahead); the last pass took them
+    bool enc_tab_ready = false, enc_onehot = false;
+    int enc_table_opt = 1;                                // option "encoder_table": 0 never, 1 layer 1 where the pass qualifies, 2 and the layers above ahead
+    bool beam_skip_last = true;                           // option "beam_skip_last": the search's last iteration launches no decoder step (decode.hip)
+    int stat_enc_table = 0; long long stat_enc_table_builds = 0;    // the last encoder pass read the table; tables built on this handle so far
     DevBuf a0; bool has_a0 = false;                       // initial alignment handed in with casv_set_encoder_outputs
     // decode session
     int R = 0, S = 0;

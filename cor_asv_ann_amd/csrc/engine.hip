@@ -55,6 +55,9 @@ extern "C" int casv_model_create(const casv_config* cfg, int device_id, casv_mod
     m->cfg = *cfg; m->device = device_id;
     { hipDeviceProp_t prop{}; if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) m->ncu = prop.multiProcessorCount; }
     m->gemm.ncu = m->ncu;
+    // (A/B measurements of a whole program: the defaults of the options "encoder_table" and "beam_skip_last" from the environment)
+    if (const char* e = getenv("CASV_ENCODER_TABLE")) m->enc_table_opt = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
+    if (const char* e = getenv("CASV_BEAM_SKIP_LAST")) m->beam_skip_last = e[0] != '0';
     m->W = cfg->width; m->V = cfg->voc_size; m->Vp = (cfg->voc_size + 31) & ~31; m->D = cfg->depth;
     m->C = (cfg->depth == 1 || cfg->deep_bidirectional_encoder) ? 2 * cfg->width : cfg->width;
     m->expect = expected_shapes(*cfg);
@@ -90,6 +93,7 @@ extern "C" void casv_model_destroy(casv_model* m) {
     for (auto* v : {&m->enc_dfw, &m->enc_dbw}) for (auto& l : *v) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
     for (auto& l : m->dec) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
     for (DevBuf* b : {&m->WaP, &m->EP, &m->p_ctx, &m->p_wq, &m->p_logits, &m->p_counters, &m->p_enc_counters, &m->d_flags}) b->release();
+    for (DevBuf* b : {&m->enc_tab[0], &m->enc_tab[1], &m->enc_tab_x, &m->enc_tab_idx, &m->enc_cidx, &m->enc_zx}) b->release();
     if (m->pin_in) (void)hipHostFree(m->pin_in);
     if (m->pin_out) (void)hipHostFree(m->pin_out);
     for (auto& b : m->st_h) b.release();
@@ -207,6 +211,7 @@ extern "C" int casv_commit_weights(casv_model* m) {
     HIPCHK(hipSetDevice(m->device));
     for (auto& l : m->dec) gemm_split_invalidate(l.wt.as<float>());          // (split arithmetic: images of the old weights)
     gemm_split_invalidate(m->WaT.as<float>()); gemm_split_invalidate(m->E.as<float>());
+    m->enc_tab_ready = false;           // (layer 1's per-character table is a function of E and the layer's kernels: rebuilt on its next use)
     for (auto& kv : m->expect)
         if (!m->host.count(kv.first)) return fail(CASV_ERR_STATE, "weight '%s' has not been set", kv.first.c_str());
     const int W = m->W, C = m->C, D = m->D;
@@ -324,6 +329,9 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "beam_sort_capacity")) { *value = 4096; return CASV_OK; }
     if (!strcmp(key, "cus")) { *value = m->ncu; return CASV_OK; }
     if (!strcmp(key, "encoder_persistent")) { *value = m->stat_enc_persistent; return CASV_OK; }
+    if (!strcmp(key, "encoder_table")) { *value = m->stat_enc_table; return CASV_OK; }
+    if (!strcmp(key, "encoder_ahead")) { *value = m->stat_enc_ahead; return CASV_OK; }
+    if (!strcmp(key, "encoder_table_builds")) { *value = m->stat_enc_table_builds; return CASV_OK; }
     if (!strcmp(key, "decoder_persistent")) { *value = m->stat_dec_persistent; return CASV_OK; }
     if (!strcmp(key, "decode_give_ups")) { *value = m->stat_decode_give_ups; return CASV_OK; }
     if (!strcmp(key, "decoder_persist_per_cu")) { *value = m->stat_dec_plan[0]; return CASV_OK; }
@@ -576,7 +584,7 @@ int check_debug_out(const casv_debug_out& o, const char* what, int j, int M, int
         if (!debug_slot_ok(steps[i], o.step_mul, o.step_add, o.slots)) return fail(CASV_ERR_ARG, "job %d %s: step %d selects a slot outside [0, %d)", j, what, steps[i], o.slots);
     return CASV_OK;
 }
-int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, int nsteps) {
+int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, int nsteps, int kmult = 32) {
     const bool lstm = epi == EPI_LSTM && !d.epi_plain;
     if (d.M < 1 || d.M > (1 << 16) || d.N < 1 || d.N > (1 << 14) || d.Ktot < 32 || d.Ktot > (1 << 14) || d.Ktot % 4 || d.nseg < 1 || d.nseg > 3)
         return fail(CASV_ERR_ARG, "job %d: M in [1, 65536], N in [1, 16384], Ktot in [32, 16384] and a multiple of 4, 1..3 segments", j);
@@ -588,7 +596,7 @@ int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, i
         const casv_debug_rows& r = d.a[i];
         const std::string what = "segment " + std::to_string(i);
         if (int rc = check_debug_rows(r, what.c_str(), j, d.M, steps, nsteps)) return rc;
-        if (r.width % 32) return fail(CASV_ERR_ARG, "job %d %s: width %d is no multiple of 32", j, what.c_str(), r.width);
+        if (r.width % kmult) return fail(CASV_ERR_ARG, "job %d %s: width %d is no multiple of %d", j, what.c_str(), r.width, kmult);
         if (r.koff < 0 || r.koff % 4 || (long long)r.koff + r.width > d.Ktot) return fail(CASV_ERR_ARG, "job %d %s: koff a non-negative multiple of 4, koff + width <= Ktot", j, what.c_str());
         wsum += r.width;
     }
@@ -616,16 +624,24 @@ int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, i
 }
 }  // namespace
 
-extern "C" int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr) {
+// (`acc`: casv_debug_gemm_jobs_acc -- per job an accumulator input, pool == NULL: none)
+static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc, int32_t step, int32_t step_by_ptr) {
     if (!m || !jobs) return fail(CASV_ERR_ARG, "null argument");
     if ((epi != EPI_PLAIN && epi != EPI_LSTM) || count < 1 || count > GEMM_MAX_JOBS || step < 0 || step > 4096 || (step_by_ptr != 0 && step_by_ptr != 1))
         return fail(CASV_ERR_ARG, "epi 0 / 1, 1..%d jobs, step in [0, 4096], step_by_ptr 0 / 1", GEMM_MAX_JOBS);
     // (a step that arrives through the device word: the arguments' immediate step is 0, and must be harmless if a kernel took it)
     const int steps[2] = {step, 0};
     const int nsteps = step_by_ptr ? 2 : 1;
-    for (int j = 0; j < count; ++j) if (int rc = check_debug_job(epi, jobs[j], j, steps, nsteps)) return rc;
+    // (the split tiles contract K in tiles of 16: with `acc` the segments may be that narrow, and every form is a split one, below)
+    for (int j = 0; j < count; ++j) if (int rc = check_debug_job(epi, jobs[j], j, steps, nsteps, acc ? 16 : 32)) return rc;
+    for (int j = 0; j < count && acc; ++j) {
+        if (!acc[j].pool) continue;
+        if (int rc = check_debug_rows(acc[j], "acc_in", j, jobs[j].M, steps, nsteps)) return rc;
+        if (acc[j].width != jobs[j].N || acc[j].first || acc[j].skip_first) return fail(CASV_ERR_ARG, "job %d acc_in: width = N, no first / skip_first", j);
+    }
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
+    if (acc && !m->gemm.arithmetic) return fail(CASV_ERR_ARG, "casv_debug_gemm_jobs_acc needs a split arithmetic (option \"arithmetic\" or \"split_bf16\" = 1 or 2)");
     DebugBuffers dev{{}, nullptr, m->stream};
     int rc = CASV_OK;
     const int* step_word = nullptr;
@@ -673,9 +689,15 @@ extern "C" int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, c
         g.epi_plain = epi == EPI_LSTM ? d.epi_plain : 0;
         g.b_static = d.b_static;
         g.step_imm = step_by_ptr ? 0 : step; g.step_ptr = step_word;
+        if (acc && acc[j].pool) {
+            seg(acc[j], g.acc_in); if (rc) return rc;
+            g.acc_in.width = 0; g.acc_in.koff = 0;
+        }
     }
     // (launch_gemm_batch, keeping the plan that ran for the statistic)
-    const GemmPlan plan = run_gemm_plan(m->gemm, epi, b, plan_gemm_launches(m->gemm, gemm_switches(), epi, b), m->stream);
+    const GemmPlan planned = plan_gemm_launches(m->gemm, gemm_switches(), epi, b);
+    if (!gemm_plan_takes_acc_in(planned)) return fail(CASV_ERR_ARG, "a job with acc_in would not run as 128x128 split tiles");
+    const GemmPlan plan = run_gemm_plan(m->gemm, epi, b, planned, m->stream);
     HIPCHK(hipGetLastError());
     m->stat_jobs[0] = 0; m->stat_jobs[1] = plan.count;
     for (int i = 0; i < plan.count; ++i) m->stat_jobs[0] |= 1 << plan.launch[i].form;
@@ -689,6 +711,15 @@ extern "C" int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, c
     HIPCHK(hipStreamSynchronize(m->stream));
     for (const auto& gd : guards) for (uint32_t v : gd) if (v != 0xffffffffu) return fail(CASV_ERR_STATE, "a launch stored past the last row of an output");
     return CASV_OK;
+}
+
+extern "C" int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr) {
+    return debug_gemm_jobs(m, epi, count, jobs, nullptr, step, step_by_ptr);
+}
+extern "C" int casv_debug_gemm_jobs_acc(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc,
+                                        int32_t step, int32_t step_by_ptr) {
+    if (!acc) return fail(CASV_ERR_ARG, "null argument");
+    return debug_gemm_jobs(m, epi, count, jobs, acc, step, step_by_ptr);
 }
 
 extern "C" int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* in_, float* out_) {
@@ -739,6 +770,14 @@ extern "C" int casv_set_option(casv_model* m, const char* key, int64_t value) {
     if (!strcmp(key, "lm_predict")) {           // beam decode: children's costs from the LM output
         if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "lm_predict must be 0 or 1");
         m->lm_predict = value != 0; return CASV_OK;
+    }
+    if (!strcmp(key, "encoder_table")) {        // layer 1 of the search's per-step encoder from the per-character table (encoder.hip; same bits)
+        if (value < 0 || value > 2) return fail(CASV_ERR_ARG, "encoder_table must be 0 (off), 1 (layer 1 where the pass qualifies) or 2 (and the upper layers' input terms ahead)");
+        m->enc_table_opt = (int)value; return CASV_OK;
+    }
+    if (!strcmp(key, "beam_skip_last")) {       // debug switch: 0 = the search's last iteration launches its decoder step as every other (same results)
+        if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "beam_skip_last must be 0 or 1");
+        m->beam_skip_last = value != 0; return CASV_OK;
     }
     if (!strcmp(key, "vendor_gemm")) { m->vendor_gemm = value != 0; return CASV_OK; }
     if (!strcmp(key, "skinny") || !strcmp(key, "tile")) {   // process-wide: tile shape of the GEMM launches (results identical)

@@ -93,7 +93,9 @@ constexpr int SPLIT_BUF_FLOATS = 6 * SPLIT_PLANE_BYTES / 4;     // A planes 0..2
 // are read into the registers of tile kt as soon as their last product has issued (B planes 2 and 1 and A plane 0 behind the
 // tile's barrier, B plane 0 at the head of the next tile), so one barrier per tile still separates every LDS buffer's reads from
 // the stores that refill it.
-template <int EPI, int KS, bool SPLIT = false>
+// ACC (SPLIT only): the variant that honours GemmArgs.acc_in -- an instantiation of its own, so that the launches without the field
+// keep their register allocation (the accumulators are live through the whole prologue here).
+template <int EPI, int KS, bool SPLIT = false, bool ACC = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bm, const int bn, const int zidx, const int nsplit, float* smem_all) {
 #ifdef CASV_GEMM_PROF
     const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
@@ -358,6 +360,34 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bm, const
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[c][r] = 0.0f;
+    static_assert(!ACC || SPLIT, "acc_in belongs to the bf16-split variant");
+    if constexpr (ACC) {
+        // acc_in (gemm_args.h): the accumulators start from what another launch left behind the K segments in front of this job's --
+        // plain fp32 register values between two products, so the element's instruction sequence is the one of the undivided
+        // contraction.  (A raw plain output is acc + 0.0f, which differs from acc only for acc = -0.  An accumulator starts at +0,
+        // and a round-to-nearest sum is -0 only if every term is: +0 plus products never is, whatever their signs -- short of a
+        // whole product sum below 2^-150 that underflows to -0, which bf16x3 parts of weights and activations do not reach.)
+        // Ordinary loads, requested ahead of tiles 0 and 1 (whose registers are not live yet) and waited for behind those tiles' LDS
+        // stores: ahead of every hidden load, nothing pending on any path into the loop.
+        const Seg sga = g.acc_in;
+        if (sga.base) {
+            const float* abase = sga.base + (long long)(step * sga.step_mul + sga.step_add) * sga.slot_stride;
+            const float* arow[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                m = m < g.M ? m : g.M - 1;
+                arow[r] = abase + (long long)(sga.rows ? sga.rows[m] : m) * sga.ld;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                int n = n0 + c * 32 + l31;
+                n = n < g.N ? n : g.N - 1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[c][r] = arow[r][n];
+            }
+        }
+    }
     auto mma = [&](const Frag& f) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -405,6 +435,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bm, const
     if constexpr (SPLIT) {
         if (ntiles > 0) store_tile_split(g0, 0);
         if (ntiles > 1) store_tile_split(g1, 1);
+        if constexpr (ACC) { if (g.acc_in.base) asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); }
     } else {
         if (ntiles > 0) store_tile(g0, 0);
         if (ntiles > 1) store_tile(g1, 1);
@@ -748,7 +779,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bm, const
 #endif
 }
 
-template <int EPI, int KS, bool SPLIT = false>
+template <int EPI, int KS, bool SPLIT = false, bool ACC = false>
 __global__ __launch_bounds__(256 * KS, 2) void gemm_kernel(const GemmBatch batch) {
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     const GemmArgs& g = batch.g[blockIdx.y];
@@ -765,7 +796,7 @@ __global__ __launch_bounds__(256 * KS, 2) void gemm_kernel(const GemmBatch batch
         bm = (xcd / xc) * pr + local / pc;
         bn = (xcd % xc) * pc + local % pc;
     }
-    gemm_tile<EPI, KS, SPLIT>(g, bm, bn, blockIdx.z, gridDim.z, smem_all);
+    gemm_tile<EPI, KS, SPLIT, ACC>(g, bm, bn, blockIdx.z, gridDim.z, smem_all);
 }
 
 static_assert(BM == gemm_shape::BM && BN == gemm_shape::BN && BK == gemm_shape::BK, "gemm_plan.h plans these tiles");
@@ -794,15 +825,19 @@ void gemm_split_bump_epoch() { ++g_switches.epoch; }
 void set_gemm_split_override(int v) { v = v < -1 ? -1 : v > 2 ? 2 : v; if (v != g_switches.split_override) ++g_switches.epoch; g_switches.split_override = v; }
 int gemm_split_override() { return g_switches.split_override; }
 
-template <int EPI, int KS, bool SPLIT = false>
+template <int EPI, int KS, bool SPLIT = false, bool ACC = false>
 static void launch_one(const GemmLaunchPlan& l, hipStream_t stream) {
     static LdsAttribute attr;
-    (void)gemm_dynamic_lds(attr, reinterpret_cast<const void*>(&gemm_kernel<EPI, KS, SPLIT>), l.lds_bytes);
-    hipLaunchKernelGGL((gemm_kernel<EPI, KS, SPLIT>), dim3(l.grid_x, l.grid_y, l.grid_z), dim3(l.block), l.lds_bytes, stream, l.batch);
+    (void)gemm_dynamic_lds(attr, reinterpret_cast<const void*>(&gemm_kernel<EPI, KS, SPLIT, ACC>), l.lds_bytes);
+    hipLaunchKernelGGL((gemm_kernel<EPI, KS, SPLIT, ACC>), dim3(l.grid_x, l.grid_y, l.grid_z), dim3(l.block), l.lds_bytes, stream, l.batch);
 }
 
 // Runs a plan: per launch the clears, then the kernel of its form.
 static void run_launches(int epi, const GemmPlan& plan, hipStream_t stream) {
+    if (!gemm_plan_takes_acc_in(plan)) {        // (a host-side bug: the callers set the field only behind this very question)
+        fprintf(stderr, "cor_asv_ann_hip: a GEMM job with acc_in was planned for a launch form without it\n");
+        abort();
+    }
     for (int i = 0; i < plan.count; ++i) {
         const GemmLaunchPlan& l = plan.launch[i];
         for (int j = 0; j < l.batch.count; ++j) {
@@ -815,7 +850,12 @@ static void run_launches(int epi, const GemmPlan& plan, hipStream_t stream) {
         const bool lstm = epi == EPI_LSTM, two = l.form == FORM_FP32_128_2WG;
         if (l.form == FORM_SKINNY_32 || l.form == FORM_SKINNY_64) run_gemm_skinny(epi, l, stream);
         else if (l.form == FORM_SPLIT_256) run_gemm_split256(epi, l, stream);
-        else if (l.form == FORM_SPLIT_128) { if (lstm) launch_one<EPI_LSTM, 1, true>(l, stream); else launch_one<EPI_PLAIN, 1, true>(l, stream); }
+        else if (l.form == FORM_SPLIT_128) {
+            bool acc = false;           // (a launch with a job that carries acc_in: the variant that reads it)
+            for (int j = 0; j < l.batch.count; ++j) acc = acc || l.batch.g[j].acc_in.base;
+            if (acc) { if (lstm) launch_one<EPI_LSTM, 1, true, true>(l, stream); else launch_one<EPI_PLAIN, 1, true, true>(l, stream); }
+            else if (lstm) launch_one<EPI_LSTM, 1, true>(l, stream); else launch_one<EPI_PLAIN, 1, true>(l, stream);
+        }
         else if (lstm) { if (two) launch_one<EPI_LSTM, 2>(l, stream); else launch_one<EPI_LSTM, 1>(l, stream); }
         else { if (two) launch_one<EPI_PLAIN, 2>(l, stream); else launch_one<EPI_PLAIN, 1>(l, stream); }
     }

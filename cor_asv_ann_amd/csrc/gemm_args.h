@@ -52,6 +52,11 @@ struct GemmArgs {
     int xcd_rows;         // XCD-aware tile order: the 8 XCDs form an xcd_rows x (8/xcd_rows) grid over the tile grid (0 = off)
     int b_static;         // Bt changes only at casv_commit_weights (inference weights): the split-bf16 experiment may keep a pre-split image of it
     const void* Bimg;     // set by launch_gemm_split256: that image (gemm_split.hip), or nullptr
+    Seg acc_in;           // optional (base != nullptr), 128x128 split tiles only (gemm.hip, SPLIT): the tile's accumulators start from
+                          // rows of N floats in the job's column order -- row rows[m] (or m) of base + slot * slot_stride, `ld` floats
+                          // apart -- instead of from zero: the fp32 accumulators another launch left behind the K segments that come
+                          // first (its raw plain output), so that [x | h] in one launch and x, then h on top of it, are the same
+                          // instruction sequence per element.  width / koff / skip_first / first_base are not used.
     int ksplit;           // PLAIN: 0/1 = one block per tile; n > 1 = K split over n blocks (float atomics into C);
                           // -1 = let the launcher choose (train step only: sums become order-dependent)
     // step source

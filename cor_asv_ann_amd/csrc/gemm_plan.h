@@ -229,6 +229,7 @@ inline bool gemm_split256_cut_rows(const GemmContext& ctx, const GemmSwitches& s
     };
     for (int i = 0; i < g.nseg; ++i) shift(tail.a[i]);
     shift(tail.c_in);
+    shift(tail.acc_in);         // (moves with its rows like every input; a plan that pairs it with a 256x256 launch is refused all the same)
     for (SlotPtr* sp : {&tail.out, &tail.c_out, &tail.zinit, &tail.gates_out, &tail.out2})
         if (sp->base) sp->base += (long long)m_off * sp->ld;
     if (g.nact) tail.nact += m_off / g.nact_group;
@@ -363,6 +364,17 @@ inline GemmPlan plan_gemm_launches(const GemmContext& ctx, const GemmSwitches& s
     }
     if (cut_tail_rows) gemm_plan_add_skinny(plan, cut_tail, 1, cut_tail_rows);
     return plan;
+}
+// GemmArgs.acc_in is honoured by the 128x128 split tiles alone (one block per tile).  The field takes no part in any decision above;
+// a caller that wants to set it plans its batch first and asks here whether every launch that would carry it has that form -- the
+// launchers refuse a plan that fails this.
+inline bool gemm_plan_takes_acc_in(const GemmPlan& p) {
+    for (int i = 0; i < p.count; ++i) {
+        const GemmLaunchPlan& l = p.launch[i];
+        for (int j = 0; j < l.batch.count; ++j)
+            if (l.batch.g[j].acc_in.base && (l.form != FORM_SPLIT_128 || l.grid_z != 1)) return false;
+    }
+    return true;
 }
 // (which tile shape a batch starts with: the profile class of a fused-LSTM launch, engine.h)
 inline bool gemm_plan_is_skinny(const GemmPlan& p) { return p.count > 0 && (p.launch[0].form == FORM_SKINNY_32 || p.launch[0].form == FORM_SKINNY_64); }

@@ -250,6 +250,12 @@ class HipEngine(object):
         enc, st = self._stripw(enc, self.cblocks), self._stripw(st)
         return enc, [st[i] for i in range(2 * self.depth)]
 
+    def debug_u(self):
+        """Test support (casv_debug_get_u): u = attention_dense(enc_out) of the last encoder pass, (B, T, padded width) as on the device."""
+        u = np.empty((self.B, self.T, self.pwidth), np.float32)
+        nv.check(self.lib.casv_debug_get_u(self.handle, nv.ptr(u)))
+        return u
+
     def decoder_step(self, line, p_in, states, a_in):
         line = nv.carray(line, np.int32)
         R = line.shape[0]
@@ -614,15 +620,17 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_activation(self.handle, w, n, nv.ptr(x), nv.ptr(out)))
         return out
 
-    def debug_gemm_jobs(self, epi, jobs, step, step_by_ptr=False):
+    def debug_gemm_jobs(self, epi, jobs, step, step_by_ptr=False, acc=None):
         """Test support (casv_debug_gemm_jobs): ONE batch of forward GEMM jobs (epi 0 plain, 1 fused LSTM cell) with the whole
         operand machinery of csrc/gemm_args.h, on host data.  A job is an object with the attributes M, N, Ktot, segs, c_in, zinit, Bt,
         bias, out, c_out, gates_out, out2, nact, nact_group, b_static, epi_plain; an input part (segment, c_in, zinit) has pool
         (slots, pool_rows, ld) float32, width, koff, rows, first, step_mul, step_add, skip_first; an output is (slots, ld, step_mul,
         step_add) or None (tests/lstm_gemm_cases.py builds them).  Returns (outputs, forms, launches): per job a dict name ->
         (slots, M, ld) float32 with every byte the launch did not store to still 0xFF, the bit mask of the GemmForms of the plan that
-        ran, and the number of its launches."""
+        ran, and the number of its launches.  acc (casv_debug_gemm_jobs_acc): per job an input part whose rows (width N) the job's
+        accumulators start from, or None."""
         keep, cjobs, results = [], (nv.DebugJob * len(jobs))(), []
+        caccs = None if acc is None else (nv.DebugRows * len(jobs))()
 
         def arr(a, dtype):
             if a is None:
@@ -665,7 +673,14 @@ class HipEngine(object):
                 cj.nact, cj.nact_lines, cj.nact_group = arr(job.nact, np.int32), len(job.nact), job.nact_group
             cj.b_static, cj.epi_plain = int(job.b_static), int(job.epi_plain)
             results.append(res)
-        nv.check(self.lib.casv_debug_gemm_jobs(self.handle, int(epi), len(jobs), cjobs, int(step), int(bool(step_by_ptr))))
+        if acc is not None:
+            assert len(acc) == len(jobs)
+            for ca, job, part in zip(caccs, jobs, acc):
+                if part is not None:
+                    rows(ca, part)
+            nv.check(self.lib.casv_debug_gemm_jobs_acc(self.handle, int(epi), len(jobs), cjobs, caccs, int(step), int(bool(step_by_ptr))))
+        else:
+            nv.check(self.lib.casv_debug_gemm_jobs(self.handle, int(epi), len(jobs), cjobs, int(step), int(bool(step_by_ptr))))
         return results, self.stat('gemm_jobs_forms'), self.stat('gemm_jobs_launches')
 
     def debug_bwd_step(self, form, jobs, outputs=None):

@@ -417,6 +417,17 @@ typedef struct casv_debug_job {
     int32_t epi_plain;
 } casv_debug_job;
 int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, int32_t step, int32_t step_by_ptr);
+/* The same with an accumulator input per job (csrc/gemm_args.h, acc_in; acc[j].pool = NULL: none): the job's accumulators start
+ * from row (rows ? rows[m] : m) of the addressed slot of acc[j] -- width = N, no first / skip_first -- instead of from zero.  Split
+ * arithmetic only (CASV_ERR_ARG under arithmetic 0, and where a job with an accumulator input would not run as 128x128 split
+ * tiles); K segments may be multiples of 16 wide here.  tests/test_gpu_acc_in.py: [x | h] in one launch against x alone (no bias:
+ * the raw accumulators) and then h on top of them, bit for bit. */
+/* Test support: u = attention_dense(enc_out), (B,T,width) floats, as the last encoder pass behind casv_encode /
+ * casv_set_encoder_outputs left it on the device; CASV_ERR_STATE if none has run yet (the pass runs for the first entry point that
+ * consumes it, e.g. casv_get_encoder_outputs). */
+int casv_debug_get_u(casv_model* m, float* u);
+int casv_debug_gemm_jobs_acc(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc,
+                             int32_t step, int32_t step_by_ptr);
 /* Test support: ONE backward time step of 1 or 2 LSTM layers on the caller's host data, as the train step launches it where a
  * layer has no persistent backward.  form 0 = the fused launch (csrc/gemm_bwd.hip: the cell's pointwise backward inside the data
  * GEMM out = dz . Bt^T), form 1 = the two launches of the options "deterministic" and "fused_backward" off (lstm_bwd_kernel, then
@@ -494,7 +505,14 @@ int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, const casv_d
  * "persistent"; csrc/persist_split.hip: the same instruction, product and tile order as the per-step launches, the same bits); the
  * persistent greedy DECODER exists in arithmetic 0 only, so under 1 / 2 the greedy decodes step kernel by kernel.
  * "split_bf16" (process-wide; default -1 = none; also CASV_SPLIT_BF16 = 0 / 1 / 2 in the environment when the library is loaded):
- * override of every handle's "arithmetic" for all launches of the decode path (tests, A/B measurements). */
+ * override of every handle's "arithmetic" for all launches of the decode path (tests, A/B measurements).
+ * "encoder_table" (per handle; default 1; CASV_ENCODER_TABLE=0 in the environment when the handle is created sets 0): 1 = layer 1 of
+ * an encoder pass that runs step by step in a split arithmetic on plain text (one alternative of weight exactly 1 per position, no
+ * bridge) starts its cells from a per-character table of the accumulators of E[v] . K (csrc/encoder.hip) and contracts the recurrent
+ * columns only -- the same bits; 2 = also the input terms of layers 2..D ahead: per layer ONE contraction over all B x T positions, then
+ * the cells one after the other on top of its rows instead of the anti-diagonal wavefront (same bits; measured slower on c3, so not
+ * the default: DESIGN.md section 4.5); 0 = never.  "beam_skip_last" (per handle; default 1; CASV_BEAM_SKIP_LAST=0 likewise): 0 = debug
+ * switch, the last iteration of casv_decode_beam launches its decoder step although nothing reads its results (same results). */
 int casv_set_option(casv_model* m, const char* key, int64_t value);
 /* Statistics of the last call (tests): "beam_max_new_keys" = most child hypotheses one line created in one search
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
@@ -507,6 +525,8 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * admits for the persistent decoder at this model's staged rows, "decoder_persist_g_lstm" / "_g_att" / "_g_plain" = workgroups
  * per role (all 0 where the option, the arithmetic, the device or the depth rule the launch out), "encoder_persist_per_cu" and
  * "encoder_persist_grid" = the same figure and the workgroups of the last encoder pass that was planned (grid 0: no form);
+ * "encoder_table" = 1 if the last encoder pass took layer 1's input terms from the per-character table (option "encoder_table"),
+ * "encoder_ahead" = 1 if it took the upper layers' input terms ahead (value 2), "encoder_table_builds" = tables built on this handle so far (one per casv_commit_weights that was followed by such a pass);
  * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
  * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
