@@ -416,7 +416,7 @@ static void persist_args(const casv_model* m, const PersistDecPlan& plan, int mo
 
 #ifdef CASV_PERSIST_PROF
 // Diagnostic build: the launch's tick sums per role, and (CASV_PERSIST_PLACEMENT) which roles shared a CU.
-static DevBuf g_persist_profbuf;
+static DevBuf& g_persist_profbuf = *new DevBuf();     // (leaked on purpose: a static DevBuf would free into a runtime that may be gone at exit)
 static int persist_prof_dump(casv_model* m, const PersistArgs& pa) {
     unsigned long long h[32];
     HIPCHK(hipMemcpyAsync(h, g_persist_profbuf.p, sizeof h, hipMemcpyDeviceToHost, m->stream));

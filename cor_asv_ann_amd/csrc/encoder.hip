@@ -44,7 +44,7 @@ static int launch_persist_enc(casv_model* m, const PersistEncPlan& plan, float* 
     if (split) { fill_persist_enc_args(m, false, lout, ps); ps.inject = m->persist_fault_split ? 1 : 0; }
     else { fill_persist_enc_args(m, true, lout, pc); pc.lda = persist_enc_lda(PersistEncShape{D, W, false, false}); }
 #ifdef CASV_PERSIST_PROF
-    static DevBuf eprof;
+    static DevBuf& eprof = *new DevBuf();       // (leaked on purpose: a static DevBuf would free into a runtime that may be gone at exit)
     if (!split) {
         if (int rc = eprof.ensure(32 * 8)) return rc;
         HIPCHK(hipMemsetAsync(eprof.p, 0, 32 * 8, m->stream));

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstdarg>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <string>
 #include <vector>
@@ -34,8 +35,15 @@ inline int fail(int code, const char* fmt, ...) {
                 hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 inline long g_devbuf_generation = 0;    // bumped by every (re)allocation: captured hipGraphs hold raw pointers
+// A device allocation and its owner: move-only, freed with the object that holds it.  (No DevBuf has static storage: its
+// destructor would call the runtime during process teardown.)
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
         ++g_devbuf_generation;
@@ -152,9 +160,9 @@ struct casv_model {
     DevBuf b_gkey, b_gid, b_qkey, b_qid, b_qn, b_fkey, b_fid, b_fn, b_ftotal, b_beamnode, b_nact, b_done, b_steps, b_active;
     DevBuf bo_idx, bo_prob, bo_len, bo_score, bo_rej, bo_align, bo_found, bo_nsteps;
     DevBuf b_rowrec, b_candidx, b_candval;                // wide beams: phase A's per-row results (beam_expand_kernel)
-    // training session (train.hip)
+    // training session (train_state.hip)
     TrainState* train = nullptr;
-    // forward-only state of casv_score_targets outside a session (train.hip): built from the weights of commit number commit_gen
+    // forward-only state of casv_score_targets outside a session (score.hip): built from the weights of commit number commit_gen
     TrainState* score = nullptr; unsigned long long commit_gen = 0;
     // options
     int eos = 1;                                          // vocabulary index of '\n' (seq2seq.py:1255,1344,1402)
@@ -242,6 +250,29 @@ inline int upload(DevBuf& b, const std::vector<float>& v) {
     return 0;
 }
 
+
+// The device operands of a test-support entry point.  Declared BEHIND the entry's local DevBufs, it goes first on every way out
+// (an early return on a failed allocation or copy included): its destructor waits for the stream's work and drops the pre-split
+// images a split launch made of weight buffers; then the buffers put() made free themselves, then the locals.
+struct DebugBuffers {
+    hipStream_t stream;
+    const DevBuf* weight = nullptr;             // a local buffer that served as a weight
+    std::deque<DevBuf> owned = {}; std::vector<const float*> weights = {};      // put()'s buffers; those among them that served as weights
+    ~DebugBuffers() {
+        (void)hipStreamSynchronize(stream);
+        if (weight && weight->p) gemm_split_invalidate(weight->as<float>());
+        for (const float* w : weights) gemm_split_invalidate(w);
+    }
+    // a device copy of n elements of 4 bytes (src == nullptr: n elements of 0xFF bytes); nullptr: see rc
+    void* put(const void* src, size_t n, int& rc) {
+        owned.emplace_back();
+        DevBuf& b = owned.back();
+        if ((rc = b.ensure((n ? n : 1) * 4))) return nullptr;
+        const hipError_t e = src ? hipMemcpyAsync(b.p, src, n * 4, hipMemcpyHostToDevice, stream) : hipMemsetAsync(b.p, 0xff, (n ? n : 1) * 4, stream);
+        if (e != hipSuccess) { rc = fail(CASV_ERR_HIP, "copy of a debug operand failed: %s", hipGetErrorString(e)); return nullptr; }
+        return b.p;
+    }
+};
 
 inline Seg mkseg(const float* base, int ld, int width, int koff, const int* rows = nullptr,
                  long long slot_stride = 0, int mul = 0, int add = 0, int skip_first = 0) {

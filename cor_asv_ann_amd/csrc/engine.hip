@@ -1,5 +1,5 @@
 // Host side of the C ABI (include/cor_asv_ann_hip.h): the handle, weight repacking, result records, statistics, profile, debug entry
-// points and options.  The decode entry points are decode.hip, the encoder pass (seq2seq.py:237-314) encoder.hip, training train.hip.
+// points and options.  The decode entry points are decode.hip, the encoder pass (seq2seq.py:237-314) encoder.hip, the training session train_state.hip, its step train.hip, scoring score.hip.
 #include "engine.h"
 
 static std::map<std::string, size_t> expected_shapes(const casv_config& c) {
@@ -78,28 +78,8 @@ extern "C" void casv_model_destroy(casv_model* m) {
     (void)hipStreamSynchronize(m->stream);
     for (auto& l : m->dec) gemm_split_invalidate(l.wt.as<float>());
     gemm_split_invalidate(m->WaT.as<float>()); gemm_split_invalidate(m->E.as<float>());
-    DevBuf* bufs[] = {&m->E, &m->WaT, &m->bUW, &m->va, &m->bv, &m->UT, &m->enc_fw.wt, &m->enc_fw.bias,
-        &m->enc_bw.wt, &m->enc_bw.bias, &m->d_idx, &m->d_val, &m->d_srcrej, &m->x0, &m->H1, &m->Ha, &m->Hb, &m->Hc, &m->cfin,
-        &m->hfin, &m->u, &m->st_a, &m->st_p, &m->ctx, &m->wq, &m->logits, &m->prev, &m->pin, &m->apos, &m->amax1,
-        &m->d_step, &m->d_line, &m->d_nan, &m->st_q, &m->o_idx, &m->o_prob, &m->o_align, &m->a0, &m->rec, &m->st_win, &m->sp_lo, &m->sp_w, &m->b_parent, &m->b_chr, &m->b_prob,
-        &m->b_cum, &m->b_len, &m->b_exp, &m->b_k, &m->b_rejpos, &m->b_pos, &m->b_is1, &m->b_count, &m->b_created,
-        &m->b_gkey, &m->b_gid, &m->b_qkey, &m->b_qid, &m->b_qn, &m->b_fkey, &m->b_fid, &m->b_fn, &m->b_ftotal, &m->b_beamnode, &m->b_nact,
-        &m->b_done, &m->b_steps, &m->b_active, &m->bo_idx, &m->bo_prob, &m->bo_len, &m->bo_score,
-        &m->bo_rej, &m->bo_align, &m->bo_found, &m->bo_nsteps, &m->b_rowrec, &m->b_candidx, &m->b_candval,
-        &m->lm_h, &m->lm_c, &m->lm_logits, &m->lm_probs, &m->b_candlm};
-    for (DevBuf* b : bufs) b->release();
-    for (auto& l : m->enc) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
-    for (LstmW* l : {&m->enc_fw, &m->enc_bw}) { l->pw.release(); l->pbias.release(); }
-    for (auto* v : {&m->enc_dfw, &m->enc_dbw}) for (auto& l : *v) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
-    for (auto& l : m->dec) { l.wt.release(); l.bias.release(); l.pw.release(); l.pbias.release(); }
-    for (DevBuf* b : {&m->WaP, &m->EP, &m->p_ctx, &m->p_wq, &m->p_logits, &m->p_counters, &m->p_enc_counters, &m->d_flags}) b->release();
-    for (DevBuf* b : {&m->enc_tab[0], &m->enc_tab[1], &m->enc_tab_x, &m->enc_tab_idx, &m->enc_cidx, &m->enc_zx}) b->release();
     if (m->pin_in) (void)hipHostFree(m->pin_in);
     if (m->pin_out) (void)hipHostFree(m->pin_out);
-    for (auto& b : m->st_h) b.release();
-    for (auto& b : m->st_c) b.release();
-    for (auto* v : {&m->br_hT, &m->br_hb, &m->br_cT, &m->br_cb}) for (auto& b : *v) b.release();
-    m->br_tmp.release();
     (void)casv_train_release(m);
     (void)casv_score_release(m);
     vendor_gemm_release(m->stream);
@@ -110,7 +90,7 @@ extern "C" void casv_model_destroy(casv_model* m) {
     for (auto e : m->prof.pool) (void)hipEventDestroy(e);
     (void)hipEventDestroy(m->ev_inputs);
     (void)hipStreamDestroy(m->stream);
-    delete m;
+    delete m;              // (every DevBuf of the handle frees itself)
 }
 
 extern "C" int casv_set_weight(casv_model* m, const char* name, const float* data, int64_t count) {
@@ -260,7 +240,7 @@ extern "C" int casv_commit_weights(casv_model* m) {
                 if (int rc = upload(s ? m->br_cb[n] : m->br_hb[n], m->host[b + "_b"])) return rc;
             }
     m->committed = true;
-    ++m->commit_gen;                    // (a scoring state built from the weights before is rebuilt: train.hip, score_state)
+    ++m->commit_gen;                    // (a scoring state built from the weights before is rebuilt: score.hip, score_state)
     return CASV_OK;
 }
 
@@ -381,31 +361,6 @@ extern "C" int casv_profile_read(casv_model* m, const char* name, int64_t* launc
     return fail(CASV_ERR_ARG, "unknown kernel class '%s'", name);
 }
 
-// The operand buffers of the two debug entry points: released on EVERY way out (an early return on a failed allocation or copy
-// must not leak M*K + N*K + M*N floats), behind the stream's work, and the pre-split image a split launch made of Bt with them.
-// (casv_debug_gemm_jobs has as many buffers and weights as its jobs describe: `owned` are made by put() and deleted here, `weights`
-// are further weight buffers whose images go)
-struct DebugBuffers {
-    std::vector<DevBuf*> bufs; DevBuf* weight; hipStream_t stream;
-    std::vector<DevBuf*> owned = {}; std::vector<const float*> weights = {};
-    ~DebugBuffers() {
-        (void)hipStreamSynchronize(stream);
-        if (weight && weight->p) gemm_split_invalidate(weight->as<float>());
-        for (const float* w : weights) gemm_split_invalidate(w);
-        for (DevBuf* b : bufs) b->release();
-        for (DevBuf* b : owned) { b->release(); delete b; }
-    }
-    // a device copy of n elements of 4 bytes (src == nullptr: n elements of 0xFF bytes); nullptr: see rc
-    void* put(const void* src, size_t n, int& rc) {
-        DevBuf* b = new DevBuf();
-        owned.push_back(b);
-        if ((rc = b->ensure((n ? n : 1) * 4))) return nullptr;
-        const hipError_t e = src ? hipMemcpyAsync(b->p, src, n * 4, hipMemcpyHostToDevice, stream) : hipMemsetAsync(b->p, 0xff, (n ? n : 1) * 4, stream);
-        if (e != hipSuccess) { rc = fail(CASV_ERR_HIP, "copy of a debug operand failed: %s", hipGetErrorString(e)); return nullptr; }
-        return b->p;
-    }
-};
-
 // Measurement aid: time `iters` launches of one GEMM shape in isolation (random operands).
 extern "C" int casv_debug_gemm(casv_model* m, int32_t lstm, int32_t M, int32_t N, int32_t K, int32_t gather,
                                int32_t iters, double* ms_per_launch) {
@@ -414,7 +369,7 @@ extern "C" int casv_debug_gemm(casv_model* m, int32_t lstm, int32_t M, int32_t N
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     DevBuf A, Bt, bias, C, cst, rows;
-    DebugBuffers release_on_exit{{&A, &Bt, &bias, &C, &cst, &rows}, &Bt, m->stream};
+    DebugBuffers release_on_exit{m->stream, &Bt};
     if (int rc = A.ensure((size_t)M * K * 4)) return rc;
     if (int rc = Bt.ensure((size_t)N * K * 4)) return rc;
     if (int rc = bias.ensure((size_t)N * 4)) return rc;
@@ -462,7 +417,7 @@ extern "C" int casv_debug_contract(casv_model* m, int32_t flags, int32_t M, int3
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     DevBuf A, Bt, bias, C;
-    DebugBuffers release_on_exit{{&A, &Bt, &bias, &C}, &Bt, m->stream};
+    DebugBuffers release_on_exit{m->stream, &Bt};
     if (int rc = A.ensure((size_t)M * K * 4)) return rc;
     if (int rc = Bt.ensure((size_t)N * K * 4)) return rc;
     if (int rc = bias.ensure((size_t)N * 4)) return rc;
@@ -514,7 +469,7 @@ extern "C" int casv_debug_contract_tn(casv_model* m, int32_t flags, int32_t M, i
     const size_t na = (size_t)(K - 1) * lda + M, nb = (size_t)(K - 1) * ldb + N;
     const size_t nc = (size_t)(Mstore - 1) * ldc + N, nc_all = (size_t)M * ldc + N;      // (guard: every row of M and one more)
     DevBuf A, B, C, cs, ws;
-    DebugBuffers release_on_exit{{&A, &B, &C, &cs, &ws}, nullptr, m->stream};
+    DebugBuffers release_on_exit{m->stream};
     if (int rc = A.ensure(na * 4)) return rc;
     if (int rc = B.ensure(nb * 4)) return rc;
     if (int rc = C.ensure(nc_all * 4)) return rc;
@@ -642,7 +597,7 @@ static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
     if (acc && !m->gemm.arithmetic) return fail(CASV_ERR_ARG, "casv_debug_gemm_jobs_acc needs a split arithmetic (option \"arithmetic\" or \"split_bf16\" = 1 or 2)");
-    DebugBuffers dev{{}, nullptr, m->stream};
+    DebugBuffers dev{m->stream};
     int rc = CASV_OK;
     const int* step_word = nullptr;
     if (step_by_ptr) { step_word = static_cast<const int*>(dev.put(&step, 1, rc)); if (rc) return rc; }
@@ -730,7 +685,7 @@ extern "C" int casv_debug_activation(casv_model* m, int32_t which, int64_t n, co
     HIPCHK(hipSetDevice(m->device));
     const size_t nin = (size_t)n * (which == 2 ? 5 : 1), nout = (size_t)n * (which == 2 ? 2 : 1);
     DevBuf in, out;
-    DebugBuffers release_on_exit{{&in, &out}, nullptr, m->stream};
+    DebugBuffers release_on_exit{m->stream};
     if (int rc = in.ensure(nin * 4)) return rc;
     if (int rc = out.ensure(nout * 4)) return rc;
     HIPCHK(hipMemcpyAsync(in.p, in_, nin * 4, hipMemcpyHostToDevice, m->stream));

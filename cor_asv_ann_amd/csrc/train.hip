@@ -22,76 +22,10 @@
 // train_plan.h decides and counts the persistent launches of a step; persist_launch is the one place that asks it and launches.
 // casv_train_step_soft is the same step on soft targets: K (index, mass) slots per position (Step::K / soft_idx / soft_q) staged in
 // place of the target indices in phase 2, the soft head's launcher in phase 5; every other phase does not know the difference.
-// casv_score_targets (teacher-forced log-probabilities of given targets) makes the same two attempts (score_attempt): phases 1-4 as
-// they are, then the projection and the scoring head in place of the loss -- give-up check; on a forward-only state outside a session.
-// casv_score_candidates is the same call with N targets per source: the encoder side of the forward phases works on the Be sources,
-// the decoder side on the B = Be * N rows (Step::Be / N, TLayer::rows); casv_train_step and casv_score_targets have Be = B, N = 1.
-#include "engine.h"
-#include "train_kernels.h"
+// The state the step works on is train_state.h / train_state.hip; Step and the phases a scoring call shares are declared in train_step.h.
+#include "train_step.h"
 
-namespace {
-
-struct TTensor { std::string name; DevBuf w, g, m, v; size_t n = 0; bool frozen = false; };
-
-struct TLayer {
-    std::string name;
-    int kx = 0, kr = 0, len = 0;
-    int rows = 0;                          // rows per time step: the step's B, an encoder layer of a candidates call its Be sources (plan_buffers)
-    bool reverse = false;
-    int iwx = -1, iwr = -1, ib = -1;
-    DevBuf wxT, wrT;                       // derived: [kx][4W], [kr][4W]
-    DevBuf Hown, Cs, Gt, Z, dRec;
-    bool drec_cleared = false;             // this step's forward recurrence has cleared dRec (train_persist.hip: RecJob.zero)
-    float* hs = nullptr; long long hs_ld = 0;
-};
-
-}  // namespace
-
-struct TrainState {
-    casv_adam_params ap{};
-    long step = 0;
-    std::vector<TTensor> tens;
-    std::vector<TLayer> layers;            // enc1_fw, enc1_bw, enc2.., dec1..decD
-    int iE = -1, iUT = -1, iWaT = -1, ibUW = -1, iva = -1, ibv = -1;
-    DevBuf ETp, WaN, UaN;                  // derived: E^T padded [W][Vp], W_a [W][W], U_a [C][W]
-    // bridge_dense (seq2seq.py:299-301): per encoder layer n (index n - 1) and state s (0 = h, 1 = c) the Dense kernel transposed
-    // [W out][W in] (the B operand of the forward product), its bias, and -- derived -- the kernel as Keras holds it [W in][W out]
-    // (the B operand of the data gradient); the bridged states, and the tanh' products of the backward pass
-    struct Bridge { int ikt = -1, ib = -1; DevBuf kn; };
-    std::vector<Bridge> bridge;            // [2 * (n - 1) + s]
-    DevBuf hbr, cbr, brtmp, Ytop;          // [D][Be][W] bridged final states; scratch [Be][W]; residual_connections: top output + its input [U*B][W]
-    DevBuf h0rep, c0rep;                   // casv_score_candidates, N > 1: the decoder's initial states [D][B][W], every source's rows N times
-    int B = 0, T = 0, U = 0, A = 0;        // B: the step's batch = the decoder's rows
-    int Be = 0, N = 1;                     // the encoder's lines and the decoder rows per line, Be * N == B (N > 1: casv_score_candidates only)
-    DevBuf e_idx, e_val, d_in, d_out, d_w, m_enc, m_dec, m_cell;
-    DevBuf d_sidx, d_sq;                   // casv_train_step_soft: the soft targets' slots [B][U][K] (index, mass) in place of d_out
-    DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
-    std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])
-    std::vector<DevBuf> XD;                // deep_bidirectional_encoder: layer n's input = the cross sum of O[n-1] (seq2seq.py:246-259)
-    DevBuf loss, normsq;
-    DevBuf dcalt;                          // second dL/dc buffers of the fused backward steps (two layers)
-    // "deterministic" option: the ordered K-major contractions' partial sums, the workgroups' loss / norm parts, the per-character
-    // segments of the embedding gradient (encoder, decoder input) and their host images
-    int tn_ws_rc = 0;                      // the ordered contractions' workspace could not be had this step (its error, reported by the step)
-    DevBuf tn_ws, sum_parts, seg_enc_off, seg_enc_pos, seg_dec_off, seg_dec_pos;
-    std::vector<int> h_seg_enc_off, h_seg_enc_pos, h_seg_dec_off, h_seg_dec_pos;
-    DevBuf rec_cnt; TrainStepPlan plan; int rec_checked = 0, rec_skip = 0, rec_penalty = 0;   // persistent recurrences: counters per launch, the step's launches, back-off
-    const unsigned* rec_abort[TRAIN_LAUNCH_CAP] = {nullptr};    // ... and where each launch leaves its "gave up" word
-    // The attention cell's backward recurrence as TWO launches side by side (train_persist_topb.hip, split_a): the second stream and
-    // the events that tie it into the step; split_off: a step gave up with the two launches in flight -- one launch from then on.
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool split_off = false; int split_launch = -1;
-    // casv_score_targets: the head's results on the device in the caller's order -- logp / best / rank [B][U], nll / count [B], the
-    // window form of the attention rows -- and whether the buffers hold a scoring call's attention rows (score_B x score_U x score_T).
-    // forward_only: the state of a scoring call outside a session (m->score) -- weights in the train layout, the derived transposes,
-    // the forward buffers; no gradient, no Adam moment, no backward buffer.  commit_gen: the commit of the handle's weights it holds.
-    DevBuf s_logp, s_best, s_rank, s_nll, s_count, s_lo, s_w;
-    DevBuf s_alt_idx, s_alt_logp, s_entropy;     // casv_score_get_alternatives: [B][U][K], [B][U] of the last retrieval
-    int score_B = 0, score_U = 0, score_T = 0;
-    bool forward_only = false; unsigned long long commit_gen = 0;
-    int find(const std::string& n) const { for (size_t i = 0; i < tens.size(); ++i) if (tens[i].name == n) return (int)i; return -1; }
-    float* W_(int i) { return tens[i].w.as<float>(); }
-    float* G_(int i) { return tens[i].g.as<float>(); }
-};
+namespace casv {
 
 // CASV_ATTN_DEFER and CASV_TOPB_SPLIT, read once, as train_plan.h takes them.
 // CASV_ATTN_DEFER: d_enc / du summed behind the cell's backward recurrence instead of by float atomics inside it (attn_bwd.h,
@@ -149,184 +83,6 @@ static int persist_launch(casv_model* m, TrainSite site, double flops, bool* per
     ts->rec_abort[plan.slot] = persist_give_up_word(counters, plan.counter_bytes);
     *persistent = true;
     return 0;
-}
-
-static int gate_row(int W, int u, int g) { return (u / 32) * 128 + g * 32 + (u % 32); }
-
-// Keras (K (kin,4W), R (W,4W), b) -> Wx [4W][kx], Wr [4W][kr], bias [4W]; top: K rows [W, W+C) join the recurrent part
-static void pack_train_lstm(int W, int kx, int kctx, const std::vector<float>& K, const std::vector<float>& R,
-                            const std::vector<float>& b, std::vector<float>& wx, std::vector<float>& wr, std::vector<float>& bias) {
-    const int kr = kctx + W;
-    wx.assign((size_t)4 * W * kx, 0.f); wr.assign((size_t)4 * W * kr, 0.f); bias.assign(4 * W, 0.f);
-    for (int u = 0; u < W; ++u)
-        for (int g = 0; g < 4; ++g) {
-            const int n = gate_row(W, u, g), col = g * W + u;
-            for (int k = 0; k < kx; ++k) wx[(size_t)n * kx + k] = K[(size_t)k * 4 * W + col];
-            for (int k = 0; k < kctx; ++k) wr[(size_t)n * kr + k] = K[(size_t)(kx + k) * 4 * W + col];
-            for (int k = 0; k < W; ++k) wr[(size_t)n * kr + kctx + k] = R[(size_t)k * 4 * W + col];
-            bias[n] = b[col];
-        }
-}
-static void unpack_train_lstm(int W, int kx, int kctx, const std::vector<float>& wx, const std::vector<float>& wr,
-                              const std::vector<float>& bias, std::vector<float>& K, std::vector<float>& R, std::vector<float>& b) {
-    const int kr = kctx + W;
-    K.assign((size_t)(kx + kctx) * 4 * W, 0.f); R.assign((size_t)W * 4 * W, 0.f); b.assign(4 * W, 0.f);
-    for (int u = 0; u < W; ++u)
-        for (int g = 0; g < 4; ++g) {
-            const int n = gate_row(W, u, g), col = g * W + u;
-            for (int k = 0; k < kx; ++k) K[(size_t)k * 4 * W + col] = wx[(size_t)n * kx + k];
-            for (int k = 0; k < kctx; ++k) K[(size_t)(kx + k) * 4 * W + col] = wr[(size_t)n * kr + k];
-            for (int k = 0; k < W; ++k) R[(size_t)k * 4 * W + col] = wr[(size_t)n * kr + kctx + k];
-            b[col] = bias[n];
-        }
-}
-
-static int add_tensor(TrainState* ts, const std::string& name, const std::vector<float>& host, bool frozen) {
-    ts->tens.emplace_back();
-    TTensor& t = ts->tens.back();
-    t.name = name; t.n = host.size(); t.frozen = frozen;
-    const size_t bytes = host.size() * 4;
-    if (t.w.ensure(bytes)) return -1;
-    if (hipMemcpy(t.w.p, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (ts->forward_only) return (int)ts->tens.size() - 1;       // (a scoring state: weights only)
-    if (t.g.ensure(bytes) || t.m.ensure(bytes) || t.v.ensure(bytes)) return -1;
-    (void)hipMemset(t.m.p, 0, bytes); (void)hipMemset(t.v.p, 0, bytes); (void)hipMemset(t.g.p, 0, bytes);
-    return (int)ts->tens.size() - 1;
-}
-
-static bool is_frozen(const std::string& name, const std::string& csv) {
-    size_t pos = 0;
-    while (pos < csv.size()) {
-        size_t e = csv.find(',', pos);
-        if (e == std::string::npos) e = csv.size();
-        const std::string p = csv.substr(pos, e - pos);
-        if (!p.empty() && name.compare(0, p.size(), p) == 0) return true;
-        pos = e + 1;
-    }
-    return false;
-}
-
-static void release_state(casv_model* m, TrainState* ts) {
-    (void)hipSetDevice(m->device);
-    (void)hipStreamSynchronize(m->stream);
-    if (ts->side) { (void)hipStreamSynchronize(ts->side); (void)hipStreamDestroy(ts->side); if (ts->ev_fork) (void)hipEventDestroy(ts->ev_fork); if (ts->ev_join) (void)hipEventDestroy(ts->ev_join); ts->side = nullptr; }
-    for (auto& t : ts->tens) { t.w.release(); t.g.release(); t.m.release(); t.v.release(); }
-    for (auto& l : ts->layers) { l.wxT.release(); l.wrT.release(); l.Hown.release(); l.Cs.release(); l.Gt.release(); l.Z.release(); l.dRec.release(); }
-    for (auto& b : ts->bridge) b.kn.release();
-    for (DevBuf* b : {&ts->hbr, &ts->cbr, &ts->brtmp, &ts->Ytop, &ts->h0rep, &ts->c0rep}) b->release();
-    DevBuf* bufs[] = {&ts->ETp, &ts->WaN, &ts->UaN, &ts->e_idx, &ts->e_val, &ts->d_in, &ts->d_out, &ts->d_w, &ts->m_enc, &ts->m_dec,
-        &ts->m_cell, &ts->X0, &ts->H1, &ts->u, &ts->Y0, &ts->Ym, &ts->WQ, &ts->Ast, &ts->WIN, &ts->RecIn,
-        &ts->logits, &ts->dG, &ts->d_enc, &ts->du, &ts->DWQ, &ts->DSrows, &ts->dhatt, &ts->dfin, &ts->dcbuf, &ts->dX0, &ts->dXtop, &ts->dXl, &ts->dYl, &ts->dOin, &ts->dcbuf2, &ts->dvaP, &ts->dbvP,
-        &ts->loss, &ts->normsq, &ts->rec_cnt, &ts->dcalt, &ts->tn_ws, &ts->sum_parts, &ts->seg_enc_off, &ts->seg_enc_pos, &ts->seg_dec_off,
-        &ts->seg_dec_pos, &ts->s_logp, &ts->s_best, &ts->s_rank, &ts->s_nll, &ts->s_count, &ts->s_lo, &ts->s_w,
-        &ts->s_alt_idx, &ts->s_alt_logp, &ts->s_entropy, &ts->d_sidx, &ts->d_sq};
-    for (DevBuf* b : bufs) b->release();
-    for (auto& b : ts->O) b.release();
-    for (auto& b : ts->DO) b.release();
-    for (auto& b : ts->XD) b.release();
-    delete ts;
-}
-int casv_train_release(casv_model* m) {
-    if (!m || !m->train) return 0;
-    release_state(m, m->train);
-    m->train = nullptr;
-    return 0;
-}
-// The forward-only state a scoring call outside a session built (casv_score_targets); allowed when there is none.
-extern "C" int casv_score_release(casv_model* m) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->score) return CASV_OK;
-    release_state(m, m->score);
-    m->score = nullptr;
-    return CASV_OK;
-}
-
-// Refresh the layouts derived from the master tensors (after set-up and after every update).
-static void refresh_derived(casv_model* m, TrainState* ts) {
-    const int W = m->W, V = m->V, Vp = m->Vp, C = m->C;
-    for (auto& l : ts->layers) {
-        launch_transpose(ts->W_(l.iwx), 4 * W, l.kx, l.kx, l.wxT.as<float>(), 4 * W, m->stream);
-        launch_transpose(ts->W_(l.iwr), 4 * W, l.kr, l.kr, l.wrT.as<float>(), 4 * W, m->stream);
-    }
-    launch_transpose(ts->W_(ts->iE), V, W, W, ts->ETp.as<float>(), Vp, m->stream);
-    launch_transpose(ts->W_(ts->iWaT), W, W, W, ts->WaN.as<float>(), W, m->stream);
-    launch_transpose(ts->W_(ts->iUT), W, C, C, ts->UaN.as<float>(), W, m->stream);
-    for (auto& b : ts->bridge) launch_transpose(ts->W_(b.ikt), W, W, W, b.kn.as<float>(), W, m->stream);
-}
-
-// The handle's weights (Keras layout, m->host) as the step's packed tensors in ts, with the derived layouts: a session's state
-// (with gradients and Adam moments) or, ts->forward_only, a scoring state.  On an error the caller releases ts.
-static int build_state(casv_model* m, TrainState* ts, const std::string& fz) {
-    const int W = m->W, D = m->D, C = m->C, Vp = m->Vp;
-    auto add_lstm = [&](const std::string& prefix, int kx, int kctx, bool reverse) -> int {
-        std::vector<float> wx, wr, bias;
-        pack_train_lstm(W, kx, kctx, m->host[prefix + "_K"], m->host[prefix + "_R"], m->host[prefix + "_b"], wx, wr, bias);
-        TLayer l;
-        l.name = prefix; l.kx = kx; l.kr = kctx + W; l.reverse = reverse;
-        const bool frozen = is_frozen(prefix + "_", fz);
-        l.iwx = add_tensor(ts, prefix + "_Wx", wx, frozen);
-        l.iwr = add_tensor(ts, prefix + "_Wr", wr, frozen);
-        l.ib = add_tensor(ts, prefix + "_b", bias, frozen);
-        if (l.iwx < 0 || l.iwr < 0 || l.ib < 0) return -1;
-        if (l.wxT.ensure((size_t)kx * 4 * W * 4) || l.wrT.ensure((size_t)l.kr * 4 * W * 4)) return -1;
-        ts->layers.push_back(std::move(l));
-        return 0;
-    };
-    ts->iE = add_tensor(ts, "E", m->host["E"], false);
-    int rc = add_lstm("enc1_fw", W, 0, false) | add_lstm("enc1_bw", W, 0, true);
-    const bool deep_b = m->cfg.deep_bidirectional_encoder != 0;
-    for (int n = 2; n <= D && !deep_b; ++n) rc |= add_lstm("enc" + std::to_string(n), n == 2 ? 2 * W : W, 0, false);
-    for (int n = 2; n <= D && deep_b; ++n)      // every layer bidirectional, 2W-wide inputs (seq2seq.py:273-276): [.. encN_fw, encN_bw ..]
-        rc |= add_lstm("enc" + std::to_string(n) + "_fw", 2 * W, 0, false) | add_lstm("enc" + std::to_string(n) + "_bw", 2 * W, 0, true);
-    for (int n = 1; n < D; ++n) rc |= add_lstm("dec" + std::to_string(n), W, 0, false);
-    rc |= add_lstm("dec" + std::to_string(D), W, C, false);
-    std::vector<float> ut((size_t)W * C), wat((size_t)W * W);
-    const auto& Uk = m->host["att_U"]; const auto& Wa = m->host["att_Wa"];
-    for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) ut[(size_t)j * C + c] = Uk[(size_t)c * W + j];
-    for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) wat[(size_t)j * W + k] = Wa[(size_t)k * W + j];
-    ts->iUT = add_tensor(ts, "att_UT", ut, false);
-    ts->iWaT = add_tensor(ts, "att_WaT", wat, false);
-    ts->ibUW = add_tensor(ts, "att_bUW", m->host["att_bUW"], false);
-    ts->iva = add_tensor(ts, "att_va", m->host["att_va"], false);
-    ts->ibv = add_tensor(ts, "att_bv", m->host["att_bv"], false);
-    if (m->cfg.bridge_dense)
-        for (int n = 1; n <= D; ++n)
-            for (int s = 0; s < 2; ++s) {
-                const std::string b = "bridge" + std::to_string(n) + (s ? "_c" : "_h");
-                const auto& K = m->host[b + "_K"];
-                std::vector<float> kt((size_t)W * W);
-                for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) kt[(size_t)j * W + k] = K[(size_t)k * W + j];
-                TrainState::Bridge br;
-                const bool frozen = is_frozen(b + "_", fz);
-                br.ikt = add_tensor(ts, b + "_KT", kt, frozen);
-                br.ib = add_tensor(ts, b + "_b", m->host[b + "_b"], frozen);
-                if (br.ikt < 0 || br.ib < 0 || br.kn.ensure((size_t)W * W * 4)) rc |= -1;
-                ts->bridge.push_back(std::move(br));
-            }
-    if (rc || ts->iE < 0 || ts->iUT < 0 || ts->iWaT < 0 || ts->ibUW < 0 || ts->iva < 0 || ts->ibv < 0)
-        return fail(CASV_ERR_NOMEM, "could not allocate the training tensors");
-    if (ts->ETp.ensure((size_t)W * Vp * 4) || ts->WaN.ensure((size_t)W * W * 4) || ts->UaN.ensure((size_t)C * W * 4) ||
-        ts->loss.ensure(16) || ts->normsq.ensure(16)) return fail(CASV_ERR_NOMEM, "out of memory");
-    HIPCHK(hipMemset(ts->ETp.p, 0, (size_t)W * Vp * 4));
-    ts->O.resize(D + 1); ts->DO.resize(D + 1); ts->XD.resize(D + 1);
-    refresh_derived(m, ts);
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-extern "C" int casv_train_begin(casv_model* m, const casv_adam_params* ap, const char* frozen_csv) {
-    if (!m || !ap) return fail(CASV_ERR_ARG, "null argument");
-    if (m->W > 1024) return fail(CASV_ERR_ARG, "training supports width <= 1024");
-    HIPCHK(hipSetDevice(m->device));
-    for (auto& kv : m->expect)
-        if (!m->host.count(kv.first)) return fail(CASV_ERR_STATE, "weight '%s' has not been set", kv.first.c_str());
-    casv_train_release(m);
-    (void)casv_score_release(m);
-    TrainState* ts = new TrainState();
-    m->train = ts;
-    ts->ap = *ap;
-    if (int rc = build_state(m, ts, frozen_csv ? frozen_csv : "")) { casv_train_release(m); return rc; }
-    return CASV_OK;
 }
 
 static GemmArgs plain_gemm(const float* A, long long lda, int M, int K, const float* Bt, int N, const float* bias, float* C_, long long ldc,
@@ -601,49 +357,9 @@ static int layers_forward(casv_model* m, const LayerFwd* a, int count, bool* mas
     return 0;
 }
 
-// One attempt's view of the step: what the caller passed, the model's shapes, the step's flags, and what one phase leaves for the
-// next.  casv_train_step fills the first three groups once; every attempt starts from a copy and its phases fill in the rest.
-struct Step {
-    casv_model* m; TrainState* ts; hipStream_t st;
-    int mode, B, T, U, A;           // B: the step's batch, the decoder's rows
-    int Be, N;                      // the encoder's lines, decoder rows per line: Be * N == B (casv_train_step: Be = B, N = 1)
-    const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
-    const float* mask_enc; const float* mask_dec; const float* mask_cell;
-    int K; const int32_t* soft_idx; const float* soft_q;      // casv_train_step_soft: K > 0, (B,U,K) slots in place of dec_out (nullptr)
-    int W, V, Vp, C, D;
-    long long TB, UB;
-    // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent
-    // recurrence, hence no give-up fallback; no fused backward step), no split-K in the launcher, the K-major contractions'
-    // shares added in order, the workgroups' loss / norm parts added by one ordered pass, the embedding gradient per character
-    bool training, det, fused, deep, residual, bridged;
-    // plan_buffers: the encoder's final states [n-1][Be][W], the decoder's initial states [n-1][B][W] (the bridged ones with
-    // bridge_dense; N > 1: either, every row N times), the
-    // gradients w.r.t. the final states [n-1][0|1][B][W], the ordered sums' parts (deterministic only)
-    float* hfin; float* cfin; const float* h0base; const float* c0base; float* dfin; double* parts;
-    // stage_inputs: the dropout masks on the device (nullptr: none) -- enc = 2W + (D-1)*W floats (deep: D * 2W), dec = (D-1)*W floats,
-    // cell = B*(W+C) -- and 1 / the number of weighted targets
-    const float* menc; const float* mdec; const float* mcell; float inv_count;
-    // forward_layers: the cell's input sequence (decoder layer D - 1's masked outputs, Y0 when D == 1) and the attended sequence O[D]
-    const float* y; const float* enc_out;
-    // loss_head: the projection's input
-    const float* proj_in; long long proj_ld;
-
-    const float* menc_n(int n) const { return menc ? menc + (n == 1 ? 0 : deep ? (n - 1) * 2 * W : 2 * W + (n - 2) * W) : nullptr; }   // layer n (1-based)
-    const float* mdec_n(int n) const { return mdec ? mdec + (n - 1) * W : nullptr; }
-    TLayer& enc_layer(int n) const { return ts->layers[n]; }            // n >= 2 -> index n (not with a deep bidirectional encoder)
-    TLayer& enc_dir(int n, int dir) const { return ts->layers[2 * (n - 1) + dir]; }      // deep: layer n = 1..D, direction 0 fw / 1 bw
-    TLayer& dec_layer(int n) const { return ts->layers[(deep ? 2 * D - 1 : D) + n]; }    // n = 1..D
-    TLayer& top() const { return dec_layer(D); }                        // the attention cell
-    const float* dec_h0(int n) const { return h0base + (size_t)(n - 1) * B * W; }        // decoder layer n starts from encoder layer n's final state
-    const float* dec_c0(int n) const { return c0base + (size_t)(n - 1) * B * W; }
-    float* dfin_h(int n) const { return dfin + (size_t)(2 * (n - 1)) * B * W; }
-    float* dfin_c(int n) const { return dfin + (size_t)(2 * (n - 1) + 1) * B * W; }
-    bool res_top() const { return residual && D >= 2; }                 // the projection reads the cell's outputs PLUS its input sequence
-};
-
 // Phase 1 leaves every buffer of the session at least as large as this step's shapes ask, every layer's len / hs / hs_ld, and the
 // view's pointers into the state buffers (read behind the calls that may have moved them).
-static int plan_buffers(Step& s) {
+int plan_buffers(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts;
     const int B = s.B, Be = s.Be, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, Vp = s.Vp, C = s.C, D = s.D;
     const long long TB = s.TB, UB = s.UB;
@@ -661,13 +377,13 @@ static int plan_buffers(Step& s) {
     BWD(ts->dX0, TB * W * 4) BWD(ts->dXtop, UB * W * 4) BWD(ts->dXl, TB * 2 * W * 4) BWD(ts->dYl, UB * W * 4) BWD(ts->dOin, TB * 2 * W * 4)
     BWD(ts->dcbuf2, (size_t)B * W * 4) BWD(ts->dvaP, (size_t)B * W * 4) BWD(ts->dbvP, (size_t)B * 4)
     for (auto& l : ts->layers) {
-        const bool enc = l.name.compare(0, 3, "enc") == 0;
+        const bool enc = l.encoder;
         l.len = enc ? T : U; l.rows = enc ? Be : B;
         const long long rows = (long long)l.len * l.rows;
         ENS(l.Cs, rows * W * 4) ENS(l.Gt, rows * 4 * W * 4) ENS(l.Z, rows * 4 * W * 4) BWD(l.dRec, rows * l.kr * 4)
-        if (l.name == "enc1_fw") { l.hs = ts->H1.as<float>(); l.hs_ld = 2 * W; }
-        else if (l.name == "enc1_bw") { l.hs = ts->H1.as<float>() + W; l.hs_ld = 2 * W; }
-        else if (deep && enc && l.name.size() > 3 && l.name.compare(l.name.size() - 3, 3, "_fw") == 0) { ENS(l.Hown, rows * 2 * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = 2 * W; }
+        const bool first = &l < &ts->layers[2];         // (layer 1's two directions share H1)
+        if (first) { l.hs = ts->H1.as<float>() + l.dir * W; l.hs_ld = 2 * W; }
+        else if (deep && enc && l.dir == 0) { ENS(l.Hown, rows * 2 * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = 2 * W; }
         else if (deep && enc) { l.hs = (&l - 1)->hs + W; l.hs_ld = 2 * W; }        // (a backward direction: the second half of its forward partner's rows)
         else { ENS(l.Hown, rows * W * 4) l.hs = l.Hown.as<float>(); l.hs_ld = W; }
     }
@@ -712,7 +428,7 @@ static void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::
 
 // Phase 2 leaves the batch, the masks and (deterministic) the characters' segments on the device, the step's sums, hand-off counters
 // and (training) gradients cleared, and the session's per-step state reset.
-static int stage_inputs(Step& s) {
+int stage_inputs(Step& s) {
     TrainState* ts = s.ts; hipStream_t st = s.st;
     const int B = s.B, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;
     const long long TB = s.TB, UB = s.UB;
@@ -778,7 +494,7 @@ static void repeat_states(Step& s, int n) {
 // Phase 3 leaves every encoder layer's and every decoder layer's below the cell outputs, cell states and gates, the masked outputs
 // O[n] / DO[n], the final states (and the bridged ones), the cell's input sequence s.y, the attended sequence s.enc_out and its
 // projection u.
-static int forward_layers(Step& s) {
+int forward_layers(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
     const int B = s.B, Be = s.Be, T = s.T, U = s.U, A = s.A, W = s.W, V = s.V, C = s.C, D = s.D;      // (Be: the encoder's rows, B: the decoder's)
     const long long TB = s.TB, UB = s.UB;
@@ -867,7 +583,7 @@ static int forward_layers(Step& s) {
 
 // Phase 4 leaves the attention cell's outputs, cell states and gates, its input rows RecIn, the queries WQ, the attention rows Ast
 // and the windows WIN of every step.
-static int forward_cell(Step& s) {
+int forward_cell(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
     const int B = s.B, T = s.T, U = s.U, W = s.W, C = s.C, D = s.D;
     const long long UB = s.UB;
@@ -918,7 +634,7 @@ static int forward_cell(Step& s) {
 }
 
 // The tied output projection: leaves its input s.proj_in and the logits [U*B][Vp] (columns [V, Vp) are not written).
-static int projection(Step& s) {
+int projection(Step& s) {
     casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
     const int W = s.W, V = s.V, Vp = s.Vp;
     const long long UB = s.UB;
@@ -953,7 +669,7 @@ static int loss_head(Step& s) {
 // Did every persistent recurrence so far run to its end?  (A launch gives up when its workgroups wait too long for each
 // other -- a GPU shared with another process: handoff.h.)  Nothing has been updated yet: the caller starts over with per-step
 // launches, and keeps to them for the next 16, 32, ... steps.  Asked after the forward pass and again in front of the update.
-static int recurrences_gave_up(casv_model* m, bool& any) {
+int recurrences_gave_up(casv_model* m, bool& any) {
     TrainState* ts = m->train; hipStream_t st = m->stream;
     any = false;
     if (ts->plan.launches == ts->rec_checked) return 0;
@@ -1304,6 +1020,7 @@ static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo)
     m->stat_train_launches = ts->plan.launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
     return CASV_OK;
 }
+}  // namespace casv
 
 extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
                                const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
@@ -1395,8 +1112,7 @@ extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int3
     std::vector<float> x((size_t)R * Vp, pad_value);
     for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
     DevBuf dx, di, dq, dw, dl, dp;
-    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
-        release_on_exit{{&dx, &di, &dq, &dw, &dl, &dp}, m->stream};
+    DebugBuffers release_on_exit{m->stream};
     if (int rc = dx.ensure(x.size() * 4)) return rc;
     if (int rc = di.ensure((size_t)R * K * 4)) return rc;
     if (int rc = dq.ensure((size_t)R * K * 4)) return rc;
@@ -1428,19 +1144,6 @@ extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int3
 // a buffer allocated here: they clamp rows to rows - 1 and columns to N - 1, read W floats of every input row ([rows][ld], the
 // last row W floats long) and of the mask, 4W of a gates row and of a Bt row; they store rows < rows only.
 namespace {
-struct DebugBwdBuffers {
-    std::vector<DevBuf*> owned; hipStream_t stream;
-    ~DebugBwdBuffers() { (void)hipStreamSynchronize(stream); for (DevBuf* b : owned) { b->release(); delete b; } }
-    // n floats on the device: a copy of src, or (src == nullptr) 0xFF bytes
-    float* put(const float* src, size_t n, int& rc) {
-        DevBuf* b = new DevBuf();
-        owned.push_back(b);
-        if ((rc = b->ensure(n * 4))) return nullptr;
-        const hipError_t e = src ? hipMemcpyAsync(b->p, src, n * 4, hipMemcpyHostToDevice, stream) : hipMemsetAsync(b->p, 0xff, n * 4, stream);
-        if (e != hipSuccess) { rc = fail(CASV_ERR_HIP, "copy of a debug operand failed: %s", hipGetErrorString(e)); return nullptr; }
-        return b->as<float>();
-    }
-};
 int check_debug_bwd_job(const casv_debug_bwd_job& d, int j, int W0) {
     if (d.rows < 1 || d.rows > (1 << 16) || d.N < 1 || d.N > (1 << 14)) return fail(CASV_ERR_ARG, "job %d: rows in [1, 65536], N in [1, 16384]", j);
     if (d.W < 32 || d.W > 1024 || d.W % 32 || d.W != W0) return fail(CASV_ERR_ARG, "job %d: W a multiple of 32 in [32, 1024], the same in every job", j);
@@ -1461,8 +1164,9 @@ extern "C" int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, c
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
     OrderedScope ordered(m, m->deterministic);          // (as casv_train_step: form 1's GEMM then sums in a fixed order)
-    DebugBwdBuffers dev{{}, m->stream};
+    DebugBuffers dev{m->stream};
     int rc = CASV_OK;
+    auto put = [&](const float* src, size_t n) { return static_cast<float*>(dev.put(src, n, rc)); };     // n floats: a copy of src, or (nullptr) 0xFF bytes
     BwdStepBatch fb{};
     LstmBwdBatch pw{};
     GemmBatch gb{};
@@ -1470,26 +1174,26 @@ extern "C" int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, c
     for (int j = 0; j < count; ++j) {
         const casv_debug_bwd_job& d = jobs[j];
         const size_t rows = (size_t)d.rows, W = (size_t)d.W;
-        auto in = [&](const float* src, int64_t ld) -> const float* { return src ? dev.put(src, (rows - 1) * (size_t)ld + W, rc) : nullptr; };
+        auto in = [&](const float* src, int64_t ld) -> const float* { return src ? put(src, (rows - 1) * (size_t)ld + W) : nullptr; };
         BwdStepJob& q = fb.j[j];
         LstmBwdArgs& p = q.p;
         p.a = in(d.a, d.lda); if (rc) return rc;
         p.lda = d.lda;
-        if (d.mask_a) { p.mask_a = dev.put(d.mask_a, W, rc); if (rc) return rc; }
+        if (d.mask_a) { p.mask_a = put(d.mask_a, W); if (rc) return rc; }
         p.b = in(d.b, d.ldb); if (rc) return rc;
         p.ldb = d.ldb;
         p.c = in(d.c, d.ldc); if (rc) return rc;
         p.ldc = d.ldc;
         p.c_prev = in(d.c_prev, d.ld_cprev); if (rc) return rc;
         p.ld_cprev = d.ld_cprev;
-        p.gates = dev.put(d.gates, rows * 4 * W, rc); if (rc) return rc;
-        p.cell = dev.put(d.cell, rows * W, rc); if (rc) return rc;
-        q.dc_in = dev.put(d.dc_in, rows * W, rc); if (rc) return rc;
-        q.Bt = dev.put(d.Bt, (size_t)d.N * 4 * W, rc); if (rc) return rc;
+        p.gates = put(d.gates, rows * 4 * W); if (rc) return rc;
+        p.cell = put(d.cell, rows * W); if (rc) return rc;
+        q.dc_in = put(d.dc_in, rows * W); if (rc) return rc;
+        q.Bt = put(d.Bt, (size_t)d.N * 4 * W); if (rc) return rc;
         // outputs: 0xFF bytes and one guard row; out[:rows][:N] cleared (the split-K shares add into it)
-        p.dz = dev.put(nullptr, (rows + 1) * 4 * W, rc); if (rc) return rc;
-        p.dc = dev.put(nullptr, (rows + 1) * W, rc); if (rc) return rc;
-        q.out = dev.put(nullptr, (rows + 1) * (size_t)d.ld_out, rc); if (rc) return rc;
+        p.dz = put(nullptr, (rows + 1) * 4 * W); if (rc) return rc;
+        p.dc = put(nullptr, (rows + 1) * W); if (rc) return rc;
+        q.out = put(nullptr, (rows + 1) * (size_t)d.ld_out); if (rc) return rc;
         q.ld_out = d.ld_out; q.N = d.N; p.rows = d.rows; p.W = d.W;
         HIPCHK(hipMemset2DAsync(q.out, (size_t)d.ld_out * 4, 0, (size_t)d.N * 4, rows, m->stream));
         if (form == 1) {            // lstm_bwd_kernel works in place: dL/dc of the step lies where dL/dc of the step before goes
@@ -1530,443 +1234,4 @@ extern "C" int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, c
             if (!untouched(d.out + r * ld + d.N, ld - d.N)) return fail(CASV_ERR_STATE, "job %d: a launch stored behind column N - 1 of out, row %zu", j, r);
     }
     return CASV_OK;
-}
-
-// ---- scoring: teacher-forced log-probabilities of given targets (kt:407 / s2s:491-497, the forward pass of a mode-0 step) ----
-// What a scoring call hands back: (B,U) arrays in the caller's order, (B) sums, the dense alignment rows (B,U,T) or nullptr.
-struct ScoreOut { float* logp; int32_t* best; int32_t* rank; double* nll; int32_t* count; float* align; };
-
-// The head: log-probability, argmax and rank of every row, the lines' sums; leaves them on the device in the caller's order.
-static int score_head(Step& s) {
-    TrainState* ts = s.ts; hipStream_t st = s.st;
-    const int B = s.B, U = s.U, V = s.V, Vp = s.Vp;
-    if (int rc = projection(s)) return rc;
-    launch_score_rows(ts->logits.as<float>(), ts->d_out.as<int>(), B, U, V, Vp, ts->s_logp.as<float>(), ts->s_best.as<int>(),
-                      ts->s_rank.as<int>(), st);
-    launch_score_lines(ts->s_logp.as<float>(), ts->d_out.as<int>(), B, U, V, ts->s_nll.as<double>(), ts->s_count.as<int>(), st);
-    return 0;
-}
-
-// One attempt at a scoring call: the first four phases of the step, the scoring head, the give-up check (as a mode-0 step:
-// *redo -- a persistent forward recurrence gave up, the back-off is set and the caller starts over).
-static int score_attempt(Step s, const ScoreOut& out, bool* redo) {
-    casv_model* m = s.m; TrainState* ts = s.ts; hipStream_t st = s.st;
-    const int B = s.B, T = s.T, U = s.U;
-    ts->B = B; ts->Be = s.Be; ts->N = s.N; ts->T = T; ts->U = U; ts->A = s.A;
-    ts->score_B = 0;
-    m->encoded = false;                    // the final-state buffers are shared with the inference session
-    if (int rc = plan_buffers(s)) return rc;
-    if (int rc = ts->s_logp.ensure(s.UB * 4)) return rc;
-    if (int rc = ts->s_best.ensure(s.UB * 4)) return rc;
-    if (int rc = ts->s_rank.ensure(s.UB * 4)) return rc;
-    if (int rc = ts->s_nll.ensure((size_t)B * 8)) return rc;
-    if (int rc = ts->s_count.ensure((size_t)B * 4)) return rc;
-    if (int rc = stage_inputs(s)) return rc;
-    if (int rc = forward_layers(s)) return rc;
-    if (int rc = forward_cell(s)) return rc;
-    if (int rc = score_head(s)) return rc;
-    HIPCHK(hipGetLastError());
-    if (int rc = recurrences_gave_up(m, *redo)) return rc;
-    if (*redo) return CASV_OK;
-    HIPCHK(hipMemcpyAsync(out.logp, ts->s_logp.p, s.UB * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out.best, ts->s_best.p, s.UB * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out.rank, ts->s_rank.p, s.UB * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out.nll, ts->s_nll.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out.count, ts->s_count.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    std::vector<float> rows;               // the attention rows as the cell left them, [U][B][T] behind the initial row
-    if (out.align) {
-        rows.resize((size_t)s.UB * T);
-        HIPCHK(hipMemcpyAsync(rows.data(), ts->Ast.as<float>() + (size_t)B * T, rows.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    for (int b = 0; b < B && out.align; ++b)
-        for (int u = 0; u < U; ++u)
-            memcpy(out.align + ((size_t)b * U + u) * T, rows.data() + ((size_t)u * B + b) * T, (size_t)T * 4);
-    ts->score_B = B; ts->score_U = U; ts->score_T = T;
-    m->stat_train_launches = ts->plan.launches;      // (statistic "train_persistent_launches", as a mode-0 step reports it)
-    if (m->prof.on) m->prof.collect();
-    return CASV_OK;
-}
-
-// Outside a session the scoring call runs on a forward-only state of its own (m->score), built from the handle's committed weights
-// and kept until they are committed anew; the phases find it where they find a session's state, in m->train, for the call's duration.
-struct ScoreStateScope {
-    casv_model* m; bool borrowed;
-    ~ScoreStateScope() { if (borrowed) m->train = nullptr; }
-};
-static int score_state(casv_model* m) {
-    if (m->score && m->score->commit_gen == m->commit_gen) return CASV_OK;
-    (void)casv_score_release(m);
-    if (m->W > 1024) return fail(CASV_ERR_ARG, "scoring supports width <= 1024");
-    if (!m->committed) return fail(CASV_ERR_STATE, "casv_commit_weights must run first");
-    TrainState* ts = new TrainState();
-    ts->forward_only = true; ts->commit_gen = m->commit_gen;
-    m->score = ts;
-    if (int rc = build_state(m, ts, "")) { (void)casv_score_release(m); return rc; }
-    return CASV_OK;
-}
-
-// The scoring call on Be sources with N given targets each (decoder row r = b * N + n reads source b's encoder pass): the range
-// check over all rows before anything is launched, the state, at most two attempts.
-static int score_call(casv_model* m, int32_t Be, int32_t N, int32_t T, int32_t U, int32_t A,
-                      const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out, const ScoreOut& out) {
-    if (!m || !enc_idx || !dec_in || !dec_out || !out.logp || !out.best || !out.rank || !out.nll || !out.count) return fail(CASV_ERR_ARG, "null argument");
-    if (Be < 1 || N < 1 || T < 1 || U < 1 || A < 1 || (long long)Be * N > INT32_MAX) return fail(CASV_ERR_ARG, "bad shape");
-    const int B = Be * N;
-    const long long UB = (long long)U * B;
-    for (long long i = 0; i < UB; ++i) {     // (before anything is launched)
-        if (dec_out[i] < -1 || dec_out[i] >= m->V) return fail(CASV_ERR_ARG, "dec_out[%lld] = %d outside [-1, %d)", i, dec_out[i], m->V);
-        if (dec_in[i] < -1 || dec_in[i] >= m->V) return fail(CASV_ERR_ARG, "dec_in[%lld] = %d outside [-1, %d)", i, dec_in[i], m->V);
-    }
-    HIPCHK(hipSetDevice(m->device));
-    ScoreStateScope scope{m, false};
-    if (!m->train) {
-        if (int rc = score_state(m)) return rc;
-        m->train = m->score; scope.borrowed = true;
-    }
-    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (the forward pass of a mode-0 step, in its arithmetic)
-    OrderedScope ordered(m, m->deterministic);
-    const std::vector<float> ones((size_t)UB, 1.0f);            // (stage_inputs stages the step's sample weights: the head reads none)
-    Step s{};
-    s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = 0; s.B = B; s.Be = Be; s.N = N; s.T = T; s.U = U; s.A = A;
-    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = ones.data();
-    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * Be; s.UB = UB;
-    // (no masks, no regulariser; det / fused govern the backward pass and the ordered sums of the loss: the head has neither, and
-    // persist_launch and the launchers read the "deterministic" option from the handle)
-    s.training = false; s.det = false; s.fused = false;
-    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
-    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        bool redo = false;
-        if (int rc = score_attempt(s, out, &redo)) return rc;
-        if (!redo) return CASV_OK;
-    }
-    return fail(CASV_ERR_STATE, "the scoring call gave up twice: its second attempt took a persistent launch");
-}
-
-extern "C" int casv_score_targets(casv_model* m, int32_t B, int32_t T, int32_t U, int32_t A,
-                                  const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
-                                  float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
-    return score_call(m, B, 1, T, U, A, enc_idx, enc_val, dec_in, dec_out, ScoreOut{logp, best, rank, nll, count, align});
-}
-
-// N candidate targets per source on ONE encoder pass (kt:407 / s2s:491-497 as casv_score_targets, whose N = 1 call this is): the
-// embedding, the encoder stack, its final states and u = enc_out . U_a are computed for the B sources; every decoder row -- the
-// decoder layers, the attention cell, the projection, the head -- for the B * N candidates, row b * N + n on source b.
-extern "C" int casv_score_candidates(casv_model* m, int32_t B, int32_t N, int32_t T, int32_t U, int32_t A,
-                                     const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
-                                     float* logp, int32_t* best, int32_t* rank, double* nll, int32_t* count, float* align) {
-    return score_call(m, B, N, T, U, A, enc_idx, enc_val, dec_in, dec_out, ScoreOut{logp, best, rank, nll, count, align});
-}
-
-extern "C" int casv_score_get_alignments_sparse(casv_model* m, int32_t K, int32_t* lo, float* w) {
-    if (!m || !lo || !w) return fail(CASV_ERR_ARG, "null argument");
-    TrainState* ts = m->train ? m->train : m->score;
-    if (!ts || !ts->score_B) return fail(CASV_ERR_STATE, "no scoring call to take alignments from");
-    if (K < 2 * m->cfg.window_width + 1 || K > 64) return fail(CASV_ERR_ARG, "K=%d: need at least 2*window_width+1 = %d weights per step (at most 64)", K, 2 * m->cfg.window_width + 1);
-    HIPCHK(hipSetDevice(m->device));
-    const size_t n = (size_t)ts->score_B * ts->score_U;
-    if (int rc = ts->s_lo.ensure(n * 4)) return rc;
-    if (int rc = ts->s_w.ensure(n * K * 4)) return rc;
-    launch_score_extract_sparse(ts->Ast.as<float>(), ts->WIN.as<int>(), ts->score_B, ts->score_U, ts->score_T, K, ts->s_lo.as<int>(),
-                                ts->s_w.as<float>(), m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(lo, ts->s_lo.p, n * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(w, ts->s_w.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// The K likeliest characters and the entropy of every position of the LAST scoring call: the logits of its B * U rows still lie in
-// the state's buffer (the head writes nothing back into them), one launch reads them; nothing a later call reads is changed.
-extern "C" int casv_score_get_alternatives(casv_model* m, int32_t K, int32_t* alt_idx, float* alt_logp, float* entropy) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (K < 1 || K > m->V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, m->V < 64 ? m->V : 64);
-    TrainState* ts = m->train ? m->train : m->score;
-    if (!ts || !ts->score_B) return fail(CASV_ERR_STATE, "no scoring call to take alternatives from");
-    if (!alt_idx || !alt_logp) return fail(CASV_ERR_ARG, "null argument");      // (after the state: a caller without a shape learns why)
-    HIPCHK(hipSetDevice(m->device));
-    const size_t n = (size_t)ts->score_B * ts->score_U;
-    if (int rc = ts->s_alt_idx.ensure(n * K * 4)) return rc;
-    if (int rc = ts->s_alt_logp.ensure(n * K * 4)) return rc;
-    if (int rc = ts->s_entropy.ensure(n * 4)) return rc;
-    launch_score_alternatives(ts->logits.as<float>(), ts->score_B, ts->score_U, m->V, m->Vp, K, ts->s_alt_idx.as<int>(),
-                              ts->s_alt_logp.as<float>(), entropy ? ts->s_entropy.as<float>() : nullptr, m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(alt_idx, ts->s_alt_idx.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(alt_logp, ts->s_alt_logp.p, n * K * 4, hipMemcpyDeviceToHost, m->stream));
-    if (entropy) HIPCHK(hipMemcpyAsync(entropy, ts->s_entropy.p, n * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// Test support: the head alone on the caller's logits (R,V), laid out with the library's row stride and the padding filled.
-extern "C" int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
-                                     float* logp, int32_t* best, int32_t* rank) {
-    if (!m || !logits || !target || !logp || !best || !rank) return fail(CASV_ERR_ARG, "null argument");
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DevBuf dx, dt, dl, db, dr;
-    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
-        release_on_exit{{&dx, &dt, &dl, &db, &dr}, m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    for (DevBuf* b : {&dt, &dl, &db, &dr}) if (int rc = b->ensure((size_t)R * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dt.p, target, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
-    launch_score_rows(dx.as<float>(), dt.as<int>(), R, 1, V, Vp, dl.as<float>(), db.as<int>(), dr.as<int>(), m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(logp, dl.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(best, db.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(rank, dr.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// Test support: score_alternatives_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out.
-extern "C" int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, float pad_value,
-                                            int32_t* alt_idx, float* alt_logp, float* entropy) {
-    if (!m || !logits || !alt_idx || !alt_logp) return fail(CASV_ERR_ARG, "null argument");
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    if (K < 1 || K > V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, V < 64 ? V : 64);
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DevBuf dx, di, dl, de;
-    struct Release { std::vector<DevBuf*> bufs; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); for (DevBuf* b : bufs) b->release(); } }
-        release_on_exit{{&dx, &di, &dl, &de}, m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    if (int rc = di.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = dl.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = de.ensure((size_t)R * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    launch_score_alternatives(dx.as<float>(), R, 1, V, Vp, K, di.as<int>(), dl.as<float>(), entropy ? de.as<float>() : nullptr, m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(alt_idx, di.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(alt_logp, dl.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
-    if (entropy) HIPCHK(hipMemcpyAsync(entropy, de.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// Keras-layout view of the master weights (which = 0), of the last gradients (which = 1) or of Adam's m (2) / v (3).
-static DevBuf& which_buf(TTensor& t, int which) { return which == 0 ? t.w : which == 1 ? t.g : which == 2 ? t.m : t.v; }
-static int keras_view(casv_model* m, int which, std::map<std::string, std::vector<float>>& out) {
-    TrainState* ts = m->train;
-    const int W = m->W, C = m->C, D = m->D;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    auto fetch = [&](int i, std::vector<float>& v) -> int {
-        v.resize(ts->tens[i].n);
-        HIPCHK(hipMemcpy(v.data(), which_buf(ts->tens[i], which).p, v.size() * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    if (int rc = fetch(ts->iE, out["E"])) return rc;
-    for (auto& l : ts->layers) {
-        std::vector<float> wx, wr, b;
-        if (int rc = fetch(l.iwx, wx)) return rc;
-        if (int rc = fetch(l.iwr, wr)) return rc;
-        if (int rc = fetch(l.ib, b)) return rc;
-        unpack_train_lstm(W, l.kx, l.kr - W, wx, wr, b, out[l.name + "_K"], out[l.name + "_R"], out[l.name + "_b"]);
-    }
-    std::vector<float> ut, wat;
-    if (int rc = fetch(ts->iUT, ut)) return rc;
-    if (int rc = fetch(ts->iWaT, wat)) return rc;
-    auto& Uk = out["att_U"]; auto& Wa = out["att_Wa"];
-    Uk.resize((size_t)C * W); Wa.resize((size_t)W * W);
-    for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) Uk[(size_t)c * W + j] = ut[(size_t)j * C + c];
-    for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) Wa[(size_t)k * W + j] = wat[(size_t)j * W + k];
-    if (int rc = fetch(ts->ibUW, out["att_bUW"])) return rc;
-    if (int rc = fetch(ts->iva, out["att_va"])) return rc;
-    if (int rc = fetch(ts->ibv, out["att_bv"])) return rc;
-    for (size_t i = 0; i < ts->bridge.size(); ++i) {
-        const std::string b = "bridge" + std::to_string(i / 2 + 1) + (i % 2 ? "_c" : "_h");
-        std::vector<float> kt;
-        if (int rc = fetch(ts->bridge[i].ikt, kt)) return rc;
-        auto& K = out[b + "_K"];
-        K.resize((size_t)W * W);
-        for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) K[(size_t)k * W + j] = kt[(size_t)j * W + k];
-        if (int rc = fetch(ts->bridge[i].ib, out[b + "_b"])) return rc;
-    }
-    (void)D;
-    return 0;
-}
-
-extern "C" int casv_train_get_gradient(casv_model* m, const char* name, float* out, int64_t capacity) {
-    if (!m || !name || !out) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    HIPCHK(hipSetDevice(m->device));
-    std::map<std::string, std::vector<float>> view;
-    if (int rc = keras_view(m, 1, view)) return rc;
-    auto it = view.find(name);
-    if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
-    if ((size_t)capacity < it->second.size()) return fail(CASV_ERR_ARG, "buffer too small");
-    memcpy(out, it->second.data(), it->second.size() * 4);
-    return CASV_OK;
-}
-
-// ---- optimizer state (resumable training) ----
-// The packed tensors (Wx / Wr / bias, transposed attention and bridge kernels) that hold a Keras tensor's values, or -1.
-static void keras_parts(TrainState* ts, const std::string& name, std::vector<int>& idx) {
-    idx.clear();
-    auto ends = [&](const std::string& suf) { return name.size() > suf.size() && name.compare(name.size() - suf.size(), suf.size(), suf) == 0; };
-    if (name == "E") { idx.push_back(ts->iE); return; }
-    if (name == "att_U") { idx.push_back(ts->iUT); return; }
-    if (name == "att_Wa") { idx.push_back(ts->iWaT); return; }
-    if (name == "att_bUW") { idx.push_back(ts->ibUW); return; }
-    if (name == "att_va") { idx.push_back(ts->iva); return; }
-    if (name == "att_bv") { idx.push_back(ts->ibv); return; }
-    for (auto& l : ts->layers)
-        if ((ends("_K") || ends("_R") || ends("_b")) && name.compare(0, name.size() - 2, l.name) == 0 && name.size() - 2 == l.name.size()) {
-            idx = {l.iwx, l.iwr, l.ib}; return;
-        }
-    for (size_t i = 0; i < ts->bridge.size(); ++i) {
-        const std::string b = "bridge" + std::to_string(i / 2 + 1) + (i % 2 ? "_c" : "_h");
-        if (name == b + "_K") { idx.push_back(ts->bridge[i].ikt); return; }
-        if (name == b + "_b") { idx.push_back(ts->bridge[i].ib); return; }
-    }
-}
-
-static int state_check(casv_model* m, const char* name, int which, std::vector<int>& parts) {
-    if (!m || !name) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    if (which != 0 && which != 1) return fail(CASV_ERR_ARG, "which must be 0 (Adam m) or 1 (Adam v)");
-    keras_parts(m->train, name, parts);
-    if (parts.empty()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
-    if (m->train->tens[parts[0]].frozen) return fail(CASV_ERR_STATE, "tensor '%s' is frozen: it has no optimizer state", name);
-    return 0;
-}
-
-// Keras-layout values of ONE tensor from buffer `which` (as keras_view) -- only the packed tensors that hold it are copied: an LSTM
-// tensor comes with its layer's other two (K / R / b pack into Wx, Wr and the bias together), everything else alone.
-static int keras_tensor(casv_model* m, int which, const std::string& n, const std::vector<int>& parts,
-                        std::map<std::string, std::vector<float>>& out) {
-    TrainState* ts = m->train;
-    const int W = m->W, C = m->C;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    auto fetch = [&](int i, std::vector<float>& v) -> int {
-        v.resize(ts->tens[i].n);
-        HIPCHK(hipMemcpy(v.data(), which_buf(ts->tens[i], which).p, v.size() * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    if (parts.size() == 3) {
-        const std::string pre = n.substr(0, n.size() - 2);
-        for (auto& l : ts->layers)
-            if (l.name == pre) {
-                std::vector<float> wx, wr, b;
-                if (int rc = fetch(l.iwx, wx)) return rc;
-                if (int rc = fetch(l.iwr, wr)) return rc;
-                if (int rc = fetch(l.ib, b)) return rc;
-                unpack_train_lstm(W, l.kx, l.kr - W, wx, wr, b, out[pre + "_K"], out[pre + "_R"], out[pre + "_b"]);
-                return 0;
-            }
-        return fail(CASV_ERR_ARG, "unknown tensor '%s'", n.c_str());
-    }
-    std::vector<float> v;
-    if (int rc = fetch(parts[0], v)) return rc;
-    std::vector<float>& o = out[n];
-    o = v;
-    if (n == "att_U") {
-        for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) o[(size_t)c * W + j] = v[(size_t)j * C + c];
-    } else if (n == "att_Wa" || (n.compare(0, 6, "bridge") == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_K") == 0)) {
-        for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) o[(size_t)k * W + j] = v[(size_t)j * W + k];
-    }
-    return 0;
-}
-
-extern "C" int casv_train_get_state(casv_model* m, const char* name, int32_t which, float* out, int64_t capacity) {
-    std::vector<int> parts;
-    if (int rc = state_check(m, name, which, parts)) return rc;
-    if (!out) return fail(CASV_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(m->device));
-    std::map<std::string, std::vector<float>> view;
-    if (int rc = keras_tensor(m, 2 + which, name, parts, view)) return rc;
-    auto it = view.find(name);
-    if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
-    if ((size_t)capacity < it->second.size()) return fail(CASV_ERR_ARG, "buffer too small");
-    memcpy(out, it->second.data(), it->second.size() * 4);
-    return CASV_OK;
-}
-
-extern "C" int casv_train_set_state(casv_model* m, const char* name, int32_t which, const float* data, int64_t count) {
-    std::vector<int> parts;
-    if (int rc = state_check(m, name, which, parts)) return rc;
-    if (!data) return fail(CASV_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(m->device));
-    TrainState* ts = m->train;
-    const int W = m->W, C = m->C;
-    std::map<std::string, std::vector<float>> view;
-    if (int rc = keras_tensor(m, 2 + which, name, parts, view)) return rc;
-    auto it = view.find(name);
-    if (it == view.end()) return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
-    if ((size_t)count != it->second.size()) return fail(CASV_ERR_ARG, "tensor '%s' has %zu values, got %lld", name, it->second.size(), (long long)count);
-    it->second.assign(data, data + count);
-    auto put = [&](int i, const std::vector<float>& v) -> int {
-        HIPCHK(hipMemcpy(which_buf(ts->tens[i], 2 + which).p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-        return 0;
-    };
-    const std::string n = name;
-    if (parts.size() == 3) {            // an LSTM layer: K / R / b pack into Wx, Wr and the bias together
-        const std::string pre = n.substr(0, n.size() - 2);
-        for (auto& l : ts->layers)
-            if (l.name == pre) {
-                std::vector<float> wx, wr, bias;
-                pack_train_lstm(W, l.kx, l.kr - W, view[pre + "_K"], view[pre + "_R"], view[pre + "_b"], wx, wr, bias);
-                if (int rc = put(l.iwx, wx)) return rc;
-                if (int rc = put(l.iwr, wr)) return rc;
-                return put(l.ib, bias);
-            }
-        return fail(CASV_ERR_ARG, "unknown tensor '%s'", name);
-    }
-    std::vector<float> v = it->second;
-    if (n == "att_U") {
-        for (int j = 0; j < W; ++j) for (int c = 0; c < C; ++c) v[(size_t)j * C + c] = it->second[(size_t)c * W + j];
-    } else if (n == "att_Wa" || (n.compare(0, 6, "bridge") == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_K") == 0)) {
-        for (int j = 0; j < W; ++j) for (int k = 0; k < W; ++k) v[(size_t)j * W + k] = it->second[(size_t)k * W + j];
-    }
-    return put(parts[0], v);
-}
-
-extern "C" int casv_train_get_step(casv_model* m, int64_t* step) {
-    if (!m || !step) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    *step = m->train->step;
-    return CASV_OK;
-}
-
-extern "C" int casv_train_set_step(casv_model* m, int64_t step) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    if (step < 0) return fail(CASV_ERR_ARG, "step must be >= 0");
-    m->train->step = (long)step;
-    return CASV_OK;
-}
-
-// Copy the current master weights into the handle's Keras-layout tensors without ending the session
-// (ModelCheckpoint / EarlyStopping(restore_best_weights), seq2seq.py:619-622).
-extern "C" int casv_train_sync_weights(casv_model* m) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    HIPCHK(hipSetDevice(m->device));
-    std::map<std::string, std::vector<float>> view;
-    if (int rc = keras_view(m, 0, view)) return rc;
-    for (auto& kv : view) m->host[kv.first] = kv.second;
-    return CASV_OK;
-}
-
-// Bring the trained weights back into the handle (Keras layout) and repack them for inference
-// (the reference's _resync_decoder after training, seq2seq.py:645).
-extern "C" int casv_train_end(casv_model* m) {
-    if (!m) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "no training session");
-    HIPCHK(hipSetDevice(m->device));
-    std::map<std::string, std::vector<float>> view;
-    if (int rc = keras_view(m, 0, view)) return rc;
-    for (auto& kv : view) m->host[kv.first] = kv.second;
-    casv_train_release(m);
-    return casv_commit_weights(m);
 }

@@ -1,4 +1,4 @@
-"""Cases and references of `score_alternatives` (csrc/train_kernels.hip: score_alternatives_kernel; csrc/train.hip:
+"""Cases and references of `score_alternatives` (csrc/train_kernels.hip: score_alternatives_kernel; csrc/score.hip:
 casv_score_get_alternatives) -- helpers, no test.  The head table, the model table, the oracles and the units are tests/score_cases.py's.
 
   alts64 / alts32      the definition restated row by row: indices from the float32 logits (exact), log-probabilities and entropy

@@ -1,4 +1,4 @@
-"""Cases and references of `score_candidates` (csrc/train.hip: casv_score_candidates -- N candidate targets per source on one
+"""Cases and references of `score_candidates` (csrc/score.hip: casv_score_candidates -- N candidate targets per source on one
 encoder pass) -- helpers, no test.  The head, the bounds and the oracles' recipe are tests/score_cases.py's.
 
   CASES         the case table (d, W, V, Be, N, L, flags, confusion-network input) and what each row reaches

@@ -1,4 +1,4 @@
-"""Cases and references of the scoring head and of `score_targets` (csrc/train_kernels.hip: score_rows_kernel; csrc/train.hip:
+"""Cases and references of the scoring head and of `score_targets` (csrc/train_kernels.hip: score_rows_kernel; csrc/score.hip:
 casv_score_targets) -- helpers, no test.
 
   head64 / head32      the head restated in float64 on float32 logits, and in float32 numpy with the same formula

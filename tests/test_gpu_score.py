@@ -1,4 +1,4 @@
-"""score_targets on the device (csrc/train.hip: casv_score_targets; csrc/train_kernels.hip: score_rows_kernel): the head alone against
+"""score_targets on the device (csrc/score.hip: casv_score_targets; csrc/train_kernels.hip: score_rows_kernel): the head alone against
 float64, the model against the oracle in every launch form, what the call leaves of the handle's state, the independence of a
 batch's rows, the give-up path and the facade's score_lines.  Cases, references and bounds: tests/score_cases.py, held on the CPU by
 tests/test_score_cases.py.  Runs with and without CASV_POISON=1 (fresh device buffers hold NaN / -1)."""

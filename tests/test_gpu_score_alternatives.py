@@ -1,4 +1,4 @@
-"""score_alternatives on the device (csrc/train_kernels.hip: score_alternatives_kernel; csrc/train.hip: casv_score_get_alternatives):
+"""score_alternatives on the device (csrc/train_kernels.hip: score_alternatives_kernel; csrc/score.hip: casv_score_get_alternatives):
 the kernel alone against float64 and against the scoring head's bits, the model against the fp64 oracle in every launch form, the
 retrieval behind score_candidates and inside a training session, its state and argument errors, and the facade.  Cases, references
 and bounds: tests/alternative_cases.py, held on the CPU by tests/test_alternative_cases.py.  Runs with and without CASV_POISON=1."""

@@ -1,4 +1,4 @@
-"""score_candidates on the device (csrc/train.hip: casv_score_candidates): N candidate targets per source on one encoder pass against
+"""score_candidates on the device (csrc/score.hip: casv_score_candidates): N candidate targets per source on one encoder pass against
 score_targets on the replicated pairs and against the oracle, in every launch form; the N = 1 call, the order of a source's
 candidates, the launch form of the mixed-row pair recurrence, the window form, what the call leaves of the handle's state, the
 refusals and the facade.  Cases and references: tests/candidate_cases.py, held on the CPU by tests/test_score_candidates_host.py;

@@ -184,7 +184,7 @@ def test_the_header_documents_the_entry_point_and_native_binds_it():
     restype, argtypes = nv.SIGNATURES['casv_score_candidates']
     assert len(argtypes) == 16 and argtypes[1:6] == [nv.c_int32] * 5 and argtypes[6:] == [nv.c_void_p] * 10
     assert len(argtypes) == len(nv.SIGNATURES['casv_score_targets'][1]) + 1
-    with open(os.path.join(ROOT, 'cor_asv_ann_amd', 'csrc', 'train.hip')) as f:
+    with open(os.path.join(ROOT, 'cor_asv_ann_amd', 'csrc', 'score.hip')) as f:
         train = f.read()
     assert 'extern "C" int casv_score_candidates(' in train
     # one path: both entry points are one call of the same function, casv_score_targets with N = 1
