@@ -90,7 +90,23 @@ __device__ __forceinline__ LstmCellOut lstm_cell(float zi, float zf, float zg, f
     r.h = r.o * fast_tanh(r.c);
     return r;
 }
-
+// The cell's pointwise backward (oracle/train.py lstm_backward) on what the forward pass kept: the gate activations, the cell
+// state c and the one before it.  dh = dL/dh of this step, all its addends summed by the caller; dc = dL/dc carried from the
+// step after.  -> the gate pre-activations' derivatives and dL/dc for the step before.  ONE definition, as for the forward cell:
+// the tests that hold the fused backward paths to the per-step ones rest on every kernel evaluating this expression.
+struct LstmCellBwdOut { float zi, zf, zg, zo, dc; };
+__device__ __forceinline__ LstmCellBwdOut lstm_cell_bwd(float dh, float ig, float fg, float gg, float og, float c, float cp, float dc) {
+    LstmCellBwdOut r;
+    const float tc = tanhf(c);
+    const float dov = dh * tc;
+    const float dct = dh * og * (1.0f - tc * tc) + dc;
+    r.zi = dct * gg * ig * (1.0f - ig);
+    r.zf = dct * cp * fg * (1.0f - fg);
+    r.zg = dct * ig * (1.0f - gg * gg);
+    r.zo = dov * og * (1.0f - og);
+    r.dc = dct * fg;
+    return r;
+}
 
 // ---- GEMM launchers: the decision is the plan (gemm_plan.h), these run it.  ctx: the handle's (casv_model::gemm) ----
 const GemmSwitches& gemm_switches();       // the process-wide switches (gemm.hip: read from the environment when the library is loaded)

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void lstm_bwd_gemm_kernel(const BwdStepBatc
         CASV_LD16(in.cell, xcell, 0); CASV_LD16(in.cp, xcp, 0); CASV_LD16(in.dc, xdc, 0);
     };
 #define CASV_IN_REGS(IN) "+v"(IN.a), "+v"(IN.mk), "+v"(IN.b), "+v"(IN.c), "+v"(IN.gi), "+v"(IN.gf), "+v"(IN.gg), "+v"(IN.go), "+v"(IN.cell), "+v"(IN.cp), "+v"(IN.dc)
-    // lstm_bwd_kernel's arithmetic (train_kernels.hip), four units at a time
+    // lstm_bwd_kernel's sum of dh (train_kernels.hip), four units at a time
     auto pointwise = [&](const PwIn& in, PwOut& o) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -89,17 +89,8 @@ __global__ __launch_bounds__(256, 2) void lstm_bwd_gemm_kernel(const BwdStepBatc
             if (a_on) dh += in.a[e] * (m_on ? in.mk[e] : 1.0f);
             if (b_on) dh += in.b[e];
             if (c_on) dh += in.c[e];
-            const float ig = in.gi[e], fg = in.gf[e], gg = in.gg[e], og = in.go[e];
-            const float cc = in.cell[e];
-            const float cp = cp_on ? in.cp[e] : 0.0f;
-            const float tc = tanhf(cc);
-            const float dov = dh * tc;
-            const float dct = dh * og * (1.0f - tc * tc) + in.dc[e];
-            o.zi[e] = dct * gg * ig * (1.0f - ig);
-            o.zf[e] = dct * cp * fg * (1.0f - fg);
-            o.zg[e] = dct * ig * (1.0f - gg * gg);
-            o.zo[e] = dov * og * (1.0f - og);
-            o.dc[e] = dct * fg;
+            const LstmCellBwdOut d = lstm_cell_bwd(dh, in.gi[e], in.gf[e], in.gg[e], in.go[e], in.cell[e], cp_on ? in.cp[e] : 0.0f, in.dc[e]);
+            o.zi[e] = d.zi; o.zf[e] = d.zf; o.zg[e] = d.zg; o.zo[e] = d.zo; o.dc[e] = d.dc;
         }
     };
     auto store_group = [&](const PwOut& o, int g) {   // A image of unit group g: [row][gate * 32 + unit]

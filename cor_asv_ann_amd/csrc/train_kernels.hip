@@ -491,14 +491,12 @@ __global__ void lstm_bwd_kernel(const LstmBwdBatch batch) {
         const float ig = p.gates[gi], fg = p.gates[gi + 32], gg = p.gates[gi + 64], og = p.gates[gi + 96];
         const float cc = p.cell[r * W + u];
         const float cp = p.c_prev ? p.c_prev[r * p.ld_cprev + u] : 0.0f;
-        const float tc = tanhf(cc);
-        const float dov = dh * tc;
-        const float dct = dh * og * (1.0f - tc * tc) + p.dc[r * W + u];
-        p.dz[gi] = dct * gg * ig * (1.0f - ig);
-        p.dz[gi + 32] = dct * cp * fg * (1.0f - fg);
-        p.dz[gi + 64] = dct * ig * (1.0f - gg * gg);
-        p.dz[gi + 96] = dov * og * (1.0f - og);
-        p.dc[r * W + u] = dct * fg;
+        const LstmCellBwdOut d = lstm_cell_bwd(dh, ig, fg, gg, og, cc, cp, p.dc[r * W + u]);
+        p.dz[gi] = d.zi;
+        p.dz[gi + 32] = d.zf;
+        p.dz[gi + 64] = d.zg;
+        p.dz[gi + 96] = d.zo;
+        p.dc[r * W + u] = d.dc;
     }
 }
 void launch_lstm_bwd_batch(const LstmBwdBatch& b, hipStream_t st) {

@@ -9,11 +9,10 @@
 // per row block; sc1 loads behind the poll).  The weights of a unit group (128 rows of Wr) are read by 2 x 16 workgroups; the
 // mapping puts a unit group's workgroups on ONE XCD, whose L2 then holds 2 groups x 2 layers x 256 KB.
 //
-// What a workgroup does per step, in the order that hides the most: the first three weight stages and the step's x.Wx + b
-// values are requested BEFORE it polls (they do not depend on h); behind the poll all W/32 stages of its 32 rows of h(t-1)
-// leave at once (16 B per thread and stage: one memory round trip per step, not one per stage -- these lines were written by
-// other XCDs a moment ago and miss every cache); then gemm_skinny.hip's K loop, stage by stage through the same LDS image with
-// the same MFMA sequence, and its cell epilogue.  Results are therefore those of the per-step launches bit for bit (tested).
+// What a workgroup does per step: the staged tile of train_tile.h (the pipeline is described there), plain variant, once -- the
+// first three weight stages and the step's x.Wx + b values requested BEFORE it polls (they do not depend on h), all W/32 stages of
+// its 32 rows of h(t-1) behind the poll -- then gemm_skinny.hip's cell epilogue.  The tile walks the stages through the LDS image
+// and the MFMA sequence of gemm_skinny.hip's K loop: results are those of the per-step launches bit for bit (tested).
 //
 // The two jobs of a launch may differ in rows (casv_score_candidates: encoder layer n on the Be sources beside decoder layer n - 1
 // on Be * N candidates).  The grid, the (layer, row block, unit group) mapping and the counters are those of RecArgs.B, the larger
@@ -23,33 +22,27 @@
 #include "handoff.h"
 #include "persist_host.h"
 #include "train_kernels.h"
+#include "train_tile.h"
 
 namespace casv {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-namespace {
-constexpr int RBM = 32, RBN = 128;
-constexpr int RK2 = 32, RLD = RK2 + 4;
-constexpr int RSTAGE = (RBM + RBN) * RLD;
-}
+using namespace tile;
 
 template <int NT>        // W / 32: K stages per step
 __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs ra) {
-    __shared__ __attribute__((aligned(16))) float s_stage[2 * RSTAGE];
+    __shared__ __attribute__((aligned(16))) float s_stage[2 * Tile<>::STAGE];
     __shared__ int s_ok;
-    float (*s_gate)[16][64] = reinterpret_cast<float (*)[16][64]>(s_stage);
+    Tile<> tl(s_stage);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     constexpr int W = NT * 32;
     const int B = ra.B;
-    const int nrb = (B + RBM - 1) / RBM;
+    const int nrb = (B + BM - 1) / BM;
     // consecutive workgroups go to consecutive XCDs: unit group fastest, so that XCD x sees unit groups x, x + 8, ...
     const int ug = blockIdx.x % NT, rest = blockIdx.x / NT;
     const int rb = rest % nrb, jb = rest / nrb;
     const RecJob& job = ra.job[jb];
-    const int m0 = rb * RBM, n0 = ug * RBN;
+    const int m0 = rb * BM, n0 = ug * BN;
     unsigned* const counter = ra.counters + (long long)(jb * nrb + rb) * 32;
     unsigned* const abort_w = ra.counters + (long long)2 * nrb * 32;
     const int len = job.len;
@@ -62,41 +55,7 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
     const float* bp[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) bp[i] = job.Wr + (long long)(n0 + srow + 32 * i) * W + sk;
-
-    struct BStage { f32x4 b[4]; };
-    // stage KT of the weights / of the rows of h: the stage's offset rides in the instruction (no address registers per stage)
-#define CASV_LOAD_B(G, KT)                                                                                              \
-    {                                                                                                                   \
-        asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(G.b[0]) : "v"(bp[0]), "n"((KT) * RK2 * 4));      \
-        asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(G.b[1]) : "v"(bp[1]), "n"((KT) * RK2 * 4));      \
-        asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(G.b[2]) : "v"(bp[2]), "n"((KT) * RK2 * 4));      \
-        asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(G.b[3]) : "v"(bp[3]), "n"((KT) * RK2 * 4));      \
-    }
-#define CASV_LOAD_A(J)                                                                                                  \
-    if constexpr ((J) < NT) asm volatile("global_load_dwordx4 %0, %1, off offset:%2 sc1" : "=v"(areg[(J) < NT ? (J) : 0]) : "v"(arow), "n"((J) * RK2 * 4));
-    auto store_b = [&](const BStage& gs, int buf) {
-        float* sb = s_stage + buf * RSTAGE + (RBM + srow) * RLD + sk;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(sb + 32 * i * RLD) = gs.b[i];
-    };
-    auto store_a = [&](const f32x4& a, int buf) {
-        *reinterpret_cast<f32x4*>(s_stage + buf * RSTAGE + srow * RLD + sk) = a;
-    };
-    const int a_off = l31 * RLD + 4 * lh, b_off = (RBM + wave * 32 + l31) * RLD + 4 * lh;
-    f32x16 acc;
-    auto compute = [&](int buf) {
-        const float* base = s_stage + buf * RSTAGE;
-        f32x4 fa[4], fb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            fa[q] = *reinterpret_cast<const f32x4*>(base + a_off + 8 * q);
-            fb[q] = *reinterpret_cast<const f32x4*>(base + b_off + 8 * q);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][i], fb[q][i], acc, 0, 0, 0);
-    };
+    f32x16& acc = tl.acc;
 
     // cell state of this lane's four (row, unit) elements: rows m0 + q + 8 wave + 4 lh, unit ug * 32 + l31
     const int u = ug * 32 + l31;
@@ -115,71 +74,27 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
                                    : job.hs + ((long long)tp * R + mrow) * job.hs_ld + sk;
         // x.Wx + b of this step's elements
         float zpre[4][4];
-        {
-            const float* zin0 = job.Z + (long long)t * R * (4 * W);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + q + 8 * wave + 4 * lh;
-                const float* zr = zin0 + (long long)(m < R ? m : R - 1) * (4 * W) + n0 + l31;
-                zpre[q][0] = zr[0]; zpre[q][1] = zr[32]; zpre[q][2] = zr[64]; zpre[q][3] = zr[96];
-            }
-        }
+        tl.load_zpre(zpre, job.Z + (long long)t * R * (4 * W), 4 * W, m0, R, n0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         if (arow) {         // (uniform: a zero initial state contributes nothing -- the per-step path skips the segment too)
             BStage g0, g1;
-            CASV_LOAD_B(g0, 0)
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(g0.b[0]), "+v"(g0.b[1]), "+v"(g0.b[2]), "+v"(g0.b[3]));
-            store_b(g0, 0);
-            if constexpr (NT > 1) CASV_LOAD_B(g1, 1)
-            if constexpr (NT > 2) CASV_LOAD_B(g0, 2)
+            tl.request<NT, PLAIN>(g0, g1, bp);
             if (k > 0) {
                 if (!wait_deps(Dep{counter, (unsigned)(k * NT)}, Dep{nullptr, 0}, Dep{nullptr, 0}, abort_w, &s_ok)) return;
             }
             f32x4 areg[NT];
-            CASV_LOAD_A(0) CASV_LOAD_A(1) CASV_LOAD_A(2) CASV_LOAD_A(3) CASV_LOAD_A(4) CASV_LOAD_A(5) CASV_LOAD_A(6) CASV_LOAD_A(7)
-            CASV_LOAD_A(8) CASV_LOAD_A(9) CASV_LOAD_A(10) CASV_LOAD_A(11) CASV_LOAD_A(12) CASV_LOAD_A(13) CASV_LOAD_A(14) CASV_LOAD_A(15)
-            // everything requested so far has arrived
-#pragma unroll
-            for (int j = 0; j < NT; ++j) asm volatile("s_waitcnt vmcnt(0)" : "+v"(areg[j]));
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(g0.b[0]), "+v"(g0.b[1]), "+v"(g0.b[2]), "+v"(g0.b[3]),
-                                                "+v"(g1.b[0]), "+v"(g1.b[1]), "+v"(g1.b[2]), "+v"(g1.b[3]));
-            store_a(areg[0], 0);
-            __syncthreads();
-            // stage J + 1 goes from registers into the LDS buffer whose readers passed the last barrier, stage J + 3 leaves for the
-            // same register set, stage J is contracted; the wait in front of the store is counted (stage J + 2 stays in flight)
-#define CASV_REC_STAGE(G, J)                                                                                            \
-            if constexpr ((J) < NT) {                                                                                   \
-                if constexpr ((J) + 1 < NT) {                                                                           \
-                    if constexpr ((J) >= 2 && (J) + 2 < NT)                                                             \
-                        asm volatile("s_waitcnt vmcnt(4)" : "+v"(G.b[0]), "+v"(G.b[1]), "+v"(G.b[2]), "+v"(G.b[3]));    \
-                    else if constexpr ((J) >= 2)                                                                        \
-                        asm volatile("s_waitcnt vmcnt(0)" : "+v"(G.b[0]), "+v"(G.b[1]), "+v"(G.b[2]), "+v"(G.b[3]));    \
-                    store_a(areg[(J) + 1 < NT ? (J) + 1 : 0], ((J) + 1) & 1);                                           \
-                    store_b(G, ((J) + 1) & 1);                                                                          \
-                }                                                                                                       \
-                if constexpr ((J) + 3 < NT) CASV_LOAD_B(G, (J) + 3)                                                     \
-                compute((J) & 1);                                                                                       \
-                __syncthreads();                                                                                        \
-            }
-            CASV_REC_STAGE(g1, 0) CASV_REC_STAGE(g0, 1) CASV_REC_STAGE(g1, 2) CASV_REC_STAGE(g0, 3)
-            CASV_REC_STAGE(g1, 4) CASV_REC_STAGE(g0, 5) CASV_REC_STAGE(g1, 6) CASV_REC_STAGE(g0, 7)
-            CASV_REC_STAGE(g1, 8) CASV_REC_STAGE(g0, 9) CASV_REC_STAGE(g1, 10) CASV_REC_STAGE(g0, 11)
-            CASV_REC_STAGE(g1, 12) CASV_REC_STAGE(g0, 13) CASV_REC_STAGE(g1, 14) CASV_REC_STAGE(g0, 15)
-#undef CASV_REC_STAGE
+            load_a(areg, arow);
+            wait_a(areg);
+            tl.start<PLAIN>(g0, g1, areg[0]);
+            tl.chain<NT, PLAIN>(g1, g0, areg, bp);
         } else if (k > 0) {
             return;          // (never: only the first step can lack its input)
         }
 
         // ---- cell epilogue (gemm_skinny.hip) ----
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_gate[wave][r][lane] = acc[r];
-        __syncthreads();
         float z[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) z[q][c] = s_gate[c][4 * wave + q][lane];
+        tl.exchange_gates(z);
 #pragma unroll
         for (int q = 0; q < 4; ++q) { z[q][0] += zpre[q][0]; z[q][1] += zpre[q][1]; z[q][2] += zpre[q][2]; z[q][3] += zpre[q][3]; }
         float* cout = job.Cs + (long long)t * R * W;
@@ -206,8 +121,6 @@ __global__ __launch_bounds__(256, 2) void train_recurrence_kernel(const RecArgs 
         publish(counter);        // drain + barrier (also: the gate exchange is read before the next step's stage lands on it)
     }
 }
-
-static_assert(RBM == TRAIN_ROW_BLOCK, "train_plan.h plans for this row block");
 
 // The instantiation of a width, from train_plan.h's list (nullptr: the width has none, and no plan)
 typedef void (*RecKernel)(const RecArgs);

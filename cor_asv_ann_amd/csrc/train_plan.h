@@ -13,7 +13,7 @@ namespace casv {
 
 enum TrainKind { TRAIN_REC = 0, TRAIN_REC_BWD, TRAIN_CELL, TRAIN_CELL_BWD, TRAIN_KINDS };
 
-constexpr int TRAIN_ROW_BLOCK = 32;                 // rows of a row block: RBM, QBM, TBM, VBM of the four kernel files
+constexpr int TRAIN_ROW_BLOCK = 32;                 // rows of a row block: BM of train_tile.h, the four kernel files' tile
 constexpr int TRAIN_LAUNCH_CAP = 16;                // persistent launches of one step: the slots of rec_cnt, the words of rec_abort
 constexpr int TRAIN_MIN_CUS = 64;                   // below: no persistent launch of the train step
 // per kind: the workgroups per CU the form plans for (the kernels' launch bounds; the cell kinds one: the idle waves of a part

@@ -274,12 +274,16 @@ def test_the_plan_is_pure_and_the_sources_only_run_it():
     assert not re.search(r'\bhip|getenv', _code(plan), re.I)
     assert re.findall(r'#include [<"]([^>"]+)[>"]', plan) == ['algorithm', 'cstddef']
     assert re.findall(r'#include [<"]([^>"]+)[>"]', open(DRIVER).read())[0] == '../cor_asv_ann_amd/csrc/train_plan.h'
-    files = {'train_persist.hip': ('RBM', 'REC', [tf.KERNEL['rec']]), 'train_persist_bwd.hip': ('QBM', 'REC_BWD', [tf.KERNEL['rec_bwd']]),
-             'train_persist_top.hip': ('TBM', 'CELL', [tf.KERNEL['cell']]), 'train_persist_topb.hip': ('VBM', 'CELL_BWD', [tf.KERNEL['cell_bwd'], tf.SPLIT_KERNEL])}
+    files = {'train_persist.hip': ('REC', [tf.KERNEL['rec']]), 'train_persist_bwd.hip': ('REC_BWD', [tf.KERNEL['rec_bwd']]),
+             'train_persist_top.hip': ('CELL', [tf.KERNEL['cell']]), 'train_persist_topb.hip': ('CELL_BWD', [tf.KERNEL['cell_bwd'], tf.SPLIT_KERNEL])}
     csrc = {n: _code(_src(n)) for n in os.listdir(CSRC) if n.endswith(('.hip', '.h'))}
-    for name, (bm, widths, kernels) in files.items():
+    # the row block and the stage are train_tile.h's alone: one static_assert there, and the four files define no such constant
+    assert csrc['train_tile.h'].count('static_assert(BM == TRAIN_ROW_BLOCK') == 1
+    assert sum(code.count('== TRAIN_ROW_BLOCK') for code in csrc.values()) == 1
+    for name, (widths, kernels) in files.items():
         code = csrc[name]
-        assert 'static_assert(%s == TRAIN_ROW_BLOCK' % bm in code, name
+        assert '#include "train_tile.h"' in code, name
+        assert not re.search(r'constexpr int \w*(BM|BN|K2|LD|STAGE)\b', code), name
         assert 'switch (train_width_nt(' in code and not re.search(r'case \d+:', code), name           # (no hand-written width switch)
         for kernel in kernels:
             # a width's instantiation is named in ONE place, a case generated from the kind's list; elsewhere only as a template of NT

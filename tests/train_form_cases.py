@@ -16,7 +16,7 @@ from tests import grad_noise_cases as gn
 # ------------------------------------------------------------------------------------------------------------------ the form
 # csrc/train_plan.h restated: the C++ is held to this file by tests/test_train_form_cases.py through tests/train_plan_driver.cpp
 KINDS = ('rec', 'rec_bwd', 'cell', 'cell_bwd')
-ROW_BLOCK = 32                      # rows of a row block: TRAIN_ROW_BLOCK = RBM, QBM, TBM, VBM
+ROW_BLOCK = 32                      # rows of a row block: TRAIN_ROW_BLOCK = train_tile.h's BM
 CAP = 16                            # persistent launches of one step: TRAIN_LAUNCH_CAP (the gate, rec_abort[], rec_cnt's slots)
 MIN_CUS = 64                        # TRAIN_MIN_CUS
 # the widths NT = W / 32 with an instantiation (CASV_TRAIN_*_WIDTHS), the workgroups per CU a form plans for, the hand-off counters
