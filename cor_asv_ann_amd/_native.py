@@ -4,7 +4,7 @@ There is no fallback: if the shared library is missing or a call fails, this rai
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p)
 
 import numpy as np
 
@@ -35,6 +35,10 @@ class BeamParams(Structure):
     _fields_ = [('batch_size', c_int32), ('beam_width_in', c_int32), ('beam_width_out', c_int32),
                 ('max_results', c_int32), ('beam_threshold_in', c_double), ('rejection_threshold', c_double),
                 ('cost0', c_double)]
+
+
+class SampleParams(Structure):
+    _fields_ = [('seed', c_uint64), ('temperature', c_float), ('top_k', c_int32), ('samples', c_int32)]
 
 
 class DebugRows(Structure):
@@ -80,6 +84,9 @@ SIGNATURES = {
     'casv_decoder_step_lm': (c_int, [c_void_p, c_int32] + [c_void_p] * 8),
     'casv_decode_greedy': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'casv_decode_beam': (c_int, [c_void_p, POINTER(BeamParams), c_int32] + [c_void_p] * 8),
+    'casv_decode_sample': (c_int, [c_void_p, POINTER(SampleParams), c_int32] + [c_void_p] * 6),
+    'casv_debug_sample_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SampleParams), c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_float] + [c_void_p] * 4),
     'casv_train_begin': (c_int, [c_void_p, POINTER(AdamParams), c_char_p]),
     'casv_train_step': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8 + [POINTER(c_double), POINTER(c_double)]),
     'casv_train_get_gradient': (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),

@@ -212,6 +212,30 @@ struct LmSoftmaxArgs {
     int R, V, W;
 };
 void launch_lm_softmax(const LmSoftmaxArgs& a, hipStream_t stream);
+// The sampling pick of a step (sample_kernels.hip): in place of the softmax and the greedy pick, a draw
+// from every row's logits and the one-hot row of what was drawn as the next step's input.
+struct SampleArgs {
+    const float* logits;    // [R][Vp]
+    float* feedback;        // row r of the output slot: feedback + (step + 1) * fb_slot + r * Vp (the score store: fb_slot = R * Vp)
+    long long fb_slot;
+    int R, V;
+    int step_imm; const int* step_ptr;      // the step: counter word of the draw, output slot and column
+    int rows_per_line;      // row r draws sample r % rows_per_line of line r / rows_per_line ...
+    const long long* stream;    // ... whose stream id is stream[line], or (nullptr) the line's number
+    const int* sample;      // optional [R]: the sample number of every row instead
+    const float* u;         // optional [R]: the uniform of every row instead of the generator's (test support)
+    unsigned long long seed;
+    float temperature; int top_k;
+    int* out_idx;           // [R][S], column step * out_col
+    float* out_logp;        // log-probability of the draw under the model (all V entries, temperature 1)
+    float* out_logq;        // ... under the proposal (the candidates at this temperature)
+    int S, out_col;
+    int* nan_flag;          // set when a row is invalid
+};
+void launch_sample(const SampleArgs& a, hipStream_t stream);
+// dst row line * rows_per_line + n (n < rows_per_line) = src row line, `width` floats each, rows packed: the encoder's final
+// states under every sample row of a line
+void launch_spread_rows(const float* src, float* dst, int lines, int rows_per_line, int width, hipStream_t stream);
 
 void launch_embed_sparse(const float* E, const int* idx, const float* val, float* x0,
                          int rows, int A, int V, int W, hipStream_t stream);

@@ -1,6 +1,6 @@
 // Host side of the decode entry points (include/cor_asv_ann_hip.h): the decoder step (seq2seq.py:416-480) as a list of launches
-// built from one view (DecodeStep), the greedy and beam decode loops (seq2seq.py:1215-1544) as sequences of phases, and the sparse
-// alignments of what they left on the device.  No kernel lives here: decode_kernels.hip, beam_kernels.hip, persist.hip, gemm*.hip.
+// built from one view (DecodeStep), the greedy and beam decode loops (seq2seq.py:1215-1544) as sequences of phases, the sampling
+// decode, and the sparse alignments of what they left on the device.  No kernel lives here: decode_kernels.hip, beam_kernels.hip, persist.hip, gemm*.hip.
 #include "engine.h"
 
 // ---- decode session ----
@@ -63,12 +63,16 @@ static int init_root(casv_model* m, int rows_per_line, SmallOps ops = SmallOps{}
 // ---- one decoder step ----
 // The view of one decoder_model step on the session's R rows (seq2seq.py:416-480): every launch of the step builds its arguments
 // from (m, step) alone.
+// What a sampling step draws by (casv_decode_sample)
+struct SampleDraw { unsigned long long seed; float temperature; int top_k; const long long* stream; float* logp; float* logq; };
+
 struct DecodeStep {
-    bool beam = false;              // input rows from `pin` and parents through `prev` (the search), otherwise row r continues row r
+    bool beam = false;             // input rows from `pin` and parents through `prev` (the search), otherwise row r continues row r
                                     // of the previous slot of the stores (the fed-back softmax, seq2seq.py:1252)
     bool lm = false;                // lm_predict (seq2seq.py:464-470): also the LM output, see launch_step
     bool softmax = true;            // (the beam step kernel computes the rows it reads itself)
     int mode = -1;                  // greedy pick rule of the softmax launch; -1: probabilities only
+    const SampleDraw* draw = nullptr;   // the pick is a draw and the fed-back row its one-hot row (step_sample), in place of the softmax launch
     const int* line = nullptr;      // line of every row, or (nullptr) row / rows_per_line
     int rows_per_line = 1;
     int* o_idx = nullptr; float* o_prob = nullptr;          // greedy results [R][S]
@@ -218,6 +222,20 @@ static void step_softmax(casv_model* m, const DecodeStep& st) {
     launch_softmax(a, m->stream);
     m->prof_end(PC_SOFTMAX, ev);
 }
+static void step_sample(casv_model* m, const DecodeStep& st) {
+    const int R = m->R, V = m->V, Vp = m->Vp;
+    const SampleDraw& d = *st.draw;
+    SampleArgs a{};
+    a.logits = m->logits.as<float>(); a.feedback = m->st_p.as<float>(); a.fb_slot = (long long)R * Vp; a.R = R; a.V = V;
+    a.step_ptr = st.step_ptr; a.step_imm = st.step_imm; a.rows_per_line = st.rows_per_line; a.stream = d.stream;
+    a.seed = d.seed; a.temperature = d.temperature; a.top_k = d.top_k;
+    a.out_idx = st.o_idx; a.out_logp = d.logp; a.out_logq = d.logq; a.S = m->S; a.out_col = 1;
+    a.nan_flag = m->d_nan.as<int>();
+    hipEvent_t ev{};
+    m->prof_begin(PC_SAMPLE, 4.0 * R * V, 4.0 * R * (V + Vp), ev);
+    launch_sample(a, m->stream);
+    m->prof_end(PC_SAMPLE, ev);
+}
 
 // One decoder_model step on R rows (seq2seq.py:416-480), as its launches in order.
 // st.lm also computes the LM output: the top cell once more on the decoder's own top-layer input and states with a zero context -- a
@@ -257,8 +275,9 @@ static void launch_step(casv_model* m, const DecodeStep& st) {
         if (st.lm) b.g[b.count++] = lm_projection_of(m, proj);
         run_gemm_batch(m, EPI_PLAIN, b);
     } else run_gemm(m, EPI_PLAIN, proj);
-    // 6. softmax and pick
-    if (st.softmax) step_softmax(m, st);
+    // 6. softmax and pick, or the draw
+    if (st.draw) step_sample(m, st);
+    else if (st.softmax) step_softmax(m, st);
 }
 
 // casv_decoder_step and (lm_probs != nullptr) casv_decoder_step_lm
@@ -497,8 +516,9 @@ struct GreedyCall {
 };
 
 // results and flags come back through a pinned staging buffer: three queued copies, ONE wait for the device
-static int greedy_staging(casv_model* m, GreedyCall& c) {
-    const size_t need = 2 * c.nres + 64;
+// (`arrays` result arrays of nres bytes each: casv_decode_sample brings back three)
+static int greedy_staging(casv_model* m, GreedyCall& c, int arrays = 2) {
+    const size_t need = arrays * c.nres + 64;
     c.staged = need <= m->pin_limit;
     const size_t want = c.staged ? need : 64;
     if (m->pin_out_cap < want) {
@@ -506,7 +526,7 @@ static int greedy_staging(casv_model* m, GreedyCall& c) {
         HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->pin_out), want, hipHostMallocDefault));
         m->pin_out_cap = want;
     }
-    c.pin_flags = reinterpret_cast<unsigned*>(c.staged ? m->pin_out + 2 * c.nres : m->pin_out);
+    c.pin_flags = reinterpret_cast<unsigned*>(c.staged ? m->pin_out + arrays * c.nres : m->pin_out);
     return 0;
 }
 
@@ -617,6 +637,115 @@ extern "C" int casv_decode_greedy(casv_model* m, int32_t mode, int32_t S, int32_
     if (m->prof.on) m->prof.collect();
     m->last_decode = 1; m->last_S = S; m->last_rows = B; m->last_mode = mode; m->last_signature = decode_buffers_signature(m);
     if (nan_before_end && mode == 1) return fail(CASV_ERR_NAN, "All-NaN slice encountered");
+    return CASV_OK;
+}
+
+// ---- casv_decode_sample ----
+// N rows per line step in lockstep from the line's root; every step ends with a draw in place of the softmax (step_sample).  Session
+// buffers, result staging and the encoder's give-up handling are the greedy decode's; always the per-step form, launched eagerly
+// whatever the "graph" option says (a captured graph would replay another call's seed, temperature and top_k).
+
+static int sample_arguments(const casv_model* m, const casv_sample_params* p, int S, const void* out_idx, const void* out_logp,
+                            const void* out_logq, const void* out_len) {
+    if (!m || !p) return fail(CASV_ERR_ARG, "null argument");
+    if (S < 1 || S > 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "S=%d out of range 1..%d", S, 2 * CASV_MAX_T);
+    if (p->samples < 1) return fail(CASV_ERR_ARG, "samples=%d must be positive", p->samples);
+    if (!(p->temperature > 0.f) || !(p->temperature < INFINITY)) return fail(CASV_ERR_ARG, "temperature=%g must be finite and positive", (double)p->temperature);
+    if (p->top_k < 0 || p->top_k > 64) return fail(CASV_ERR_ARG, "top_k=%d out of range 0..64", p->top_k);
+    if (!out_idx || !out_logp || !out_logq || !out_len) return fail(CASV_ERR_ARG, "null argument");
+    return 0;
+}
+
+// the root of every row: zero input, the line's final encoder states and initial alignment under each of its N rows; cleared results
+static int sample_root(casv_model* m, const GreedyCall& c, int N) {
+    const int W = m->W, Vp = m->Vp, T = m->T, D = m->D, R = m->R, B = m->B;
+    SmallOps ops{};
+    ops.fill(m->o_idx.p, c.nres); ops.fill(m->o_prob.p, c.nres); ops.fill(m->s_logq.p, c.nres);
+    ops.fill(m->d_flags.as<unsigned>() + 1, 4);
+    ops.fill(m->st_p.p, (size_t)R * Vp * 4); ops.fill(m->logits.p, (size_t)R * Vp * 4);
+    if (!m->has_a0) ops.fill(m->st_a.p, (size_t)R * T * 4);
+    ops.fill(m->d_step.p, 16); ops.fill(m->d_nan.p, 16);
+    if (!launch_small_ops(ops, m->stream)) return too_many_ops();
+    for (int n = 1; n <= D; ++n) {
+        launch_spread_rows(m->hfin.as<float>() + (size_t)(n - 1) * B * W, m->st_h[n].as<float>(), B, N, W, m->stream);
+        launch_spread_rows(m->cfin.as<float>() + (size_t)(n - 1) * B * W, m->st_c[n].as<float>(), B, N, W, m->stream);
+    }
+    if (m->has_a0) launch_spread_rows(m->a0.as<float>(), m->st_a.as<float>(), B, N, T, m->stream);
+    return 0;
+}
+
+// One attempt: root, S steps, fetch, settle.  `again`: the persistent encoder pass behind it had given up and has been redone per step.
+static int sample_attempt(casv_model* m, const GreedyCall& c, const SampleDraw& draw, int N, float* out_logq, bool& again) {
+    if (int rc = sample_root(m, c, N)) return rc;
+    DecodeStep st;
+    st.rows_per_line = N; st.draw = &draw; st.o_idx = m->o_idx.as<int>();
+    for (int s = 0; s < c.S; ++s) { st.step_imm = s; launch_step(m, st); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c.staged ? (void*)m->pin_out : (void*)c.out_idx, m->o_idx.p, c.nres, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(c.staged ? (void*)(m->pin_out + c.nres) : (void*)c.out_prob, m->o_prob.p, c.nres, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(c.staged ? (void*)(m->pin_out + 2 * c.nres) : (void*)out_logq, m->s_logq.p, c.nres, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(c.pin_flags, m->d_flags.p, 8, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    const bool enc_was_persistent = m->enc_check_pending;
+    const int redone = settle_encoder(m, &c.pin_flags[0]);
+    if (redone < 0) return redone;
+    if (!redone && enc_was_persistent) m->persist_backoff.penalty = 0;
+    again = redone > 0;
+    return 0;
+}
+
+// a row's line ends with its first end-of-line index, or at an invalid row's step (NaN logp) -> whether there was such a step
+static bool sample_lengths(const casv_model* m, const GreedyCall& c, int R, int32_t* out_len) {
+    bool nan_before_end = false;
+    for (int r = 0; r < R; ++r) {
+        int len = c.S;
+        for (int s = 0; s < c.S; ++s) {
+            const float lp = c.out_prob[(size_t)r * c.S + s];
+            if (lp != lp) { nan_before_end = true; len = s + 1; break; }
+            if (c.out_idx[(size_t)r * c.S + s] == m->eos) { len = s + 1; break; }
+        }
+        out_len[r] = len;
+    }
+    return nan_before_end;
+}
+
+extern "C" int casv_decode_sample(casv_model* m, const casv_sample_params* p, int32_t S, const int64_t* stream, int32_t* out_idx,
+                                  float* out_logp, float* out_logq, int32_t* out_len, float* out_align) {
+    if (int rc = sample_arguments(m, p, S, out_idx, out_logp, out_logq, out_len)) return rc;
+    if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
+    const int B = m->B, T = m->T, N = p->samples;
+    if ((long long)(S + 1) * B * N >= (1LL << 31)) return fail(CASV_ERR_ARG, "samples=%d: (S + 1) * lines * samples rows overflow int32 (sample fewer lines or steps per call)", N);
+    const int R = B * N;
+    HIPCHK(hipSetDevice(m->device));
+    if (int rc = ensure_encoded(m, arithmetic_of(m, ENTRY_SEARCH))) return rc;
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_SEARCH));
+    m->last_decode = 0;         // until this call has succeeded there is nothing to take alignments from
+    GreedyCall c{};
+    c.S = S; c.out_idx = out_idx; c.out_prob = out_logp; c.nres = (size_t)R * S * 4;
+    if (int rc = ensure_session(m, R, S)) return rc;
+    const BufPlan plan[] = {{&m->o_idx, c.nres}, {&m->o_prob, c.nres}, {&m->s_logq, c.nres}, {&m->d_flags, 64}, {&m->s_stream, stream ? (size_t)B * 8 : 0}};
+    if (int rc = ensure_all(plan)) return rc;
+    if (int rc = greedy_staging(m, c, 3)) return rc;
+    if (stream) HIPCHK(hipMemcpyAsync(m->s_stream.p, stream, (size_t)B * 8, hipMemcpyHostToDevice, m->stream));
+    const SampleDraw draw{p->seed, p->temperature, p->top_k, stream ? m->s_stream.as<long long>() : nullptr, m->o_prob.as<float>(), m->s_logq.as<float>()};
+    for (int attempt = 0; ; ++attempt) {        // (the second follows an encoder pass that gave up: there is no third, see casv_decode_beam)
+        bool again = false;
+        if (int rc = sample_attempt(m, c, draw, N, out_logq, again)) return rc;
+        if (!again) break;
+        if (attempt >= 1) return fail(CASV_ERR_STATE, "the encoder pass gave up again after it was redone per step");
+    }
+    if (c.staged) { memcpy(out_idx, m->pin_out, c.nres); memcpy(out_logp, m->pin_out + c.nres, c.nres); memcpy(out_logq, m->pin_out + 2 * c.nres, c.nres); }
+    const bool nan_before_end = sample_lengths(m, c, R, out_len);
+    if (out_align) {   // store_a slot s+1 row r -> (r, s, :)
+        for (int s = 0; s < S; ++s)
+            HIPCHK(hipMemcpy2DAsync(out_align + (size_t)s * T, (size_t)S * T * 4, m->st_a.as<float>() + (size_t)(s + 1) * R * T,
+                                    (size_t)T * 4, (size_t)T * 4, R, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    if (m->prof.on) m->prof.collect();
+    // (last_mode 2: the rows are samples, not lines -- casv_records_append refuses them)
+    m->last_decode = 1; m->last_S = S; m->last_rows = R; m->last_mode = 2; m->last_signature = decode_buffers_signature(m);
+    if (nan_before_end) return fail(CASV_ERR_NAN, "a sampled row's logits were NaN or without a finite candidate");
     return CASV_OK;
 }
 

@@ -232,3 +232,46 @@ extern "C" int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V,
     HIPCHK(hipStreamSynchronize(m->stream));
     return CASV_OK;
 }
+
+// Test support: sample_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out.
+extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step, const int64_t* stream,
+                                      const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
+                                      float* out_logp, float* out_logq, float* out_feedback) {
+    if (!logits || !out_feedback) return fail(CASV_ERR_ARG, "null argument");
+    if (!m || !p || !out_idx || !out_logp || !out_logq) return fail(CASV_ERR_ARG, "null argument");
+    if (!(p->temperature > 0.f) || !(p->temperature < INFINITY)) return fail(CASV_ERR_ARG, "temperature=%g must be finite and positive", (double)p->temperature);
+    if (p->top_k < 0 || p->top_k > 64) return fail(CASV_ERR_ARG, "top_k=%d out of range 0..64", p->top_k);
+    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
+    if (step < 0 || step >= 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "step=%d out of range 0..%d", step, 2 * CASV_MAX_T - 1);
+    HIPCHK(hipSetDevice(m->device));
+    const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
+    std::vector<float> x((size_t)R * Vp, pad_value);
+    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
+    DebugBuffers bufs{m->stream};
+    int rc = 0;
+    SampleArgs a{};
+    a.logits = static_cast<const float*>(bufs.put(x.data(), x.size(), rc)); if (rc) return rc;
+    // (the output slot is step + 1 of a store whose slots all lie on the one (R,Vp) buffer)
+    a.feedback = static_cast<float*>(bufs.put(nullptr, (size_t)R * Vp, rc)); if (rc) return rc;
+    a.fb_slot = 0; a.R = R; a.V = V; a.step_imm = step; a.rows_per_line = 1;
+    if (stream) { a.stream = static_cast<const long long*>(bufs.put(stream, (size_t)R * 2, rc)); if (rc) return rc; }
+    if (sample) { a.sample = static_cast<const int*>(bufs.put(sample, (size_t)R, rc)); if (rc) return rc; }
+    if (u) { a.u = static_cast<const float*>(bufs.put(u, (size_t)R, rc)); if (rc) return rc; }
+    a.seed = p->seed; a.temperature = p->temperature; a.top_k = p->top_k;
+    a.out_idx = static_cast<int*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
+    a.out_logp = static_cast<float*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
+    a.out_logq = static_cast<float*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
+    a.S = 1; a.out_col = 0;
+    hipEvent_t ev{};
+    m->prof_begin(PC_SAMPLE, 4.0 * R * V, 4.0 * R * (V + Vp), ev);
+    launch_sample(a, m->stream);
+    m->prof_end(PC_SAMPLE, ev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_idx, a.out_idx, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(out_logp, a.out_logp, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(out_logq, a.out_logq, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(out_feedback, a.feedback, (size_t)R * Vp * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->prof.on) m->prof.collect();
+    return CASV_OK;
+}

@@ -4,6 +4,7 @@
 // sequence is a [T*B][F] matrix (operand of the batched weight-gradient GEMMs).
 #include "train_kernels.h"
 #include "attn_bwd.h"
+#include "alt_order.h"
 #include <math.h>
 
 namespace casv {
@@ -355,20 +356,7 @@ void launch_score_rows(const float* logits, const int* target, int B, int U, int
 }
 
 // ---- the K likeliest entries and the entropy of every row (casv_score_get_alternatives) ----
-// The order is total: x descending as floats (the two zeros equal), the lower index first among equals.  One 64-bit key holds it:
-// the float's bits made monotone (sign bit set for the positives, all bits flipped for the negatives; -0.0 taken as +0.0) above
-// ~index, so a larger key is an earlier place.  No key of a valid row is 0 or all ones (those are NaN bit patterns).
-__device__ __forceinline__ unsigned long long alt_key(float x, int v) {
-    unsigned b = __float_as_uint(x);
-    if (b == 0x80000000u) b = 0u;
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((unsigned long long)b << 32) | (0xffffffffu - (unsigned)v);
-}
-template <int MASK> __device__ __forceinline__ unsigned long long max_across(unsigned long long v) {
-    const unsigned lo = (unsigned)lane_xor<MASK>((int)(unsigned)v), hi = (unsigned)lane_xor<MASK>((int)(unsigned)(v >> 32));
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    return o > v ? o : v;
-}
+// The order (alt_key) and the wave-wide maximum of its keys: alt_order.h, shared with the sampling pick (sample_kernels.hip).
 // One wave per row, as score_rows_kernel, and its m, sum and validity formed by the same two loops (lane-strided, then the wave
 // butterfly): logp has the bits of the head's logp for that index as target.  The row is read from memory once, into the wave's
 // own Vp floats of LDS (no other wave touches them: no barrier); every later pass reads the entries the lane itself wrote.
@@ -409,8 +397,7 @@ __global__ __launch_bounds__(256) void score_alternatives_kernel(const float* __
                     const unsigned long long key = alt_key(s[v], v);
                     if (key < prev && key > top) top = key;
                 }
-                top = max_across<32>(top); top = max_across<16>(top); top = max_across<8>(top);
-                top = max_across<4>(top); top = max_across<2>(top); top = max_across<1>(top);
+                top = wave_max_key(top);
                 const int idx = (int)(0xffffffffu - (unsigned)top);      // (K <= V: every round finds one)
                 const int own = (idx & ~63) | lane;                      // the winner's pass: its lane reads it, the wave gets it
                 const float xw = __shfl(own < V ? s[own] : 0.f, idx & 63, 64);

@@ -319,6 +319,61 @@ class HipEngine(object):
             out['align_sparse'] = self.alignments_sparse(n, S)
         return out
 
+    def decode_sample(self, samples, temperature=1.0, top_k=0, seed=0, streams=None, steps=None, want_align=False):
+        """casv_decode_sample: `samples` lines drawn from the decoder for every encoded line.  Returns
+        (idx, logp, logq (B, samples, S), length (B, samples), align): the drawn indices, their log-probabilities under the model and
+        under the proposal, the steps up to and including the first end-of-line, and (B, samples, S, T) alignment rows, their
+        (lo, w) windows with want_align='sparse', or None.  streams (B) int64: the lines' stream ids (default: their numbers).
+        An invalid row raises NativeError (CASV_ERR_NAN) whose `outputs` holds the same tuple, filled."""
+        S = int(steps or 2 * self.T)
+        N = int(samples)
+        rows = self.B * max(N, 0)
+        p = nv.SampleParams(int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), int(top_k), N)
+        if streams is not None:
+            streams = nv.carray(streams, np.int64)
+            assert streams.shape == (self.B,)
+        idx = np.empty((rows, S), np.int32)
+        logp = np.empty((rows, S), np.float32)
+        logq = np.empty((rows, S), np.float32)
+        length = np.empty((rows,), np.int32)
+        sparse = want_align == 'sparse'
+        align = np.empty((rows, S, self.T), np.float32) if want_align and not sparse else None
+        rc = self.lib.casv_decode_sample(self.handle, byref(p), S, nv.ptr(streams), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq),
+                                         nv.ptr(length), nv.ptr(align))
+        if rc not in (0, nv.CASV_ERR_NAN):
+            nv.check(rc)
+        if sparse:
+            lo, w = self.alignments_sparse(rows, S)
+            align = (lo.reshape(self.B, N, S), w.reshape(self.B, N, S, -1))
+        elif align is not None:
+            align = align.reshape(self.B, N, S, self.T)
+        out = (idx.reshape(self.B, N, S), logp.reshape(self.B, N, S), logq.reshape(self.B, N, S), length.reshape(self.B, N), align)
+        if rc:
+            err = nv.NativeError(rc, self.lib.casv_last_error().decode('utf-8', 'replace'))
+            err.outputs = out
+            raise err
+        return out
+
+    def debug_sample_rows(self, logits, temperature=1.0, top_k=0, seed=0, step=0, streams=None, samples=None, u=None, pad_value=0.0):
+        """Test support (casv_debug_sample_rows): the sampling kernel alone on logits (R,V) as step `step` of rows with stream ids
+        streams (R; default: the row's number) and sample numbers samples (R; default 0); u (R): these uniforms instead of the
+        generator's; the padding columns of the device rows hold pad_value.  Returns (idx, logp, logq (R), feedback (R,Vp))."""
+        logits = nv.carray(logits, np.float32)
+        R, V = logits.shape
+        p = nv.SampleParams(int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), int(top_k), 1)
+        streams = None if streams is None else nv.carray(streams, np.int64)
+        samples = None if samples is None else nv.carray(samples, np.int32)
+        u = None if u is None else nv.carray(u, np.float32)
+        for a in (streams, samples, u):
+            assert a is None or a.shape == (R,)
+        idx = np.empty((R,), np.int32)
+        logp = np.empty((R,), np.float32)
+        logq = np.empty((R,), np.float32)
+        feedback = np.empty((R, (V + 31) & ~31), np.float32)
+        nv.check(self.lib.casv_debug_sample_rows(self.handle, R, V, byref(p), int(step), nv.ptr(streams), nv.ptr(samples), nv.ptr(logits),
+                                                 nv.ptr(u), float(pad_value), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq), nv.ptr(feedback)))
+        return idx, logp, logq, feedback
+
     # -- training ------------------------------------------------------------------------------
     def train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-7, clipnorm=5.0, frozen=()):
         p = nv.AdamParams(lr, beta1, beta2, epsilon, clipnorm)

@@ -825,6 +825,55 @@ class Sequence2Sequence(object):
                     aligns[j][k] = self._alignment_rows(align, b * N + n, c, idx.shape[1])
         return logprobs, scores, predictions, ranks, aligns
 
+    def sample_lines(self, lines, conf=None, n=1, temperature=1.0, top_k=0, seed=None, streams=None, alignments=False):
+        """`n` lines DRAWN from the model for each source line, on one encoder pass per source (`HipEngine.decode_sample`; DESIGN.md
+        section 4.8) -- where `correct_lines` gives the most probable line and the beam its near-duplicates.  Every character is drawn
+        from the decoder's distribution over the vocabulary without index 0, sharpened or flattened by `temperature` and, with
+        `top_k` > 0 (at most 64), cut to its `top_k` most probable characters; the decoder is then fed the character that was
+        drawn.  Each source line must end in a newline.  Returns (candidates, logprobs, scores, logqs, aligns), each a list per
+        source of `n` entries, in `score_candidates`' nesting (`candidates` can be passed straight back to it):
+        candidates -- the sampled lines; each ends in a newline unless it was cut at twice the padded source length;
+        logprobs -- per character, log p under the model itself (temperature 1, whole vocabulary), as `score_lines` gives it;
+        scores -- mean -log p over the line, the convention of `correct_lines`' scores;
+        logqs -- per character, log q under the distribution it was drawn from (for importance weights: log p - log q);
+        aligns -- [] (`alignments=False`), a `SparseAlignment` (True) or the list of T-wide rows ('dense'), as `correct_lines`.
+        An empty source gives empty lists.  `seed` (an int below 2^64) and a line's stream id and sample number fix what is drawn,
+        whatever the batch: `seed=None` draws a seed from the generator that `self.seed` seeds; `streams` (ints below 2^63, one per
+        line) default to the line's index in the call.  The sources are taken in order into chunks that grow while sources x `n`
+        stays within max(`batch_size`, `n`) decoder rows; as in `score_candidates` a result depends on its chunk's padded length."""
+        assert self.status == 2
+        assert conf is None or len(conf) == len(lines)
+        assert streams is None or len(streams) == len(lines)
+        eng = self._require_engine()
+        n = int(n)
+        if n < 1:
+            raise ValueError('n=%d samples per line: need at least one' % n)
+        if seed is None:
+            seed = int(self._rng.integers(0, 2 ** 63))
+        candidates, logprobs = [[] for _ in lines], [[] for _ in lines]
+        scores, logqs, aligns = [[] for _ in lines], [[] for _ in lines], [[] for _ in lines]
+        want_align = False if not alignments else (True if alignments == 'dense' else 'sparse')
+        live = [j for j in range(len(lines)) if lines[j]]
+        per_chunk = max(max(self.batch_size, n) // n, 1)
+        for start in range(0, len(live), per_chunk):
+            chunk = live[start:start + per_chunk]
+            idx, val, _ = self._sparse_lines([lines[j] for j in chunk], None if conf is None else [conf[j] for j in chunk])
+            eng.encode(idx, val)
+            ids = np.array([j if streams is None else int(streams[j]) for j in chunk], np.int64)
+            gi, lp, lq, length, align = eng.decode_sample(n, temperature=temperature, top_k=top_k, seed=seed, streams=ids,
+                                                          want_align=want_align)
+            if align is not None:           # (rows b * n + k, as _alignment_rows indexes them)
+                align = tuple(a.reshape((-1,) + a.shape[2:]) for a in align) if isinstance(align, tuple) else align.reshape((-1,) + align.shape[2:])
+            for b, j in enumerate(chunk):
+                for k in range(n):
+                    c = int(length[b, k])
+                    candidates[j].append(self._chars(gi[b, k, :c]))
+                    logprobs[j].append(lp[b, k, :c].tolist())
+                    scores[j].append(float(-np.sum(lp[b, k, :c], dtype=np.float64)) / max(c, 1))
+                    logqs[j].append(lq[b, k, :c].tolist())
+                    aligns[j].append(self._alignment_rows(align, b * n + k, c, idx.shape[1]))
+        return candidates, logprobs, scores, logqs, aligns
+
     def correct_batches(self, batches, fast=True, greedy=True, alignments=True, after_decode=None):
         """`correct_lines` over a stream of batches -- an iterable of `lines` or of `(lines, conf)` -- as a three-stage pipeline:
         a worker thread turns the next batch into index arrays, a second one drives the device (its C-ABI calls release the GIL),

@@ -153,6 +153,40 @@ int casv_decode_beam(casv_model* m, const casv_beam_params* p, int32_t S,
                      int32_t* out_idx, float* out_prob, int32_t* out_len, double* out_score,
                      int32_t* out_rej, float* out_align, int32_t* n_found, int32_t* n_steps);
 
+/* Sampling: `samples` lines DRAWN from the decoder for every encoded line, on one encoder pass.
+ * Row r = b * samples + n steps in lockstep with all others for S steps; at step s it draws index v from the candidates 1 .. V-1
+ * (index 0 is never drawn, seq2seq.py:1250; top_k > 0: the first min(top_k, V-1) of them in the order of casv_score_get_alternatives)
+ * with weights expf((x_v - m_C) / temperature) -- x the row's logits, m_C the candidates' maximum -- by inverting the float64
+ * prefix sums in ascending index order at u * Z, u = (o >> 8) * 2^-24 with o the first word of Philox4x32-10 on the counter
+ * (stream[b] low word, stream[b] high word, n, s) under the key (seed low, seed high); stream NULL: stream[b] = b.  The next step's
+ * decoder input is the one-hot row of v (seq2seq.py:1251), not the softmax (seq2seq.py:1252).
+ * out_idx (B*samples, S) the indices; out_logp the model's log-probability of v over all V at temperature 1, in the form of
+ * casv_score_targets; out_logq the proposal's, (x_v - m_C) / temperature - log Z; out_len (B*samples) = steps up to and including
+ * the first end-of-line index (S if there is none; what a row produces after it is unspecified); out_align (B*samples, S, T) or
+ * NULL.  A row's results are a function of (weights, line, seed, stream, n, temperature, top_k) only, whatever B, samples, the row's
+ * place and the launch shape.  A row whose logits hold a NaN or whose candidates' maximum is not finite reports index 1 with NaN
+ * logp / logq, feeds back an all-zero row and ends there; the call fills every output and returns CASV_ERR_NAN (the other rows
+ * are untouched), like mode 1 of casv_decode_greedy.  Arithmetic: the search's (casv_decode_beam), the "arithmetic" option
+ * overrides.  Always per step; with the "graph" option the steps are still launched eagerly.  Refused with CASV_ERR_ARG before
+ * anything is enqueued: NULL outputs (out_align excepted), S outside 1 .. 2 * 4096, samples < 1, a temperature that is not
+ * finite or <= 0, top_k outside 0 .. 64.  casv_get_alignments_sparse afterwards serves the call's B*samples rows.  Kernel class of
+ * casv_profile_read: "sample". */
+typedef struct {
+    uint64_t seed;
+    float temperature;
+    int32_t top_k;
+    int32_t samples;
+} casv_sample_params;
+int casv_decode_sample(casv_model* m, const casv_sample_params* p, int32_t S, const int64_t* stream,
+                       int32_t* out_idx, float* out_logp, float* out_logq, int32_t* out_len, float* out_align);
+/* Test support: the sampling kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out (pad_value
+ * fills the padding columns), as step `step` of rows with stream ids stream (R; NULL: the row's number) and sample numbers sample
+ * (R; NULL: 0).  u (R) non-NULL: these uniforms in place of the generator's.  out_idx / out_logp / out_logq (R); out_feedback
+ * (R, Vp), Vp = V rounded up to a multiple of 32: the row the next step would read.  p->samples is ignored. */
+int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step,
+                           const int64_t* stream, const int32_t* sample, const float* logits, const float* u,
+                           float pad_value, int32_t* out_idx, float* out_logp, float* out_logq, float* out_feedback);
+
 /* The soft alignments of the LAST casv_decode_greedy / casv_decode_beam call in window form, for the post-decode
  * re-alignment of wrapper/transcode.py:126,279-349 (which skips entries <= 1/V anyway, transcode.py:316): the attention
  * of attention.py:553-571 is zero outside a window of <= 2*window_width+1 positions, so step s of result row n is
