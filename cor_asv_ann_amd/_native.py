@@ -41,6 +41,11 @@ class SampleParams(Structure):
     _fields_ = [('seed', c_uint64), ('temperature', c_float), ('top_k', c_int32), ('samples', c_int32)]
 
 
+class SchedParams(Structure):
+    _fields_ = [('seed', c_uint64), ('step_id', c_uint64), ('ratio', c_float), ('temperature', c_float), ('pick', c_int32),
+                ('passes', c_int32)]
+
+
 class DebugRows(Structure):
     """casv_debug_rows: an input of casv_debug_gemm_jobs whose rows move with the step (K segment, cell state, zinit)"""
     _fields_ = [('pool', c_void_p), ('rows', c_void_p), ('first', c_void_p), ('slots', c_int32), ('pool_rows', c_int32),
@@ -103,6 +108,9 @@ SIGNATURES = {
     'casv_score_release': (c_int, [c_void_p]),
     'casv_train_step_soft': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32]
                              + [c_void_p] * 6 + [POINTER(c_double), POINTER(c_double)]),
+    'casv_train_step_sampled': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
+                                + [POINTER(SchedParams), c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_debug_sched_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SchedParams)] + [c_void_p] * 4 + [c_float, c_void_p]),
     'casv_debug_soft_ce_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                         c_int32, POINTER(c_double), c_void_p, c_int32]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

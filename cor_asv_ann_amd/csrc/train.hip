@@ -22,6 +22,8 @@
 // train_plan.h decides and counts the persistent launches of a step; persist_launch is the one place that asks it and launches.
 // casv_train_step_soft is the same step on soft targets: K (index, mass) slots per position (Step::K / soft_idx / soft_q) staged in
 // place of the target indices in phase 2, the soft head's launcher in phase 5; every other phase does not know the difference.
+// casv_train_step_sampled (train_sched.hip) is the same step with scheduled sampling: sched_passes between phases 4 and 5 (Step::sched),
+// which leaves the last pass's tape where phase 4 leaves the teacher-forced one; every later phase does not know the difference.
 // The state the step works on is train_state.h / train_state.hip; Step and the phases a scoring call shares are declared in train_step.h.
 #include "train_step.h"
 
@@ -394,6 +396,7 @@ int plan_buffers(Step& s) {
     }
     if (s.bridged) { ENS(ts->hbr, (size_t)D * Be * W * 4) ENS(ts->cbr, (size_t)D * Be * W * 4) ENS(ts->brtmp, (size_t)Be * W * 4) }
     if (s.K > 0) { ENS(ts->d_sidx, UB * s.K * 4) ENS(ts->d_sq, UB * s.K * 4) }
+    if (s.sched) { ENS(ts->d_gold, UB * 4) ENS(ts->d_mix, (size_t)s.sched->passes * UB * 4) }
     if (s.N > 1) { ENS(ts->h0rep, (size_t)D * B * W * 4) ENS(ts->c0rep, (size_t)D * B * W * 4) }
     if (s.residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
     for (int n = 1; n <= D; ++n) ENS(ts->O[n], TB * ((n == 1 || deep) ? 2 * W : W) * 4)
@@ -412,7 +415,7 @@ int plan_buffers(Step& s) {
 }
 
 // per-character segments of an index array [B][L][A_], positions in (t, b, k) order within a character (counting sort on the host)
-static void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::vector<int>& off, std::vector<int>& pos) {
+void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::vector<int>& off, std::vector<int>& pos) {
     off.assign(V + 2, 0);
     for (long long q = 0; q < (long long)B * L * A_; ++q) if (idx[q] >= 0 && idx[q] < V) ++off[idx[q] + 2];
     for (int v = 0; v < V; ++v) off[v + 2] += off[v + 1];
@@ -435,6 +438,7 @@ int stage_inputs(Step& s) {
     HIPCHK(hipMemcpyAsync(ts->e_idx.p, s.enc_idx, TB * A * 4, hipMemcpyHostToDevice, st));
     if (s.enc_val) HIPCHK(hipMemcpyAsync(ts->e_val.p, s.enc_val, TB * A * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_in.p, s.dec_in, UB * 4, hipMemcpyHostToDevice, st));
+    if (s.sched) HIPCHK(hipMemcpyAsync(ts->d_gold.p, s.dec_in, UB * 4, hipMemcpyHostToDevice, st));
     if (s.K > 0) {
         HIPCHK(hipMemcpyAsync(ts->d_sidx.p, s.soft_idx, UB * s.K * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ts->d_sq.p, s.soft_q, UB * s.K * 4, hipMemcpyHostToDevice, st));
@@ -491,6 +495,22 @@ static void repeat_states(Step& s, int n) {
     launch_repeat_rows((s.bridged ? ts->cbr.as<float>() : s.cfin) + src, ts->c0rep.as<float>() + dst, s.Be, s.N, s.W, s.st);
 }
 
+// Decoder layer k (1 .. D-1, below the cell) alone in its launch, on the input sequence y [U*B][W]: its outputs, cell states and gates,
+// and the cell's / the next layer's input DO[k] -- the outputs (residual_connections, k >= 2: plus y) times the next dropout mask.
+int decoder_layer_alone(Step& s, int k, const float* y) {
+    casv_model* m = s.m; TrainState* ts = s.ts;
+    const int W = s.W;
+    TLayer& ld = s.dec_layer(k);
+    layer_input_gemm(m, ld, y, W);
+    const bool res = s.residual && k >= 2;
+    bool masked = false;
+    const LayerFwd f[1] = {{&ld, s.dec_h0(k), s.dec_c0(k), res ? nullptr : ts->DO[k].as<float>(), W, s.mdec_n(k)}};
+    if (int rc = layers_forward(m, f, 1, &masked)) return rc;
+    if (res) launch_add_mul_mask(ld.hs, W, y, W, s.mdec_n(k), ts->DO[k].as<float>(), W, s.UB, W, s.st);
+    else if (!masked) launch_mul_mask(ld.hs, W, s.mdec_n(k), ts->DO[k].as<float>(), W, s.UB, W, s.st);
+    return 0;
+}
+
 // Phase 3 leaves every encoder layer's and every decoder layer's below the cell outputs, cell states and gates, the masked outputs
 // O[n] / DO[n], the final states (and the bridged ones), the cell's input sequence s.y, the attended sequence s.enc_out and its
 // projection u.
@@ -523,12 +543,11 @@ int forward_layers(Step& s) {
     // deep_bidirectional_encoder (seq2seq.py:246-281): every encoder layer n >= 2 is a BiLSTM on the cross sum of the (dropped-out) layer
     // below; its two directions are the pair of a launch, the decoder layer n - 1 walks alone
     for (int n = 2; n <= D && deep; ++n) {
-        TLayer& lf = s.enc_dir(n, 0); TLayer& lb = s.enc_dir(n, 1); TLayer& ld = s.dec_layer(n - 1);
+        TLayer& lf = s.enc_dir(n, 0); TLayer& lb = s.enc_dir(n, 1);
         launch_cross_sum(ts->O[n - 1].as<float>(), ts->XD[n].as<float>(), TB * 2 * W, st);
         layer_input_gemm(m, lf, ts->XD[n].as<float>(), 2 * W);
         layer_input_gemm(m, lb, ts->XD[n].as<float>(), 2 * W);
-        layer_input_gemm(m, ld, y, W);
-        bool maskede = false, maskedd = false;
+        bool maskede = false;
         {
             const LayerFwd f[2] = {{&lf, nullptr, nullptr, ts->O[n].as<float>(), 2 * W, s.menc_n(n)},
                                    {&lb, nullptr, nullptr, ts->O[n].as<float>() + W, 2 * W, s.menc_n(n) ? s.menc_n(n) + W : nullptr}};
@@ -539,13 +558,7 @@ int forward_layers(Step& s) {
         bridge_forward(s, n);
         repeat_states(s, n);
         if (!maskede) launch_mul_mask(lf.hs, 2 * W, s.menc_n(n), ts->O[n].as<float>(), 2 * W, TB, 2 * W, st);
-        const bool res_n = residual && n >= 3;
-        {
-            const LayerFwd f[1] = {{&ld, s.dec_h0(n - 1), s.dec_c0(n - 1), res_n ? nullptr : ts->DO[n - 1].as<float>(), W, s.mdec_n(n - 1)}};
-            if (int rc = layers_forward(m, f, 1, &maskedd)) return rc;
-        }
-        if (res_n) launch_add_mul_mask(ld.hs, W, y, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
-        else if (!maskedd) launch_mul_mask(ld.hs, W, s.mdec_n(n - 1), ts->DO[n - 1].as<float>(), W, UB, W, st);
+        if (int rc = decoder_layer_alone(s, n - 1, y)) return rc;
         y = ts->DO[n - 1].as<float>();
     }
     for (int n = 2; n <= D && !deep; ++n) {
@@ -988,7 +1001,7 @@ static int update(Step& s, double* loss_out, double* norm_out) {
 
 // One attempt at the step, the phases in order.  *redo: a persistent recurrence gave up -- nothing has been updated, the back-off is
 // set (recurrences_gave_up) and the caller starts over.
-static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
+int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
     casv_model* m = s.m; TrainState* ts = s.ts;
     ts->B = s.B; ts->Be = s.Be; ts->N = s.N; ts->T = s.T; ts->U = s.U; ts->A = s.A;
     ts->score_B = 0;                       // (a scoring call's attention rows are overwritten)
@@ -997,6 +1010,7 @@ static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo)
     if (int rc = stage_inputs(s)) return rc;
     if (int rc = forward_layers(s)) return rc;
     if (int rc = forward_cell(s)) return rc;
+    if (int rc = s.sched ? sched_passes(s) : 0) return rc;          // (casv_train_step_sampled: train_sched.hip)
     if (int rc = loss_head(s)) return rc;
     if (int rc = recurrences_gave_up(m, *redo)) return rc;
     if (*redo) return CASV_OK;
@@ -1020,6 +1034,23 @@ static int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo)
     m->stat_train_launches = ts->plan.launches;      // (statistic "train_persistent_launches"; a step redone per step ends here with 0)
     return CASV_OK;
 }
+
+// The view of a step on hard or soft targets (dec_out or the slots are the caller's to add): what the caller passed, the model's
+// shapes, the step's flags.
+Step step_view(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A, const int32_t* enc_idx, const float* enc_val,
+               const int32_t* dec_in, const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell) {
+    Step s{};
+    s.m = m; s.ts = m->train; s.st = m->stream;
+    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
+    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.weights = weights;
+    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
+    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
+    s.TB = (long long)T * B; s.UB = (long long)U * B;
+    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
+    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
+    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
+    return s;
+}
 }  // namespace casv
 
 extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
@@ -1033,16 +1064,8 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
     OrderedScope ordered(m, m->deterministic);
-    Step s{};
-    s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
-    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = weights;
-    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
-    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * B; s.UB = (long long)U * B;
-    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
-    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
-    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
+    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
+    s.dec_out = dec_out;
     // A persistent recurrence that gave up sets the back-off, so the second attempt takes per-step launches only and cannot give up.
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool redo = false;
@@ -1081,17 +1104,8 @@ extern "C" int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int3
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
     OrderedScope ordered(m, m->deterministic);
-    Step s{};
-    s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
-    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = nullptr; s.weights = weights;
+    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
     s.K = K; s.soft_idx = soft_idx; s.soft_q = soft_q;
-    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
-    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * B; s.UB = (long long)U * B;
-    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
-    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
-    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool redo = false;
         if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;

@@ -26,6 +26,17 @@ void launch_mul_rowmask(const float* in, long long ld_in, const float* mask, lon
 // parts (ordered form, "deterministic" train step): [min(ceil(B*U/4), 2048)] doubles of workspace, or nullptr
 void launch_softmax_ce(float* logits, const int* target, const float* weight, int B, int U, int V, int Vp, float inv_count,
                        double* loss, int want_grad, hipStream_t st, double* parts = nullptr);
+// Scheduled sampling's mix of one pass (sched_kernels.hip; casv_train_step_sampled in include/cor_asv_ann_hip.h has the definition):
+// one wave per position q < R.  Step form (row_b == nullptr): q = b * U + u over the step's B * U positions, the logits row of
+// u >= 1 is (u - 1) * B + b of the step's [U*B][Vp] buffer; gold / out / d_in [B][U].  Rows form: position (row_b[q], row_u[q]),
+// logits row q; gold / out [R], d_in nullptr.  out and d_in (where given) both receive the mix; columns [V, Vp) are never read.
+struct SchedMixArgs {
+    const float* logits; const int* gold; int* d_in; int* out;
+    const int* row_b; const int* row_u;
+    long long R; int B, U, V, Vp;
+    unsigned long long seed, step_id; float ratio, temperature; int pick;
+};
+void launch_sched_mix(const SchedMixArgs& a, hipStream_t stream);
 // The same head on soft targets (casv_train_step_soft): soft_idx / soft_q [B][U][K], 1 <= K <= 64, slot k of a position = (index,
 // mass), index -1 = empty; per row loss += w * inv_count * sum_k q_k * -log(clip(p[i_k])), dlogit[v] = (p_v * S - q_k ok_k of the
 // slot with i_k == v) * w * inv_count with ok_k = 1e-7 < p[i_k] < 1 - 1e-7 and S = sum_k q_k ok_k.  The indices of a position are

@@ -49,6 +49,8 @@ struct TrainState {
     int B = 0, T = 0, U = 0, A = 0;        // B: the step's batch = the decoder's rows
     int Be = 0, N = 1;                     // the encoder's lines and the decoder rows per line, Be * N == B (N > 1: casv_score_candidates only)
     DevBuf e_idx, e_val, d_in, d_out, d_w, m_enc, m_dec, m_cell;
+    DevBuf d_gold, d_mix;                  // casv_train_step_sampled: the gold decoder input [B][U] (d_in holds the mix), every pass's mix [passes][B][U]
+    std::vector<int32_t> h_mix;            // ... and ("deterministic") the last mix on the host, for the decoder's character segments
     DevBuf d_sidx, d_sq;                   // casv_train_step_soft: the soft targets' slots [B][U][K] (index, mass) in place of d_out
     DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
     std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])

@@ -14,6 +14,7 @@ struct Step {
     const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
     const float* mask_enc; const float* mask_dec; const float* mask_cell;
     int K; const int32_t* soft_idx; const float* soft_q;      // casv_train_step_soft: K > 0, (B,U,K) slots in place of dec_out (nullptr)
+    const casv_sched_params* sched; int32_t* mix_out;         // casv_train_step_sampled with ratio > 0: the passes' parameters, (passes,B,U) out
     int W, V, Vp, C, D;
     long long TB, UB;
     // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent
@@ -51,6 +52,15 @@ int stage_inputs(Step& s);          // 2: batch, masks, segments on the device; 
 int forward_layers(Step& s);        // 3: encoder stack beside the decoder layers below the cell; final states, bridges, u
 int forward_cell(Step& s);          // 4: the attention cell
 int projection(Step& s);            // the tied output projection: s.proj_in, the logits [U*B][Vp]
+int decoder_layer_alone(Step& s, int k, const float* y);      // decoder layer k < D alone in its launch on the input sequence y: DO[k]
+int sched_passes(Step& s);          // between 4 and 5, casv_train_step_sampled only (train_sched.hip): the passes of scheduled sampling
+// per-character segments of an index array [B][L][A_] for the ordered embedding gradient ("deterministic")
+void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::vector<int>& off, std::vector<int>& pos);
+// One attempt at the step, the phases in order; *redo: a persistent recurrence gave up, the caller starts over.  step_view: the view
+// an entry hands it (the targets are the entry's to add).
+int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo);
+Step step_view(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A, const int32_t* enc_idx, const float* enc_val,
+               const int32_t* dec_in, const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell);
 int recurrences_gave_up(casv_model* m, bool& any);      // did a persistent recurrence so far give up?  (then nothing has been updated)
 
 }  // namespace casv

@@ -438,6 +438,50 @@ class HipEngine(object):
                                                nv.ptr(m_cell), byref(loss), byref(norm)))
         return loss.value, norm.value
 
+    @staticmethod
+    def _sched_params(seed, step_id, ratio, pick, passes, temperature):
+        picks = {'greedy': 0, 'sample': 1}
+        return nv.SchedParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step_id) & 0xFFFFFFFFFFFFFFFF, float(ratio), float(temperature),
+                              picks.get(pick, pick), int(passes))
+
+    def train_step_sampled(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1, ratio=0.0, seed=0, step_id=0,
+                           pick='greedy', passes=1, temperature=1.0):
+        """train_step with scheduled sampling in its parallel form (casv_train_step_sampled): after the teacher-forced forward
+        pass, `passes` times a pick ('greedy' or 'sample' at `temperature`) at every decoder position from the logits of the
+        position before it, mixed into the decoder input where the position's coin -- a function of (seed, step_id, b, u) -- falls
+        below `ratio`, and the decoder again; loss, backward pass and update on the last pass.  Modes 1 and 2 only.  Returns
+        (loss, grad_norm, mixes) with mixes int32 (passes,B,U): slice p - 1 is the decoder input after pass p."""
+        enc_idx = nv.carray(enc_idx, np.int32)
+        if enc_idx.ndim == 2:
+            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
+        B, T, A = enc_idx.shape
+        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        dec_in = nv.carray(dec_in, np.int32)
+        dec_out = nv.carray(dec_out, np.int32)
+        weights = nv.carray(weights, np.float32)
+        U = dec_in.shape[1]
+        m_enc, m_dec, m_cell = self._step_masks(masks)
+        p = self._sched_params(seed, step_id, ratio, pick, passes, temperature)
+        mixes = np.empty((max(int(passes), 0), B, U), np.int32)
+        loss, norm = c_double(), c_double()
+        nv.check(self.lib.casv_train_step_sampled(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
+                                                  nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
+                                                  byref(p), nv.ptr(mixes), byref(loss), byref(norm)))
+        return loss.value, norm.value, mixes
+
+    def debug_sched_rows(self, logits, gold, b, u, ratio=1.0, seed=0, step_id=0, pick='greedy', temperature=1.0, pad_value=0.0):
+        """Test support (casv_debug_sched_rows): the mix kernel alone on logits (R,V) -- row r is decoder position (b[r], u[r])
+        with the gold input gold[r]; the padding columns of the device rows hold pad_value.  Returns the mix (R) int32."""
+        logits = nv.carray(logits, np.float32)
+        R, V = logits.shape
+        gold, b, u = (nv.carray(a, np.int32) for a in (gold, b, u))
+        assert gold.shape == b.shape == u.shape == (R,)
+        p = self._sched_params(seed, step_id, ratio, pick, 1, temperature)
+        out = np.empty((R,), np.int32)
+        nv.check(self.lib.casv_debug_sched_rows(self.handle, R, V, byref(p), nv.ptr(b), nv.ptr(u), nv.ptr(logits), nv.ptr(gold),
+                                                float(pad_value), nv.ptr(out)))
+        return out
+
     def train_gradients(self):
         out = {}
         for name, shape in self.pshapes.items():

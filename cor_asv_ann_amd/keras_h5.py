@@ -26,6 +26,8 @@ layers that is not named in `layer_names`, so that keras' `load_weights` and thi
     /training_state/adam                        float64[5]: lr, beta1, beta2, epsilon, clipnorm
     /training_state/frozen                      bytes: the frozen tensor-name prefixes, comma-separated
     /training_state/{distill_k,distill_alpha}   int64 / float64 scalars: a distilled run's K and alpha (absent: no teacher)
+    /training_state/sample                      bytes: JSON of a scheduled-sampling run's settings {seed, schedule, pick, passes,
+                                                temperature} (absent: no sample_schedule)
     /training_state/rng                         bytes: JSON of the numpy bit generator's state
     /training_state/split_rand                  float64[lines]: the validation split (absent: validation files were given)
     /training_state/history_{loss,val_loss}     float64[epochs]
@@ -257,6 +259,8 @@ def _write_state(w, st):
     if st.get('distill') is not None:
         w.create_dataset(g + 'distill_k', np.asarray(int(st['distill'][0]), np.int64))
         w.create_dataset(g + 'distill_alpha', np.asarray(float(st['distill'][1]), np.float64))
+    if st.get('sample') is not None:
+        w.create_dataset(g + 'sample', np.bytes_(json.dumps(st['sample'], sort_keys=True).encode('utf-8')))
     if st.get('split_rand') is not None:
         w.create_dataset(g + 'split_rand', np.asarray(st['split_rand'], np.float64))
     hist = st.get('history') or []
@@ -289,6 +293,8 @@ def read_training_state(filename):
         st['split_rand'] = np.asarray(g['split_rand'].read(), np.float64) if 'split_rand' in g else None
         if 'distill_k' in g:           # (a distilled run only: a plain run's state has the keys it always had)
             st['distill'] = (int(np.asarray(g['distill_k'].read())), float(np.asarray(g['distill_alpha'].read())))
+        if 'sample' in g:              # (a scheduled-sampling run only)
+            st['sample'] = json.loads(text('sample'))
         st['history'] = []
         if 'history_loss' in g:
             st['history'] = [{'loss': float(a), 'val_loss': float(b)} for a, b in

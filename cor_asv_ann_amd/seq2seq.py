@@ -182,7 +182,9 @@ class Sequence2Sequence(object):
                 raise NotImplementedError('%s is not implemented in the MI355X hot path (only the default '
                                           'topology of the published models is)%s' % (
                                               flag, '; set lm_predict after configure() / load_config(): it is read at '
-                                              'every beam decode' if flag == 'lm_predict' else ''))
+                                              'every beam decode' if flag == 'lm_predict' else
+                                              '; scheduled sampling is the keyword train(..., sample_schedule=...) here'
+                                              if flag == 'scheduled_sampling' else ''))
         self.logger.info('using HIP/gfx950 implementation to compile %s model of depth %d width %d size %d '
                          'with attention', 'stateless', self.depth, self.width, self.voc_size)
         if self.engine is not None:
@@ -1237,7 +1239,8 @@ class Sequence2Sequence(object):
             for k in names:
                 self.logger.info('%s %-7s %.3f±%.3f', what, labels[k].strip() + ':', counts[k].mean, math.sqrt(counts[k].varia))
 
-    def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5):
+    def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
+              sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0):
         """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
         from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
         restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint).
@@ -1247,10 +1250,19 @@ class Sequence2Sequence(object):
         is `HipEngine.train_step_soft`.  The teacher must have this model's `voc_size` and character mapping once the files'
         characters are mapped (ValueError otherwise, before anything runs); validation stays the hard loss, so `val_loss`, early
         stopping and the checkpoints' names mean what they mean without a teacher.  A distilled run's state checkpoints record
-        `distill_k` and `distill_alpha`; `resume` refuses a mismatch or a missing teacher.  distill_alpha = 1 is plain training."""
+        `distill_k` and `distill_alpha`; `resume` refuses a mismatch or a missing teacher.  distill_alpha = 1 is plain training.
+        sample_schedule: scheduled sampling in its parallel form (`HipEngine.train_step_sampled`) -- 'linear',
+        'sigmoid' or 'exponential' (the reference's formulas of the completed epochs and `epochs`, `training.schedule_ratio`), a
+        float (that ratio in every epoch) or a callable completed epochs -> ratio; each training step then mixes its own picks
+        (`sample_pick` 'greedy' or 'sample' at `sample_temperature`) into the decoder input with that probability per position,
+        `sample_passes` (1..8) times, on one encoder pass.  The coins' seed is drawn once from the model's generator, the step
+        number is the session's; both, the schedule's name, the pick, the passes and the temperature go into the state
+        checkpoints, and `resume` refuses other values.  Validation stays teacher-forced.  Not together with `teacher`
+        (ValueError)."""
         from .training import train_files
         return train_files(self, filenames, val_filenames, resume=resume, teacher=teacher, distill_k=distill_k,
-                           distill_alpha=distill_alpha)
+                           distill_alpha=distill_alpha, sample_schedule=sample_schedule, sample_pick=sample_pick,
+                           sample_passes=sample_passes, sample_temperature=sample_temperature)
 
 
 class _EncoderModel(object):

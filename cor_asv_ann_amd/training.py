@@ -1,7 +1,9 @@
 """Host side of `Sequence2Sequence.train()` (seq2seq.py:590-649 + lib/keras_train.py:27-438): epochs over the
 generator, validation, early stopping / NaN termination / per-epoch checkpoints.  Each batch is ONE call into
 the C ABI (`casv_train_step`), which runs forward, backward, clipping and Adam on the device.  With a teacher
-(distillation) a batch is the teacher's scoring call, its K alternatives per position and `casv_train_step_soft`."""
+(distillation) a batch is the teacher's scoring call, its K alternatives per position and `casv_train_step_soft`; with a
+sample schedule (scheduled sampling) it is `casv_train_step_sampled` at the epoch's ratio."""
+import math
 import queue
 import signal
 import threading
@@ -213,7 +215,86 @@ def distill_step(engine, teacher_engine, batch, distill_k, distill_alpha):
     return engine.train_step_soft(idx, val, dec_in, soft_idx, soft_q, w, masks, mode=1)
 
 
-def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5):
+SCHEDULES = ('linear', 'sigmoid', 'exponential')
+
+
+def schedule_name(sample_schedule):
+    """What a checkpoint records of `sample_schedule`: the name, 'const:<ratio>' of a float, 'callable' of a callable."""
+    if callable(sample_schedule):
+        return 'callable'
+    if isinstance(sample_schedule, str):
+        return sample_schedule
+    return 'const:%r' % float(sample_schedule)
+
+
+def schedule_ratio(sample_schedule, epoch, epochs):
+    """The sampling ratio of the epoch that follows `epoch` completed ones, out of `epochs`.  The named schedules are the
+    reference's formulas at attenuation 3 (seq2seq.py:867-873), which it evaluates at the end of every epoch for the next one
+    and starts from 0: linear 3 (epoch - 1) / (epochs - 1), clamped to [0, 1] and 0 where epochs == 1; sigmoid
+    1 / (1 + exp(5 - 30 epoch / epochs)); exponential 1 - 0.9 ** (150 epoch / epochs).  A float is that ratio in every epoch; a
+    callable is asked with `epoch`.  Raises ValueError for a ratio outside [0, 1]."""
+    attenuation = 3
+    if callable(sample_schedule):
+        ratio = float(sample_schedule(epoch))
+    elif not isinstance(sample_schedule, str):
+        ratio = float(sample_schedule)
+    elif epoch < 1:
+        ratio = 0.0
+    elif sample_schedule == 'linear':
+        ratio = 0.0 if epochs <= 1 else min(1.0, max(0.0, attenuation * (epoch - 1) / (epochs - 1)))
+    elif sample_schedule == 'sigmoid':
+        ratio = 1 / (1 + math.exp(5 - 10 * attenuation * epoch / epochs))
+    else:
+        ratio = 1 - 0.9 ** (50 * attenuation * epoch / epochs)
+    if not 0.0 <= ratio <= 1.0:             # (NaN fails too)
+        raise ValueError('sample_schedule gives the ratio %r for epoch %d: it must lie in [0, 1]' % (ratio, epoch))
+    return ratio
+
+
+def check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher):
+    """The scheduled-sampling keywords of train(), checked on the host before anything runs: ValueError with the first fault."""
+    if teacher is not None:
+        raise ValueError('sample_schedule together with teacher: soft targets and scheduled sampling do not combine')
+    if isinstance(sample_schedule, str):
+        if sample_schedule not in SCHEDULES:
+            raise ValueError('sample_schedule must be one of %s, a float or a callable, got %r' % (', '.join(SCHEDULES), sample_schedule))
+    elif not callable(sample_schedule):
+        try:
+            ok = 0.0 <= float(sample_schedule) <= 1.0
+        except (TypeError, ValueError):
+            raise ValueError('sample_schedule must be one of %s, a float or a callable, got %r' % (', '.join(SCHEDULES), sample_schedule))
+        if not ok:
+            raise ValueError('sample_schedule as a float is a ratio in [0, 1], got %r' % (sample_schedule,))
+    if sample_pick not in ('greedy', 'sample'):
+        raise ValueError("sample_pick must be 'greedy' or 'sample', got %r" % (sample_pick,))
+    if int(sample_passes) != sample_passes or not 1 <= sample_passes <= 8:
+        raise ValueError('sample_passes must be in [1, 8], got %r' % (sample_passes,))
+    if not (math.isfinite(float(sample_temperature)) and float(sample_temperature) > 0.0):
+        raise ValueError('sample_temperature must be finite and positive, got %r' % (sample_temperature,))
+
+
+def check_sampling_resume(state, filename, settings):
+    """A scheduled-sampling run resumes with the settings it recorded (its seed is taken from the file), a plain run as a
+    plain run: ValueError otherwise."""
+    theirs = state.get('sample')
+    if theirs is None and settings is None:
+        return
+    if theirs is None:
+        raise ValueError('cannot resume from "%s": it was trained without a sample schedule' % filename)
+    if settings is None:
+        raise ValueError('cannot resume from "%s": it was trained with the sample schedule %r' % (filename, theirs['schedule']))
+    for key in ('schedule', 'pick', 'passes', 'temperature'):
+        if theirs[key] != settings[key]:
+            raise ValueError('cannot resume from "%s": sample %s differs (file %r, now %r)' % (filename, key, theirs[key], settings[key]))
+
+
+def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
+                sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0):
+    sampling = None                          # scheduled sampling: what the checkpoints record (the seed joins below)
+    if sample_schedule is not None:
+        check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher)
+        sampling = {'schedule': schedule_name(sample_schedule), 'pick': sample_pick, 'passes': int(sample_passes),
+                    'temperature': float(sample_temperature)}
     num_lines = s2s.map_files(filenames)
     s2s.logger.info('Training on "%d" files with %d lines', len(filenames), num_lines)
     if val_filenames:
@@ -225,6 +306,7 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
     state = resume_state(s2s, resume) if resume else None        # (after map_files: the mapping is part of what must match)
     if state is not None:
         check_distill_resume(state, resume, teacher, distill_k, distill_alpha)
+        check_sampling_resume(state, resume, sampling)
     if val_filenames:
         if state is not None and state['split_rand'] is not None:
             raise ValueError('cannot resume from "%s": it was trained without validation files' % resume)
@@ -239,6 +321,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
         s2s._assign_layers(layers, keras_h5.layer_tensors(s2s.depth, s2s.bridge_dense, s2s.deep_bidirectional_encoder), skip_mismatch=False)
         s2s._rng.bit_generator.state = state['rng']      # ... and the generator as the next epoch found it
     rng = s2s._rng
+    if sampling is not None:                 # the coins' seed: drawn once per run, a resumed run keeps its own
+        sampling['seed'] = int(state['sample']['seed']) if state is not None else int(rng.integers(0, 2 ** 63))
     engine = s2s._require_engine()
     engine.set_option('deterministic', 1 if s2s.deterministic else 0)
     teacher_engine = None
@@ -249,6 +333,7 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
     engine.train_begin(*adam, frozen=tuple(s2s.frozen_prefixes))
     if state is not None:
         engine.set_train_state(state['m'], state['v'], state['step'])
+    step_id = int(state['step']) if state is not None else 0     # the session's step count: every mode-1 step adds one
     stop = {'flag': False}
     old_handler = None
     try:
@@ -271,10 +356,16 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
         for epoch in range(first, s2s.epochs):
             total, nb = 0.0, 0
             nan = cut = False
+            ratio = schedule_ratio(sample_schedule, epoch, s2s.epochs) if sampling is not None else None
             # the next batches are vectorised by a worker thread while the device runs this one (kt:133-145)
             for idx, val, dec_in, dec_out, w, masks in prefetch(train_batches(s2s, filenames, split_rand, rng)):
                 if teacher_engine is not None:
                     loss, _ = distill_step(engine, teacher_engine, (idx, val, dec_in, dec_out, w, masks), distill_k, distill_alpha)
+                elif sampling is not None:
+                    loss, _, _ = engine.train_step_sampled(idx, val, dec_in, dec_out, w, masks, mode=1, ratio=ratio, seed=sampling['seed'],
+                                                           step_id=step_id, pick=sample_pick, passes=sample_passes,
+                                                           temperature=sample_temperature)
+                    step_id += 1
                 else:
                     loss, _ = engine.train_step(idx, val, dec_in, dec_out, w, masks, mode=1)
                 if not np.isfinite(loss):
@@ -292,7 +383,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
                     vtotal += loss; vn += 1
             val_loss = vtotal / vn if vn else float('nan')
             history.append({'loss': total / max(nb, 1), 'val_loss': val_loss})
-            s2s.logger.info('epoch %d: loss %.4f val_loss %.4f (%d/%d batches)', epoch + 1, history[-1]['loss'], val_loss, nb, vn)
+            s2s.logger.info('epoch %d: loss %.4f val_loss %.4f (%d/%d batches)%s', epoch + 1, history[-1]['loss'], val_loss, nb, vn,
+                            '' if ratio is None else ' sample ratio %.4f' % ratio)
             if nan or not np.isfinite(val_loss):
                 break
             weights = engine.train_weights()
@@ -311,6 +403,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
                               'split_rand': split_rand, 'history': history, 'm': m, 'v': v, 'best': best_weights or {}}
                 if teacher is not None:
                     ckpt_state['distill'] = (int(distill_k), float(distill_alpha))
+                if sampling is not None:
+                    ckpt_state['sample'] = dict(sampling)
             keras_h5.write_model('model.ckpt.weights-%02d-%.2f.h5' % (epoch + 1, val_loss), s2s._config_dict(), weights, ckpt_state)
             if wait >= 3:                              # EarlyStopping(patience=3, restore_best_weights)
                 s2s.logger.info('Epoch %05d: early stopping', epoch + 1)

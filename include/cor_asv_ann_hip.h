@@ -258,6 +258,39 @@ int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int32_t T, int3
 int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, const int32_t* soft_idx,
                             const float* soft_q, const float* weight, float inv_count, float pad_value, int32_t want_grad,
                             double* loss, float* dlogits, int32_t ordered);
+/* casv_train_step with scheduled sampling in its parallel form (Duckworth et al. 2019): the teacher-forced
+ * forward pass, then `passes` times { logits of the current tape; a pick at every decoder position from the logits of the position
+ * before it; a coin per position; the decoder again on the mixed input }, then casv_train_step's loss head, backward pass, clip and
+ * update on the last pass's tape.  The encoder, u and the final / bridged states are computed once; the pick carries no gradient.
+ * For decoder position (b, u), x the V logits of row (u - 1, b):
+ *   coin     = (o0 >> 8) * 2^-24 < ratio, o0 .. o3 = Philox4x32-10 on the counter (step_id low, step_id high, b, u) under the key
+ *              (seed low, seed high): a function of (seed, step_id, b, u) only, the same in every pass of a step
+ *   eligible = u >= 1 and dec_in[b,u] >= 0
+ *   pick 0   = greedy: the largest x_v over v = 1 .. V-1, the lowest index among equals, -0 == +0 (index 0 is never picked)
+ *   pick 1   = the draw of casv_decode_sample at top_k = 0 and `temperature`, with the uniform (o1 >> 8) * 2^-24
+ *   a row with a NaN, or whose candidates' maximum is not finite, keeps dec_in[b,u] (the step's loss is then NaN anyway)
+ *   mix[b,u] = the pick where the position is eligible and the coin is true, dec_in[b,u] otherwise
+ * out_dec_in (passes, B, U): slice p - 1 is the mix after pass p; the last slice is the decoder input the step trained on.  With
+ * ratio 0 no pass is run -- the launches and the bits of casv_train_step -- and every slice is dec_in.  Modes 1 and 2 only
+ * (validation stays teacher-forced).  Refused with CASV_ERR_ARG before anything is enqueued or cleared, the session's step count,
+ * moments and gradients untouched: mode 0; NULL p or out_dec_in; ratio outside [0, 1] or NaN; passes outside 1 .. 8; pick outside
+ * {0, 1}; with pick 1 a temperature that is not finite or <= 0.  Everything else is casv_train_step's.  Kernel class of
+ * casv_profile_read for the mix: "sample". */
+typedef struct {
+    uint64_t seed, step_id;
+    float ratio, temperature;
+    int32_t pick;                   /* 0 greedy, 1 sample */
+    int32_t passes;
+} casv_sched_params;
+int casv_train_step_sampled(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                            const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                            const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
+                            const casv_sched_params* p, int32_t* out_dec_in, double* loss, double* grad_norm);
+/* Test support: the mix kernel alone on the caller's R rows, laid out as casv_debug_score_rows lays them out (pad_value fills the
+ * columns [V, Vp), which no output may depend on): row r is decoder position (b[r], u[r]) with the logits row logits[r] (R,V) and
+ * the gold input gold[r]; out[r] = its mix.  p->passes is ignored; the other fields are checked as casv_train_step_sampled's. */
+int casv_debug_sched_rows(casv_model* m, int32_t R, int32_t V, const casv_sched_params* p, const int32_t* b, const int32_t* u,
+                          const float* logits, const int32_t* gold, float pad_value, int32_t* out);
 /* Gradient of the last step for one tensor, in Keras layout (parity tests). */
 int casv_train_get_gradient(casv_model* m, const char* name, float* out, int64_t capacity);
 /* Adam's optimizer state of one trained tensor in Keras layout, like casv_train_get_gradient: which = 0 the first moment m,
