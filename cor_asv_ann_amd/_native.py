@@ -41,6 +41,11 @@ class SampleParams(Structure):
     _fields_ = [('seed', c_uint64), ('temperature', c_float), ('top_k', c_int32), ('samples', c_int32)]
 
 
+class SampleCut(Structure):
+    """casv_sample_cut: the truncation of a sampled pick, top_k in 0 .. 4095 (0 = none) and top_p in (0, 1] (1 = none)"""
+    _fields_ = [('top_k', c_int32), ('top_p', c_float)]
+
+
 class SchedParams(Structure):
     _fields_ = [('seed', c_uint64), ('step_id', c_uint64), ('ratio', c_float), ('temperature', c_float), ('pick', c_int32),
                 ('passes', c_int32)]
@@ -92,6 +97,9 @@ SIGNATURES = {
     'casv_decode_sample': (c_int, [c_void_p, POINTER(SampleParams), c_int32] + [c_void_p] * 6),
     'casv_debug_sample_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SampleParams), c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_float] + [c_void_p] * 4),
+    'casv_decode_sample_cut': (c_int, [c_void_p, POINTER(SampleParams), POINTER(SampleCut), c_int32] + [c_void_p] * 6),
+    'casv_debug_sample_cut_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SampleParams), POINTER(SampleCut), c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_float] + [c_void_p] * 4),
     'casv_train_begin': (c_int, [c_void_p, POINTER(AdamParams), c_char_p]),
     'casv_train_step': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8 + [POINTER(c_double), POINTER(c_double)]),
     'casv_train_get_gradient': (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
@@ -111,6 +119,10 @@ SIGNATURES = {
     'casv_train_step_sampled': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
                                 + [POINTER(SchedParams), c_void_p, POINTER(c_double), POINTER(c_double)]),
     'casv_debug_sched_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SchedParams)] + [c_void_p] * 4 + [c_float, c_void_p]),
+    'casv_train_step_sampled_cut': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
+                                    + [POINTER(SchedParams), POINTER(SampleCut), c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_debug_sched_cut_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SchedParams), POINTER(SampleCut)] + [c_void_p] * 4
+                                  + [c_float, c_void_p]),
     'casv_debug_soft_ce_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                         c_int32, POINTER(c_double), c_void_p, c_int32]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
@@ -158,8 +170,8 @@ def load():
                            '(there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in SIGNATURES.items():
-        if os.environ.get('CASV_LIB_PATH') and name.startswith('casv_debug_') and not hasattr(lib, name):
-            continue                     # (A/B against an older build of the library: it may lack a test-support entry)
+        if os.environ.get('CASV_LIB_PATH') and (name.startswith('casv_debug_') or name.endswith('_cut')) and not hasattr(lib, name):
+            continue                     # (A/B against an older build of the library: it may lack a test-support entry, or the cut entries)
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -231,8 +231,25 @@ struct SampleArgs {
     float* out_logq;        // ... under the proposal (the candidates at this temperature)
     int S, out_col;
     int* nan_flag;          // set when a row is invalid
+    float top_p;            // launch_sample_cut only: the nucleus of the cut (top_k, top_p); 1 = none
 };
 void launch_sample(const SampleArgs& a, hipStream_t stream);
+// The same pick under a cut (top_k <= 4095, top_p): sample_cut_kernel, which sorts every row's keys in LDS (DESIGN.md section 4.8,
+// items 11 to 13).  A row takes Vp floats and P keys of 8 bytes, P = V rounded up to a power of two, so the rows (= waves) of a
+// workgroup follow from V: as many as SAMPLE_CUT_LDS holds, at most 4 -- and at most `rows_max` where that is positive (a test
+// switch: the results do not depend on it).
+constexpr int SAMPLE_CUT_LDS = 160 * 1024;
+constexpr int SAMPLE_CUT_MAX_K = 4095;
+inline int sample_cut_sort_size(int V) { int P = 2; while (P < V) P <<= 1; return P; }
+inline int sample_cut_row_bytes(int V) { return ((V + 31) & ~31) * 4 + sample_cut_sort_size(V) * 8; }
+inline int sample_cut_rows_per_workgroup(int V, int rows_max) {
+    const int fit = std::min(4, SAMPLE_CUT_LDS / sample_cut_row_bytes(V));
+    return std::max(1, rows_max > 0 ? std::min(fit, rows_max) : fit);
+}
+// false: the runtime refused the kernels' dynamic LDS (nothing may be launched then); callers ask before they enqueue anything
+bool sample_cut_ready();
+// returns the rows per workgroup it launched with
+int launch_sample_cut(const SampleArgs& a, int rows_max, hipStream_t stream);
 // dst row line * rows_per_line + n (n < rows_per_line) = src row line, `width` floats each, rows packed: the encoder's final
 // states under every sample row of a line
 void launch_spread_rows(const float* src, float* dst, int lines, int rows_per_line, int width, hipStream_t stream);

@@ -64,7 +64,10 @@ static int init_root(casv_model* m, int rows_per_line, SmallOps ops = SmallOps{}
 // The view of one decoder_model step on the session's R rows (seq2seq.py:416-480): every launch of the step builds its arguments
 // from (m, step) alone.
 // What a sampling step draws by (casv_decode_sample)
-struct SampleDraw { unsigned long long seed; float temperature; int top_k; const long long* stream; float* logp; float* logq; };
+struct SampleDraw {
+    unsigned long long seed; float temperature; int top_k; const long long* stream; float* logp; float* logq;
+    const casv_sample_cut* cut;     // casv_decode_sample_cut: the draw under this cut, by sample_cut_kernel (nullptr: sample_kernel at top_k)
+};
 
 struct DecodeStep {
     bool beam = false;             // input rows from `pin` and parents through `prev` (the search), otherwise row r continues row r
@@ -233,7 +236,10 @@ static void step_sample(casv_model* m, const DecodeStep& st) {
     a.nan_flag = m->d_nan.as<int>();
     hipEvent_t ev{};
     m->prof_begin(PC_SAMPLE, 4.0 * R * V, 4.0 * R * (V + Vp), ev);
-    launch_sample(a, m->stream);
+    if (d.cut) {                // (casv_decode_sample_cut has asked sample_cut_ready())
+        a.top_k = d.cut->top_k; a.top_p = d.cut->top_p;
+        m->stat_sample_cut_rows = launch_sample_cut(a, m->sample_cut_rows_opt, m->stream);
+    } else launch_sample(a, m->stream);
     m->prof_end(PC_SAMPLE, ev);
 }
 
@@ -709,9 +715,9 @@ static bool sample_lengths(const casv_model* m, const GreedyCall& c, int R, int3
     return nan_before_end;
 }
 
-extern "C" int casv_decode_sample(casv_model* m, const casv_sample_params* p, int32_t S, const int64_t* stream, int32_t* out_idx,
-                                  float* out_logp, float* out_logq, int32_t* out_len, float* out_align) {
-    if (int rc = sample_arguments(m, p, S, out_idx, out_logp, out_logq, out_len)) return rc;
+// the call behind casv_decode_sample (cut == nullptr) and casv_decode_sample_cut, its arguments checked
+static int decode_sample_call(casv_model* m, const casv_sample_params* p, const casv_sample_cut* cut, int32_t S, const int64_t* stream,
+                              int32_t* out_idx, float* out_logp, float* out_logq, int32_t* out_len, float* out_align) {
     if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
     const int B = m->B, T = m->T, N = p->samples;
     if ((long long)(S + 1) * B * N >= (1LL << 31)) return fail(CASV_ERR_ARG, "samples=%d: (S + 1) * lines * samples rows overflow int32 (sample fewer lines or steps per call)", N);
@@ -727,7 +733,7 @@ extern "C" int casv_decode_sample(casv_model* m, const casv_sample_params* p, in
     if (int rc = ensure_all(plan)) return rc;
     if (int rc = greedy_staging(m, c, 3)) return rc;
     if (stream) HIPCHK(hipMemcpyAsync(m->s_stream.p, stream, (size_t)B * 8, hipMemcpyHostToDevice, m->stream));
-    const SampleDraw draw{p->seed, p->temperature, p->top_k, stream ? m->s_stream.as<long long>() : nullptr, m->o_prob.as<float>(), m->s_logq.as<float>()};
+    const SampleDraw draw{p->seed, p->temperature, p->top_k, stream ? m->s_stream.as<long long>() : nullptr, m->o_prob.as<float>(), m->s_logq.as<float>(), cut};
     for (int attempt = 0; ; ++attempt) {        // (the second follows an encoder pass that gave up: there is no third, see casv_decode_beam)
         bool again = false;
         if (int rc = sample_attempt(m, c, draw, N, out_logq, again)) return rc;
@@ -747,6 +753,24 @@ extern "C" int casv_decode_sample(casv_model* m, const casv_sample_params* p, in
     m->last_decode = 1; m->last_S = S; m->last_rows = R; m->last_mode = 2; m->last_signature = decode_buffers_signature(m);
     if (nan_before_end) return fail(CASV_ERR_NAN, "a sampled row's logits were NaN or without a finite candidate");
     return CASV_OK;
+}
+
+extern "C" int casv_decode_sample(casv_model* m, const casv_sample_params* p, int32_t S, const int64_t* stream, int32_t* out_idx,
+                                  float* out_logp, float* out_logq, int32_t* out_len, float* out_align) {
+    if (int rc = sample_arguments(m, p, S, out_idx, out_logp, out_logq, out_len)) return rc;
+    return decode_sample_call(m, p, nullptr, S, stream, out_idx, out_logp, out_logq, out_len, out_align);
+}
+
+// ... under a cut (top_k, top_p): the same call with sample_cut_kernel as every step's draw
+extern "C" int casv_decode_sample_cut(casv_model* m, const casv_sample_params* p, const casv_sample_cut* cut, int32_t S, const int64_t* stream,
+                                      int32_t* out_idx, float* out_logp, float* out_logq, int32_t* out_len, float* out_align) {
+    if (int rc = sample_arguments(m, p, S, out_idx, out_logp, out_logq, out_len)) return rc;
+    if (int rc = check_sample_cut(cut)) return rc;
+    if (p->top_k != 0) return fail(CASV_ERR_ARG, "top_k=%d beside a cut: the cut carries it", p->top_k);
+    if (!m->encoded) return fail(CASV_ERR_STATE, "casv_encode must run first");
+    HIPCHK(hipSetDevice(m->device));
+    if (!sample_cut_ready()) return fail(CASV_ERR_HIP, "the runtime refused sample_cut_kernel's %d bytes of dynamic LDS", SAMPLE_CUT_LDS);
+    return decode_sample_call(m, p, cut, S, stream, out_idx, out_logp, out_logq, out_len, out_align);
 }
 
 // ---- casv_decode_beam ----

@@ -34,7 +34,15 @@ inline int fail(int code, const char* fmt, ...) {
     return fail(e_ == hipErrorOutOfMemory ? CASV_ERR_NOMEM : CASV_ERR_HIP, "%s failed: %s (%s:%d)", #x, \
                 hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
-inline long g_devbuf_generation = 0;    // bumped by every (re)allocation: captured hipGraphs hold raw pointers
+// The rules of a cut (casv_sample_cut in include/cor_asv_ann_hip.h), checked before anything is launched or cleared.
+inline int check_sample_cut(const casv_sample_cut* cut) {
+    if (!cut) return fail(CASV_ERR_ARG, "null argument");
+    if (cut->top_k < 0 || cut->top_k > SAMPLE_CUT_MAX_K) return fail(CASV_ERR_ARG, "cut top_k=%d out of range 0..%d", cut->top_k, SAMPLE_CUT_MAX_K);
+    if (!(cut->top_p > 0.f && cut->top_p <= 1.f)) return fail(CASV_ERR_ARG, "cut top_p=%g outside (0, 1]", (double)cut->top_p);
+    return 0;
+}
+
+inline long g_devbuf_generation = 0;   // bumped by every (re)allocation: captured hipGraphs hold raw pointers
 // A device allocation and its owner: move-only, freed with the object that holds it.  (No DevBuf has static storage: its
 // destructor would call the runtime during process teardown.)
 struct DevBuf {
@@ -142,7 +150,8 @@ struct casv_model {
     bool enc_tab_ready = false, enc_onehot = false;
     int enc_table_opt = 1;                                // option "encoder_table": 0 never, 1 layer 1 where the pass qualifies, 2 and the layers above ahead
     bool beam_skip_last = true;                           // option "beam_skip_last": the search's last iteration launches no decoder step (decode.hip)
-    int stat_enc_table = 0; long long stat_enc_table_builds = 0;    // the last encoder pass read the table; tables built on this handle so far
+    int sample_cut_rows_opt = 0, stat_sample_cut_rows = 0;          // option / statistic "sample_cut_rows": sample_cut_kernel's rows per workgroup
+    int stat_enc_table = 0; long long stat_enc_table_builds = 0;   // the last encoder pass read the table; tables built on this handle so far
     DevBuf a0; bool has_a0 = false;                       // initial alignment handed in with casv_set_encoder_outputs
     // decode session
     int R = 0, S = 0;

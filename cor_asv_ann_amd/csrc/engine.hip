@@ -329,6 +329,7 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }
+    if (!strcmp(key, "sample_cut_rows")) { *value = m->stat_sample_cut_rows; return CASV_OK; }
     return fail(CASV_ERR_ARG, "unknown statistic '%s'", key);
 }
 
@@ -733,6 +734,10 @@ extern "C" int casv_set_option(casv_model* m, const char* key, int64_t value) {
     if (!strcmp(key, "beam_skip_last")) {       // debug switch: 0 = the search's last iteration launches its decoder step as every other (same results)
         if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "beam_skip_last must be 0 or 1");
         m->beam_skip_last = value != 0; return CASV_OK;
+    }
+    if (!strcmp(key, "sample_cut_rows")) {      // test switch: at most this many rows per workgroup of sample_cut_kernel (same results)
+        if (value < 0 || value > 4) return fail(CASV_ERR_ARG, "sample_cut_rows must be 0 (as many as fit) or 1 .. 4");
+        m->sample_cut_rows_opt = (int)value; return CASV_OK;
     }
     if (!strcmp(key, "vendor_gemm")) { m->vendor_gemm = value != 0; return CASV_OK; }
     if (!strcmp(key, "skinny") || !strcmp(key, "tile")) {   // process-wide: tile shape of the GEMM launches (results identical)

@@ -22,15 +22,11 @@ namespace casv {
 //      over the lanes in ascending order; the first lane with off_l + c_l > u * Z walks its indices again, and the pick is the first
 //      with off_l + (w_first + ... + w_v) > u * Z.  No lane (a caller's u >= 1): the last index with w > 0.
 // Passes 4 -> 5 hand LDS entries from lane to lane inside the wave: a wavefront fence, no workgroup barrier.
-__global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
-    extern __shared__ float sample_rows[];          // [4][Vp]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = blockIdx.x * 4 + wave;
-    if (r >= a.R) return;
+// The row r of a launch on its wave's LDS: s = the row's Vp floats; CUT: keys = its P sort entries, the bound from the cut.
+template <bool CUT> __device__ __forceinline__ void sample_row(const SampleArgs& a, int r, int lane, float* s, unsigned long long* keys, int P) {
     const int step = a.step_ptr ? *a.step_ptr : a.step_imm;
     const int V = a.V, Vp = (V + 31) & ~31;
     const float* x = a.logits + (long long)r * Vp;
-    float* s = sample_rows + wave * Vp;
     float* fb = a.feedback + (long long)(step + 1) * a.fb_slot + (long long)r * Vp;
     const SampleRowStats rs = sample_row_stage(x, s, V, lane);
     const float m = rs.m, mc = rs.mc;
@@ -50,7 +46,10 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
             u = philox_uniform(philox4x32_10_word0((unsigned)id, (unsigned)(id >> 32), n, (unsigned)step, (unsigned)a.seed, (unsigned)(a.seed >> 32)));
         }
         double Z;
-        pick = sample_row_draw(s, V, lane, a.top_k, a.temperature, mc, u, &Z);
+        if constexpr (CUT)
+            pick = sample_row_draw_under(s, V, lane, sample_row_cut_bound(s, keys, V, P, lane, a.top_k, a.top_p, a.temperature, mc), a.temperature, mc, u, &Z);
+        else
+            pick = sample_row_draw(s, V, lane, a.top_k, a.temperature, mc, u, &Z);
         const float xp = x[pick];
         lp = m < INFINITY ? (xp - m) - logf(sum) : __builtin_nanf("");
         lq = (float)((double)((xp - mc) / a.temperature) - log(Z));
@@ -67,9 +66,39 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
+    extern __shared__ float sample_rows[];          // [4][Vp]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= a.R) return;
+    sample_row<false>(a, r, lane, sample_rows + wave * ((a.V + 31) & ~31), nullptr, 0);
+}
+
 void launch_sample(const SampleArgs& a, hipStream_t stream) {
     const int Vp = (a.V + 31) & ~31;
     hipLaunchKernelGGL(sample_kernel, dim3((a.R + 3) / 4), dim3(256), (size_t)4 * Vp * sizeof(float), stream, a);
+}
+
+// The same under a cut (sample_row.h, sample_row_cut_bound): blockDim.x / 64 rows per workgroup (common.h,
+// sample_cut_rows_per_workgroup), the rows' sort entries [rows][P] in front of their floats [rows][Vp].
+__global__ __launch_bounds__(256) void sample_cut_kernel(const SampleArgs a, int P) {
+    extern __shared__ unsigned long long sample_cut_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rows = blockDim.x >> 6;
+    const int r = blockIdx.x * rows + wave;
+    if (r >= a.R) return;
+    float* floats = reinterpret_cast<float*>(sample_cut_lds + (size_t)rows * P);
+    sample_row<true>(a, r, lane, floats + wave * ((a.V + 31) & ~31), sample_cut_lds + (size_t)wave * P, P);
+}
+
+static LdsAttribute sample_cut_attr;
+bool sample_cut_ready() { return gemm_dynamic_lds(sample_cut_attr, reinterpret_cast<const void*>(&sample_cut_kernel), SAMPLE_CUT_LDS); }
+
+int launch_sample_cut(const SampleArgs& a, int rows_max, hipStream_t stream) {
+    const int rows = sample_cut_rows_per_workgroup(a.V, rows_max);
+    if (!sample_cut_ready()) return 0;
+    hipLaunchKernelGGL(sample_cut_kernel, dim3((a.R + rows - 1) / rows), dim3(64 * rows), (size_t)rows * sample_cut_row_bytes(a.V), stream, a,
+                       sample_cut_sort_size(a.V));
+    return rows;
 }
 
 __global__ void spread_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n, int rows_per_line, int width) {

@@ -47,11 +47,11 @@ __device__ __forceinline__ SampleRowStats sample_row_stage(const float* __restri
     return SampleRowStats{m, mc, !nan && mc > -INFINITY && mc < INFINITY};
 }
 
-// Passes 3 to 5 of a valid row staged in s (sample_kernels.hip numbers them): the top_k bound, the weights w = expf((x - m_C) /
-// temperature) of the candidates over the row in LDS, the ordered float64 prefix sum and the pick for the uniform u.  *Z: the total.
-// Passes 4 -> 5 hand LDS entries from lane to lane inside the wave: a wavefront fence, no workgroup barrier.
-__device__ __forceinline__ int sample_row_draw(float* s, int V, int lane, int top_k, float temperature, float mc, float u, double* Zout) {
-    unsigned long long kth = 0ull;              // the candidates: indices >= 1 whose key is no smaller
+// Pass 3 of a valid row staged in s (sample_kernels.hip numbers the passes): the bound of the top_k candidates, by top_k rounds of
+// the wave-wide maximum over the keys strictly below the previous winner's.  The candidates are the indices >= 1 whose key is no
+// smaller than the bound; 0 = all of them.
+__device__ __forceinline__ unsigned long long sample_row_bound(const float* s, int V, int lane, int top_k) {
+    unsigned long long kth = 0ull;
     if (top_k > 0 && top_k < V - 1) {
         unsigned long long prev = ~0ull;
         for (int j = 0; j < top_k; ++j) {
@@ -64,13 +64,25 @@ __device__ __forceinline__ int sample_row_draw(float* s, int V, int lane, int to
         }
         kth = prev;
     }
+    return kth;
+}
+
+// LDS entries written by one lane of the wave and read by another: a wavefront fence, no workgroup barrier
+__device__ __forceinline__ void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Passes 4 and 5 under the bound kth: the weights w = expf((x - m_C) / temperature) of the candidates over the row in LDS, the
+// ordered float64 prefix sum and the pick for the uniform u.  *Z: the total.
+__device__ __forceinline__ int sample_row_draw_under(float* s, int V, int lane, unsigned long long kth, float temperature, float mc, float u,
+                                                     double* Zout) {
     for (int v = lane; v < V; v += 64) {
         const float xv = s[v];
         s[v] = (v >= 1 && alt_key(xv, v) >= kth) ? expf((xv - mc) / temperature) : 0.f;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
     const int chunk = (V + 63) >> 6;
     const int lo = lane * chunk, hi = min(V, lo + chunk);
     double c = 0.0;
@@ -99,6 +111,67 @@ __device__ __forceinline__ int sample_row_draw(float* s, int V, int lane, int to
         return __shfl(mine, holder, 64);
     }
     return wave_butterfly(last, [](int p, int q) { return max(p, q); });
+}
+
+// Passes 3 to 5 of the pick without a nucleus and with top_k <= 64 (sample_kernel, sched_mix_kernel)
+__device__ __forceinline__ int sample_row_draw(float* s, int V, int lane, int top_k, float temperature, float mc, float u, double* Zout) {
+    return sample_row_draw_under(s, V, lane, sample_row_bound(s, V, lane, top_k), temperature, mc, u, Zout);
+}
+
+// Pass 3 under a cut (top_k, top_p) (sample_cut_kernel, sched_mix_cut_kernel): the bound from
+// the row's keys SORTED by the wave in its own P entries of LDS, P = the power of two >= V (sample_cut_sort_size).
+//   a. keys[v] = alt_key of the candidates 1 .. V-1, 0 at index 0 and at the padding V .. P-1 (below every key of a valid row); a
+//      bitonic network, descending: log2(P) (log2(P) + 1) / 2 stages, every lane the pairs p = lane, lane + 64, ... of the P / 2 of
+//      a stage, a handover between stages.  Place j of the sorted keys is rank j; top_k > 0 keeps n = min(top_k, V - 1) places.
+//   b. top_p < 1: lane l owns the places [l * ceil(V / 64), (l + 1) * ceil(V / 64)) below n, their weights summed in ascending
+//      order in float64, the lanes' offsets by one sequential pass over the lanes -- pass 5's scan on places instead of indices;
+//      the nucleus ends at the first place j with P_j >= (double)top_p * Z_s, which exists (P_{n-1} = Z_s, the same additions)
+//      and has a positive weight (a P_j that first reaches a positive target has just grown).
+// Returns the key of the last place kept, 0 where all V - 1 candidates are.  LDS banking: the 8-byte keys of a stage with
+// distance >= 32 are read by consecutive lanes at consecutive entries (conflict-free for ds_read_b64: a half-wave covers one 256-byte
+// bank row); below that a half-wave's 32 lower (or upper) entries spread over 64 entries = two bank rows, a 2-way conflict.  The
+// rank-order scan of (b) strides the lanes by ceil(V / 64) entries like pass 5: the same known conflict.
+__device__ __forceinline__ unsigned long long sample_row_cut_bound(const float* s, unsigned long long* keys, int V, int P, int lane, int top_k,
+                                                                   float top_p, float temperature, float mc) {
+    for (int v = lane; v < P; v += 64) keys[v] = (v >= 1 && v < V) ? alt_key(s[v], v) : 0ull;
+    wave_lds_handover();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = lane; p < (P >> 1); p += 64) {
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), o = i | j;       // (i < o < P: p < P / 2, j <= P / 2)
+                const unsigned long long ki = keys[i], ko = keys[o];
+                if ((i & k) == 0 ? ki < ko : ki > ko) { keys[i] = ko; keys[o] = ki; }
+            }
+            wave_lds_handover();
+        }
+    const int nc = V - 1;
+    int n = top_k > 0 && top_k < nc ? top_k : nc;
+    if (top_p < 1.f) {
+        const int chunk = (V + 63) >> 6;
+        const int lo = min(n, lane * chunk), hi = min(n, lo + chunk);
+        double c = 0.0;
+        for (int j = lo; j < hi; ++j) c += (double)expf((s[0xffffffffu - (unsigned)keys[j]] - mc) / temperature);
+        double off = 0.0, Z = 0.0;
+#pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            const double cj = __shfl(c, j, 64);
+            if (j < lane) off += cj;
+            Z += cj;
+        }
+        const double target = (double)top_p * Z;
+        const unsigned long long holders = __ballot(off + c >= target);
+        const int holder = holders ? __ffsll((long long)holders) - 1 : 63;
+        int mine = n - 1;
+        if (holders && lane == holder) {
+            double run = 0.0;
+            for (int j = lo; j < hi; ++j) {
+                run += (double)expf((s[0xffffffffu - (unsigned)keys[j]] - mc) / temperature);
+                if (off + run >= target) { mine = j; break; }
+            }
+        }
+        n = __shfl(mine, holder, 64) + 1;
+    }
+    return n < nc ? keys[n - 1] : 0ull;
 }
 
 }  // namespace casv

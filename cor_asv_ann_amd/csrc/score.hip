@@ -233,10 +233,11 @@ extern "C" int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V,
     return CASV_OK;
 }
 
-// Test support: sample_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out.
-extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step, const int64_t* stream,
-                                      const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
-                                      float* out_logp, float* out_logq, float* out_feedback) {
+// Test support: sample_kernel (cut == nullptr) or sample_cut_kernel alone on the caller's logits (R,V), laid out as
+// casv_debug_score_rows lays them out.
+static int debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, const casv_sample_cut* cut, int32_t step,
+                             const int64_t* stream, const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
+                             float* out_logp, float* out_logq, float* out_feedback) {
     if (!logits || !out_feedback) return fail(CASV_ERR_ARG, "null argument");
     if (!m || !p || !out_idx || !out_logp || !out_logq) return fail(CASV_ERR_ARG, "null argument");
     if (!(p->temperature > 0.f) || !(p->temperature < INFINITY)) return fail(CASV_ERR_ARG, "temperature=%g must be finite and positive", (double)p->temperature);
@@ -244,6 +245,7 @@ extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const
     if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
     if (step < 0 || step >= 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "step=%d out of range 0..%d", step, 2 * CASV_MAX_T - 1);
     HIPCHK(hipSetDevice(m->device));
+    if (cut && !sample_cut_ready()) return fail(CASV_ERR_HIP, "the runtime refused sample_cut_kernel's %d bytes of dynamic LDS", SAMPLE_CUT_LDS);
     const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
     std::vector<float> x((size_t)R * Vp, pad_value);
     for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
@@ -264,7 +266,10 @@ extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const
     a.S = 1; a.out_col = 0;
     hipEvent_t ev{};
     m->prof_begin(PC_SAMPLE, 4.0 * R * V, 4.0 * R * (V + Vp), ev);
-    launch_sample(a, m->stream);
+    if (cut) {
+        a.top_k = cut->top_k; a.top_p = cut->top_p;
+        m->stat_sample_cut_rows = launch_sample_cut(a, m->sample_cut_rows_opt, m->stream);
+    } else launch_sample(a, m->stream);
     m->prof_end(PC_SAMPLE, ev);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_idx, a.out_idx, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
@@ -274,4 +279,18 @@ extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->prof.on) m->prof.collect();
     return CASV_OK;
+}
+
+extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step, const int64_t* stream,
+                                      const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
+                                      float* out_logp, float* out_logq, float* out_feedback) {
+    return debug_sample_rows(m, R, V, p, nullptr, step, stream, sample, logits, u, pad_value, out_idx, out_logp, out_logq, out_feedback);
+}
+
+extern "C" int casv_debug_sample_cut_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, const casv_sample_cut* cut,
+                                          int32_t step, const int64_t* stream, const int32_t* sample, const float* logits, const float* u,
+                                          float pad_value, int32_t* out_idx, float* out_logp, float* out_logq, float* out_feedback) {
+    if (int rc = check_sample_cut(cut)) return rc;
+    if (p && p->top_k != 0) return fail(CASV_ERR_ARG, "top_k=%d beside a cut: the cut carries it", p->top_k);
+    return debug_sample_rows(m, R, V, p, cut, step, stream, sample, logits, u, pad_value, out_idx, out_logp, out_logq, out_feedback);
 }

@@ -35,8 +35,10 @@ struct SchedMixArgs {
     const int* row_b; const int* row_u;
     long long R; int B, U, V, Vp;
     unsigned long long seed, step_id; float ratio, temperature; int pick;
+    int top_k = 0; float top_p = 1.f;   // the cut of the sampled pick (casv_train_step_sampled_cut): other than (0, 1) with pick 1 takes sched_mix_cut_kernel
 };
 void launch_sched_mix(const SchedMixArgs& a, hipStream_t stream);
+bool sched_mix_cut_ready();     // false: the runtime refused sched_mix_cut_kernel's dynamic LDS; asked before a step with a cut enqueues anything
 // The same head on soft targets (casv_train_step_soft): soft_idx / soft_q [B][U][K], 1 <= K <= 64, slot k of a position = (index,
 // mass), index -1 = empty; per row loss += w * inv_count * sum_k q_k * -log(clip(p[i_k])), dlogit[v] = (p_v * S - q_k ok_k of the
 // slot with i_k == v) * w * inv_count with ok_k = 1e-7 < p[i_k] < 1 - 1e-7 and S = sum_k q_k ok_k.  The indices of a position are

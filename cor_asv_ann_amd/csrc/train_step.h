@@ -15,6 +15,7 @@ struct Step {
     const float* mask_enc; const float* mask_dec; const float* mask_cell;
     int K; const int32_t* soft_idx; const float* soft_q;      // casv_train_step_soft: K > 0, (B,U,K) slots in place of dec_out (nullptr)
     const casv_sched_params* sched; int32_t* mix_out;         // casv_train_step_sampled with ratio > 0: the passes' parameters, (passes,B,U) out
+    const casv_sample_cut* cut;     // casv_train_step_sampled_cut: the cut of the sampled pick (nullptr: none)
     int W, V, Vp, C, D;
     long long TB, UB;
     // "deterministic": every sum of the step in a fixed order -- the per-step launch forms only (no persistent

@@ -320,6 +320,15 @@ class HipEngine(object):
         return out
 
     def decode_sample(self, samples, temperature=1.0, top_k=0, seed=0, streams=None, steps=None, want_align=False):
+        return self._decode_sample(None, samples, temperature, top_k, seed, streams, steps, want_align)
+
+    def decode_sample_cut(self, samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, steps=None, want_align=False):
+        """casv_decode_sample_cut: decode_sample under the cut (top_k in 0 .. 4095, top_p in (0, 1]; DESIGN.md section 4.8, items 11
+        to 13): every draw comes from the first top_k candidates in rank order, and of those from the nucleus whose float64 mass
+        first reaches top_p.  Returns what decode_sample returns."""
+        return self._decode_sample(nv.SampleCut(int(top_k), float(top_p)), samples, temperature, 0, seed, streams, steps, want_align)
+
+    def _decode_sample(self, cut, samples, temperature, top_k, seed, streams, steps, want_align):
         """casv_decode_sample: `samples` lines drawn from the decoder for every encoded line.  Returns
         (idx, logp, logq (B, samples, S), length (B, samples), align): the drawn indices, their log-probabilities under the model and
         under the proposal, the steps up to and including the first end-of-line, and (B, samples, S, T) alignment rows, their
@@ -338,8 +347,12 @@ class HipEngine(object):
         length = np.empty((rows,), np.int32)
         sparse = want_align == 'sparse'
         align = np.empty((rows, S, self.T), np.float32) if want_align and not sparse else None
-        rc = self.lib.casv_decode_sample(self.handle, byref(p), S, nv.ptr(streams), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq),
-                                         nv.ptr(length), nv.ptr(align))
+        if cut is None:
+            rc = self.lib.casv_decode_sample(self.handle, byref(p), S, nv.ptr(streams), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq),
+                                             nv.ptr(length), nv.ptr(align))
+        else:
+            rc = self.lib.casv_decode_sample_cut(self.handle, byref(p), byref(cut), S, nv.ptr(streams), nv.ptr(idx), nv.ptr(logp),
+                                                 nv.ptr(logq), nv.ptr(length), nv.ptr(align))
         if rc not in (0, nv.CASV_ERR_NAN):
             nv.check(rc)
         if sparse:
@@ -355,6 +368,16 @@ class HipEngine(object):
         return out
 
     def debug_sample_rows(self, logits, temperature=1.0, top_k=0, seed=0, step=0, streams=None, samples=None, u=None, pad_value=0.0):
+        return self._debug_sample_rows(None, logits, temperature, top_k, seed, step, streams, samples, u, pad_value)
+
+    def debug_sample_cut_rows(self, logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, streams=None, samples=None, u=None,
+                              pad_value=0.0):
+        """Test support (casv_debug_sample_cut_rows): debug_sample_rows under the cut (top_k, top_p), by sample_cut_kernel;
+        stat('sample_cut_rows') then tells the rows per workgroup of the launch."""
+        return self._debug_sample_rows(nv.SampleCut(int(top_k), float(top_p)), logits, temperature, 0, seed, step, streams, samples, u,
+                                       pad_value)
+
+    def _debug_sample_rows(self, cut, logits, temperature, top_k, seed, step, streams, samples, u, pad_value):
         """Test support (casv_debug_sample_rows): the sampling kernel alone on logits (R,V) as step `step` of rows with stream ids
         streams (R; default: the row's number) and sample numbers samples (R; default 0); u (R): these uniforms instead of the
         generator's; the padding columns of the device rows hold pad_value.  Returns (idx, logp, logq (R), feedback (R,Vp))."""
@@ -370,8 +393,13 @@ class HipEngine(object):
         logp = np.empty((R,), np.float32)
         logq = np.empty((R,), np.float32)
         feedback = np.empty((R, (V + 31) & ~31), np.float32)
-        nv.check(self.lib.casv_debug_sample_rows(self.handle, R, V, byref(p), int(step), nv.ptr(streams), nv.ptr(samples), nv.ptr(logits),
-                                                 nv.ptr(u), float(pad_value), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq), nv.ptr(feedback)))
+        if cut is None:
+            nv.check(self.lib.casv_debug_sample_rows(self.handle, R, V, byref(p), int(step), nv.ptr(streams), nv.ptr(samples), nv.ptr(logits),
+                                                     nv.ptr(u), float(pad_value), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq), nv.ptr(feedback)))
+        else:
+            nv.check(self.lib.casv_debug_sample_cut_rows(self.handle, R, V, byref(p), byref(cut), int(step), nv.ptr(streams), nv.ptr(samples),
+                                                         nv.ptr(logits), nv.ptr(u), float(pad_value), nv.ptr(idx), nv.ptr(logp), nv.ptr(logq),
+                                                         nv.ptr(feedback)))
         return idx, logp, logq, feedback
 
     # -- training ------------------------------------------------------------------------------
@@ -445,12 +473,13 @@ class HipEngine(object):
                               picks.get(pick, pick), int(passes))
 
     def train_step_sampled(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1, ratio=0.0, seed=0, step_id=0,
-                           pick='greedy', passes=1, temperature=1.0):
+                           pick='greedy', passes=1, temperature=1.0, top_k=0, top_p=1.0):
         """train_step with scheduled sampling in its parallel form (casv_train_step_sampled): after the teacher-forced forward
         pass, `passes` times a pick ('greedy' or 'sample' at `temperature`) at every decoder position from the logits of the
         position before it, mixed into the decoder input where the position's coin -- a function of (seed, step_id, b, u) -- falls
         below `ratio`, and the decoder again; loss, backward pass and update on the last pass.  Modes 1 and 2 only.  Returns
-        (loss, grad_norm, mixes) with mixes int32 (passes,B,U): slice p - 1 is the decoder input after pass p."""
+        (loss, grad_norm, mixes) with mixes int32 (passes,B,U): slice p - 1 is the decoder input after pass p.  top_k / top_p:
+        the 'sample' pick draws under this cut (casv_train_step_sampled_cut, called only when one of them is set)."""
         enc_idx = nv.carray(enc_idx, np.int32)
         if enc_idx.ndim == 2:
             enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
@@ -464,9 +493,15 @@ class HipEngine(object):
         p = self._sched_params(seed, step_id, ratio, pick, passes, temperature)
         mixes = np.empty((max(int(passes), 0), B, U), np.int32)
         loss, norm = c_double(), c_double()
-        nv.check(self.lib.casv_train_step_sampled(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                                  nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
-                                                  byref(p), nv.ptr(mixes), byref(loss), byref(norm)))
+        if top_k == 0 and top_p == 1.0:
+            nv.check(self.lib.casv_train_step_sampled(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
+                                                      nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
+                                                      byref(p), nv.ptr(mixes), byref(loss), byref(norm)))
+        else:
+            cut = nv.SampleCut(int(top_k), float(top_p))
+            nv.check(self.lib.casv_train_step_sampled_cut(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val),
+                                                          nv.ptr(dec_in), nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec),
+                                                          nv.ptr(m_cell), byref(p), byref(cut), nv.ptr(mixes), byref(loss), byref(norm)))
         return loss.value, norm.value, mixes
 
     def debug_sched_rows(self, logits, gold, b, u, ratio=1.0, seed=0, step_id=0, pick='greedy', temperature=1.0, pad_value=0.0):
@@ -480,6 +515,20 @@ class HipEngine(object):
         out = np.empty((R,), np.int32)
         nv.check(self.lib.casv_debug_sched_rows(self.handle, R, V, byref(p), nv.ptr(b), nv.ptr(u), nv.ptr(logits), nv.ptr(gold),
                                                 float(pad_value), nv.ptr(out)))
+        return out
+
+    def debug_sched_cut_rows(self, logits, gold, b, u, ratio=1.0, seed=0, step_id=0, pick='sample', temperature=1.0, top_k=0, top_p=1.0,
+                             pad_value=0.0):
+        """Test support (casv_debug_sched_cut_rows): debug_sched_rows with the sampled pick under the cut (top_k, top_p)."""
+        logits = nv.carray(logits, np.float32)
+        R, V = logits.shape
+        gold, b, u = (nv.carray(a, np.int32) for a in (gold, b, u))
+        assert gold.shape == b.shape == u.shape == (R,)
+        p = self._sched_params(seed, step_id, ratio, pick, 1, temperature)
+        cut = nv.SampleCut(int(top_k), float(top_p))
+        out = np.empty((R,), np.int32)
+        nv.check(self.lib.casv_debug_sched_cut_rows(self.handle, R, V, byref(p), byref(cut), nv.ptr(b), nv.ptr(u), nv.ptr(logits),
+                                                    nv.ptr(gold), float(pad_value), nv.ptr(out)))
         return out
 
     def train_gradients(self):

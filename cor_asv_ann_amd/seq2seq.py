@@ -827,12 +827,13 @@ class Sequence2Sequence(object):
                     aligns[j][k] = self._alignment_rows(align, b * N + n, c, idx.shape[1])
         return logprobs, scores, predictions, ranks, aligns
 
-    def sample_lines(self, lines, conf=None, n=1, temperature=1.0, top_k=0, seed=None, streams=None, alignments=False):
+    def sample_lines(self, lines, conf=None, n=1, temperature=1.0, top_k=0, seed=None, streams=None, alignments=False, top_p=1.0):
         """`n` lines DRAWN from the model for each source line, on one encoder pass per source (`HipEngine.decode_sample`; DESIGN.md
         section 4.8) -- where `correct_lines` gives the most probable line and the beam its near-duplicates.  Every character is drawn
         from the decoder's distribution over the vocabulary without index 0, sharpened or flattened by `temperature` and, with
-        `top_k` > 0 (at most 64), cut to its `top_k` most probable characters; the decoder is then fed the character that was
-        drawn.  Each source line must end in a newline.  Returns (candidates, logprobs, scores, logqs, aligns), each a list per
+        `top_k` > 0 (at most 4095), cut to its `top_k` most probable characters, and with `top_p` < 1 to the nucleus of those: the
+        most probable characters whose mass first reaches `top_p` (`HipEngine.decode_sample_cut`, taken where `top_p` < 1 or
+        `top_k` > 64; ValueError for a `top_p` outside (0, 1]); the decoder is then fed the character that was drawn.  Each source line must end in a newline.  Returns (candidates, logprobs, scores, logqs, aligns), each a list per
         source of `n` entries, in `score_candidates`' nesting (`candidates` can be passed straight back to it):
         candidates -- the sampled lines; each ends in a newline unless it was cut at twice the padded source length;
         logprobs -- per character, log p under the model itself (temperature 1, whole vocabulary), as `score_lines` gives it;
@@ -850,6 +851,13 @@ class Sequence2Sequence(object):
         n = int(n)
         if n < 1:
             raise ValueError('n=%d samples per line: need at least one' % n)
+        try:
+            top_p_ok = 0.0 < float(top_p) <= 1.0
+        except (TypeError, ValueError):
+            top_p_ok = False
+        if not top_p_ok:
+            raise ValueError('top_p=%r: the nucleus mass must lie in (0, 1]' % (top_p,))
+        with_cut = float(top_p) != 1.0 or int(top_k) > 64
         if seed is None:
             seed = int(self._rng.integers(0, 2 ** 63))
         candidates, logprobs = [[] for _ in lines], [[] for _ in lines]
@@ -862,8 +870,12 @@ class Sequence2Sequence(object):
             idx, val, _ = self._sparse_lines([lines[j] for j in chunk], None if conf is None else [conf[j] for j in chunk])
             eng.encode(idx, val)
             ids = np.array([j if streams is None else int(streams[j]) for j in chunk], np.int64)
-            gi, lp, lq, length, align = eng.decode_sample(n, temperature=temperature, top_k=top_k, seed=seed, streams=ids,
-                                                          want_align=want_align)
+            if with_cut:
+                gi, lp, lq, length, align = eng.decode_sample_cut(n, temperature=temperature, top_k=top_k, top_p=float(top_p), seed=seed,
+                                                                  streams=ids, want_align=want_align)
+            else:
+                gi, lp, lq, length, align = eng.decode_sample(n, temperature=temperature, top_k=top_k, seed=seed, streams=ids,
+                                                              want_align=want_align)
             if align is not None:           # (rows b * n + k, as _alignment_rows indexes them)
                 align = tuple(a.reshape((-1,) + a.shape[2:]) for a in align) if isinstance(align, tuple) else align.reshape((-1,) + align.shape[2:])
             for b, j in enumerate(chunk):
@@ -1240,7 +1252,7 @@ class Sequence2Sequence(object):
                 self.logger.info('%s %-7s %.3f±%.3f', what, labels[k].strip() + ':', counts[k].mean, math.sqrt(counts[k].varia))
 
     def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
-              sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0):
+              sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0):
         """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
         from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
         restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint).
@@ -1258,11 +1270,14 @@ class Sequence2Sequence(object):
         `sample_passes` (1..8) times, on one encoder pass.  The coins' seed is drawn once from the model's generator, the step
         number is the session's; both, the schedule's name, the pick, the passes and the temperature go into the state
         checkpoints, and `resume` refuses other values.  Validation stays teacher-forced.  Not together with `teacher`
-        (ValueError)."""
-        from .training import train_files
+        (ValueError).  sample_top_k (0..4095) / sample_top_p (in (0, 1]): the 'sample' pick draws under this cut, as
+        `sample_lines(top_k=, top_p=)` does (`casv_train_step_sampled_cut`); not with sample_pick='greedy' (ValueError); a cut that
+        is set joins the recorded settings, a run without one writes the checkpoints it always wrote."""
+        from .training import train_files, cut_is_set
+        cut = {'sample_top_k': sample_top_k, 'sample_top_p': sample_top_p} if cut_is_set(sample_top_k, sample_top_p) else {}
         return train_files(self, filenames, val_filenames, resume=resume, teacher=teacher, distill_k=distill_k,
                            distill_alpha=distill_alpha, sample_schedule=sample_schedule, sample_pick=sample_pick,
-                           sample_passes=sample_passes, sample_temperature=sample_temperature)
+                           sample_passes=sample_passes, sample_temperature=sample_temperature, **cut)
 
 
 class _EncoderModel(object):

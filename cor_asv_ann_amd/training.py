@@ -251,7 +251,28 @@ def schedule_ratio(sample_schedule, epoch, epochs):
     return ratio
 
 
-def check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher):
+def cut_is_set(top_k, top_p):
+    """Whether (top_k, top_p) truncates anything: (0, 1.0) is no cut."""
+    return int(top_k) != 0 or float(top_p) != 1.0
+
+
+def check_cut(top_k, top_p, what=''):
+    """A cut's rules (casv_sample_cut): top_k an int in [0, 4095], top_p in (0, 1].  ValueError with the first fault."""
+    try:
+        ok = int(top_k) == top_k and 0 <= int(top_k) <= 4095
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%stop_k must be an int in [0, 4095] (0: none), got %r' % (what, top_k))
+    try:
+        ok = 0.0 < float(top_p) <= 1.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%stop_p must lie in (0, 1] (1: none), got %r' % (what, top_p))
+
+
+def check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher, sample_top_k=0, sample_top_p=1.0):
     """The scheduled-sampling keywords of train(), checked on the host before anything runs: ValueError with the first fault."""
     if teacher is not None:
         raise ValueError('sample_schedule together with teacher: soft targets and scheduled sampling do not combine')
@@ -271,6 +292,9 @@ def check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperatu
         raise ValueError('sample_passes must be in [1, 8], got %r' % (sample_passes,))
     if not (math.isfinite(float(sample_temperature)) and float(sample_temperature) > 0.0):
         raise ValueError('sample_temperature must be finite and positive, got %r' % (sample_temperature,))
+    check_cut(sample_top_k, sample_top_p, 'sample_')
+    if sample_pick == 'greedy' and cut_is_set(sample_top_k, sample_top_p):
+        raise ValueError("sample_top_k / sample_top_p truncate the 'sample' pick: they do not combine with sample_pick='greedy'")
 
 
 def check_sampling_resume(state, filename, settings):
@@ -283,18 +307,23 @@ def check_sampling_resume(state, filename, settings):
         raise ValueError('cannot resume from "%s": it was trained without a sample schedule' % filename)
     if settings is None:
         raise ValueError('cannot resume from "%s": it was trained with the sample schedule %r' % (filename, theirs['schedule']))
-    for key in ('schedule', 'pick', 'passes', 'temperature'):
-        if theirs[key] != settings[key]:
-            raise ValueError('cannot resume from "%s": sample %s differs (file %r, now %r)' % (filename, key, theirs[key], settings[key]))
+    for key in ('schedule', 'pick', 'passes', 'temperature', 'top_k', 'top_p'):       # (the cut is recorded only where one is set)
+        if theirs.get(key) != settings.get(key):
+            raise ValueError('cannot resume from "%s": sample %s differs (file %r, now %r)' % (filename, key, theirs.get(key), settings.get(key)))
 
 
 def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
-                sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0):
+                sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0):
     sampling = None                          # scheduled sampling: what the checkpoints record (the seed joins below)
     if sample_schedule is not None:
-        check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher)
+        check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher, sample_top_k, sample_top_p)
         sampling = {'schedule': schedule_name(sample_schedule), 'pick': sample_pick, 'passes': int(sample_passes),
                     'temperature': float(sample_temperature)}
+        if cut_is_set(sample_top_k, sample_top_p):       # (only where set: a run without a cut writes the checkpoints it always wrote)
+            sampling.update(top_k=int(sample_top_k), top_p=float(sample_top_p))
+    elif cut_is_set(sample_top_k, sample_top_p):
+        raise ValueError('sample_top_k / sample_top_p without sample_schedule: there is no pick to truncate')
+    cut_keywords = {'top_k': sampling['top_k'], 'top_p': sampling['top_p']} if sampling is not None and 'top_k' in sampling else {}
     num_lines = s2s.map_files(filenames)
     s2s.logger.info('Training on "%d" files with %d lines', len(filenames), num_lines)
     if val_filenames:
@@ -364,7 +393,7 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
                 elif sampling is not None:
                     loss, _, _ = engine.train_step_sampled(idx, val, dec_in, dec_out, w, masks, mode=1, ratio=ratio, seed=sampling['seed'],
                                                            step_id=step_id, pick=sample_pick, passes=sample_passes,
-                                                           temperature=sample_temperature)
+                                                           temperature=sample_temperature, **cut_keywords)
                     step_id += 1
                 else:
                     loss, _ = engine.train_step(idx, val, dec_in, dec_out, w, masks, mode=1)

@@ -186,6 +186,36 @@ int casv_decode_sample(casv_model* m, const casv_sample_params* p, int32_t S, co
 int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step,
                            const int64_t* stream, const int32_t* sample, const float* logits, const float* u,
                            float pad_value, int32_t* out_idx, float* out_logp, float* out_logq, float* out_feedback);
+/* Sampling under a cut: the draw of casv_decode_sample from a truncated candidate set.
+ * top_k in 0 .. 4095 (0 = none), top_p in (0, 1] (exactly 1 = none).  For a valid row, with the candidates 1 .. V-1, m_C and the
+ * float32 weights w_v = expf((x_v - m_C) / temperature) of casv_decode_sample:
+ *   a. the candidates in the order of casv_score_get_alternatives (x descending, -0 = +0, the lower index first among equals);
+ *      place 0 is the maximum; top_k > 0 keeps the places j < min(top_k, V-1);
+ *   b. top_p < 1: over the n places that survive (a), float64 prefix sums in place order -- lane l of 64 owns the places
+ *      [l * ceil(V/64), (l+1) * ceil(V/64)) and adds their weights in ascending order, the lanes' offsets come from one sequential
+ *      pass over the lanes in ascending order, P_j = off_l + run_j, Z_s = P_{n-1}; the nucleus is the places 0 .. j*, j* the first j
+ *      with P_j >= (double)top_p * Z_s.  It is never empty, holds no candidate of weight 0, and a tie group at its border is entered
+ *      in index order, not taken whole;
+ *   c. the kept candidates are drawn from as casv_decode_sample draws: the prefix sums in ascending INDEX order inverted at u * Z,
+ *      logq = (x_v - m_C) / temperature - log Z with Z the kept set's total.
+ * (top_k <= 64, 1.0) gives every output bit of casv_decode_sample at that top_k; a row whose nucleus has n members gives the bits
+ * of top_k = n; the smallest positive top_p gives the bits of top_k = 1.  A row's results are a function of (weights, line, seed,
+ * stream, n, temperature, cut) only.  In the _cut entries p->top_k must be 0: the cut carries it.  Refused with CASV_ERR_ARG before
+ * anything is enqueued or cleared: NULL cut, top_k outside 0 .. 4095, top_p NaN, <= 0 or > 1, p->top_k != 0, and whatever the
+ * entry without a cut refuses.  Everything else -- CASV_ERR_NAN, the arithmetic, the eager launches, the give-up path,
+ * casv_get_alignments_sparse afterwards, the kernel class "sample" -- is casv_decode_sample's.  The _cut entries always run
+ * sample_cut_kernel (a wave-wide sort of the row's keys in LDS), the entries without a cut never do. */
+typedef struct {
+    int32_t top_k;
+    float top_p;
+} casv_sample_cut;
+int casv_decode_sample_cut(casv_model* m, const casv_sample_params* p, const casv_sample_cut* cut, int32_t S, const int64_t* stream,
+                           int32_t* out_idx, float* out_logp, float* out_logq, int32_t* out_len, float* out_align);
+/* Test support: casv_debug_sample_rows under a cut.  casv_get_stat "sample_cut_rows" then reports the rows per workgroup of the
+ * launch (they follow from V; the option "sample_cut_rows" bounds them). */
+int casv_debug_sample_cut_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, const casv_sample_cut* cut,
+                               int32_t step, const int64_t* stream, const int32_t* sample, const float* logits, const float* u,
+                               float pad_value, int32_t* out_idx, float* out_logp, float* out_logq, float* out_feedback);
 
 /* The soft alignments of the LAST casv_decode_greedy / casv_decode_beam call in window form, for the post-decode
  * re-alignment of wrapper/transcode.py:126,279-349 (which skips entries <= 1/V anyway, transcode.py:316): the attention
@@ -291,6 +321,20 @@ int casv_train_step_sampled(casv_model* m, int32_t mode, int32_t B, int32_t T, i
  * the gold input gold[r]; out[r] = its mix.  p->passes is ignored; the other fields are checked as casv_train_step_sampled's. */
 int casv_debug_sched_rows(casv_model* m, int32_t R, int32_t V, const casv_sched_params* p, const int32_t* b, const int32_t* u,
                           const float* logits, const int32_t* gold, float pad_value, int32_t* out);
+/* casv_train_step_sampled with pick 1 drawing under a cut (casv_sample_cut above: the draw of casv_decode_sample_cut at p's
+ * temperature, with the uniform (o1 >> 8) * 2^-24).  The cut (0, 1.0) is casv_train_step_sampled, bit for bit.  Refused with
+ * CASV_ERR_ARG before anything is enqueued or cleared, the session's state untouched: NULL cut, top_k outside 0 .. 4095, top_p NaN,
+ * <= 0 or > 1, a cut other than (0, 1.0) together with pick 0, and whatever casv_train_step_sampled refuses.  A position's pick
+ * stays a function of (seed, step_id, b, u, the row, the cut). */
+int casv_train_step_sampled_cut(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                                const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                                const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
+                                const casv_sched_params* p, const casv_sample_cut* cut, int32_t* out_dec_in, double* loss,
+                                double* grad_norm);
+/* Test support: casv_debug_sched_rows under a cut, checked as casv_train_step_sampled_cut checks it. */
+int casv_debug_sched_cut_rows(casv_model* m, int32_t R, int32_t V, const casv_sched_params* p, const casv_sample_cut* cut,
+                              const int32_t* b, const int32_t* u, const float* logits, const int32_t* gold, float pad_value,
+                              int32_t* out);
 /* Gradient of the last step for one tensor, in Keras layout (parity tests). */
 int casv_train_get_gradient(casv_model* m, const char* name, float* out, int64_t capacity);
 /* Adam's optimizer state of one trained tensor in Keras layout, like casv_train_get_gradient: which = 0 the first moment m,
@@ -579,7 +623,9 @@ int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, const casv_d
  * columns only -- the same bits; 2 = also the input terms of layers 2..D ahead: per layer ONE contraction over all B x T positions, then
  * the cells one after the other on top of its rows instead of the anti-diagonal wavefront (same bits; measured slower on c3, so not
  * the default: DESIGN.md section 4.5); 0 = never.  "beam_skip_last" (per handle; default 1; CASV_BEAM_SKIP_LAST=0 likewise): 0 = debug
- * switch, the last iteration of casv_decode_beam launches its decoder step although nothing reads its results (same results). */
+ * switch, the last iteration of casv_decode_beam launches its decoder step although nothing reads its results (same results).
+ * "sample_cut_rows" (per handle; default 0 = as many as fit) = 1 .. 4: at most this many rows per workgroup in sample_cut_kernel's
+ * launches -- a test switch, the same results bit for bit. */
 int casv_set_option(casv_model* m, const char* key, int64_t value);
 /* Statistics of the last call (tests): "beam_max_new_keys" = most child hypotheses one line created in one search
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
@@ -598,7 +644,7 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
  * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
- * give-up on this handle so far. */
+ * give-up on this handle so far; "sample_cut_rows" = rows per workgroup of the last sample_cut_kernel launch (0: none so far). */
 int casv_get_stat(casv_model* m, const char* key, int64_t* value);
 int casv_synchronize(casv_model* m);
 
