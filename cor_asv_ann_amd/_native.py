@@ -114,6 +114,7 @@ SIGNATURES = {
     'casv_score_get_alignments_sparse': (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'casv_score_get_alternatives': (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'casv_score_release': (c_int, [c_void_p]),
+    'casv_consensus': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6),
     'casv_train_step_soft': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32]
                              + [c_void_p] * 6 + [POINTER(c_double), POINTER(c_double)]),
     'casv_train_step_sampled': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
@@ -170,8 +171,9 @@ def load():
                            '(there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in SIGNATURES.items():
-        if os.environ.get('CASV_LIB_PATH') and (name.startswith('casv_debug_') or name.endswith('_cut')) and not hasattr(lib, name):
-            continue                     # (A/B against an older build of the library: it may lack a test-support entry, or the cut entries)
+        if (os.environ.get('CASV_LIB_PATH') and (name.startswith('casv_debug_') or name.endswith('_cut') or name == 'casv_consensus')
+                and not hasattr(lib, name)):
+            continue                     # (A/B against an older build of the library: it may lack a test-support entry, the cut entries or the vote)
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

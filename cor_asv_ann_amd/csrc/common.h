@@ -254,6 +254,27 @@ int launch_sample_cut(const SampleArgs& a, int rows_max, hipStream_t stream);
 // states under every sample row of a line
 void launch_spread_rows(const float* src, float* dst, int lines, int rows_per_line, int width, hipStream_t stream);
 
+// The vote over N candidates per source (consensus_kernels.hip).  sym [B][N][L] arbitrary int32 symbols
+// compared for equality only, len [B][N] in -1 .. L (-1: a padding candidate), weight [B][N] or nullptr (all 1.0);
+// dist [B][N][N], risk [B][N], pick [B].
+struct ConsensusArgs {
+    const int* sym; const int* len; const double* weight;
+    int* dist; double* risk; int* pick;
+    int B, N, L, mode;
+};
+constexpr int CONSENSUS_MAX_N = 256, CONSENSUS_MAX_L = 8192;
+// a wave's LDS at the longest pair: one string's symbols, and per column the other's symbol and one DP row's entry, with
+// CONSENSUS_GUARD columns in front and behind for the lanes that stand outside the matrix (consensus_pair)
+constexpr int CONSENSUS_GUARD = 64;
+inline int consensus_lds_bytes(int max_len) { return (3 * max_len + 4 * CONSENSUS_GUARD) * 4; }
+// sources a launch takes side by side (the blocks of a pair loop over the rest): at most 2^20 blocks in all
+inline int consensus_grid_z(int B, int N) { return std::max(1, std::min(std::min(B, 65535), (1 << 20) / (N * N))); }
+// false: the runtime refused consensus_dist_kernel's dynamic LDS at the longest strings (nothing may be launched then)
+bool consensus_ready();
+// max_len: the longest live candidate of the call (the LDS a wave gets)
+void launch_consensus_dist(const ConsensusArgs& a, int max_len, hipStream_t stream);
+void launch_consensus_risk(const ConsensusArgs& a, hipStream_t stream);
+
 void launch_embed_sparse(const float* E, const int* idx, const float* val, float* x0,
                          int rows, int A, int V, int W, hipStream_t stream);
 // one-alternative input idx [B][T] -> out [T][B]: the character of (line, position), V where there is none (encoder.hip: rows of

@@ -70,11 +70,12 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-enum ProfClass { PC_LSTM = 0, PC_GEMM, PC_ATTN, PC_SOFTMAX, PC_BEAM, PC_EMBED, PC_LSTM_SMALL, PC_PERSIST, PC_SAMPLE, PC_COUNT };
+enum ProfClass { PC_LSTM = 0, PC_GEMM, PC_ATTN, PC_SOFTMAX, PC_BEAM, PC_EMBED, PC_LSTM_SMALL, PC_PERSIST, PC_SAMPLE, PC_CONSENSUS, PC_COUNT };
 // "lstm_gemm" = the 128x128-tile fused LSTM GEMM (the dominant kernel); "lstm_gemm_small" = its 32x128-tile variant
 // "persist" = the persistent small-batch decoder (all steps of a greedy decode in one launch)
 // "sample" = the sampling pick of casv_decode_sample / casv_debug_sample_rows (sample_kernels.hip)
-inline const char* kProfNames[PC_COUNT] = {"lstm_gemm", "gemm", "attention", "softmax", "beam", "embed", "lstm_gemm_small", "persist", "sample"};
+// "consensus" = the two kernels of casv_consensus, one record per call (consensus_kernels.hip)
+inline const char* kProfNames[PC_COUNT] = {"lstm_gemm", "gemm", "attention", "softmax", "beam", "embed", "lstm_gemm_small", "persist", "sample", "consensus"};
 
 struct Prof {
     bool on = false;
@@ -159,6 +160,7 @@ struct casv_model {
     DevBuf st_a, st_p, ctx, wq, logits, prev, pin, apos, amax1, d_step, d_line, d_nan;
     DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (decode.hip, launch_step)
     DevBuf o_idx, o_prob, o_align, st_win, sp_lo, sp_w;
+    DevBuf cs_sym, cs_len, cs_weight, cs_dist, cs_risk, cs_pick;   // casv_consensus: its own scratch, nothing of a session (consensus.hip)
     DevBuf s_logq, s_stream;                              // casv_decode_sample: the proposal's log-probabilities [R][S], the lines' stream ids [B]
     // lm_predict: per-step scratch of the LM output -- h of the LM cell [R][W] (its c [R][W] is written and
     // never read), LM logits [R][Vp], casv_decoder_step_lm's probabilities [R][Vp]; wide beams: the LM probability of every child

@@ -661,6 +661,27 @@ class HipEngine(object):
         """Drop the forward-only state score_targets keeps outside a training session (allowed when there is none)."""
         nv.check(self.lib.casv_score_release(self.handle))
 
+    def consensus(self, sym, length, weights=None, mode=0, want_dist=False):
+        """The vote over N candidates per source (casv_consensus): sym (B,N,L) int32 symbols compared for equality only, length
+        (B,N) in -1 .. L (-1: a padding candidate), weights (B,N) float64, not negative and finite, or None (all 1.0); mode 0 sums
+        weight * distance, mode 1 weight * distance / max(the two lengths, 1).  Returns (risk float64 (B,N), pick int32 (B), dist
+        int32 (B,N,N) or None): the unit-cost Levenshtein distances, each candidate's risk summed over the live candidates in
+        ascending order (+inf for padding), and the live candidate of smallest risk, the lowest index among equals (-1: none).
+        Needs no weights and no encoded batch, and changes nothing another call reads."""
+        sym = nv.carray(sym, np.int32)
+        length = nv.carray(length, np.int32)
+        assert sym.ndim == 3 and length.shape == sym.shape[:2]
+        B, N, L = sym.shape
+        if weights is not None:
+            weights = nv.carray(weights, np.float64)
+            assert weights.shape == (B, N)
+        risk = np.empty((B, N), np.float64)
+        pick = np.empty((B,), np.int32)
+        dist = np.empty((B, N, N), np.int32) if want_dist else None
+        nv.check(self.lib.casv_consensus(self.handle, B, N, L, int(mode), nv.ptr(sym), nv.ptr(length), nv.ptr(weights), nv.ptr(dist),
+                                         nv.ptr(risk), nv.ptr(pick)))
+        return risk, pick, dist
+
     def debug_score_rows(self, logits, target, pad_value=0.0):
         """Test support (casv_debug_score_rows): the scoring head alone on logits (R,V) and targets (R); the padding columns of the
         device rows hold pad_value.  Returns (logp, best, rank)."""

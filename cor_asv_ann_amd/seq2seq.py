@@ -888,6 +888,126 @@ class Sequence2Sequence(object):
                     aligns[j].append(self._alignment_rows(align, b * n + k, c, idx.shape[1]))
         return candidates, logprobs, scores, logqs, aligns
 
+    def _consensus_engine(self):
+        """The device handle `consensus_of` votes on: the model's own where there is one or can be one, else a minimal handle
+        without weights (the vote reads none), kept for further calls."""
+        if self.engine is not None:
+            return self.engine
+        if self.status >= 1 and self.voc_size >= 2:
+            return self._require_engine()
+        if getattr(self, '_vote_engine', None) is None:
+            self._vote_engine = HipEngine(1, 32, 2, device=self.device)
+        return self._vote_engine
+
+    def consensus_of(self, candidates, weights=None, normalise=False, distances=False):
+        """The line that a list of candidate lines agrees on: per source the candidate with the smallest expected edit distance to
+        the others -- the minimum-Bayes-risk pick, the medoid under Levenshtein distance (`HipEngine.consensus`; DESIGN.md section
+        4.9).  `candidates[j]` is the list of candidate strings of source j, in `score_candidates`' nesting (what `sample_lines`
+        returns, or the lines of several OCR engines); they are compared as sequences of Unicode code points, so characters the
+        model does not know vote like any other, and an empty string is a candidate of length 0.  `weights[j]` is None or one
+        float per candidate, not negative and finite: how much a candidate's opinion counts (all None: every candidate 1.0).
+        `normalise` divides each distance by the longer of the two lines (at least 1) before it is weighted.  Returns
+        (picks, risks, dists), one entry per source: the index of the chosen candidate (the lowest among equal risks; None for
+        a source without candidates), the list of the candidates' risks -- the sum over the source's candidates k in input order of
+        weight k x distance to k, in float64 -- and, with `distances`, the distance matrix as N lists of N ints, else [].
+        Needs a device but no weights: it works at any `status`.  At most 256 candidates per source and 8192 code points per
+        candidate (ValueError).  The sources are taken in order into chunks as `score_candidates` takes them: a chunk grows while
+        sources x the largest candidate count stays within max(`batch_size`, that count) rows, and shorter lists are filled with
+        padding candidates; a source's result does not depend on its chunk."""
+        if weights is not None and len(weights) != len(candidates):
+            raise ValueError('weights for %d sources beside %d candidate lists' % (len(weights), len(candidates)))
+        points, rows_w = [], []
+        for j, cands in enumerate(candidates):
+            if len(cands) > 256:
+                raise ValueError('source %d has %d candidates: at most 256' % (j, len(cands)))
+            for k, line in enumerate(cands):
+                if not isinstance(line, str):
+                    raise ValueError('candidate %d of source %d is %s, not a string' % (k, j, type(line).__name__))
+                if len(line) > 8192:
+                    raise ValueError('candidate %d of source %d has %d code points: at most 8192' % (k, j, len(line)))
+            # (UTF-32 is the code points themselves; 'surrogatepass': a lone surrogate is a symbol like any other)
+            points.append([np.frombuffer(line.encode('utf-32-le', 'surrogatepass'), '<i4') for line in cands])
+            w = None if weights is None else weights[j]
+            if w is not None:
+                if len(w) != len(cands):
+                    raise ValueError('source %d has %d weights for %d candidates' % (j, len(w), len(cands)))
+                w = [float(x) for x in w]
+                for k, x in enumerate(w):
+                    if not (x >= 0.0 and math.isfinite(x)):
+                        raise ValueError('weight %r of candidate %d of source %d: must be finite and not negative' % (x, k, j))
+            rows_w.append(w)
+        picks, risks = [None] * len(candidates), [[] for _ in candidates]
+        dists = [[] for _ in candidates]
+        live = [j for j in range(len(candidates)) if candidates[j]]
+        if not live:
+            return picks, risks, dists
+        eng = self._consensus_engine()
+        chunks, chunk, most = [], [], 0
+        for j in live:
+            grown = max(most, len(candidates[j]))
+            if chunk and (len(chunk) + 1) * grown > max(self.batch_size, grown):
+                chunks.append((chunk, most))
+                chunk, grown = [], len(candidates[j])
+            chunk.append(j)
+            most = grown
+        chunks.append((chunk, most))
+        for chunk, N in chunks:
+            L = max(len(p) for j in chunk for p in points[j])
+            sym = np.zeros((len(chunk), N, L), np.int32)
+            length = np.full((len(chunk), N), -1, np.int32)          # (-1: a padding candidate)
+            weighted = any(rows_w[j] is not None for j in chunk)
+            w = np.ones((len(chunk), N), np.float64) if weighted else None
+            for b, j in enumerate(chunk):
+                for k, p in enumerate(points[j]):
+                    sym[b, k, :len(p)] = p
+                    length[b, k] = len(p)
+                if rows_w[j] is not None:
+                    w[b, :len(rows_w[j])] = rows_w[j]
+            risk, pick, dist = eng.consensus(sym, length, weights=w, mode=1 if normalise else 0, want_dist=bool(distances))
+            for b, j in enumerate(chunk):
+                n = len(points[j])
+                picks[j] = int(pick[b])
+                risks[j] = risk[b, :n].tolist()
+                if distances:
+                    dists[j] = dist[b, :n, :n].tolist()
+        return picks, risks, dists
+
+    def consensus_lines(self, lines, conf=None, n=16, temperature=1.0, top_k=0, top_p=1.0, seed=None, streams=None,
+                        include_greedy=True, weights='uniform', normalise=False):
+        """Sampling as a decoder: `n` lines drawn per source by `sample_lines` (same arguments, same draws), with `include_greedy`
+        the `correct_lines(fast=True)` result in front of them as candidate 0, and of these the one `consensus_of` picks -- the
+        candidate closest to all the others.  `weights` is 'uniform' (every candidate counts 1) or 'importance': sampled line k
+        counts w_k = e_k / (e_1 + ... + e_n) with e_k = exp(s_k - max s) and s_k the sum over its characters of log p - log q as
+        `sample_lines` returns them, all in float64 on the host and summed in order; the greedy candidate counts the mean of the
+        w_k.  `normalise` as in `consensus_of`.  Returns (lines, risks, candidates, picks), one entry per source: the chosen
+        line, its risk, the list of candidates that voted and the index of the chosen one.  An empty source gives '', 0.0, [],
+        None.  What `sample_lines` says about seeds, streams and chunks holds here."""
+        if weights not in ('uniform', 'importance'):
+            raise ValueError("weights=%r: 'uniform' or 'importance'" % (weights,))
+        sampled, logprobs, _, logqs, _ = self.sample_lines(lines, conf=conf, n=n, temperature=temperature, top_k=top_k, seed=seed,
+                                                           streams=streams, alignments=False, top_p=top_p)
+        greedy = self.correct_lines(lines, conf=conf, fast=True, greedy=True, alignments=False)[0] if include_greedy and lines else None
+        candidates, votes = [], []
+        for j, line in enumerate(lines):
+            if not line:
+                candidates.append([])
+                votes.append(None)
+                continue
+            w = None
+            if weights == 'importance':
+                s = [sum(float(p) - float(q) for p, q in zip(lp, lq)) for lp, lq in zip(logprobs[j], logqs[j])]
+                top = max(s)
+                e = [math.exp(x - top) for x in s]
+                total = sum(e)
+                w = [x / total for x in e]
+                if greedy is not None:
+                    w = [sum(w) / len(w)] + w
+            candidates.append(([greedy[j]] if greedy is not None else []) + list(sampled[j]))
+            votes.append(w)
+        picks, risks, _ = self.consensus_of(candidates, weights=None if weights == 'uniform' else votes, normalise=normalise)
+        chosen = ['' if picks[j] is None else candidates[j][picks[j]] for j in range(len(lines))]
+        return chosen, [0.0 if picks[j] is None else risks[j][picks[j]] for j in range(len(lines))], candidates, picks
+
     def correct_batches(self, batches, fast=True, greedy=True, alignments=True, after_decode=None):
         """`correct_lines` over a stream of batches -- an iterable of `lines` or of `(lines, conf)` -- as a three-stage pipeline:
         a worker thread turns the next batch into index arrays, a second one drives the device (its C-ABI calls release the GIL),

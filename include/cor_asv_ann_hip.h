@@ -419,6 +419,28 @@ int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logi
 int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, float pad_value,
                                  int32_t* alt_idx, float* alt_logp, float* entropy);
 
+/* The vote over N candidate lines per source: the candidate with the smallest expected edit distance to the
+ * others -- the minimum-Bayes-risk pick, the medoid under Levenshtein distance.  The reference has no counterpart.  sym (B,N,L)
+ * holds the candidates' symbols, arbitrary int32 values compared for equality only (the facade passes Unicode code points); len
+ * (B,N) their lengths in 0 .. L, or -1 for a padding candidate (a source with fewer than N); a symbol at or beyond a candidate's
+ * length influences nothing.  weight (B,N) or NULL = all 1.0.  With the candidates i, j, k of one source:
+ *   D[i][j] = the unit-cost Levenshtein distance (insertion, deletion, substitution 1 each) of candidates i and j, D[i][i] = 0;
+ *             -1 where i or j is padding;
+ *   risk[i] = the sum over the live candidates k in ascending k of weight[k] * (double)D[i][k] (mode 0), or of
+ *             weight[k] * ((double)D[i][k] / (double)max(len[i], len[k], 1)) (mode 1): float64, one rounding per operation,
+ *             no fused multiply-add, starting from +0.0; +inf for a padding candidate;
+ *   pick    = the live candidate of smallest risk, the lowest index among equals; -1 for a source without a live candidate.
+ * out_dist (B,N,N) or NULL, out_risk (B,N), out_pick (B).  A source's results are a function of its own candidates, lengths and
+ * weights only, whatever B, N, L and the other sources.  Refused with CASV_ERR_ARG before anything is enqueued: B < 1, N outside
+ * 1 .. 256, L outside 0 .. 8192, mode outside 0 .. 1; NULL len, out_risk or out_pick, NULL sym where L > 0; a len outside -1 .. L;
+ * a weight that is negative, NaN or infinite.  The call runs on the handle's stream in scratch of its own, which the handle owns
+ * and grows on demand; it reads and changes nothing of an encode, decode, score or train session and may stand between any two
+ * other calls, before the weights are committed too.  Kernel class of casv_profile_read: "consensus" (one record per call, both
+ * kernels). */
+int casv_consensus(casv_model* m, int32_t B, int32_t N, int32_t L, int32_t mode,
+                   const int32_t* sym, const int32_t* len, const double* weight,
+                   int32_t* out_dist, double* out_risk, int32_t* out_pick);
+
 /* Multi-GPU: lines are independent (seq2seq.py:113 stateful=False), so one process per GPU decodes a
  * contiguous shard of the lines with its own handle and NO data-path collective; what crosses the GPUs is one all-gather
  * of fixed-width result records per batch -- RCCL over xGMI.  The reference has no counterpart (single process,
@@ -456,7 +478,7 @@ int casv_comm_all_gather_records(casv_model* m, int32_t* recv);
  * event records inside a timed region), casv_profile(m, 3) only for every 13th launch of it (an event pair keeps the next
  * launch from overlapping the kernel's tail, ~8 us each: level 2 costs a beamed decode 2 %, level 3 0.2 %),
  * casv_profile(m, 0) stops; casv_profile_read returns, for kernel class `name`
- * ("lstm_gemm", "lstm_gemm_small", "gemm", "attention", "softmax", "beam", "embed", "persist"), the number of launches, their
+ * ("lstm_gemm", "lstm_gemm_small", "gemm", "attention", "softmax", "beam", "embed", "persist", "sample", "consensus"), the number of launches, their
  * summed duration (ms) and their summed algorithmic FLOPs and bytes. */
 int casv_profile(casv_model* m, int32_t enable);
 int casv_profile_read(casv_model* m, const char* name, int64_t* launches, double* total_ms,
