@@ -115,6 +115,9 @@ SIGNATURES = {
     'casv_score_get_alternatives': (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'casv_score_release': (c_int, [c_void_p]),
     'casv_consensus': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6),
+    'casv_consensus_align': (c_int, [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 5),
+    'casv_consensus_vote': (c_int, [c_void_p, c_int32] + [c_void_p] * 4),
+    'casv_debug_set_align_budget': (c_int, [c_void_p, c_int64]),
     'casv_train_step_soft': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32]
                              + [c_void_p] * 6 + [POINTER(c_double), POINTER(c_double)]),
     'casv_train_step_sampled': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
@@ -171,9 +174,9 @@ def load():
                            '(there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in SIGNATURES.items():
-        if (os.environ.get('CASV_LIB_PATH') and (name.startswith('casv_debug_') or name.endswith('_cut') or name == 'casv_consensus')
+        if (os.environ.get('CASV_LIB_PATH') and (name.startswith('casv_debug_') or name.endswith('_cut') or name.startswith('casv_consensus'))
                 and not hasattr(lib, name)):
-            continue                     # (A/B against an older build of the library: it may lack a test-support entry, the cut entries or the vote)
+            continue                     # (A/B against an older build of the library: it may lack a test-support entry, the cut entries, the vote or the confusion network)
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -275,6 +275,37 @@ bool consensus_ready();
 void launch_consensus_dist(const ConsensusArgs& a, int max_len, hipStream_t stream);
 void launch_consensus_risk(const ConsensusArgs& a, hipStream_t stream);
 
+// The confusion network voted from N candidates per source (consensus_kernels.hip).  sym, len as above,
+// pivot [B] in -1 .. N-1 (-1: the source is skipped); where [B][N][L]: per candidate symbol the pivot symbol it stands against
+// (>= 0) or -1 - slot of its insertion, CASV_ALIGN_NONE beyond a length; ins / start [B][stride]: per slot 0 .. len[pivot] the
+// most symbols a candidate inserts there and the slot's first column; ncol [B].  dir: the direction words of the sources
+// b0 .. b1-1 of one round, [b - b0][N][rows][wpr] of {diagonal holds, pivot-against-gap holds}, bit k & 31 of word k >> 5 for
+// candidate symbol k, one row per pivot symbol.
+struct AlignArgs {
+    const int* sym; const int* len; const int* pivot;
+    int* where; int* ins; int* start; int* ncol;
+    uint2* dir;
+    unsigned long long* stamps;     // nullptr, or two sums over the waves of s_memtime clocks: [0] in the fill, [1] in the walk
+    int B, N, L, stride, rows, wpr, b0, b1;
+};
+// src / mass [B][C][N], best [B][C] (include/cor_asv_ann_hip.h, casv_consensus_vote)
+struct VoteArgs {
+    const int* sym; const int* len; const int* pivot; const int* where; const int* ins; const int* start; const int* ncol;
+    const double* weight;
+    int* src; double* mass; int* best;
+    int B, N, L, stride, C;
+};
+constexpr int CONSENSUS_ALIGN_MAX_L = 2048;
+constexpr int CASV_ALIGN_NONE_VALUE = INT32_MIN;
+// the direction words of one round of casv_consensus_align (at least one source's, whatever the budget)
+constexpr size_t CONSENSUS_ALIGN_BUDGET = (size_t)256 << 20;
+// bytes of one pair's direction words: `rows` pivot symbols by `cols` candidate symbols
+inline int consensus_align_wpr(int cols) { return (cols + 31) >> 5; }
+inline size_t consensus_align_pair_bytes(int rows, int cols) { return (size_t)rows * consensus_align_wpr(cols) * sizeof(uint2); }
+void launch_consensus_align(const AlignArgs& a, int max_len, hipStream_t stream);
+void launch_consensus_layout(const AlignArgs& a, hipStream_t stream);
+void launch_consensus_vote(const VoteArgs& a, hipStream_t stream);
+
 void launch_embed_sparse(const float* E, const int* idx, const float* val, float* x0,
                          int rows, int A, int V, int W, hipStream_t stream);
 // one-alternative input idx [B][T] -> out [T][B]: the character of (line, position), V where there is none (encoder.hip: rows of

@@ -74,7 +74,7 @@ enum ProfClass { PC_LSTM = 0, PC_GEMM, PC_ATTN, PC_SOFTMAX, PC_BEAM, PC_EMBED, P
 // "lstm_gemm" = the 128x128-tile fused LSTM GEMM (the dominant kernel); "lstm_gemm_small" = its 32x128-tile variant
 // "persist" = the persistent small-batch decoder (all steps of a greedy decode in one launch)
 // "sample" = the sampling pick of casv_decode_sample / casv_debug_sample_rows (sample_kernels.hip)
-// "consensus" = the two kernels of casv_consensus, one record per call (consensus_kernels.hip)
+// "consensus" = the kernels of casv_consensus, of casv_consensus_align and of casv_consensus_vote, one record per call (consensus_kernels.hip)
 inline const char* kProfNames[PC_COUNT] = {"lstm_gemm", "gemm", "attention", "softmax", "beam", "embed", "lstm_gemm_small", "persist", "sample", "consensus"};
 
 struct Prof {
@@ -161,7 +161,13 @@ struct casv_model {
     DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (decode.hip, launch_step)
     DevBuf o_idx, o_prob, o_align, st_win, sp_lo, sp_w;
     DevBuf cs_sym, cs_len, cs_weight, cs_dist, cs_risk, cs_pick;   // casv_consensus: its own scratch, nothing of a session (consensus.hip)
-    DevBuf s_logq, s_stream;                              // casv_decode_sample: the proposal's log-probabilities [R][S], the lines' stream ids [B]
+    // casv_consensus_align / casv_consensus_vote (consensus_align.hip): what the last align left on the device for the votes after
+    // it -- symbols, lengths, pivots, where, the layout -- the direction words of one round, and the vote's own inputs and results
+    DevBuf al_sym, al_len, al_pivot, al_where, al_ins, al_start, al_ncol, al_dir, al_weight, al_src, al_mass, al_best;
+    int al_B = 0, al_N = 0, al_L = 0, al_stride = 0, al_max_ncol = 0; bool al_valid = false;
+    size_t align_budget = 0; int stat_align_rounds = 0;   // test support (casv_debug_set_align_budget; 0: CONSENSUS_ALIGN_BUDGET); launches of the last align
+    bool align_stamps = false; DevBuf al_stamps; long long stat_align_ticks[2] = {0, 0};   // option "align_stamps": the last align's clocks in fill / walk, summed over its waves
+    DevBuf s_logq, s_stream;                             // casv_decode_sample: the proposal's log-probabilities [R][S], the lines' stream ids [B]
     // lm_predict: per-step scratch of the LM output -- h of the LM cell [R][W] (its c [R][W] is written and
     // never read), LM logits [R][Vp], casv_decoder_step_lm's probabilities [R][Vp]; wide beams: the LM probability of every child
     DevBuf lm_h, lm_c, lm_logits, lm_probs, b_candlm;

@@ -330,6 +330,9 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "tn_shares")) { *value = m->stat_tn[1]; return CASV_OK; }
     if (!strcmp(key, "tn_nonempty_shares")) { *value = m->stat_tn[2]; return CASV_OK; }
     if (!strcmp(key, "sample_cut_rows")) { *value = m->stat_sample_cut_rows; return CASV_OK; }
+    if (!strcmp(key, "align_rounds")) { *value = m->stat_align_rounds; return CASV_OK; }
+    if (!strcmp(key, "align_fill_ticks")) { *value = m->stat_align_ticks[0]; return CASV_OK; }
+    if (!strcmp(key, "align_walk_ticks")) { *value = m->stat_align_ticks[1]; return CASV_OK; }
     return fail(CASV_ERR_ARG, "unknown statistic '%s'", key);
 }
 
@@ -738,6 +741,10 @@ extern "C" int casv_set_option(casv_model* m, const char* key, int64_t value) {
     if (!strcmp(key, "sample_cut_rows")) {      // test switch: at most this many rows per workgroup of sample_cut_kernel (same results)
         if (value < 0 || value > 4) return fail(CASV_ERR_ARG, "sample_cut_rows must be 0 (as many as fit) or 1 .. 4");
         m->sample_cut_rows_opt = (int)value; return CASV_OK;
+    }
+    if (!strcmp(key, "align_stamps")) {         // measurement aid: consensus_align_kernel adds up its waves' clocks in the fill and in the walk (same results)
+        if (value < 0 || value > 1) return fail(CASV_ERR_ARG, "align_stamps must be 0 or 1");
+        m->align_stamps = value != 0; return CASV_OK;
     }
     if (!strcmp(key, "vendor_gemm")) { m->vendor_gemm = value != 0; return CASV_OK; }
     if (!strcmp(key, "skinny") || !strcmp(key, "tile")) {   // process-wide: tile shape of the GEMM launches (results identical)

@@ -682,6 +682,46 @@ class HipEngine(object):
                                          nv.ptr(risk), nv.ptr(pick)))
         return risk, pick, dist
 
+    def consensus_align(self, sym, length, pivot):
+        """Every candidate of a source aligned to its pivot (casv_consensus_align): sym (B,N,L) int32 symbols, L at most 2048,
+        length (B,N) in -1 .. L, pivot (B) the index of a live candidate or -1 to skip the source.  Returns (where int32 (B,N,L),
+        ncol int32 (B)): per candidate symbol the pivot symbol it stands against (>= 0) or -1 - slot of its insertion, ALIGN_NONE
+        beyond a length, and the columns of the source's confusion network.  The device keeps what `consensus_vote` reads."""
+        sym = nv.carray(sym, np.int32)
+        length = nv.carray(length, np.int32)
+        pivot = nv.carray(pivot, np.int32)
+        assert sym.ndim == 3 and length.shape == sym.shape[:2] and pivot.shape == sym.shape[:1]
+        B, N, L = sym.shape
+        where = np.empty((B, N, L), np.int32)
+        ncol = np.empty((B,), np.int32)
+        nv.check(self.lib.casv_consensus_align(self.handle, B, N, L, nv.ptr(sym), nv.ptr(length), nv.ptr(pivot), nv.ptr(where), nv.ptr(ncol)))
+        self._align_shape = (B, N)
+        return where, ncol
+
+    def consensus_vote(self, C, weights=None):
+        """The vote per column over what the last `consensus_align` left on the device (casv_consensus_vote): C columns per source,
+        at least the largest ncol; weights (B,N) float64, not negative and finite, or None (all 1.0).  Returns (src int32 (B,C,N),
+        mass float64 (B,C,N), best int32 (B,C)): the candidate position in the column (-1 a gap, -2 padding or no column), per
+        class of equal entries at its lowest index the members' weights summed in ascending order (-1.0 elsewhere), and the
+        representative of the largest mass, the lowest index among equals (-1: no column).  May be repeated with other weights."""
+        shape = getattr(self, '_align_shape', None)
+        if shape is None:
+            nv.check(self.lib.casv_consensus_vote(self.handle, int(C), None, None, None, None))      # (answers CASV_ERR_STATE or _ARG)
+        B, N = shape
+        C = int(C)
+        if weights is not None:
+            weights = nv.carray(weights, np.float64)
+            assert weights.shape == (B, N)
+        src = np.empty((B, max(C, 0), N), np.int32)
+        mass = np.empty((B, max(C, 0), N), np.float64)
+        best = np.empty((B, max(C, 0)), np.int32)
+        nv.check(self.lib.casv_consensus_vote(self.handle, C, nv.ptr(weights), nv.ptr(src), nv.ptr(mass), nv.ptr(best)))
+        return src, mass, best
+
+    def debug_set_align_budget(self, nbytes):
+        """Test support (casv_debug_set_align_budget): the direction workspace of `consensus_align` in bytes, 0 = the default."""
+        nv.check(self.lib.casv_debug_set_align_budget(self.handle, int(nbytes)))
+
     def debug_score_rows(self, logits, target, pad_value=0.0):
         """Test support (casv_debug_score_rows): the scoring head alone on logits (R,V) and targets (R); the padding columns of the
         device rows hold pad_value.  Returns (logp, best, rank)."""

@@ -914,6 +914,27 @@ class Sequence2Sequence(object):
         candidate (ValueError).  The sources are taken in order into chunks as `score_candidates` takes them: a chunk grows while
         sources x the largest candidate count stays within max(`batch_size`, that count) rows, and shorter lists are filled with
         padding candidates; a source's result does not depend on its chunk."""
+        points, rows_w = self._vote_inputs(candidates, weights, 8192)
+        picks, risks = [None] * len(candidates), [[] for _ in candidates]
+        dists = [[] for _ in candidates]
+        if not any(candidates):
+            return picks, risks, dists
+        eng = self._consensus_engine()
+        for chunk, N in self._vote_chunks(candidates):
+            sym, length, w = self._vote_arrays(chunk, N, points, rows_w)
+            risk, pick, dist = eng.consensus(sym, length, weights=w, mode=1 if normalise else 0, want_dist=bool(distances))
+            for b, j in enumerate(chunk):
+                n = len(points[j])
+                picks[j] = int(pick[b])
+                risks[j] = risk[b, :n].tolist()
+                if distances:
+                    dists[j] = dist[b, :n, :n].tolist()
+        return picks, risks, dists
+
+    # what consensus_of and confusion_of share: the checks, the code points, the chunks, a chunk's arrays ------------------------
+    @staticmethod
+    def _vote_inputs(candidates, weights, longest):
+        """(points, rows_w): per source the candidates' code points as int32 arrays, and its weights as floats or None."""
         if weights is not None and len(weights) != len(candidates):
             raise ValueError('weights for %d sources beside %d candidate lists' % (len(weights), len(candidates)))
         points, rows_w = [], []
@@ -923,8 +944,8 @@ class Sequence2Sequence(object):
             for k, line in enumerate(cands):
                 if not isinstance(line, str):
                     raise ValueError('candidate %d of source %d is %s, not a string' % (k, j, type(line).__name__))
-                if len(line) > 8192:
-                    raise ValueError('candidate %d of source %d has %d code points: at most 8192' % (k, j, len(line)))
+                if len(line) > longest:
+                    raise ValueError('candidate %d of source %d has %d code points: at most %d' % (k, j, len(line), longest))
             # (UTF-32 is the code points themselves; 'surrogatepass': a lone surrogate is a symbol like any other)
             points.append([np.frombuffer(line.encode('utf-32-le', 'surrogatepass'), '<i4') for line in cands])
             w = None if weights is None else weights[j]
@@ -936,41 +957,122 @@ class Sequence2Sequence(object):
                     if not (x >= 0.0 and math.isfinite(x)):
                         raise ValueError('weight %r of candidate %d of source %d: must be finite and not negative' % (x, k, j))
             rows_w.append(w)
-        picks, risks = [None] * len(candidates), [[] for _ in candidates]
-        dists = [[] for _ in candidates]
-        live = [j for j in range(len(candidates)) if candidates[j]]
-        if not live:
-            return picks, risks, dists
-        eng = self._consensus_engine()
+        return points, rows_w
+
+    def _vote_chunks(self, candidates):
+        """[(sources, N)]: the sources that have candidates, in order, in chunks of at most max(`batch_size`, N) rows."""
         chunks, chunk, most = [], [], 0
-        for j in live:
+        for j in (j for j in range(len(candidates)) if candidates[j]):
             grown = max(most, len(candidates[j]))
             if chunk and (len(chunk) + 1) * grown > max(self.batch_size, grown):
                 chunks.append((chunk, most))
                 chunk, grown = [], len(candidates[j])
             chunk.append(j)
             most = grown
-        chunks.append((chunk, most))
-        for chunk, N in chunks:
-            L = max(len(p) for j in chunk for p in points[j])
-            sym = np.zeros((len(chunk), N, L), np.int32)
-            length = np.full((len(chunk), N), -1, np.int32)          # (-1: a padding candidate)
-            weighted = any(rows_w[j] is not None for j in chunk)
-            w = np.ones((len(chunk), N), np.float64) if weighted else None
+        if chunk:
+            chunks.append((chunk, most))
+        return chunks
+
+    @staticmethod
+    def _vote_arrays(chunk, N, points, rows_w):
+        """(sym (B,N,L) int32, length (B,N) int32 with -1 for the padding candidates, weights (B,N) float64 or None)."""
+        L = max(len(p) for j in chunk for p in points[j])
+        sym = np.zeros((len(chunk), N, L), np.int32)
+        length = np.full((len(chunk), N), -1, np.int32)          # (-1: a padding candidate)
+        weighted = any(rows_w[j] is not None for j in chunk)
+        w = np.ones((len(chunk), N), np.float64) if weighted else None
+        for b, j in enumerate(chunk):
+            for k, p in enumerate(points[j]):
+                sym[b, k, :len(p)] = p
+                length[b, k] = len(p)
+            if rows_w[j] is not None:
+                w[b, :len(rows_w[j])] = rows_w[j]
+        return sym, length, w
+
+    def confusion_of(self, candidates, weights=None, pivots=None, normalise=False, floor=0.0):
+        """The confusion network that a list of candidate lines votes: per source every candidate is aligned to one of them, the
+        pivot, by unit-cost edit distance; the pivot's symbols and the insertions in front of, between and behind them are the
+        columns, and in each column the candidates that put the same character there (or none: a gap) pool their weights
+        (`HipEngine.consensus_align`, `HipEngine.consensus_vote`) -- the character-level vote of ROVER, and
+        the model's primary input form.  `candidates` and `weights` as in `consensus_of`, at most 2048 code points per candidate.
+        `pivots` is None -- the picks of `consensus_of(candidates, weights, normalise)` -- or one candidate index per source (None
+        for a source without candidates).  Returns (lines, confmats, pivots, columns), one entry per source:
+        lines -- the voted line: the heaviest class of every column in order, gaps dropped;
+        confmats -- the network as `correct_lines(conf=...)` reads it: one chunk per column, each a list of (char or '', p), the
+        classes by descending mass (equal masses: the one whose first voter has the lower index first), p = mass / the sum of the
+        source's weights (float64, in order); alternatives with p < `floor` are dropped, except the first;
+        pivots -- the pivot used;
+        columns -- per column the same classes before the floor as (char or '', mass, [indices of the voters]).
+        A source without candidates gives '', [], None, [].  ValueError, before anything runs: what `consensus_of` refuses, a
+        candidate longer than 2048, weights of a source that sum to 0, a pivot that names no candidate.  Chunks as `consensus_of`;
+        a source's result does not depend on its chunk."""
+        points, rows_w = self._vote_inputs(candidates, weights, 2048)
+        n_src = len(candidates)
+        if pivots is not None:
+            if len(pivots) != n_src:
+                raise ValueError('pivots for %d sources beside %d candidate lists' % (len(pivots), n_src))
+            for j, p in enumerate(pivots):
+                if not candidates[j]:
+                    if p is not None:
+                        raise ValueError('pivot %r of source %d, which has no candidates' % (p, j))
+                elif isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= p < len(candidates[j]):
+                    raise ValueError('pivot %r of source %d: an index into its %d candidates' % (p, j, len(candidates[j])))
+        totals = []
+        for j, cands in enumerate(candidates):
+            total = 0.0
+            for x in (rows_w[j] if rows_w[j] is not None else [1.0] * len(cands)):
+                total = total + x
+            if cands and not total > 0.0:
+                raise ValueError('the weights of source %d sum to 0' % j)
+            totals.append(total)
+        if pivots is None:
+            pivots = self.consensus_of(candidates, weights=weights, normalise=normalise)[0]
+        pivots = [None if p is None else int(p) for p in pivots]
+        lines, confmats, columns = [''] * n_src, [[] for _ in candidates], [[] for _ in candidates]
+        if not any(candidates):
+            return lines, confmats, pivots, columns
+        eng = self._consensus_engine()
+        for chunk, N in self._vote_chunks(candidates):
+            sym, length, w = self._vote_arrays(chunk, N, points, rows_w)
+            _, ncol = eng.consensus_align(sym, length, np.array([pivots[j] for j in chunk], np.int32))
+            src, mass, best = eng.consensus_vote(max(1, int(ncol.max())), weights=w)
             for b, j in enumerate(chunk):
-                for k, p in enumerate(points[j]):
-                    sym[b, k, :len(p)] = p
-                    length[b, k] = len(p)
-                if rows_w[j] is not None:
-                    w[b, :len(rows_w[j])] = rows_w[j]
-            risk, pick, dist = eng.consensus(sym, length, weights=w, mode=1 if normalise else 0, want_dist=bool(distances))
-            for b, j in enumerate(chunk):
-                n = len(points[j])
-                picks[j] = int(pick[b])
-                risks[j] = risk[b, :n].tolist()
-                if distances:
-                    dists[j] = dist[b, :n, :n].tolist()
-        return picks, risks, dists
+                n, nc = len(points[j]), int(ncol[b])
+                # per column the candidates' entries as keys (the code point, -1 for a gap) and the representatives by descending
+                # mass -- a stable sort, so the lower index first among equals and the -1.0 of everyone else behind them
+                put, masses = src[b, :nc, :n], mass[b, :nc, :n]
+                keys = np.where(put >= 0, sym[b, np.arange(n)[None, :], np.maximum(put, 0)], -1)
+                order = np.argsort(-masses, axis=1, kind='stable')
+                assert nc == 0 or np.array_equal(order[:, 0], best[b, :nc])
+                text, total = [], totals[j]
+                for key, m, by_mass, reps in zip(keys.tolist(), masses.tolist(), order.tolist(), (masses >= 0.0).sum(axis=1).tolist()):
+                    voters = {}
+                    for k, x in enumerate(key):
+                        voters.setdefault(x, []).append(k)
+                    classes = [('' if key[c] < 0 else chr(key[c]), m[c], voters[key[c]]) for c in by_mass[:reps]]
+                    columns[j].append(classes)
+                    alts = [(char, x / total) for char, x, _ in classes]
+                    confmats[j].append(alts[:1] + [a for a in alts[1:] if a[1] >= floor])
+                    text.append(classes[0][0])
+                lines[j] = ''.join(text)
+        return lines, confmats, pivots, columns
+
+    def correct_candidates(self, candidates, weights=None, pivots=None, normalise=False, floor=0.0, fast=True, greedy=True,
+                           alignments=True):
+        """`confusion_of(candidates, weights, pivots, normalise, floor)`, then the model's correction of the voted network:
+        `correct_lines(voted lines, conf=the networks, fast, greedy, alignments)` over the sources whose network has at least one
+        column.  Returns what `correct_lines` returns, one entry per source; a source without columns (no candidates, or nothing
+        but empty ones) gives '', [], 0.0, [].  Characters outside the model's mapping behave as in any `conf=` input."""
+        voted, confmats, _, _ = self.confusion_of(candidates, weights=weights, pivots=pivots, normalise=normalise, floor=floor)
+        out = ([''] * len(voted), [[] for _ in voted], [0.0] * len(voted), [[] for _ in voted])
+        live = [j for j in range(len(voted)) if confmats[j]]
+        if live:
+            got = self.correct_lines([voted[j] for j in live], conf=[confmats[j] for j in live], fast=fast, greedy=greedy,
+                                     alignments=alignments)
+            for part, full in zip(got, out):
+                for j, x in zip(live, part):
+                    full[j] = x
+        return out
 
     def consensus_lines(self, lines, conf=None, n=16, temperature=1.0, top_k=0, top_p=1.0, seed=None, streams=None,
                         include_greedy=True, weights='uniform', normalise=False):

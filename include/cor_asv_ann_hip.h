@@ -441,6 +441,46 @@ int casv_consensus(casv_model* m, int32_t B, int32_t N, int32_t L, int32_t mode,
                    const int32_t* sym, const int32_t* len, const double* weight,
                    int32_t* out_dist, double* out_risk, int32_t* out_pick);
 
+/* The confusion network voted from N candidate lines per source: every candidate aligned to one of them,
+ * the pivot, then a vote per column -- the input form of the model (seq2seq.py:1020-1119: a list of chunks of (chars, p)), which the
+ * reference only ever receives from an OCR engine.  sym (B,N,L), len (B,N) as for casv_consensus, L at most 2048; pivot (B) names a
+ * live candidate of each source, or is -1: that source is skipped (ncol 0, where all CASV_ALIGN_NONE).  With p the pivot's lp
+ * symbols, c a candidate's, D[i][j] the unit-cost Levenshtein matrix of p[:i] against c[:j]:
+ *   the path  walks from (lp, len[c]) to (0, 0).  At (i, j): if i, j > 0 and D[i][j] == D[i-1][j-1] + (p[i-1] != c[j-1]), c[j-1]
+ *             stands against p[i-1] and the walk goes to (i-1, j-1); else if i > 0 and D[i][j] == D[i-1][j] + 1, p[i-1] stands
+ *             against a gap, on to (i-1, j); else c[j-1] is an insertion in slot i (in front of p[i], behind the last symbol for
+ *             i == lp), on to (i, j-1);
+ *   where[c][j] = i >= 0: symbol j stands against pivot symbol i; -1 - g: it is inserted in slot g; the pivot's own where[j] = j;
+ *             CASV_ALIGN_NONE at j >= len[c] and in every position of a padding candidate;
+ *   columns   ins[g] = the most symbols any live candidate inserts in slot g.  In order g = 0 .. lp: ins[g] insertion columns, then
+ *             (g < lp) the column of p[g]; ncol = lp + the sum of ins.  A candidate's k-th symbol of slot g, in order of j, stands
+ *             in the slot's k-th insertion column;
+ *   src[col][c] = the position j that candidate c puts into the column; -1: c is live and puts a gap there; -2: c is padding;
+ *   mass[col][c] = for the lowest index c of a class -- the live candidates that put a gap, or those that put equal symbols -- the
+ *             sum of weight[k] over the members k in ascending order: float64 from +0.0, one rounding per addition; -1.0 for
+ *             every other c, padding included;
+ *   best[col] = the class representative of the largest mass, the lowest index among equals.
+ * Columns at or beyond ncol hold src -2, mass -1.0, best -1.  A source's results are a function of its own candidates, lengths, pivot
+ * and weights only.  casv_consensus_align fills out_where (B,N,L) and out_ncol (B) and keeps symbols, lengths, where and layout on
+ * the device; casv_consensus_vote(C, weight) votes on what the last casv_consensus_align of this handle left there -- out_src
+ * (B,C,N), out_mass (B,C,N), out_best (B,C), weight (B,N) or NULL = all 1.0 -- and may be called again with other weights.
+ * CASV_ERR_STATE: a vote without an align to read.  Refused with CASV_ERR_ARG before anything is enqueued, nothing written and the
+ * kept state untouched: B < 1, N outside 1 .. 256, L outside 0 .. 2048; a NULL argument (sym and out_where may be NULL where
+ * L == 0, weight always); a len outside -1 .. L; a pivot outside -1 .. N-1 or one that names a padding candidate; C < 1 or C below
+ * the largest ncol; a weight that is negative, NaN or infinite.  Both run on the handle's stream in buffers of their own and may
+ * stand between any two other calls, casv_consensus included, before the weights are committed too.  The direction bits of the
+ * paths live in a workspace of at most 256 MiB (one source's, where that is more): the align call takes its sources in rounds,
+ * with the same results.  Kernel class of casv_profile_read: "consensus", one record per call. */
+#define CASV_ALIGN_NONE INT32_MIN
+int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t L,
+                         const int32_t* sym, const int32_t* len, const int32_t* pivot,
+                         int32_t* out_where, int32_t* out_ncol);
+int casv_consensus_vote(casv_model* m, int32_t C, const double* weight,
+                        int32_t* out_src, double* out_mass, int32_t* out_best);
+/* Test support: the workspace budget of casv_consensus_align in bytes (0: the default), so that small calls take several rounds;
+ * casv_get_stat "align_rounds" reports the rounds of the last call. */
+int casv_debug_set_align_budget(casv_model* m, int64_t bytes);
+
 /* Multi-GPU: lines are independent (seq2seq.py:113 stateful=False), so one process per GPU decodes a
  * contiguous shard of the lines with its own handle and NO data-path collective; what crosses the GPUs is one all-gather
  * of fixed-width result records per batch -- RCCL over xGMI.  The reference has no counterpart (single process,
@@ -647,7 +687,8 @@ int casv_debug_bwd_step(casv_model* m, int32_t form, int32_t count, const casv_d
  * the default: DESIGN.md section 4.5); 0 = never.  "beam_skip_last" (per handle; default 1; CASV_BEAM_SKIP_LAST=0 likewise): 0 = debug
  * switch, the last iteration of casv_decode_beam launches its decoder step although nothing reads its results (same results).
  * "sample_cut_rows" (per handle; default 0 = as many as fit) = 1 .. 4: at most this many rows per workgroup in sample_cut_kernel's
- * launches -- a test switch, the same results bit for bit. */
+ * launches -- a test switch, the same results bit for bit.  "align_stamps" (per handle; default 0) = 1: a measurement aid,
+ * casv_consensus_align's waves add up the shader clocks of their fill and of their walk (casv_get_stat; the same results). */
 int casv_set_option(casv_model* m, const char* key, int64_t value);
 /* Statistics of the last call (tests): "beam_max_new_keys" = most child hypotheses one line created in one search
  * iteration of the last casv_decode_beam; "beam_sort_capacity" = how many of them are sorted in LDS at once (more are
@@ -666,7 +707,10 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
  * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
- * give-up on this handle so far; "sample_cut_rows" = rows per workgroup of the last sample_cut_kernel launch (0: none so far). */
+ * give-up on this handle so far; "sample_cut_rows" = rows per workgroup of the last sample_cut_kernel launch (0: none so far);
+ * "align_rounds" = launches of consensus_align_kernel the last casv_consensus_align took under its workspace budget;
+ * "align_fill_ticks" / "align_walk_ticks" = with option "align_stamps" = 1 (a measurement aid, same results) the shader clocks the
+ * waves of that call spent filling their direction words and walking the paths, each summed over the waves (0 without). */
 int casv_get_stat(casv_model* m, const char* key, int64_t* value);
 int casv_synchronize(casv_model* m);
 
