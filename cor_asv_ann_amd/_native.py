@@ -69,6 +69,11 @@ class DebugJob(Structure):
                 ('b_static', c_int32), ('epi_plain', c_int32)]
 
 
+class DebugSum(Structure):
+    """casv_debug_sum: the train step's launch fields of one job (casv_debug_gemm_jobs_sum)"""
+    _fields_ = [('ksplit', c_int32), ('kgroups', c_int32), ('accumulate', c_int32), ('out_zeroed', c_int32)]
+
+
 class DebugBwdJob(Structure):
     """casv_debug_bwd_job: one layer's backward time step (casv_debug_bwd_step)"""
     _fields_ = [('rows', c_int32), ('W', c_int32), ('N', c_int32), ('Bt', c_void_p), ('a', c_void_p), ('lda', c_int64), ('mask_a', c_void_p),
@@ -141,6 +146,7 @@ SIGNATURES = {
     'casv_debug_activation': (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     'casv_debug_gemm_jobs': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), c_int32, c_int32]),
     'casv_debug_gemm_jobs_acc': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), POINTER(DebugRows), c_int32, c_int32]),
+    'casv_debug_gemm_jobs_sum': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugJob), POINTER(DebugSum), c_int32, c_int32, c_int32]),
     'casv_debug_get_u': (c_int, [c_void_p, c_void_p]),
     'casv_debug_bwd_step': (c_int, [c_void_p, c_int32, c_int32, POINTER(DebugBwdJob)]),
     'casv_set_option': (c_int, [c_void_p, c_char_p, c_int64]),

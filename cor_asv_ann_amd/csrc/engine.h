@@ -204,7 +204,7 @@ struct casv_model {
     int stat_dec_plan[4] = {0, 0, 0, 0};                  // last plan of the persistent decoder (decode.hip, plan_decode): workgroups per CU, g_lstm, g_att, g_plain
     int stat_enc_plan[2] = {0, 0};                        // last plan of a persistent encoder pass (encoder.hip, plan_persist_enc): workgroups per CU, grid (0: no form)
     int stat_train_launches = 0; long long stat_train_give_ups = 0;   // train step: persistent launches of the last step that was not redone; steps redone after a give-up (train.hip)
-    int stat_jobs[2] = {0, 0};                            // last casv_debug_gemm_jobs: bit f = a launch of GemmForm f ran, launches of the plan
+    int stat_jobs[3] = {0, 0, 0};                         // last casv_debug_gemm_jobs: bit f = a launch of GemmForm f ran, launches of the plan (clears included), its largest grid_z
     int stat_bwd_step[2] = {0, 0};                        // last casv_debug_bwd_step: K shares and unit groups per share of the fused launch (form 1: 0, 0)
     int stat_tn[3] = {0, 0, 0};                           // last casv_debug_contract_tn: split kernel (0/1), K shares launched, shares holding k-tiles
                                                           // and distinct parent expansions among them (N <= 16 only)

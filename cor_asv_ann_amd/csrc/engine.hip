@@ -324,6 +324,7 @@ extern "C" int casv_get_stat(casv_model* m, const char* key, int64_t* value) {
     if (!strcmp(key, "train_give_ups")) { *value = m->stat_train_give_ups; return CASV_OK; }
     if (!strcmp(key, "gemm_jobs_forms")) { *value = m->stat_jobs[0]; return CASV_OK; }
     if (!strcmp(key, "gemm_jobs_launches")) { *value = m->stat_jobs[1]; return CASV_OK; }
+    if (!strcmp(key, "gemm_jobs_shares")) { *value = m->stat_jobs[2]; return CASV_OK; }
     if (!strcmp(key, "bwd_step_shares")) { *value = m->stat_bwd_step[0]; return CASV_OK; }
     if (!strcmp(key, "bwd_step_groups")) { *value = m->stat_bwd_step[1]; return CASV_OK; }
     if (!strcmp(key, "tn_split")) { *value = m->stat_tn[0]; return CASV_OK; }
@@ -581,10 +582,22 @@ int check_debug_job(int epi, const casv_debug_job& d, int j, const int* steps, i
     }
     return CASV_OK;
 }
+// the train step's launch fields of job j (casv_debug_gemm_jobs_sum): plain_gemm()'s, on plain-epilogue jobs of a plain batch only
+int check_debug_sum(int epi, const casv_debug_job& d, const casv_debug_sum& s, int j, int step_by_ptr) {
+    if (s.ksplit < -1 || s.ksplit > 64 || (s.kgroups != 0 && s.kgroups != 2) || (s.accumulate != 0 && s.accumulate != 1) || (s.out_zeroed != 0 && s.out_zeroed != 1))
+        return fail(CASV_ERR_ARG, "job %d: ksplit in [-1, 64], kgroups 0 or 2, accumulate and out_zeroed 0 or 1", j);
+    const bool any = s.ksplit || s.kgroups || s.accumulate || s.out_zeroed;
+    if (any && (epi != EPI_PLAIN || d.epi_plain)) return fail(CASV_ERR_ARG, "job %d: ksplit, kgroups, accumulate and out_zeroed belong to the plain-epilogue jobs of an epi = 0 batch", j);
+    if (s.ksplit != 0 && step_by_ptr) return fail(CASV_ERR_ARG, "job %d: a job that asks for split-K cannot take its step from a device word", j);
+    if (s.accumulate && s.out_zeroed) return fail(CASV_ERR_ARG, "job %d: accumulate and out_zeroed exclude each other", j);
+    return CASV_OK;
+}
 }  // namespace
 
-// (`acc`: casv_debug_gemm_jobs_acc -- per job an accumulator input, pool == NULL: none)
-static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc, int32_t step, int32_t step_by_ptr) {
+// (`acc`: casv_debug_gemm_jobs_acc -- per job an accumulator input, pool == NULL: none; `sums`: casv_debug_gemm_jobs_sum -- per job the
+// train step's launch fields, under ordered sums if `ordered`)
+static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc, int32_t step, int32_t step_by_ptr,
+                           const casv_debug_sum* sums = nullptr, int32_t ordered = 0) {
     if (!m || !jobs) return fail(CASV_ERR_ARG, "null argument");
     if ((epi != EPI_PLAIN && epi != EPI_LSTM) || count < 1 || count > GEMM_MAX_JOBS || step < 0 || step > 4096 || (step_by_ptr != 0 && step_by_ptr != 1))
         return fail(CASV_ERR_ARG, "epi 0 / 1, 1..%d jobs, step in [0, 4096], step_by_ptr 0 / 1", GEMM_MAX_JOBS);
@@ -598,8 +611,11 @@ static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv
         if (int rc = check_debug_rows(acc[j], "acc_in", j, jobs[j].M, steps, nsteps)) return rc;
         if (acc[j].width != jobs[j].N || acc[j].first || acc[j].skip_first) return fail(CASV_ERR_ARG, "job %d acc_in: width = N, no first / skip_first", j);
     }
+    if (ordered != 0 && ordered != 1) return fail(CASV_ERR_ARG, "ordered is 0 or 1");
+    for (int j = 0; j < count && sums; ++j) if (int rc = check_debug_sum(epi, jobs[j], sums[j], j, step_by_ptr)) return rc;
     HIPCHK(hipSetDevice(m->device));
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_CHAIN));
+    OrderedScope ordered_sums(m, ordered != 0);         // (the train step's "deterministic" option: no launch splits K over workgroups)
     if (acc && !m->gemm.arithmetic) return fail(CASV_ERR_ARG, "casv_debug_gemm_jobs_acc needs a split arithmetic (option \"arithmetic\" or \"split_bf16\" = 1 or 2)");
     DebugBuffers dev{m->stream};
     int rc = CASV_OK;
@@ -634,6 +650,15 @@ static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv
         dev.weights.push_back(g.Bt);
         if (d.bias) { g.bias = static_cast<const float*>(dev.put(d.bias, (size_t)d.N, rc)); if (rc) return rc; }
         out(d.out, g.out); if (rc) return rc;
+        if (sums) {
+            // the addressed slot, rows < M and columns < N: C0 from the host for `accumulate`, zeros for `out_zeroed` (the caller's
+            // clear); its pad columns, every other slot and the guard row keep the 0xFF bytes
+            const casv_debug_sum& s = sums[j];
+            g.ksplit = s.ksplit; g.kgroups = s.kgroups; g.accumulate = s.accumulate; g.out_zeroed = s.out_zeroed;
+            const size_t slot = (size_t)((long long)step * d.out.step_mul + d.out.step_add) * d.M * d.out.ld, pitch = (size_t)d.out.ld * 4;
+            if (s.accumulate) HIPCHK(hipMemcpy2DAsync(g.out.base + slot, pitch, d.out.data + slot, pitch, (size_t)d.N * 4, d.M, hipMemcpyHostToDevice, m->stream));
+            if (s.out_zeroed) HIPCHK(hipMemset2DAsync(g.out.base + slot, pitch, 0, (size_t)d.N * 4, d.M, m->stream));
+        }
         if (lstm) {
             seg(d.c_in, g.c_in); if (rc) return rc;
             out(d.c_out, g.c_out); if (rc) return rc;
@@ -658,8 +683,13 @@ static int debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv
     if (!gemm_plan_takes_acc_in(planned)) return fail(CASV_ERR_ARG, "a job with acc_in would not run as 128x128 split tiles");
     const GemmPlan plan = run_gemm_plan(m->gemm, epi, b, planned, m->stream);
     HIPCHK(hipGetLastError());
-    m->stat_jobs[0] = 0; m->stat_jobs[1] = plan.count;
-    for (int i = 0; i < plan.count; ++i) m->stat_jobs[0] |= 1 << plan.launch[i].form;
+    m->stat_jobs[0] = 0; m->stat_jobs[1] = plan.count; m->stat_jobs[2] = 0;
+    for (int i = 0; i < plan.count; ++i) {
+        const GemmLaunchPlan& l = plan.launch[i];
+        m->stat_jobs[0] |= 1 << l.form;
+        for (int j = 0; j < l.batch.count; ++j) m->stat_jobs[1] += l.clear_jobs >> j & 1;       // (a clear is a launch of its own)
+        m->stat_jobs[2] = std::max(m->stat_jobs[2], l.grid_z);
+    }
     std::vector<std::vector<uint32_t>> guards(back.size());
     for (size_t i = 0; i < back.size(); ++i) {
         const size_t n = back[i].rows * back[i].o->ld;
@@ -679,6 +709,11 @@ extern "C" int casv_debug_gemm_jobs_acc(casv_model* m, int32_t epi, int32_t coun
                                         int32_t step, int32_t step_by_ptr) {
     if (!acc) return fail(CASV_ERR_ARG, "null argument");
     return debug_gemm_jobs(m, epi, count, jobs, acc, step, step_by_ptr);
+}
+extern "C" int casv_debug_gemm_jobs_sum(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_sum* sums,
+                                        int32_t ordered, int32_t step, int32_t step_by_ptr) {
+    if (!sums) return fail(CASV_ERR_ARG, "null argument");
+    return debug_gemm_jobs(m, epi, count, jobs, nullptr, step, step_by_ptr, sums, ordered);
 }
 
 extern "C" int casv_debug_activation(casv_model* m, int32_t which, int64_t n, const float* in_, float* out_) {

@@ -829,7 +829,7 @@ class HipEngine(object):
         nv.check(self.lib.casv_debug_activation(self.handle, w, n, nv.ptr(x), nv.ptr(out)))
         return out
 
-    def debug_gemm_jobs(self, epi, jobs, step, step_by_ptr=False, acc=None):
+    def debug_gemm_jobs(self, epi, jobs, step, step_by_ptr=False, acc=None, sums=None, ordered=False):
         """Test support (casv_debug_gemm_jobs): ONE batch of forward GEMM jobs (epi 0 plain, 1 fused LSTM cell) with the whole
         operand machinery of csrc/gemm_args.h, on host data.  A job is an object with the attributes M, N, Ktot, segs, c_in, zinit, Bt,
         bias, out, c_out, gates_out, out2, nact, nact_group, b_static, epi_plain; an input part (segment, c_in, zinit) has pool
@@ -837,8 +837,14 @@ class HipEngine(object):
         step_add) or None (tests/lstm_gemm_cases.py builds them).  Returns (outputs, forms, launches): per job a dict name ->
         (slots, M, ld) float32 with every byte the launch did not store to still 0xFF, the bit mask of the GemmForms of the plan that
         ran, and the number of its launches.  acc (casv_debug_gemm_jobs_acc): per job an input part whose rows (width N) the job's
-        accumulators start from, or None."""
+        accumulators start from, or None.  sums (casv_debug_gemm_jobs_sum): per job None or a dict of the train step's launch fields
+        ksplit, kgroups, accumulate, out_zeroed (those left out are 0) and, with accumulate, C0 (M, N): what the addressed slot of
+        `out` holds before the launch; ordered: the launch runs under ordered sums, as the deterministic train step's do.
+        stat('gemm_jobs_shares') then tells the largest number of K shares of a launch of the plan."""
         keep, cjobs, results = [], (nv.DebugJob * len(jobs))(), []
+        assert acc is None or sums is None
+        assert sums is not None or not ordered
+        csums = None if sums is None else (nv.DebugSum * len(jobs))()
         caccs = None if acc is None else (nv.DebugRows * len(jobs))()
 
         def arr(a, dtype):
@@ -882,7 +888,21 @@ class HipEngine(object):
                 cj.nact, cj.nact_lines, cj.nact_group = arr(job.nact, np.int32), len(job.nact), job.nact_group
             cj.b_static, cj.epi_plain = int(job.b_static), int(job.epi_plain)
             results.append(res)
-        if acc is not None:
+        if sums is not None:
+            assert len(sums) == len(jobs)
+            for cs, job, res, fields in zip(csums, jobs, results, sums):
+                fields = dict(fields or {})
+                c0 = fields.pop('C0', None)
+                for name in ('ksplit', 'kgroups', 'accumulate', 'out_zeroed'):
+                    setattr(cs, name, int(fields.pop(name, 0)))
+                assert not fields, fields
+                if c0 is not None:
+                    slots, ld, mul, add = job.out
+                    assert np.shape(c0) == (job.M, job.N) and 0 <= step * mul + add < slots
+                    res['out'][step * mul + add, :, :job.N] = c0
+            nv.check(self.lib.casv_debug_gemm_jobs_sum(self.handle, int(epi), len(jobs), cjobs, csums, int(bool(ordered)), int(step),
+                                                       int(bool(step_by_ptr))))
+        elif acc is not None:
             assert len(acc) == len(jobs)
             for ca, job, part in zip(caccs, jobs, acc):
                 if part is not None:

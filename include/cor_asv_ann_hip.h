@@ -601,6 +601,21 @@ int casv_debug_gemm_jobs(casv_model* m, int32_t epi, int32_t count, const casv_d
 int casv_debug_get_u(casv_model* m, float* u);
 int casv_debug_gemm_jobs_acc(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_rows* acc,
                              int32_t step, int32_t step_by_ptr);
+/* The same with the train step's launch fields per job (csrc/gemm_args.h; csrc/train.hip, plain_gemm): ksplit (-1: the launcher may
+ * share K out over workgroups, whose partial sums meet in float atomics; n > 1: n shares; 0 / 1: one block per tile), kgroups (2: it
+ * may share K out over the two wave groups of a workgroup as well), accumulate (C += instead of C =) and out_zeroed (the caller has
+ * cleared C: the launcher adds no clear of its own).  ordered = 1 runs the launch under ordered sums, as the "deterministic" train
+ * step does: no launch splits K over workgroups then.  Tile shape and arithmetic come from the options "tile" and "split_bf16" as
+ * above.  The addressed slot of `out` starts, over rows < M and columns < N, as uploaded from out.data with accumulate, as zeros
+ * with out_zeroed, else as 0xFF; its pad columns [N, ld), every other slot and the guard row start as 0xFF in all three cases.
+ * Checked on the host before anything is launched (CASV_ERR_ARG), besides everything casv_debug_gemm_jobs checks: ksplit in
+ * [-1, 64], kgroups 0 or 2, the flags 0 or 1 and not both set, a field other than 0 only on the plain-epilogue jobs of an epi = 0
+ * batch, ksplit other than 0 not together with step_by_ptr.  casv_get_stat reports "gemm_jobs_shares" too: the largest grid_z of
+ * the plan that ran; "gemm_jobs_launches" counts a clear of C as a launch.  tests/test_gpu_plain_sums.py holds every form the
+ * planner makes of these fields (tests/plain_sum_cases.py) to float64. */
+typedef struct casv_debug_sum { int32_t ksplit, kgroups, accumulate, out_zeroed; } casv_debug_sum;
+int casv_debug_gemm_jobs_sum(casv_model* m, int32_t epi, int32_t count, const casv_debug_job* jobs, const casv_debug_sum* sums,
+                             int32_t ordered, int32_t step, int32_t step_by_ptr);
 /* Test support: ONE backward time step of 1 or 2 LSTM layers on the caller's host data, as the train step launches it where a
  * layer has no persistent backward.  form 0 = the fused launch (csrc/gemm_bwd.hip: the cell's pointwise backward inside the data
  * GEMM out = dz . Bt^T), form 1 = the two launches of the options "deterministic" and "fused_backward" off (lstm_bwd_kernel, then
@@ -704,7 +719,7 @@ int casv_set_option(casv_model* m, const char* key, int64_t value);
  * "encoder_table" = 1 if the last encoder pass took layer 1's input terms from the per-character table (option "encoder_table"),
  * "encoder_ahead" = 1 if it took the upper layers' input terms ahead (value 2), "encoder_table_builds" = tables built on this handle so far (one per casv_commit_weights that was followed by such a pass);
  * "cus" = compute units of the device; "tn_split" / "tn_shares" / "tn_nonempty_shares": see casv_debug_contract_tn;
- * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
+ * "gemm_jobs_forms" / "gemm_jobs_launches": see casv_debug_gemm_jobs; "gemm_jobs_shares": see casv_debug_gemm_jobs_sum; "bwd_step_shares" / "bwd_step_groups": see casv_debug_bwd_step;
  * "train_persistent_launches" = persistent recurrences (at most 16: csrc/train.hip) of the last casv_train_step that ran to its
  * end without being redone -- a step redone per step after a give-up reports 0; "train_give_ups" = steps redone after a
  * give-up on this handle so far; "sample_cut_rows" = rows per workgroup of the last sample_cut_kernel launch (0: none so far);
