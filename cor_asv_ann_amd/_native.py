@@ -134,6 +134,10 @@ SIGNATURES = {
                                   + [c_float, c_void_p]),
     'casv_debug_soft_ce_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                         c_int32, POINTER(c_double), c_void_p, c_int32]),
+    'casv_train_step_risk': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
+                             + [c_int32, c_void_p, c_double, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_debug_risk_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                     c_float, c_int32, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'casv_debug_alternatives_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'casv_profile': (c_int, [c_void_p, c_int32]),

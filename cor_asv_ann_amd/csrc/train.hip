@@ -396,6 +396,10 @@ int plan_buffers(Step& s) {
     }
     if (s.bridged) { ENS(ts->hbr, (size_t)D * Be * W * 4) ENS(ts->cbr, (size_t)D * Be * W * 4) ENS(ts->brtmp, (size_t)Be * W * 4) }
     if (s.K > 0) { ENS(ts->d_sidx, UB * s.K * 4) ENS(ts->d_sq, UB * s.K * 4) }
+    if (s.RN > 0) {
+        ENS(ts->r_cost, (size_t)B * 4) ENS(ts->r_coef, (size_t)B * 4) ENS(ts->r_q, (size_t)B * 8) ENS(ts->r_risk, (size_t)(B / s.RN) * 8)
+        ENS(ts->r_parts, (size_t)(B / s.RN) * 8) ENS(ts->s_logp, UB * 4) ENS(ts->s_best, UB * 4) ENS(ts->s_rank, UB * 4)
+    }
     if (s.sched) { ENS(ts->d_gold, UB * 4) ENS(ts->d_mix, (size_t)s.sched->passes * UB * 4) }
     if (s.N > 1) { ENS(ts->h0rep, (size_t)D * B * W * 4) ENS(ts->c0rep, (size_t)D * B * W * 4) }
     if (s.residual && D >= 2) ENS(ts->Ytop, UB * W * 4)
@@ -444,6 +448,7 @@ int stage_inputs(Step& s) {
         HIPCHK(hipMemcpyAsync(ts->d_sq.p, s.soft_q, UB * s.K * 4, hipMemcpyHostToDevice, st));
     } else HIPCHK(hipMemcpyAsync(ts->d_out.p, s.dec_out, UB * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ts->d_w.p, s.weights, UB * 4, hipMemcpyHostToDevice, st));
+    if (s.RN > 0) HIPCHK(hipMemcpyAsync(ts->r_cost.p, s.cost, (size_t)B * 4, hipMemcpyHostToDevice, st));
     if (s.det) {
         char_segments(s.enc_idx, s.Be, T, A, V, ts->h_seg_enc_off, ts->h_seg_enc_pos);
         char_segments(s.dec_in, B, U, 1, V, ts->h_seg_dec_off, ts->h_seg_dec_pos);
@@ -668,8 +673,12 @@ static int loss_head(Step& s) {
     const int B = s.B, U = s.U, V = s.V, Vp = s.Vp;
     if (int rc = projection(s)) return rc;
     hipEvent_t ev{};            // (casv_profile, class "softmax": the head reads the logits once and, training, writes them once)
-    s.m->prof_begin(PC_SOFTMAX, 0.0, 4.0 * (double)s.UB * (V + (s.training ? Vp : 0)) + 8.0 * (double)s.UB * s.K, ev);
-    if (s.K > 0)
+    s.m->prof_begin(PC_SOFTMAX, 0.0, 4.0 * (double)s.UB * (V + (s.training ? Vp : 0)) + 8.0 * (double)s.UB * s.K + (s.RN > 0 ? 4.0 * (double)s.UB * V : 0.0), ev);
+    if (s.RN > 0)
+        launch_risk_head(ts->logits.as<float>(), ts->d_out.as<int>(), ts->d_w.as<float>(), ts->r_cost.as<float>(), B, U, V, Vp, s.RN, s.alpha,
+                         s.inv_groups, ts->s_logp.as<float>(), ts->s_best.as<int>(), ts->s_rank.as<int>(), ts->r_coef.as<float>(),
+                         ts->r_q.as<double>(), ts->r_risk.as<double>(), ts->r_parts.as<double>(), ts->loss.as<double>(), st);
+    else if (s.K > 0)
         launch_soft_ce(ts->logits.as<float>(), ts->d_sidx.as<int>(), ts->d_sq.as<float>(), ts->d_w.as<float>(), B, U, V, Vp, s.K, s.inv_count,
                        ts->loss.as<double>(), s.training ? 1 : 0, st, s.parts);
     else
@@ -1149,6 +1158,113 @@ extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int3
             for (int v = V; v < Vp; ++v)
                 if (x[(size_t)r * Vp + v] != 0.f) return fail(CASV_ERR_HIP, "soft head: padding column %d of row %d is %g, not zero", v, r, (double)x[(size_t)r * Vp + v]);
             memcpy(dlogits + (size_t)r * V, &x[(size_t)r * Vp], (size_t)V * 4);
+        }
+    return CASV_OK;
+}
+
+// The risk head's rules (include/cor_asv_ann_hip.h), checked on the host before anything is launched or cleared: O(B).  *inv = 1 /
+// max(number of groups with at least one member, 1).
+static int check_risk(int B, int N, const float* cost, double alpha, double* inv) {
+    if (N < 1 || N > 64 || B % N) return fail(CASV_ERR_ARG, "N=%d: 1 <= N <= 64 and B=%d a multiple of N", N, B);
+    if (!cost) return fail(CASV_ERR_ARG, "null argument");
+    if (!(alpha > 0.0) || alpha == (double)INFINITY) return fail(CASV_ERR_ARG, "alpha = %g: finite and > 0", alpha);
+    long groups = 0;
+    for (int g = 0; g < B / N; ++g) {
+        bool any = false;
+        for (int i = 0; i < N; ++i) {
+            const float c = cost[(size_t)g * N + i];
+            if (c != c || c == INFINITY || c == -INFINITY) return fail(CASV_ERR_ARG, "cost[%d] = %g: a cost is finite (negative: not a member)", g * N + i, (double)c);
+            any |= c >= 0.f;
+        }
+        groups += any;
+    }
+    *inv = 1.0 / (double)std::max(groups, 1L);
+    return CASV_OK;
+}
+
+// casv_train_step with the minimum-risk head in place of the cross-entropy: the same view, the same attempts.
+extern "C" int casv_train_step_risk(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                                    const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                                    const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
+                                    int32_t N, const float* cost, double alpha, double* out_q, double* out_risk,
+                                    double* loss_out, double* norm_out) {
+    if (!m || !enc_idx || !dec_in || !dec_out || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
+    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
+    if (mode < 1 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 1 (train) or 2 (gradients only): the risk has no evaluation form");
+    double inv = 1.0;
+    if (int rc = check_risk(B, N, cost, alpha, &inv)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
+    OrderedScope ordered(m, m->deterministic);
+    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
+    s.dec_out = dec_out;
+    s.RN = N; s.cost = cost; s.alpha = alpha; s.inv_groups = inv;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool redo = false;
+        if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
+        if (redo) continue;
+        TrainState* ts = m->train;             // (the attempt has waited for the stream)
+        if (out_q) HIPCHK(hipMemcpy(out_q, ts->r_q.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+        if (out_risk) HIPCHK(hipMemcpy(out_risk, ts->r_risk.p, (size_t)(B / N) * 8, hipMemcpyDeviceToHost));
+        return CASV_OK;
+    }
+    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
+}
+
+// Test support: the risk head alone on the caller's logits (B = G * N, U, V) in the caller's (b, u) order, laid out as the step
+// lays them out (row u * B + b, stride Vp, the padding columns filled with pad_value) -- casv_debug_soft_ce_rows with U steps.
+extern "C" int casv_debug_risk_rows(casv_model* m, int32_t G, int32_t N, int32_t U, int32_t V, const float* logits, const int32_t* target,
+                                    const float* weight, const float* cost, double alpha, float pad_value, int32_t want_grad,
+                                    double* loss, double* q, float* coef, float* dlogits) {
+    if (!m || !logits || !target || !weight || !loss || !q || !coef || (want_grad && !dlogits)) return fail(CASV_ERR_ARG, "null argument");
+    if (G < 1 || U < 1 || V < 1 || V > 4096 || N < 1 || N > 64 || (long long)G * N * U > (1 << 20))
+        return fail(CASV_ERR_ARG, "G, U >= 1, N in [1, 64], G * N * U <= 2^20, V in [1, 4096]");
+    const int B = G * N;
+    const size_t R = (size_t)B * U;
+    double inv = 1.0;
+    if (int rc = check_risk(B, N, cost, alpha, &inv)) return rc;
+    for (size_t i = 0; i < R; ++i)
+        if (target[i] < -1 || target[i] >= V) return fail(CASV_ERR_ARG, "target[%zu] = %d outside [-1, %d)", i, target[i], V);
+    HIPCHK(hipSetDevice(m->device));
+    const int Vp = (V + 31) & ~31;
+    std::vector<float> x(R * Vp, pad_value);
+    for (int b = 0; b < B; ++b)
+        for (int u = 0; u < U; ++u) memcpy(&x[((size_t)u * B + b) * Vp], logits + ((size_t)b * U + u) * V, (size_t)V * 4);
+    DevBuf dx, dt, dw, dc, dl, dlogp, dbest, drank, dcoef, dq, drisk, dparts;
+    DebugBuffers release_on_exit{m->stream};
+    if (int rc = dx.ensure(x.size() * 4)) return rc;
+    if (int rc = dt.ensure(R * 4)) return rc;
+    if (int rc = dw.ensure(R * 4)) return rc;
+    if (int rc = dc.ensure((size_t)B * 4)) return rc;
+    if (int rc = dl.ensure(16)) return rc;
+    if (int rc = dlogp.ensure(R * 4)) return rc;
+    if (int rc = dbest.ensure(R * 4)) return rc;
+    if (int rc = drank.ensure(R * 4)) return rc;
+    if (int rc = dcoef.ensure((size_t)B * 4)) return rc;
+    if (int rc = dq.ensure((size_t)B * 8)) return rc;
+    if (int rc = drisk.ensure((size_t)G * 8)) return rc;
+    if (int rc = dparts.ensure((size_t)G * 8)) return rc;
+    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dt.p, target, R * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dw.p, weight, R * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(dc.p, cost, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemsetAsync(dl.p, 0, 16, m->stream));
+    launch_risk_head(dx.as<float>(), dt.as<int>(), dw.as<float>(), dc.as<float>(), B, U, V, Vp, N, alpha, inv, dlogp.as<float>(),
+                     dbest.as<int>(), drank.as<int>(), dcoef.as<float>(), dq.as<double>(), drisk.as<double>(), dparts.as<double>(),
+                     dl.as<double>(), m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(loss, dl.p, 8, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(q, dq.p, (size_t)B * 8, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(coef, dcoef.p, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+    if (want_grad) HIPCHK(hipMemcpyAsync(x.data(), dx.p, x.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (int b = 0; b < B && want_grad; ++b)
+        for (int u = 0; u < U; ++u) {
+            const float* row = &x[((size_t)u * B + b) * Vp];
+            for (int v = V; v < Vp; ++v)
+                if (row[v] != 0.f) return fail(CASV_ERR_HIP, "risk head: padding column %d of row (%d, %d) is %g, not zero", v, b, u, (double)row[v]);
+            memcpy(dlogits + ((size_t)b * U + u) * V, row, (size_t)V * 4);
         }
     return CASV_OK;
 }

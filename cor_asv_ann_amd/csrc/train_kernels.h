@@ -51,6 +51,14 @@ void launch_soft_ce(float* logits, const int* soft_idx, const float* soft_q, con
 // gives NaN / -1 / -1.  Columns [V, Vp) are never read.
 void launch_score_rows(const float* logits, const int* target, int B, int U, int V, int Vp, float* logp, int* best, int* rank,
                        hipStream_t st);
+// The minimum-risk head (casv_train_step_risk; include/cor_asv_ann_hip.h has the definition) on the logits [U*B][Vp]: the rows form
+// G = B / N groups of N lines, cost [B] (negative: not a member), inv = 1 / max(groups with a member, 1).  launch_score_rows into
+// logp / best / rank [B][U], then one wave per group (coef [B] float32, q [B], risk [G], parts [G] = inv * risk_g), ordered_sum of
+// the parts into *loss, then dlogits in place, one wave per row.  1 <= N <= 64, B a multiple of N; one order of every sum
+// whatever the launch shape.  Columns [V, Vp) are never read and written as zeros.
+void launch_risk_head(float* logits, const int* target, const float* weight, const float* cost, int B, int U, int V, int Vp, int N,
+                      double alpha, double inv, float* logp, int* best, int* rank, float* coef, double* q, double* risk,
+                      double* parts, double* loss, hipStream_t st);
 // ... nll[b] = sum_u -(double)logp[b][u] over the scored positions in the order of u, count[b] = how many
 void launch_score_lines(const float* logp, const int* target, int B, int U, int V, double* nll, int* count, hipStream_t st);
 // ... the cell's attention rows Ast [U+1][B][T] / windows WIN [U][B] in window form, (B,U) order: lo, w [K] per step

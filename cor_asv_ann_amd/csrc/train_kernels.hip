@@ -355,6 +355,96 @@ void launch_score_rows(const float* logits, const int* target, int B, int U, int
     hipLaunchKernelGGL(score_rows_kernel, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, rows, B, U, V, Vp, logp, best, rank);
 }
 
+// ---- minimum-risk head (casv_train_step_risk): N costed candidates per group, the coefficients formed between forward and backward ----
+// Three launches on the logits [U*B][Vp]: score_rows_kernel leaves logp [B][U] (its best / rank are by-products nobody reads);
+// risk_weight_kernel turns them into one coefficient per line; risk_grad_kernel writes dL/dlogits in place.
+__device__ __forceinline__ double readlane_d(const double v, const int k) {      // k wave-uniform
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
+}
+// One wave per group g, lane i < N holds candidate i = line g * N + i: its cost (negative: not a member), its own serial float64
+// sum s over u ascending of (double)(w * logp) -- a float32 product -- at the positions the loss heads score (0 <= t < V, w != 0).
+// Max, Z and the risk are taken across the lanes by serial readlane loops in i, outside every divergent branch: one order
+// whatever the launch shape, no LDS, no atomics.  Writes coef [B] (float32), q [B], risk [G] (0 for a group without members)
+// and parts[g] = inv * risk_g, which ordered_sum adds to the loss.  Reads logp / target / weight below B * U, cost below B = G * N.
+__global__ __launch_bounds__(256) void risk_weight_kernel(const float* __restrict__ logp, const int* __restrict__ target,
+                                                          const float* __restrict__ weight, const float* __restrict__ cost, int G, int N,
+                                                          int U, int V, double alpha, double inv, float* __restrict__ coef,
+                                                          double* __restrict__ q_out, double* __restrict__ risk_out,
+                                                          double* __restrict__ parts) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long long g = blockIdx.x * 4LL + wave; g < G; g += 4LL * gridDim.x) {
+        const long long b = g * N + lane;
+        const float cst = lane < N ? cost[b] : -1.0f;
+        const bool member = cst >= 0.0f;
+        double s = 0.0;
+        if (member)
+            for (int u = 0; u < U; ++u) {
+                const int tg = target[b * U + u];
+                const float wgt = weight[b * U + u];
+                if (tg >= 0 && tg < V && wgt != 0.0f) s += (double)(wgt * logp[b * U + u]);
+            }
+        const double z = alpha * s;
+        const unsigned long long members = __ballot(member);
+        double M = -INFINITY;
+        for (int i = 0; i < N; ++i) {
+            const double zi = readlane_d(z, i);
+            if ((members >> i) & 1ull) M = zi > M ? zi : M;               // (a NaN is passed by here and reaches Z through its own e)
+        }
+        const double e = member ? exp(z - M) : 0.0;
+        double Z = 0.0;
+        for (int i = 0; i < N; ++i) Z += readlane_d(e, i);
+        const double q = member ? e / Z : 0.0;
+        const double term = member ? q * (double)cst : 0.0;
+        double risk = 0.0;
+        for (int i = 0; i < N; ++i) risk += readlane_d(term, i);
+        const double c = member ? alpha * q * ((double)cst - risk) * inv : 0.0;
+        if (lane < N) { coef[b] = (float)c; q_out[b] = q; }
+        if (lane == 0) { risk_out[g] = members ? risk : 0.0; parts[g] = members ? inv * risk : 0.0; }
+    }
+}
+// One wave per logits row r = u * B + b, m and sum formed as softmax_ce_kernel forms them: dlogit[v] = coef[b] * w * ([v == t] - p_v),
+// a zero row where the position is not scored (t outside [0, V), w = 0).  One store per element, by the lane that owns it; no LDS,
+// no atomics.  Columns [V, Vp) are never read and written as zeros.
+__global__ __launch_bounds__(256) void risk_grad_kernel(float* __restrict__ logits, const int* __restrict__ target,
+                                                        const float* __restrict__ weight, const float* __restrict__ coef, long long rows,
+                                                        int B, int U, int V, int Vp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long long r = blockIdx.x * 4LL + wave; r < rows; r += 4LL * gridDim.x) {
+        float* x = logits + r * Vp;
+        const long long b = r % B, src = b * U + r / B;
+        const int tg = target[src];
+        const float wgt = weight[src];
+        if (tg < 0 || tg >= V || wgt == 0.0f) {             // (the same in every lane)
+            for (int v = lane; v < Vp; v += 64) x[v] = 0.0f;
+            continue;
+        }
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+        m = wave_butterfly(m, [](float a, float b) { return fmaxf(a, b); });
+        float sum = 0.f;
+        for (int v = lane; v < V; v += 64) sum += expf(x[v] - m);
+        sum = wsum(sum);
+        const float sc = coef[b] * wgt;
+        for (int v = lane; v < Vp; v += 64) {
+            float gvl = 0.f;
+            if (v < V) gvl = sc * ((v == tg ? 1.0f : 0.0f) - expf(x[v] - m) / sum);
+            x[v] = gvl;
+        }
+    }
+}
+void launch_risk_head(float* logits, const int* target, const float* weight, const float* cost, int B, int U, int V, int Vp, int N,
+                      double alpha, double inv, float* logp, int* best, int* rank, float* coef, double* q, double* risk,
+                      double* parts, double* loss, hipStream_t st) {
+    const int G = B / N;
+    const long long rows = (long long)B * U;
+    const long long wgs = std::min<long long>((rows + 3) / 4, 2048);
+    launch_score_rows(logits, target, B, U, V, Vp, logp, best, rank, st);
+    hipLaunchKernelGGL(risk_weight_kernel, dim3((unsigned)std::min((G + 3) / 4, 2048)), dim3(256), 0, st, logp, target, weight, cost, G, N,
+                       U, V, alpha, inv, coef, q, risk, parts);
+    ordered_sum(parts, G, loss, st);
+    hipLaunchKernelGGL(risk_grad_kernel, dim3((unsigned)wgs), dim3(256), 0, st, logits, target, weight, coef, rows, B, U, V, Vp);
+}
+
 // ---- the K likeliest entries and the entropy of every row (casv_score_get_alternatives) ----
 // The order (alt_key) and the wave-wide maximum of its keys: alt_order.h, shared with the sampling pick (sample_kernels.hip).
 // One wave per row, as score_rows_kernel, and its m, sum and validity formed by the same two loops (lane-strided, then the wave

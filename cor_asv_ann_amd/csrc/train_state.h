@@ -52,6 +52,7 @@ struct TrainState {
     DevBuf d_gold, d_mix;                  // casv_train_step_sampled: the gold decoder input [B][U] (d_in holds the mix), every pass's mix [passes][B][U]
     std::vector<int32_t> h_mix;            // ... and ("deterministic") the last mix on the host, for the decoder's character segments
     DevBuf d_sidx, d_sq;                   // casv_train_step_soft: the soft targets' slots [B][U][K] (index, mass) in place of d_out
+    DevBuf r_cost, r_coef, r_q, r_risk, r_parts;   // casv_train_step_risk: cost / coefficient / q [B], risk and its share of the loss [G] (logp: s_logp)
     DevBuf X0, H1, u, Y0, Ym, WQ, Ast, WIN, RecIn, logits, dG, d_enc, du, DWQ, DSrows, dhatt, dfin, dcbuf, dcbuf2, dX0, dXtop, dXl, dYl, dOin, dvaP, dbvP;
     std::vector<DevBuf> O, DO;             // masked layer outputs (encoder O[n], decoder DO[n])
     std::vector<DevBuf> XD;                // deep_bidirectional_encoder: layer n's input = the cross sum of O[n-1] (seq2seq.py:246-259)

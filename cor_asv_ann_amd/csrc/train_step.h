@@ -14,6 +14,7 @@ struct Step {
     const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const int32_t* dec_out; const float* weights;
     const float* mask_enc; const float* mask_dec; const float* mask_cell;
     int K; const int32_t* soft_idx; const float* soft_q;      // casv_train_step_soft: K > 0, (B,U,K) slots in place of dec_out (nullptr)
+    int RN; const float* cost; double alpha, inv_groups;     // casv_train_step_risk: RN > 0 candidates per group, cost (B), 1 / max(groups with a member, 1)
     const casv_sched_params* sched; int32_t* mix_out;         // casv_train_step_sampled with ratio > 0: the passes' parameters, (passes,B,U) out
     const casv_sample_cut* cut;     // casv_train_step_sampled_cut: the cut of the sampled pick (nullptr: none)
     int W, V, Vp, C, D;

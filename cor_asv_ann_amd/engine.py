@@ -466,6 +466,36 @@ class HipEngine(object):
                                                nv.ptr(m_cell), byref(loss), byref(norm)))
         return loss.value, norm.value
 
+    def train_step_risk(self, enc_idx, enc_val, dec_in, dec_out, weights, cost, n, alpha=1.0, masks=None, mode=1, details=False):
+        """train_step with the minimum-risk head (casv_train_step_risk): the B rows are B // n groups of n candidate lines, row
+        g * n + i = candidate i of group g; cost (B) float32, a finite value >= 0 = a member with that cost, negative = not a
+        member.  The loss is the mean over the groups with a member of sum_i q_i cost_i, q the model's distribution renormalised
+        over the group's members with sharpness alpha.  mode 1 or 2; 1 <= n <= 64, B a multiple of n, costs finite, alpha finite and
+        > 0 (NativeError CASV_ERR_ARG otherwise, nothing touched).  Returns (loss, grad_norm), with details=True (loss, grad_norm,
+        q (B) float64, risk (B // n) float64)."""
+        enc_idx = nv.carray(enc_idx, np.int32)
+        if enc_idx.ndim == 2:
+            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
+        B, T, A = enc_idx.shape
+        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        dec_in = nv.carray(dec_in, np.int32)
+        dec_out = nv.carray(dec_out, np.int32)
+        weights = nv.carray(weights, np.float32)
+        cost = None if cost is None else nv.carray(cost, np.float32)
+        U = dec_in.shape[1]
+        assert dec_out.shape == (B, U) and weights.shape == (B, U) and (cost is None or cost.shape == (B,))
+        m_enc, m_dec, m_cell = self._step_masks(masks)
+        n = int(n)
+        q = np.empty((B,), np.float64) if details else None
+        risk = np.empty((max(B // max(n, 1), 1),), np.float64) if details else None
+        loss, norm = c_double(), c_double()
+        nv.check(self.lib.casv_train_step_risk(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
+                                               nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell), n,
+                                               nv.ptr(cost), float(alpha), nv.ptr(q), nv.ptr(risk), byref(loss), byref(norm)))
+        if details:
+            return loss.value, norm.value, q, risk[:B // n]
+        return loss.value, norm.value
+
     @staticmethod
     def _sched_params(seed, step_id, ratio, pick, passes, temperature):
         picks = {'greedy': 0, 'sample': 1}
@@ -767,6 +797,26 @@ class HipEngine(object):
                                                   float(inv_count), float(pad_value), int(bool(want_grad)), byref(loss), nv.ptr(dlogits),
                                                   int(bool(ordered))))
         return loss.value, dlogits
+
+    def debug_risk_rows(self, logits, target, weight, cost, n, alpha=1.0, pad_value=0.0, want_grad=True):
+        """Test support (casv_debug_risk_rows): the minimum-risk head alone on logits (B,U,V), targets / weights (B,U) and cost (B),
+        B = groups * n; the padding columns of the device rows hold pad_value and are checked to come back as zeros.  Returns
+        (loss float64, q (B) float64, coef (B) float32, dlogits (B,U,V) or None)."""
+        logits = nv.carray(logits, np.float32)
+        target = nv.carray(target, np.int32)
+        weight = nv.carray(weight, np.float32)
+        cost = nv.carray(cost, np.float32)
+        B, U, V = logits.shape
+        n = int(n)
+        assert target.shape == (B, U) and weight.shape == (B, U) and cost.shape == (B,) and n >= 1 and B % n == 0
+        loss = c_double()
+        q = np.empty((B,), np.float64)
+        coef = np.empty((B,), np.float32)
+        dlogits = np.empty((B, U, V), np.float32) if want_grad else None
+        nv.check(self.lib.casv_debug_risk_rows(self.handle, B // n, n, U, V, nv.ptr(logits), nv.ptr(target), nv.ptr(weight), nv.ptr(cost),
+                                               float(alpha), float(pad_value), int(bool(want_grad)), byref(loss), nv.ptr(q), nv.ptr(coef),
+                                               nv.ptr(dlogits)))
+        return loss.value, q, coef, dlogits
 
     # -- measurement ---------------------------------------------------------------------------
     def profile(self, enable=True):

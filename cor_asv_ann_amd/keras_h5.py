@@ -28,6 +28,8 @@ layers that is not named in `layer_names`, so that keras' `load_weights` and thi
     /training_state/{distill_k,distill_alpha}   int64 / float64 scalars: a distilled run's K and alpha (absent: no teacher)
     /training_state/sample                      bytes: JSON of a scheduled-sampling run's settings {seed, schedule, pick, passes,
                                                 temperature} (absent: no sample_schedule)
+    /training_state/risk                        bytes: JSON of a minimum-risk run's settings {seed, samples, alpha, temperature, top_k,
+                                                top_p, own_proposal} (absent: no risk_samples)
     /training_state/rng                         bytes: JSON of the numpy bit generator's state
     /training_state/split_rand                  float64[lines]: the validation split (absent: validation files were given)
     /training_state/history_{loss,val_loss}     float64[epochs]
@@ -261,6 +263,8 @@ def _write_state(w, st):
         w.create_dataset(g + 'distill_alpha', np.asarray(float(st['distill'][1]), np.float64))
     if st.get('sample') is not None:
         w.create_dataset(g + 'sample', np.bytes_(json.dumps(st['sample'], sort_keys=True).encode('utf-8')))
+    if st.get('risk') is not None:
+        w.create_dataset(g + 'risk', np.bytes_(json.dumps(st['risk'], sort_keys=True).encode('utf-8')))
     if st.get('split_rand') is not None:
         w.create_dataset(g + 'split_rand', np.asarray(st['split_rand'], np.float64))
     hist = st.get('history') or []
@@ -295,6 +299,8 @@ def read_training_state(filename):
             st['distill'] = (int(np.asarray(g['distill_k'].read())), float(np.asarray(g['distill_alpha'].read())))
         if 'sample' in g:              # (a scheduled-sampling run only)
             st['sample'] = json.loads(text('sample'))
+        if 'risk' in g:                # (a minimum-risk run only)
+            st['risk'] = json.loads(text('risk'))
         st['history'] = []
         if 'history_loss' in g:
             st['history'] = [{'loss': float(a), 'val_loss': float(b)} for a, b in

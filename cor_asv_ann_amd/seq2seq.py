@@ -1474,7 +1474,8 @@ class Sequence2Sequence(object):
                 self.logger.info('%s %-7s %.3f±%.3f', what, labels[k].strip() + ':', counts[k].mean, math.sqrt(counts[k].varia))
 
     def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
-              sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0):
+              sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0,
+              risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None):
         """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
         from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
         restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint).
@@ -1494,9 +1495,24 @@ class Sequence2Sequence(object):
         checkpoints, and `resume` refuses other values.  Validation stays teacher-forced.  Not together with `teacher`
         (ValueError).  sample_top_k (0..4095) / sample_top_p (in (0, 1]): the 'sample' pick draws under this cut, as
         `sample_lines(top_k=, top_p=)` does (`casv_train_step_sampled_cut`); not with sample_pick='greedy' (ValueError); a cut that
-        is set joins the recorded settings, a run without one writes the checkpoints it always wrote."""
+        is set joins the recorded settings, a run without one writes the checkpoints it always wrote.
+        risk_samples: minimum-risk training (Shen et al. 2016; `HipEngine.train_step_risk`) on n = 2..64
+        candidates per source, at most `batch_size` -- every loaded batch is taken `batch_size` // n sources at a time; per source
+        the gold target (candidate 0) joins n - 1 lines that `proposal.sample_lines` draws at `risk_temperature` under the cut
+        `risk_top_k` / `risk_top_p`; an exact duplicate of an earlier candidate leaves the set; a candidate's cost is its edit
+        distance to the gold line over the gold line's length (`consensus_of(distances=True)`); the step lowers the cost expected
+        under the model's own distribution over the set, sharpened by `risk_alpha`.  proposal: a second configured and loaded
+        `Sequence2Sequence` with this model's `voc_size` and mapping (checked like a teacher), or None for a private copy of
+        this model whose weights are refreshed from the training weights at the start of every epoch.  The training loss in
+        `history` is then the mean expected cost; validation stays the hard loss.  The candidates' seed is drawn once from the
+        model's generator, the stream ids are the lines' running numbers; the settings and the seed go into the state checkpoints
+        and `resume` refuses other values; a run without `risk_samples` writes the checkpoints it always wrote.  Not together
+        with `teacher` or `sample_schedule` (ValueError, before anything runs)."""
         from .training import train_files, cut_is_set
         cut = {'sample_top_k': sample_top_k, 'sample_top_p': sample_top_p} if cut_is_set(sample_top_k, sample_top_p) else {}
+        if risk_samples or proposal is not None:
+            cut.update(risk_samples=risk_samples, risk_alpha=risk_alpha, risk_temperature=risk_temperature, risk_top_k=risk_top_k,
+                       risk_top_p=risk_top_p, proposal=proposal)
         return train_files(self, filenames, val_filenames, resume=resume, teacher=teacher, distill_k=distill_k,
                            distill_alpha=distill_alpha, sample_schedule=sample_schedule, sample_pick=sample_pick,
                            sample_passes=sample_passes, sample_temperature=sample_temperature, **cut)

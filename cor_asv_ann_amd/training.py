@@ -2,7 +2,8 @@
 generator, validation, early stopping / NaN termination / per-epoch checkpoints.  Each batch is ONE call into
 the C ABI (`casv_train_step`), which runs forward, backward, clipping and Adam on the device.  With a teacher
 (distillation) a batch is the teacher's scoring call, its K alternatives per position and `casv_train_step_soft`; with a
-sample schedule (scheduled sampling) it is `casv_train_step_sampled` at the epoch's ratio."""
+sample schedule (scheduled sampling) it is `casv_train_step_sampled` at the epoch's ratio; with risk samples (minimum-risk
+training) it is slices of sources with their candidate sets, each `casv_train_step_risk` (`risk_step`)."""
 import math
 import queue
 import signal
@@ -98,10 +99,24 @@ def validation_batches(s2s, filenames, split_rand):
         yield batch_to_indices(s2s, src, tgt, conf)
 
 
+def line_batches(s2s, filenames, split_rand):
+    """One epoch of training batches as gen_lines loads them, (source lines, confidences, target lines): what `risk_step` takes."""
+    for batch in s2s.gen_lines(filenames, True, split_rand, True):
+        if not batch:
+            return
+        src, conf, tgt, _ = batch
+        yield src, conf, tgt
+
+
 def batch_to_indices(s2s, lines_source, lines_target, lines_conf):
     """The arrays of vectorize_lines (seq2seq.py:1020-1119) in index form: encoder (idx, val) (B,T,A),
     decoder input / target character indices (B,U) with -1 for true-zero rows, temporal weights (B,U)."""
     idx, val, _ = s2s._sparse_lines(lines_source, lines_conf)
+    return (idx, val) + targets_to_indices(s2s, lines_target)
+
+
+def targets_to_indices(s2s, lines_target):
+    """The decoder side of batch_to_indices: (dec_in, dec_out, weights), each (B,U)."""
     B = len(lines_target)
     U = max(map(len, lines_target)) + 1
     dec_in = np.full((B, U), -1, np.int32)
@@ -111,7 +126,7 @@ def batch_to_indices(s2s, lines_source, lines_target, lines_conf):
         dec_in[i, 1:len(codes) + 1] = codes
         dec_out[i, :len(codes)] = codes
     weights = (dec_out >= 0).astype(np.float32)
-    return idx, val, dec_in, dec_out, weights
+    return dec_in, dec_out, weights
 
 
 def degrade(idx, val, rng):
@@ -312,8 +327,131 @@ def check_sampling_resume(state, filename, settings):
             raise ValueError('cannot resume from "%s": sample %s differs (file %r, now %r)' % (filename, key, theirs.get(key), settings.get(key)))
 
 
+def check_risk(s2s, risk_samples, risk_alpha, risk_temperature, risk_top_k, risk_top_p, proposal, teacher, sample_schedule):
+    """The minimum-risk keywords of train(), checked on the host before anything runs: ValueError with the first fault.  The
+    proposal (None: a private copy of the model) is checked like a teacher: another, loaded model with this model's vocabulary
+    size and character mapping -- its candidates are vectorised with this model's mapping."""
+    if teacher is not None:
+        raise ValueError('risk_samples together with teacher: soft targets and minimum-risk training do not combine')
+    if sample_schedule is not None:
+        raise ValueError('risk_samples together with sample_schedule: scheduled sampling and minimum-risk training do not combine')
+    try:
+        ok = int(risk_samples) == risk_samples and 2 <= int(risk_samples) <= 64
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('risk_samples must be an int in [2, 64] (0: none), got %r' % (risk_samples,))
+    if risk_samples > s2s.batch_size:
+        raise ValueError('risk_samples=%d candidates per source do not fit batch_size=%d decoder rows' % (risk_samples, s2s.batch_size))
+    for name, value in (('risk_alpha', risk_alpha), ('risk_temperature', risk_temperature)):
+        try:
+            ok = math.isfinite(float(value)) and float(value) > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('%s must be finite and positive, got %r' % (name, value))
+    check_cut(risk_top_k, risk_top_p, 'risk_')
+    if proposal is None:
+        return
+    if proposal is s2s:
+        raise ValueError('the proposal must be another model than the one in training (None: a private copy of it)')
+    if getattr(proposal, 'status', 0) != 2:
+        raise ValueError('the proposal must be a configured and loaded model (status 2), its status is %r' % getattr(proposal, 'status', None))
+    if proposal.voc_size != s2s.voc_size:
+        raise ValueError('proposal and model differ in voc_size (proposal %d, model %d)' % (proposal.voc_size, s2s.voc_size))
+    if proposal.mapping[0] != s2s.mapping[0]:
+        theirs, mine = proposal.mapping[0], s2s.mapping[0]
+        char = next(c for c in sorted(set(theirs) | set(mine)) if theirs.get(c) != mine.get(c))
+        raise ValueError('proposal and model differ in their character mapping (%r: proposal %r, model %r)'
+                         % (char, theirs.get(char), mine.get(char)))
+
+
+def check_risk_resume(state, filename, settings):
+    """A minimum-risk run resumes with the settings it recorded (its seed is taken from the file), a plain run as a plain run:
+    ValueError otherwise."""
+    theirs = state.get('risk')
+    if theirs is None and settings is None:
+        return
+    if theirs is None:
+        raise ValueError('cannot resume from "%s": it was trained without risk_samples' % filename)
+    if settings is None:
+        raise ValueError('cannot resume from "%s": it was trained with risk_samples=%r' % (filename, theirs['samples']))
+    for key in ('samples', 'alpha', 'temperature', 'top_k', 'top_p', 'own_proposal'):
+        if theirs.get(key) != settings.get(key):
+            raise ValueError('cannot resume from "%s": risk %s differs (file %r, now %r)' % (filename, key, theirs.get(key), settings.get(key)))
+
+
+def proposal_copy(s2s):
+    """A second model of `s2s`'s shape, mapping and device with a handle of its own, for the candidates of a minimum-risk run
+    without a given proposal; train_files installs the training weights at the start of every epoch."""
+    copy = type(s2s)(logger=s2s.logger, progbars=False, device=s2s.device)
+    for name in ('batch_size', 'stateful', 'width', 'depth', 'residual_connections', 'deep_bidirectional_encoder', 'bridge_dense',
+                 'arithmetic', 'voc_size'):
+        setattr(copy, name, getattr(s2s, name))
+    copy.mapping = s2s.mapping
+    copy._rng = np.random.default_rng(0)     # (configure()'s initial weights are replaced before use: nothing is drawn from the model's generator)
+    copy.configure()
+    copy.status = 2
+    return copy
+
+
+def risk_candidates(proposal, src, conf, tgt, settings, first_stream):
+    """The candidate sets of the sources `src`: per source the gold line `tgt` as candidate 0 and samples - 1 lines drawn from the
+    proposal (stream ids first_stream + the source's index).  Returns (candidates, cost): the lists per source and the float32
+    costs in row order g * samples + i -- the candidate's edit distance to the gold line over max(len(gold), 1), and -1 for an
+    exact duplicate of an earlier candidate of the same source (not a member of its set).  The distances are one row of the
+    N x N matrix that `consensus_of` computes on the device."""
+    n = settings['samples']
+    drawn = proposal.sample_lines(src, conf, n=n - 1, temperature=settings['temperature'], top_k=settings['top_k'], seed=settings['seed'],
+                                  streams=[first_stream + j for j in range(len(src))], top_p=settings['top_p'])[0]
+    candidates = [[gold] + list(lines) for gold, lines in zip(tgt, drawn)]
+    dists = proposal.consensus_of(candidates, distances=True)[2]
+    cost = np.empty((len(src) * n,), np.float32)
+    for g, cands in enumerate(candidates):
+        assert len(cands) == n, 'source %d has %d candidates, not %d' % (g, len(cands), n)
+        for i, line in enumerate(cands):
+            cost[g * n + i] = -1.0 if line in cands[:i] else dists[g][0][i] / max(len(cands[0]), 1)
+    return candidates, cost
+
+
+def risk_step(engine, proposal, batch, settings, rng):
+    """One loaded training batch (source lines, confidences, target lines) under minimum-risk training: the batch is taken
+    batch_size // samples sources at a time, so that a step never has more decoder rows than batch_size; each slice gets its
+    candidate sets (`risk_candidates`), is vectorised as a hard batch would be -- the sources degraded and repeated once per
+    candidate, the dropout masks drawn for the slice's rows -- and stepped with `HipEngine.train_step_risk`.  settings: the run's
+    recorded settings plus 'model' (whose mapping vectorises), 'batch_size' and 'stream', the running number of the next line,
+    which this advances.  Returns the slices' losses."""
+    s2s, n = settings['model'], settings['samples']
+    src, conf, tgt = batch
+    per_slice = max(settings['batch_size'] // n, 1)
+    losses = []
+    for start in range(0, len(src), per_slice):
+        part = slice(start, start + per_slice)
+        lines, lines_conf = src[part], (conf[part] if conf else conf)
+        candidates, cost = risk_candidates(proposal, lines, lines_conf, tgt[part], settings, settings['stream'])
+        settings['stream'] += len(lines)
+        idx, val, _ = s2s._sparse_lines(lines, lines_conf)
+        idx, val = degrade(idx, val, rng)
+        idx, val = np.repeat(idx, n, axis=0), np.repeat(val, n, axis=0)
+        dec_in, dec_out, w = targets_to_indices(s2s, [line for cands in candidates for line in cands])
+        masks = dropout_masks(s2s, len(lines) * n, rng)
+        loss, _ = engine.train_step_risk(idx, val, dec_in, dec_out, w, cost, n, settings['alpha'], masks, mode=1)
+        losses.append(loss)
+        if not np.isfinite(loss):
+            break
+    return losses
+
+
 def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
-                sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0):
+                sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0,
+                risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None):
+    risk = None                              # minimum-risk training: what the checkpoints record (the seed joins below)
+    if risk_samples:
+        check_risk(s2s, risk_samples, risk_alpha, risk_temperature, risk_top_k, risk_top_p, None, teacher, sample_schedule)
+        risk = {'samples': int(risk_samples), 'alpha': float(risk_alpha), 'temperature': float(risk_temperature),
+                'top_k': int(risk_top_k), 'top_p': float(risk_top_p), 'own_proposal': proposal is None}
+    elif proposal is not None:
+        raise ValueError('proposal without risk_samples: there is nothing to propose for')
     sampling = None                          # scheduled sampling: what the checkpoints record (the seed joins below)
     if sample_schedule is not None:
         check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher, sample_top_k, sample_top_p)
@@ -332,10 +470,13 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
         split_rand = None
     if teacher is not None:
         check_teacher(s2s, teacher, distill_k, distill_alpha)    # (after map_files: the student's mapping is final only now)
+    if risk is not None and proposal is not None:
+        check_risk(s2s, risk_samples, risk_alpha, risk_temperature, risk_top_k, risk_top_p, proposal, teacher, sample_schedule)
     state = resume_state(s2s, resume) if resume else None        # (after map_files: the mapping is part of what must match)
     if state is not None:
         check_distill_resume(state, resume, teacher, distill_k, distill_alpha)
         check_sampling_resume(state, resume, sampling)
+        check_risk_resume(state, resume, risk)
     if val_filenames:
         if state is not None and state['split_rand'] is not None:
             raise ValueError('cannot resume from "%s": it was trained without validation files' % resume)
@@ -352,12 +493,17 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
     rng = s2s._rng
     if sampling is not None:                 # the coins' seed: drawn once per run, a resumed run keeps its own
         sampling['seed'] = int(state['sample']['seed']) if state is not None else int(rng.integers(0, 2 ** 63))
+    if risk is not None:                     # the candidates' seed, likewise
+        risk['seed'] = int(state['risk']['seed']) if state is not None else int(rng.integers(0, 2 ** 63))
     engine = s2s._require_engine()
     engine.set_option('deterministic', 1 if s2s.deterministic else 0)
     teacher_engine = None
     if teacher is not None:
         teacher_engine = teacher._require_engine()
         teacher_engine.set_option('deterministic', 1 if s2s.deterministic else 0)      # (governs the scoring pass as it governs a step)
+    own_proposal = None
+    if risk is not None and proposal is None:        # a private copy of the model: its weights follow the training weights per epoch
+        proposal = own_proposal = proposal_copy(s2s)
     adam = tuple(state['adam']) if state is not None else ADAM
     engine.train_begin(*adam, frozen=tuple(s2s.frozen_prefixes))
     if state is not None:
@@ -386,8 +532,25 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
             total, nb = 0.0, 0
             nan = cut = False
             ratio = schedule_ratio(sample_schedule, epoch, s2s.epochs) if sampling is not None else None
+            if risk is not None:
+                # every random draw of a minimum-risk epoch happens in this thread (risk_step): the worker only loads lines; the
+                # lines' running numbers start at epoch * 2^32, so that a resumed run draws what the uninterrupted one drew
+                if own_proposal is not None:
+                    own_proposal.set_weights(engine.train_weights())
+                settings = dict(risk, model=s2s, batch_size=s2s.batch_size, stream=epoch << 32)
+                for batch in prefetch(line_batches(s2s, filenames, split_rand)):
+                    losses = risk_step(engine, proposal, batch, settings, rng)
+                    if not all(np.isfinite(losses)):
+                        s2s.logger.warning('Batch %d: Invalid loss, terminating training', nb)
+                        nan = True
+                        break
+                    total += sum(losses) / max(len(losses), 1); nb += 1
+                    if stop['flag']:
+                        cut = True
+                        break
             # the next batches are vectorised by a worker thread while the device runs this one (kt:133-145)
-            for idx, val, dec_in, dec_out, w, masks in prefetch(train_batches(s2s, filenames, split_rand, rng)):
+            hard_batches = prefetch(train_batches(s2s, filenames, split_rand, rng)) if risk is None else ()
+            for idx, val, dec_in, dec_out, w, masks in hard_batches:
                 if teacher_engine is not None:
                     loss, _ = distill_step(engine, teacher_engine, (idx, val, dec_in, dec_out, w, masks), distill_k, distill_alpha)
                 elif sampling is not None:
@@ -434,6 +597,8 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
                     ckpt_state['distill'] = (int(distill_k), float(distill_alpha))
                 if sampling is not None:
                     ckpt_state['sample'] = dict(sampling)
+                if risk is not None:
+                    ckpt_state['risk'] = dict(risk)
             keras_h5.write_model('model.ckpt.weights-%02d-%.2f.h5' % (epoch + 1, val_loss), s2s._config_dict(), weights, ckpt_state)
             if wait >= 3:                              # EarlyStopping(patience=3, restore_best_weights)
                 s2s.logger.info('Epoch %05d: early stopping', epoch + 1)
@@ -446,6 +611,9 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
         engine.train_end()
         if teacher_engine is not None:
             teacher_engine.score_release()             # (the teacher's forward-only scoring state)
+        if own_proposal is not None and own_proposal.engine is not None:
+            own_proposal.engine.close()
+            own_proposal.engine = None
     s2s.history = history
     if best_weights is not None:
         s2s.logger.info('training finished with val_loss %f', best)

@@ -288,6 +288,44 @@ int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int32_t T, int3
 int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, const int32_t* soft_idx,
                             const float* soft_q, const float* weight, float inv_count, float pad_value, int32_t want_grad,
                             double* loss, float* dlogits, int32_t ordered);
+/* casv_train_step with the minimum-risk head (Shen et al. 2016) in place of the cross-entropy: the expected
+ * cost of N costed candidates per source under the model's own distribution renormalised over the set.  Arrays, masks, the options
+ * ("deterministic", "persistent", "fused_backward", the arithmetic), the give-up path, clip and Adam are casv_train_step's.  The
+ * rows form G = B / N groups of N candidates, candidate i of group g being line b = g * N + i; the caller puts the same source
+ * into the rows of a group (the entry does not check it, the math does not need it).  cost (B) float32: a finite value >= 0 makes
+ * the line a member of its group with that cost, any negative value marks a line that is not a member (padding, or a duplicate the
+ * caller removed).  alpha is finite and > 0.  Per position (b,u) with t = dec_out[b,u] >= 0 and w = weights[b,u] != 0 the entry
+ * forms logp[b,u] as casv_score_targets forms it (float32, log domain, not clipped), then works in float64:
+ *   s_b     = sum over u ascending of (double)(w * logp[b,u])      (float32 product, double adds)
+ *   members of group g:  z_i = alpha * s_i,  M = max z_i,  e_i = exp(z_i - M),  Z = sum e_i (i ascending)
+ *   q_i     = e_i / Z            risk_g = sum q_i * cost_i (i ascending)
+ *   inv     = 1 / max(number of groups with at least one member, 1)
+ *   c_i     = alpha * q_i * (cost_i - risk_g) * inv        non-members: q = 0, c = 0
+ *   loss    = sum of inv * risk_g, added in one fixed order  (+ the embedding regulariser where casv_train_step adds it)
+ *   dlogit[(u,b)][v] = (float)c_b * w * ([v == t] - p_v)   p_v = expf(x_v - m) / sum as the hard head forms it
+ * -- the gradient of the loss: d risk_g / d s_i = alpha * q_i * (cost_i - risk_g) and d logp / d x_v = [v == t] - p_v, so a
+ * candidate that costs more than its group expects has its characters made less likely.
+ * Rows with t = -1 or w = 0 get a zero gradient row; columns [V, Vp) are never read and are written as zeros.  There is no
+ * inv_count and no 1e-7 clip: this is not Keras' loss (the reference has no such head).  A group without members adds nothing and
+ * is not counted (its out_risk is 0); a group whose members all have s = -inf, or that holds a NaN, gives a NaN loss, as the hard
+ * step does on NaN logits.  out_q (B) and out_risk (G) are doubles and may be NULL.  The sums have one order whatever the launch
+ * shape: the head is deterministic with or without the "deterministic" option.  N = 1 is legal: q = 1, c = 0, a zero gradient, the
+ * loss is the mean cost.  Refused with CASV_ERR_ARG before anything is enqueued or cleared, the session's step count, moments and
+ * gradients untouched: mode 0; N < 1, N > 64 or B not a multiple of N; a NULL cost; a cost that is NaN or infinite; an alpha that
+ * is not finite or <= 0; whatever casv_train_step refuses. */
+int casv_train_step_risk(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
+                         const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
+                         const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
+                         int32_t N, const float* cost, double alpha, double* out_q, double* out_risk,
+                         double* loss, double* grad_norm);
+/* Test support, like casv_debug_soft_ce_rows: the minimum-risk head alone on the caller's logits (G*N, U, V), targets and weights
+ * (G*N, U) in the caller's order and cost (G*N), checked as casv_train_step_risk checks them (targets in [-1, V)).  The entry lays
+ * the rows out as the step does (row u * B + b, stride Vp = (V+31)&~31) and fills the columns [V, Vp) with pad_value, which no
+ * output may depend on.  *loss, q (G*N) doubles, coef (G*N) float32; want_grad != 0: dlogits (G*N, U, V) = the first V columns after
+ * the launch, and the entry checks that the padding columns came back as zeros (CASV_ERR_HIP with a message otherwise). */
+int casv_debug_risk_rows(casv_model* m, int32_t G, int32_t N, int32_t U, int32_t V, const float* logits, const int32_t* target,
+                         const float* weight, const float* cost, double alpha, float pad_value, int32_t want_grad,
+                         double* loss, double* q, float* coef, float* dlogits);
 /* casv_train_step with scheduled sampling in its parallel form (Duckworth et al. 2019): the teacher-forced
  * forward pass, then `passes` times { logits of the current tape; a pick at every decoder position from the logits of the position
  * before it; a coin per position; the decoder again on the mixed input }, then casv_train_step's loss head, backward pass, clip and
