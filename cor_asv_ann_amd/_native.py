@@ -82,6 +82,11 @@ class DebugBwdJob(Structure):
                 ('ld_out', c_int64)]
 
 
+# what every casv_train_step* entry begins with: handle, mode, B, T, U, A, then enc_idx, enc_val, dec_in
+_STEP = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+# ... the hard-target entries go on with dec_out, weights and the three masks
+_STEP_HARD = _STEP + [c_void_p] * 5
+
 # name -> (restype, argtypes); every symbol declared in the header is listed here and checked at load
 SIGNATURES = {
     'casv_last_error': (c_char_p, []),
@@ -106,7 +111,7 @@ SIGNATURES = {
     'casv_debug_sample_cut_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SampleParams), POINTER(SampleCut), c_int32, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_float] + [c_void_p] * 4),
     'casv_train_begin': (c_int, [c_void_p, POINTER(AdamParams), c_char_p]),
-    'casv_train_step': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8 + [POINTER(c_double), POINTER(c_double)]),
+    'casv_train_step': (c_int, _STEP_HARD + [POINTER(c_double)] * 2),
     'casv_train_get_gradient': (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     'casv_train_get_state': (c_int, [c_void_p, c_char_p, c_int32, c_void_p, c_int64]),
     'casv_train_set_state': (c_int, [c_void_p, c_char_p, c_int32, c_void_p, c_int64]),
@@ -123,19 +128,15 @@ SIGNATURES = {
     'casv_consensus_align': (c_int, [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 5),
     'casv_consensus_vote': (c_int, [c_void_p, c_int32] + [c_void_p] * 4),
     'casv_debug_set_align_budget': (c_int, [c_void_p, c_int64]),
-    'casv_train_step_soft': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32]
-                             + [c_void_p] * 6 + [POINTER(c_double), POINTER(c_double)]),
-    'casv_train_step_sampled': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
-                                + [POINTER(SchedParams), c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_train_step_soft': (c_int, _STEP + [c_int32] + [c_void_p] * 6 + [POINTER(c_double)] * 2),
+    'casv_train_step_sampled': (c_int, _STEP_HARD + [POINTER(SchedParams), c_void_p] + [POINTER(c_double)] * 2),
     'casv_debug_sched_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SchedParams)] + [c_void_p] * 4 + [c_float, c_void_p]),
-    'casv_train_step_sampled_cut': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
-                                    + [POINTER(SchedParams), POINTER(SampleCut), c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_train_step_sampled_cut': (c_int, _STEP_HARD + [POINTER(SchedParams), POINTER(SampleCut), c_void_p] + [POINTER(c_double)] * 2),
     'casv_debug_sched_cut_rows': (c_int, [c_void_p, c_int32, c_int32, POINTER(SchedParams), POINTER(SampleCut)] + [c_void_p] * 4
                                   + [c_float, c_void_p]),
     'casv_debug_soft_ce_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                         c_int32, POINTER(c_double), c_void_p, c_int32]),
-    'casv_train_step_risk': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 8
-                             + [c_int32, c_void_p, c_double, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double)]),
+    'casv_train_step_risk': (c_int, _STEP_HARD + [c_int32, c_void_p, c_double, c_void_p, c_void_p] + [POINTER(c_double)] * 2),
     'casv_debug_risk_rows': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                      c_float, c_int32, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     'casv_debug_score_rows': (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1,5 +1,5 @@
 // Host side of the C ABI (include/cor_asv_ann_hip.h): the handle, weight repacking, result records, statistics, profile, debug entry
-// points and options.  The decode entry points are decode.hip, the encoder pass (seq2seq.py:237-314) encoder.hip, the training session train_state.hip, its step train.hip, scoring score.hip.
+// points and options.  The decode entry points are decode.hip, the encoder pass (seq2seq.py:237-314) encoder.hip, the training session train_state.hip, its step train.hip, scoring score.hip, the row heads' test entries debug_rows.hip.
 #include "engine.h"
 
 static std::map<std::string, size_t> expected_shapes(const casv_config& c) {

@@ -108,17 +108,11 @@ static int score_call(casv_model* m, int32_t Be, int32_t N, int32_t T, int32_t U
     SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (the forward pass of a mode-0 step, in its arithmetic)
     OrderedScope ordered(m, m->deterministic);
     const std::vector<float> ones((size_t)UB, 1.0f);            // (stage_inputs stages the step's sample weights: the head reads none)
-    Step s{};
-    s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = 0; s.B = B; s.Be = Be; s.N = N; s.T = T; s.U = U; s.A = A;
-    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.dec_out = dec_out; s.weights = ones.data();
-    s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * Be; s.UB = UB;
+    Step s = step_view(m, StepArgs{0, B, T, U, A, enc_idx, enc_val, dec_in}, Be, N);
+    s.dec_out = dec_out; s.weights = ones.data();
     // (no masks, no regulariser; det / fused govern the backward pass and the ordered sums of the loss: the head has neither, and
     // persist_launch and the launchers read the "deterministic" option from the handle)
     s.training = false; s.det = false; s.fused = false;
-    s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
-    s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool redo = false;
         if (int rc = score_attempt(s, out, &redo)) return rc;
@@ -181,116 +175,4 @@ extern "C" int casv_score_get_alternatives(casv_model* m, int32_t K, int32_t* al
     if (entropy) HIPCHK(hipMemcpyAsync(entropy, ts->s_entropy.p, n * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return CASV_OK;
-}
-
-// Test support: the head alone on the caller's logits (R,V), laid out with the library's row stride and the padding filled.
-extern "C" int casv_debug_score_rows(casv_model* m, int32_t R, int32_t V, const float* logits, const int32_t* target, float pad_value,
-                                     float* logp, int32_t* best, int32_t* rank) {
-    if (!m || !logits || !target || !logp || !best || !rank) return fail(CASV_ERR_ARG, "null argument");
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DevBuf dx, dt, dl, db, dr;
-    DebugBuffers release_on_exit{m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    for (DevBuf* b : {&dt, &dl, &db, &dr}) if (int rc = b->ensure((size_t)R * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dt.p, target, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
-    launch_score_rows(dx.as<float>(), dt.as<int>(), R, 1, V, Vp, dl.as<float>(), db.as<int>(), dr.as<int>(), m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(logp, dl.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(best, db.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(rank, dr.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// Test support: score_alternatives_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out.
-extern "C" int casv_debug_alternatives_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, float pad_value,
-                                            int32_t* alt_idx, float* alt_logp, float* entropy) {
-    if (!m || !logits || !alt_idx || !alt_logp) return fail(CASV_ERR_ARG, "null argument");
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    if (K < 1 || K > V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, V < 64 ? V : 64);
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DevBuf dx, di, dl, de;
-    DebugBuffers release_on_exit{m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    if (int rc = di.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = dl.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = de.ensure((size_t)R * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    launch_score_alternatives(dx.as<float>(), R, 1, V, Vp, K, di.as<int>(), dl.as<float>(), entropy ? de.as<float>() : nullptr, m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(alt_idx, di.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(alt_logp, dl.p, (size_t)R * K * 4, hipMemcpyDeviceToHost, m->stream));
-    if (entropy) HIPCHK(hipMemcpyAsync(entropy, de.p, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return CASV_OK;
-}
-
-// Test support: sample_kernel (cut == nullptr) or sample_cut_kernel alone on the caller's logits (R,V), laid out as
-// casv_debug_score_rows lays them out.
-static int debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, const casv_sample_cut* cut, int32_t step,
-                             const int64_t* stream, const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
-                             float* out_logp, float* out_logq, float* out_feedback) {
-    if (!logits || !out_feedback) return fail(CASV_ERR_ARG, "null argument");
-    if (!m || !p || !out_idx || !out_logp || !out_logq) return fail(CASV_ERR_ARG, "null argument");
-    if (!(p->temperature > 0.f) || !(p->temperature < INFINITY)) return fail(CASV_ERR_ARG, "temperature=%g must be finite and positive", (double)p->temperature);
-    if (p->top_k < 0 || p->top_k > 64) return fail(CASV_ERR_ARG, "top_k=%d out of range 0..64", p->top_k);
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    if (step < 0 || step >= 2 * CASV_MAX_T) return fail(CASV_ERR_ARG, "step=%d out of range 0..%d", step, 2 * CASV_MAX_T - 1);
-    HIPCHK(hipSetDevice(m->device));
-    if (cut && !sample_cut_ready()) return fail(CASV_ERR_HIP, "the runtime refused sample_cut_kernel's %d bytes of dynamic LDS", SAMPLE_CUT_LDS);
-    const int Vp = (V + 31) & ~31;           // (the library's row stride: engine.hip, casv_model_create)
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DebugBuffers bufs{m->stream};
-    int rc = 0;
-    SampleArgs a{};
-    a.logits = static_cast<const float*>(bufs.put(x.data(), x.size(), rc)); if (rc) return rc;
-    // (the output slot is step + 1 of a store whose slots all lie on the one (R,Vp) buffer)
-    a.feedback = static_cast<float*>(bufs.put(nullptr, (size_t)R * Vp, rc)); if (rc) return rc;
-    a.fb_slot = 0; a.R = R; a.V = V; a.step_imm = step; a.rows_per_line = 1;
-    if (stream) { a.stream = static_cast<const long long*>(bufs.put(stream, (size_t)R * 2, rc)); if (rc) return rc; }
-    if (sample) { a.sample = static_cast<const int*>(bufs.put(sample, (size_t)R, rc)); if (rc) return rc; }
-    if (u) { a.u = static_cast<const float*>(bufs.put(u, (size_t)R, rc)); if (rc) return rc; }
-    a.seed = p->seed; a.temperature = p->temperature; a.top_k = p->top_k;
-    a.out_idx = static_cast<int*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
-    a.out_logp = static_cast<float*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
-    a.out_logq = static_cast<float*>(bufs.put(nullptr, (size_t)R, rc)); if (rc) return rc;
-    a.S = 1; a.out_col = 0;
-    hipEvent_t ev{};
-    m->prof_begin(PC_SAMPLE, 4.0 * R * V, 4.0 * R * (V + Vp), ev);
-    if (cut) {
-        a.top_k = cut->top_k; a.top_p = cut->top_p;
-        m->stat_sample_cut_rows = launch_sample_cut(a, m->sample_cut_rows_opt, m->stream);
-    } else launch_sample(a, m->stream);
-    m->prof_end(PC_SAMPLE, ev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_idx, a.out_idx, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_logp, a.out_logp, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_logq, a.out_logq, (size_t)R * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(out_feedback, a.feedback, (size_t)R * Vp * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (m->prof.on) m->prof.collect();
-    return CASV_OK;
-}
-
-extern "C" int casv_debug_sample_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, int32_t step, const int64_t* stream,
-                                      const int32_t* sample, const float* logits, const float* u, float pad_value, int32_t* out_idx,
-                                      float* out_logp, float* out_logq, float* out_feedback) {
-    return debug_sample_rows(m, R, V, p, nullptr, step, stream, sample, logits, u, pad_value, out_idx, out_logp, out_logq, out_feedback);
-}
-
-extern "C" int casv_debug_sample_cut_rows(casv_model* m, int32_t R, int32_t V, const casv_sample_params* p, const casv_sample_cut* cut,
-                                          int32_t step, const int64_t* stream, const int32_t* sample, const float* logits, const float* u,
-                                          float pad_value, int32_t* out_idx, float* out_logp, float* out_logq, float* out_feedback) {
-    if (int rc = check_sample_cut(cut)) return rc;
-    if (p && p->top_k != 0) return fail(CASV_ERR_ARG, "top_k=%d beside a cut: the cut carries it", p->top_k);
-    return debug_sample_rows(m, R, V, p, cut, step, stream, sample, logits, u, pad_value, out_idx, out_logp, out_logq, out_feedback);
 }

@@ -1044,38 +1044,62 @@ int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo) {
     return CASV_OK;
 }
 
-// The view of a step on hard or soft targets (dec_out or the slots are the caller's to add): what the caller passed, the model's
+// The view of a step of Be lines with N decoder rows each (the targets are the entry's to add): what the caller passed, the model's
 // shapes, the step's flags.
-Step step_view(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A, const int32_t* enc_idx, const float* enc_val,
-               const int32_t* dec_in, const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell) {
+Step step_view(casv_model* m, const StepArgs& a, int Be, int N) {
     Step s{};
     s.m = m; s.ts = m->train; s.st = m->stream;
-    s.mode = mode; s.B = B; s.Be = B; s.N = 1; s.T = T; s.U = U; s.A = A;
-    s.enc_idx = enc_idx; s.enc_val = enc_val; s.dec_in = dec_in; s.weights = weights;
-    s.mask_enc = mask_enc; s.mask_dec = mask_dec; s.mask_cell = mask_cell;
+    s.mode = a.mode; s.B = Be * N; s.Be = Be; s.N = N; s.T = a.T; s.U = a.U; s.A = a.A;
+    s.enc_idx = a.enc_idx; s.enc_val = a.enc_val; s.dec_in = a.dec_in; s.weights = a.weights;
+    s.mask_enc = a.mask_enc; s.mask_dec = a.mask_dec; s.mask_cell = a.mask_cell;
     s.W = m->W; s.V = m->V; s.Vp = m->Vp; s.C = m->C; s.D = m->D;
-    s.TB = (long long)T * B; s.UB = (long long)U * B;
-    s.training = mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
+    s.TB = (long long)a.T * Be; s.UB = (long long)a.U * s.B;
+    s.training = a.mode != 0; s.det = m->deterministic; s.fused = m->fused_backward && !s.det;
     s.deep = m->cfg.deep_bidirectional_encoder != 0 && s.D >= 2;
     s.residual = m->cfg.residual_connections != 0; s.bridged = m->cfg.bridge_dense != 0;
     return s;
 }
+
+// What every step entry refuses, in this order (own_pointers: the entry's own arguments are there; modes min_mode .. 2 pass).
+int check_step_args(const casv_model* m, const StepArgs& a, bool own_pointers, int min_mode, const char* mode_message) {
+    if (!m || !a.enc_idx || !a.dec_in || !own_pointers || !a.weights || !a.loss_out) return fail(CASV_ERR_ARG, "null argument");
+    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
+    if (a.B < 1 || a.T < 1 || a.U < 1 || a.A < 1) return fail(CASV_ERR_ARG, "bad shape");
+    if (a.mode < min_mode || a.mode > 2) return fail(CASV_ERR_ARG, "%s", mode_message);
+    return CASV_OK;
+}
+
+// The body of every step entry behind its checks: the scopes that make the step's bits a function of the options alone, its view
+// with the entry's fields (fill), at most two attempts, what the entry takes from a finished one (done).
+int run_step(casv_model* m, const StepArgs& a, const StepHook& fill, const StepHook& done) {
+    HIPCHK(hipSetDevice(m->device));
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
+    OrderedScope ordered(m, m->deterministic);
+    Step s = step_view(m, a, a.B, 1);
+    if (int rc = fill(s)) return rc;
+    // A persistent recurrence that gave up (in a scheduled-sampling pass too) sets the back-off: the second attempt takes per-step launches only.
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool redo = false;
+        if (int rc = train_attempt(s, a.loss_out, a.norm_out, &redo)) return rc;
+        if (!redo) return done ? done(s) : CASV_OK;
+    }
+    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
+}
 }  // namespace casv
+
+static const char* const kStepModes = "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)";
 
 extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
                                const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
                                const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
                                double* loss_out, double* norm_out) {
-    if (!m || !enc_idx || !dec_in || !dec_out || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
-    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
-    if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
+    const StepArgs a{mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out};
+    if (int rc = check_step_args(m, a, dec_out, 0, kStepModes)) return rc;
+    // (run_step's body spelled out: tests/test_train_form_cases.py reads the step's launch order from this function's text)
     HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));       // (engine.h: the whole-sequence contractions with a split form take the bf16x3-split arithmetic)
+    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
     OrderedScope ordered(m, m->deterministic);
-    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
-    s.dec_out = dec_out;
-    // A persistent recurrence that gave up sets the back-off, so the second attempt takes per-step launches only and cannot give up.
+    Step s = step_view(m, a, B, 1); s.dec_out = dec_out;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool redo = false;
         if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
@@ -1085,7 +1109,7 @@ extern "C" int casv_train_step(casv_model* m, int32_t mode, int32_t B, int32_t T
 }
 
 // The soft targets' rules (include/cor_asv_ann_hip.h), checked on the host before anything is launched or cleared: O(B*U*K).
-static int check_soft_targets(long long positions, int K, int V, const int32_t* soft_idx, const float* soft_q) {
+int check_soft_targets(long long positions, int K, int V, const int32_t* soft_idx, const float* soft_q) {
     if (K < 1 || K > V || K > 64) return fail(CASV_ERR_ARG, "K=%d outside [1, min(V, 64)] = [1, %d]", K, V < 64 ? V : 64);
     for (long long p = 0; p < positions; ++p) {
         const int32_t* ix = soft_idx + p * K; const float* q = soft_q + p * K;
@@ -1100,71 +1124,20 @@ static int check_soft_targets(long long positions, int K, int V, const int32_t* 
     return CASV_OK;
 }
 
-// casv_train_step with the target array replaced by K (index, mass) slots per position: the same view, the same attempts.
+// casv_train_step with the target array replaced by K (index, mass) slots per position.
 extern "C" int casv_train_step_soft(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
                                     const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, int32_t K,
                                     const int32_t* soft_idx, const float* soft_q, const float* weights, const float* mask_enc,
                                     const float* mask_dec, const float* mask_cell, double* loss_out, double* norm_out) {
-    if (!m || !enc_idx || !dec_in || !soft_idx || !soft_q || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
-    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
-    if (mode < 0 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 0 (evaluate), 1 (train) or 2 (gradients only)");
+    const StepArgs a{mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out};
+    if (int rc = check_step_args(m, a, soft_idx && soft_q, 0, kStepModes)) return rc;
     if (int rc = check_soft_targets((long long)B * U, K, m->V, soft_idx, soft_q)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
-    OrderedScope ordered(m, m->deterministic);
-    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
-    s.K = K; s.soft_idx = soft_idx; s.soft_q = soft_q;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        bool redo = false;
-        if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
-        if (!redo) return CASV_OK;
-    }
-    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
-}
-
-// Test support: soft_ce_kernel alone on the caller's logits (R,V), laid out as casv_debug_score_rows lays them out (B = R, U = 1).
-extern "C" int casv_debug_soft_ce_rows(casv_model* m, int32_t R, int32_t V, int32_t K, const float* logits, const int32_t* soft_idx,
-                                       const float* soft_q, const float* weight, float inv_count, float pad_value, int32_t want_grad,
-                                       double* loss, float* dlogits, int32_t ordered) {
-    if (!m || !logits || !soft_idx || !soft_q || !weight || !loss || (want_grad && !dlogits)) return fail(CASV_ERR_ARG, "null argument");
-    if (R < 1 || R > (1 << 20) || V < 1 || V > 4096) return fail(CASV_ERR_ARG, "R must be in [1, 2^20], V in [1, 4096]");
-    if (int rc = check_soft_targets(R, K, V, soft_idx, soft_q)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;
-    std::vector<float> x((size_t)R * Vp, pad_value);
-    for (int r = 0; r < R; ++r) memcpy(&x[(size_t)r * Vp], logits + (size_t)r * V, (size_t)V * 4);
-    DevBuf dx, di, dq, dw, dl, dp;
-    DebugBuffers release_on_exit{m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    if (int rc = di.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = dq.ensure((size_t)R * K * 4)) return rc;
-    if (int rc = dw.ensure((size_t)R * 4)) return rc;
-    if (int rc = dl.ensure(16)) return rc;
-    if (int rc = dp.ensure((size_t)2048 * 8)) return rc;         // (launch_soft_ce: at most 2048 workgroups)
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(di.p, soft_idx, (size_t)R * K * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dq.p, soft_q, (size_t)R * K * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dw.p, weight, (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemsetAsync(dl.p, 0, 16, m->stream));
-    launch_soft_ce(dx.as<float>(), di.as<int>(), dq.as<float>(), dw.as<float>(), R, 1, V, Vp, K, inv_count, dl.as<double>(),
-                   want_grad ? 1 : 0, m->stream, ordered ? dp.as<double>() : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(loss, dl.p, 8, hipMemcpyDeviceToHost, m->stream));
-    if (want_grad) HIPCHK(hipMemcpyAsync(x.data(), dx.p, x.size() * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (want_grad)
-        for (int r = 0; r < R; ++r) {
-            for (int v = V; v < Vp; ++v)
-                if (x[(size_t)r * Vp + v] != 0.f) return fail(CASV_ERR_HIP, "soft head: padding column %d of row %d is %g, not zero", v, r, (double)x[(size_t)r * Vp + v]);
-            memcpy(dlogits + (size_t)r * V, &x[(size_t)r * Vp], (size_t)V * 4);
-        }
-    return CASV_OK;
+    return run_step(m, a, [&](Step& s) { s.K = K; s.soft_idx = soft_idx; s.soft_q = soft_q; return 0; });
 }
 
 // The risk head's rules (include/cor_asv_ann_hip.h), checked on the host before anything is launched or cleared: O(B).  *inv = 1 /
 // max(number of groups with at least one member, 1).
-static int check_risk(int B, int N, const float* cost, double alpha, double* inv) {
+int check_risk(int B, int N, const float* cost, double alpha, double* inv) {
     if (N < 1 || N > 64 || B % N) return fail(CASV_ERR_ARG, "N=%d: 1 <= N <= 64 and B=%d a multiple of N", N, B);
     if (!cost) return fail(CASV_ERR_ARG, "null argument");
     if (!(alpha > 0.0) || alpha == (double)INFINITY) return fail(CASV_ERR_ARG, "alpha = %g: finite and > 0", alpha);
@@ -1182,91 +1155,22 @@ static int check_risk(int B, int N, const float* cost, double alpha, double* inv
     return CASV_OK;
 }
 
-// casv_train_step with the minimum-risk head in place of the cross-entropy: the same view, the same attempts.
+// casv_train_step with the minimum-risk head in place of the cross-entropy; a finished step hands over the head's q and risks.
 extern "C" int casv_train_step_risk(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A,
                                     const int32_t* enc_idx, const float* enc_val, const int32_t* dec_in, const int32_t* dec_out,
                                     const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell,
                                     int32_t N, const float* cost, double alpha, double* out_q, double* out_risk,
                                     double* loss_out, double* norm_out) {
-    if (!m || !enc_idx || !dec_in || !dec_out || !weights || !loss_out) return fail(CASV_ERR_ARG, "null argument");
-    if (!m->train) return fail(CASV_ERR_STATE, "casv_train_begin must run first");
-    if (B < 1 || T < 1 || U < 1 || A < 1) return fail(CASV_ERR_ARG, "bad shape");
-    if (mode < 1 || mode > 2) return fail(CASV_ERR_ARG, "mode must be 1 (train) or 2 (gradients only): the risk has no evaluation form");
+    const StepArgs a{mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell, loss_out, norm_out};
+    if (int rc = check_step_args(m, a, dec_out, 1, "mode must be 1 (train) or 2 (gradients only): the risk has no evaluation form")) return rc;
     double inv = 1.0;
     if (int rc = check_risk(B, N, cost, alpha, &inv)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    SplitScope arithmetic(m, arithmetic_of(m, ENTRY_TRAIN));
-    OrderedScope ordered(m, m->deterministic);
-    Step s = step_view(m, mode, B, T, U, A, enc_idx, enc_val, dec_in, weights, mask_enc, mask_dec, mask_cell);
-    s.dec_out = dec_out;
-    s.RN = N; s.cost = cost; s.alpha = alpha; s.inv_groups = inv;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        bool redo = false;
-        if (int rc = train_attempt(s, loss_out, norm_out, &redo)) return rc;
-        if (redo) continue;
-        TrainState* ts = m->train;             // (the attempt has waited for the stream)
-        if (out_q) HIPCHK(hipMemcpy(out_q, ts->r_q.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-        if (out_risk) HIPCHK(hipMemcpy(out_risk, ts->r_risk.p, (size_t)(B / N) * 8, hipMemcpyDeviceToHost));
-        return CASV_OK;
-    }
-    return fail(CASV_ERR_STATE, "the train step gave up twice: its second attempt took a persistent launch");
-}
-
-// Test support: the risk head alone on the caller's logits (B = G * N, U, V) in the caller's (b, u) order, laid out as the step
-// lays them out (row u * B + b, stride Vp, the padding columns filled with pad_value) -- casv_debug_soft_ce_rows with U steps.
-extern "C" int casv_debug_risk_rows(casv_model* m, int32_t G, int32_t N, int32_t U, int32_t V, const float* logits, const int32_t* target,
-                                    const float* weight, const float* cost, double alpha, float pad_value, int32_t want_grad,
-                                    double* loss, double* q, float* coef, float* dlogits) {
-    if (!m || !logits || !target || !weight || !loss || !q || !coef || (want_grad && !dlogits)) return fail(CASV_ERR_ARG, "null argument");
-    if (G < 1 || U < 1 || V < 1 || V > 4096 || N < 1 || N > 64 || (long long)G * N * U > (1 << 20))
-        return fail(CASV_ERR_ARG, "G, U >= 1, N in [1, 64], G * N * U <= 2^20, V in [1, 4096]");
-    const int B = G * N;
-    const size_t R = (size_t)B * U;
-    double inv = 1.0;
-    if (int rc = check_risk(B, N, cost, alpha, &inv)) return rc;
-    for (size_t i = 0; i < R; ++i)
-        if (target[i] < -1 || target[i] >= V) return fail(CASV_ERR_ARG, "target[%zu] = %d outside [-1, %d)", i, target[i], V);
-    HIPCHK(hipSetDevice(m->device));
-    const int Vp = (V + 31) & ~31;
-    std::vector<float> x(R * Vp, pad_value);
-    for (int b = 0; b < B; ++b)
-        for (int u = 0; u < U; ++u) memcpy(&x[((size_t)u * B + b) * Vp], logits + ((size_t)b * U + u) * V, (size_t)V * 4);
-    DevBuf dx, dt, dw, dc, dl, dlogp, dbest, drank, dcoef, dq, drisk, dparts;
-    DebugBuffers release_on_exit{m->stream};
-    if (int rc = dx.ensure(x.size() * 4)) return rc;
-    if (int rc = dt.ensure(R * 4)) return rc;
-    if (int rc = dw.ensure(R * 4)) return rc;
-    if (int rc = dc.ensure((size_t)B * 4)) return rc;
-    if (int rc = dl.ensure(16)) return rc;
-    if (int rc = dlogp.ensure(R * 4)) return rc;
-    if (int rc = dbest.ensure(R * 4)) return rc;
-    if (int rc = drank.ensure(R * 4)) return rc;
-    if (int rc = dcoef.ensure((size_t)B * 4)) return rc;
-    if (int rc = dq.ensure((size_t)B * 8)) return rc;
-    if (int rc = drisk.ensure((size_t)G * 8)) return rc;
-    if (int rc = dparts.ensure((size_t)G * 8)) return rc;
-    HIPCHK(hipMemcpyAsync(dx.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dt.p, target, R * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dw.p, weight, R * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(dc.p, cost, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemsetAsync(dl.p, 0, 16, m->stream));
-    launch_risk_head(dx.as<float>(), dt.as<int>(), dw.as<float>(), dc.as<float>(), B, U, V, Vp, N, alpha, inv, dlogp.as<float>(),
-                     dbest.as<int>(), drank.as<int>(), dcoef.as<float>(), dq.as<double>(), drisk.as<double>(), dparts.as<double>(),
-                     dl.as<double>(), m->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(loss, dl.p, 8, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(q, dq.p, (size_t)B * 8, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(coef, dcoef.p, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-    if (want_grad) HIPCHK(hipMemcpyAsync(x.data(), dx.p, x.size() * 4, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    for (int b = 0; b < B && want_grad; ++b)
-        for (int u = 0; u < U; ++u) {
-            const float* row = &x[((size_t)u * B + b) * Vp];
-            for (int v = V; v < Vp; ++v)
-                if (row[v] != 0.f) return fail(CASV_ERR_HIP, "risk head: padding column %d of row (%d, %d) is %g, not zero", v, b, u, (double)row[v]);
-            memcpy(dlogits + ((size_t)b * U + u) * V, row, (size_t)V * 4);
-        }
-    return CASV_OK;
+    return run_step(m, a, [&](Step& s) { s.dec_out = dec_out; s.RN = N; s.cost = cost; s.alpha = alpha; s.inv_groups = inv; return 0; },
+        [&](Step& s) {                         // (the attempt has waited for the stream)
+            if (out_q) HIPCHK(hipMemcpy(out_q, s.ts->r_q.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+            if (out_risk) HIPCHK(hipMemcpy(out_risk, s.ts->r_risk.p, (size_t)(B / N) * 8, hipMemcpyDeviceToHost));
+            return 0;
+        });
 }
 
 // Test support: one backward time step of 1 or 2 layers on host data (casv_debug_bwd_step), in the fused form or as the two

@@ -2,6 +2,7 @@
 // runs the first four and the projection in front of its own head).
 #pragma once
 #include "train_state.h"
+#include <functional>
 
 namespace casv {
 
@@ -58,11 +59,29 @@ int decoder_layer_alone(Step& s, int k, const float* y);      // decoder layer k
 int sched_passes(Step& s);          // between 4 and 5, casv_train_step_sampled only (train_sched.hip): the passes of scheduled sampling
 // per-character segments of an index array [B][L][A_] for the ordered embedding gradient ("deterministic")
 void char_segments(const int32_t* idx, int B, int L, int A_, int V, std::vector<int>& off, std::vector<int>& pos);
-// One attempt at the step, the phases in order; *redo: a persistent recurrence gave up, the caller starts over.  step_view: the view
-// an entry hands it (the targets are the entry's to add).
+// One attempt at the step, the phases in order; *redo: a persistent recurrence gave up, the caller starts over.
 int train_attempt(Step s, double* loss_out, double* norm_out, bool* redo);
-Step step_view(casv_model* m, int32_t mode, int32_t B, int32_t T, int32_t U, int32_t A, const int32_t* enc_idx, const float* enc_val,
-               const int32_t* dec_in, const float* weights, const float* mask_enc, const float* mask_dec, const float* mask_cell);
+
+// What every step entry takes from its caller, as the C ABI names it (B: the step's batch).
+struct StepArgs {
+    int32_t mode, B, T, U, A;
+    const int32_t* enc_idx; const float* enc_val; const int32_t* dec_in; const float* weights;
+    const float* mask_enc; const float* mask_dec; const float* mask_cell;
+    double* loss_out; double* norm_out;
+};
+// The view of Be lines with N decoder rows each that an entry hands an attempt (the targets are the entry's to add).
+Step step_view(casv_model* m, const StepArgs& a, int Be, int N);
+// The step entries' common refusals and common body (train.hip): fill adds the entry's fields to the view, done (if any) takes what
+// the entry hands back beside loss and norm from the attempt that finished; either returns 0 or the error the call ends with.
+using StepHook = std::function<int(Step&)>;
+int check_step_args(const casv_model* m, const StepArgs& a, bool own_pointers, int min_mode, const char* mode_message);
+int run_step(casv_model* m, const StepArgs& a, const StepHook& fill, const StepHook& done = nullptr);
 int recurrences_gave_up(casv_model* m, bool& any);      // did a persistent recurrence so far give up?  (then nothing has been updated)
 
 }  // namespace casv
+
+// The rules of an entry's own arguments, which its head's test entry (debug_rows.hip) checks as the entry does
+int check_soft_targets(long long positions, int K, int V, const int32_t* soft_idx, const float* soft_q);   // train.hip
+int check_risk(int B, int N, const float* cost, double alpha, double* inv);
+int check_sched_params(const casv_sched_params* p, bool with_passes);                                      // train_sched.hip
+int check_sched_cut(const casv_sched_params* p, const casv_sample_cut* cut);

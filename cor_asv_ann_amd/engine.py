@@ -422,49 +422,52 @@ class HipEngine(object):
         m_cell = nv.carray(self._padw(np.asarray(masks['cell'], np.float32), 1 + self.cblocks), np.float32)
         return m_enc, m_dec, m_cell
 
-    def train_step(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1):
-        """One train_on_batch (mode 1), test_on_batch (mode 0) or loss+gradients (mode 2).
-        enc_idx (B,T[,A]) int32, dec_in/dec_out (B,U) int32 (-1 = zero row), weights (B,U).
-        masks: {'enc': [..], 'dec': [..], 'cell': (B,W+C)} of scaled keep-masks, or None."""
+    @staticmethod
+    def _encoder_batch(enc_idx, enc_val):
+        """The encoder's half of a batch as the library takes it: enc_idx (B,T,A) int32 (from (B,T[,A])), enc_val float32 of that
+        shape or None, and (B, T, A)."""
         enc_idx = nv.carray(enc_idx, np.int32)
         if enc_idx.ndim == 2:
             enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
         B, T, A = enc_idx.shape
         enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        return enc_idx, enc_val, (B, T, A)
+
+    def _step_batch(self, enc_idx, enc_val, dec_in):
+        """_encoder_batch and the decoder input (B,U) int32 beside it: enc_idx, enc_val, dec_in, (B, T, A, U)."""
+        enc_idx, enc_val, (B, T, A) = self._encoder_batch(enc_idx, enc_val)
         dec_in = nv.carray(dec_in, np.int32)
-        dec_out = nv.carray(dec_out, np.int32)
-        weights = nv.carray(weights, np.float32)
-        U = dec_in.shape[1]
-        m_enc, m_dec, m_cell = self._step_masks(masks)
+        return enc_idx, enc_val, dec_in, (B, T, A, dec_in.shape[1])
+
+    def _step_call(self, entry, mode, batch, targets, weights, masks, extra=()):
+        """One call of a casv_train_step* entry on a _step_batch: the common arguments with the entry's targets between dec_in and
+        the weights and what else it takes (`extra`) in front of loss and norm.  Returns (loss, grad_norm)."""
+        enc_idx, enc_val, dec_in, (B, T, A, U) = batch
         loss, norm = c_double(), c_double()
-        nv.check(self.lib.casv_train_step(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                          nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
-                                          byref(loss), byref(norm)))
+        nv.check(entry(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), *targets, nv.ptr(weights),
+                       *[nv.ptr(m) for m in self._step_masks(masks)], *extra, byref(loss), byref(norm)))
         return loss.value, norm.value
+
+    def train_step(self, enc_idx, enc_val, dec_in, dec_out, weights, masks=None, mode=1):
+        """One train_on_batch (mode 1), test_on_batch (mode 0) or loss+gradients (mode 2).
+        enc_idx (B,T[,A]) int32, dec_in/dec_out (B,U) int32 (-1 = zero row), weights (B,U).
+        masks: {'enc': [..], 'dec': [..], 'cell': (B,W+C)} of scaled keep-masks, or None."""
+        batch = self._step_batch(enc_idx, enc_val, dec_in)
+        dec_out = nv.carray(dec_out, np.int32)
+        return self._step_call(self.lib.casv_train_step, mode, batch, (nv.ptr(dec_out),), nv.carray(weights, np.float32), masks)
 
     def train_step_soft(self, enc_idx, enc_val, dec_in, soft_idx, soft_q, weights, masks=None, mode=1):
         """train_step on soft targets (casv_train_step_soft): soft_idx int32 / soft_q float32 (B,U,K) hold K (index, mass) slots
         per position in place of dec_out -- index -1 = empty slot, all empty = zero row, masses finite and >= 0, a position's indices
         distinct, 1 <= K <= min(V, 64) (NativeError CASV_ERR_ARG otherwise, nothing touched).  One slot (dec_out, 1.0) is the hard
         step.  Everything else as train_step; returns (loss, grad_norm)."""
-        enc_idx = nv.carray(enc_idx, np.int32)
-        if enc_idx.ndim == 2:
-            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
-        B, T, A = enc_idx.shape
-        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
-        dec_in = nv.carray(dec_in, np.int32)
+        batch = self._step_batch(enc_idx, enc_val, dec_in)
+        (B, _, _, U) = batch[3]
         soft_idx = nv.carray(soft_idx, np.int32)
         soft_q = nv.carray(soft_q, np.float32)
         weights = nv.carray(weights, np.float32)
-        U = dec_in.shape[1]
         assert soft_idx.ndim == 3 and soft_idx.shape[:2] == (B, U) and soft_q.shape == soft_idx.shape and weights.shape == (B, U)
-        K = soft_idx.shape[2]
-        m_enc, m_dec, m_cell = self._step_masks(masks)
-        loss, norm = c_double(), c_double()
-        nv.check(self.lib.casv_train_step_soft(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                               K, nv.ptr(soft_idx), nv.ptr(soft_q), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec),
-                                               nv.ptr(m_cell), byref(loss), byref(norm)))
-        return loss.value, norm.value
+        return self._step_call(self.lib.casv_train_step_soft, mode, batch, (soft_idx.shape[2], nv.ptr(soft_idx), nv.ptr(soft_q)), weights, masks)
 
     def train_step_risk(self, enc_idx, enc_val, dec_in, dec_out, weights, cost, n, alpha=1.0, masks=None, mode=1, details=False):
         """train_step with the minimum-risk head (casv_train_step_risk): the B rows are B // n groups of n candidate lines, row
@@ -473,28 +476,18 @@ class HipEngine(object):
         over the group's members with sharpness alpha.  mode 1 or 2; 1 <= n <= 64, B a multiple of n, costs finite, alpha finite and
         > 0 (NativeError CASV_ERR_ARG otherwise, nothing touched).  Returns (loss, grad_norm), with details=True (loss, grad_norm,
         q (B) float64, risk (B // n) float64)."""
-        enc_idx = nv.carray(enc_idx, np.int32)
-        if enc_idx.ndim == 2:
-            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
-        B, T, A = enc_idx.shape
-        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
-        dec_in = nv.carray(dec_in, np.int32)
+        batch = self._step_batch(enc_idx, enc_val, dec_in)
+        (B, _, _, U) = batch[3]
         dec_out = nv.carray(dec_out, np.int32)
         weights = nv.carray(weights, np.float32)
         cost = None if cost is None else nv.carray(cost, np.float32)
-        U = dec_in.shape[1]
         assert dec_out.shape == (B, U) and weights.shape == (B, U) and (cost is None or cost.shape == (B,))
-        m_enc, m_dec, m_cell = self._step_masks(masks)
         n = int(n)
         q = np.empty((B,), np.float64) if details else None
         risk = np.empty((max(B // max(n, 1), 1),), np.float64) if details else None
-        loss, norm = c_double(), c_double()
-        nv.check(self.lib.casv_train_step_risk(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                               nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell), n,
-                                               nv.ptr(cost), float(alpha), nv.ptr(q), nv.ptr(risk), byref(loss), byref(norm)))
-        if details:
-            return loss.value, norm.value, q, risk[:B // n]
-        return loss.value, norm.value
+        out = self._step_call(self.lib.casv_train_step_risk, mode, batch, (nv.ptr(dec_out),), weights, masks,
+                              (n, nv.ptr(cost), float(alpha), nv.ptr(q), nv.ptr(risk)))
+        return out + (q, risk[:B // n]) if details else out
 
     @staticmethod
     def _sched_params(seed, step_id, ratio, pick, passes, temperature):
@@ -510,55 +503,40 @@ class HipEngine(object):
         below `ratio`, and the decoder again; loss, backward pass and update on the last pass.  Modes 1 and 2 only.  Returns
         (loss, grad_norm, mixes) with mixes int32 (passes,B,U): slice p - 1 is the decoder input after pass p.  top_k / top_p:
         the 'sample' pick draws under this cut (casv_train_step_sampled_cut, called only when one of them is set)."""
-        enc_idx = nv.carray(enc_idx, np.int32)
-        if enc_idx.ndim == 2:
-            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
-        B, T, A = enc_idx.shape
-        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
-        dec_in = nv.carray(dec_in, np.int32)
+        batch = self._step_batch(enc_idx, enc_val, dec_in)
+        (B, _, _, U) = batch[3]
         dec_out = nv.carray(dec_out, np.int32)
-        weights = nv.carray(weights, np.float32)
-        U = dec_in.shape[1]
-        m_enc, m_dec, m_cell = self._step_masks(masks)
         p = self._sched_params(seed, step_id, ratio, pick, passes, temperature)
         mixes = np.empty((max(int(passes), 0), B, U), np.int32)
-        loss, norm = c_double(), c_double()
-        if top_k == 0 and top_p == 1.0:
-            nv.check(self.lib.casv_train_step_sampled(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                                      nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec), nv.ptr(m_cell),
-                                                      byref(p), nv.ptr(mixes), byref(loss), byref(norm)))
-        else:
+        entry, extra = self.lib.casv_train_step_sampled, (byref(p), nv.ptr(mixes))
+        if not (top_k == 0 and top_p == 1.0):
             cut = nv.SampleCut(int(top_k), float(top_p))
-            nv.check(self.lib.casv_train_step_sampled_cut(self.handle, int(mode), B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val),
-                                                          nv.ptr(dec_in), nv.ptr(dec_out), nv.ptr(weights), nv.ptr(m_enc), nv.ptr(m_dec),
-                                                          nv.ptr(m_cell), byref(p), byref(cut), nv.ptr(mixes), byref(loss), byref(norm)))
-        return loss.value, norm.value, mixes
+            entry, extra = self.lib.casv_train_step_sampled_cut, (byref(p), byref(cut), nv.ptr(mixes))
+        return self._step_call(entry, mode, batch, (nv.ptr(dec_out),), nv.carray(weights, np.float32), masks, extra) + (mixes,)
 
     def debug_sched_rows(self, logits, gold, b, u, ratio=1.0, seed=0, step_id=0, pick='greedy', temperature=1.0, pad_value=0.0):
         """Test support (casv_debug_sched_rows): the mix kernel alone on logits (R,V) -- row r is decoder position (b[r], u[r])
         with the gold input gold[r]; the padding columns of the device rows hold pad_value.  Returns the mix (R) int32."""
-        logits = nv.carray(logits, np.float32)
-        R, V = logits.shape
-        gold, b, u = (nv.carray(a, np.int32) for a in (gold, b, u))
-        assert gold.shape == b.shape == u.shape == (R,)
-        p = self._sched_params(seed, step_id, ratio, pick, 1, temperature)
-        out = np.empty((R,), np.int32)
-        nv.check(self.lib.casv_debug_sched_rows(self.handle, R, V, byref(p), nv.ptr(b), nv.ptr(u), nv.ptr(logits), nv.ptr(gold),
-                                                float(pad_value), nv.ptr(out)))
-        return out
+        return self._debug_sched_rows(None, logits, gold, b, u, ratio, seed, step_id, pick, temperature, pad_value)
 
     def debug_sched_cut_rows(self, logits, gold, b, u, ratio=1.0, seed=0, step_id=0, pick='sample', temperature=1.0, top_k=0, top_p=1.0,
                              pad_value=0.0):
         """Test support (casv_debug_sched_cut_rows): debug_sched_rows with the sampled pick under the cut (top_k, top_p)."""
+        return self._debug_sched_rows(nv.SampleCut(int(top_k), float(top_p)), logits, gold, b, u, ratio, seed, step_id, pick, temperature,
+                                      pad_value)
+
+    def _debug_sched_rows(self, cut, logits, gold, b, u, ratio, seed, step_id, pick, temperature, pad_value):
         logits = nv.carray(logits, np.float32)
         R, V = logits.shape
         gold, b, u = (nv.carray(a, np.int32) for a in (gold, b, u))
         assert gold.shape == b.shape == u.shape == (R,)
         p = self._sched_params(seed, step_id, ratio, pick, 1, temperature)
-        cut = nv.SampleCut(int(top_k), float(top_p))
         out = np.empty((R,), np.int32)
-        nv.check(self.lib.casv_debug_sched_cut_rows(self.handle, R, V, byref(p), byref(cut), nv.ptr(b), nv.ptr(u), nv.ptr(logits),
-                                                    nv.ptr(gold), float(pad_value), nv.ptr(out)))
+        rows = (nv.ptr(b), nv.ptr(u), nv.ptr(logits), nv.ptr(gold), float(pad_value), nv.ptr(out))
+        if cut is None:
+            nv.check(self.lib.casv_debug_sched_rows(self.handle, R, V, byref(p), *rows))
+        else:
+            nv.check(self.lib.casv_debug_sched_cut_rows(self.handle, R, V, byref(p), byref(cut), *rows))
         return out
 
     def train_gradients(self):
@@ -600,37 +578,32 @@ class HipEngine(object):
         nv.check(self.lib.casv_train_end(self.handle))
 
     # -- scoring -------------------------------------------------------------------------------
+    def _score_call(self, entry, rows, U, T, head, want_align):
+        """One scoring call: `head` = the entry's arguments up to dec_out, rows = (B,) or (B, N).  Returns (logp, best, rank
+        rows + (U,), nll, count rows, align) with the alignments as want_align asks: None, dense rows + (U, T), or ('sparse') the
+        window form (lo rows + (U,), w rows + (U, K)) of casv_score_get_alignments_sparse."""
+        logp, best, rank = np.empty(rows + (U,), np.float32), np.empty(rows + (U,), np.int32), np.empty(rows + (U,), np.int32)
+        nll, count = np.empty(rows, np.float64), np.empty(rows, np.int32)
+        sparse = want_align == 'sparse'
+        align = np.empty(rows + (U, T), np.float32) if want_align and not sparse else None
+        nv.check(entry(self.handle, *head, nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count), nv.ptr(align)))
+        self._score_shape = (int(np.prod(rows)), U)          # (score_alternatives: the rows the library now holds)
+        if sparse:
+            K = 2 * self.window_width + 1
+            align = (np.empty(rows + (U,), np.int32), np.empty(rows + (U, K), np.float32))
+            nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(align[0]), nv.ptr(align[1])))
+        return logp, best, rank, nll, count, align
+
     def score_targets(self, enc_idx, enc_val, dec_in, dec_out, want_align=False):
         """Teacher-forced log-probabilities of the targets dec_out (casv_score_targets; arrays as train_step, no weights, no masks).
         Returns (logp float32 (B,U), best int32 (B,U), rank int32 (B,U), nll float64 (B), count int32 (B), align) with align = None,
         the dense rows (B,U,T) (want_align=True) or the window form (lo (B,U), w (B,U,K)) (want_align='sparse').  Inside a training
         session the session's weights score, outside one the committed weights (a forward-only state kept until score_release)."""
-        enc_idx = nv.carray(enc_idx, np.int32)
-        if enc_idx.ndim == 2:
-            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
-        B, T, A = enc_idx.shape
-        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
-        dec_in = nv.carray(dec_in, np.int32)
+        enc_idx, enc_val, dec_in, (B, T, A, U) = self._step_batch(enc_idx, enc_val, dec_in)
         dec_out = nv.carray(dec_out, np.int32)
-        U = dec_in.shape[1]
         assert dec_in.shape == dec_out.shape == (B, U)
-        logp = np.empty((B, U), np.float32)
-        best = np.empty((B, U), np.int32)
-        rank = np.empty((B, U), np.int32)
-        nll = np.empty((B,), np.float64)
-        count = np.empty((B,), np.int32)
-        sparse = want_align == 'sparse'
-        align = np.empty((B, U, T), np.float32) if want_align and not sparse else None
-        nv.check(self.lib.casv_score_targets(self.handle, B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), nv.ptr(dec_out),
-                                             nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count), nv.ptr(align)))
-        self._score_shape = (B, U)          # (score_alternatives: the rows the library now holds)
-        if sparse:
-            K = 2 * self.window_width + 1
-            lo = np.empty((B, U), np.int32)
-            w = np.empty((B, U, K), np.float32)
-            nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(lo), nv.ptr(w)))
-            align = (lo, w)
-        return logp, best, rank, nll, count, align
+        head = (B, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), nv.ptr(dec_out))
+        return self._score_call(self.lib.casv_score_targets, (B,), U, T, head, want_align)
 
     def score_candidates(self, enc_idx, enc_val, dec_in, dec_out, want_align=False):
         """N candidate targets per source on one encoder pass (casv_score_candidates): enc_idx / enc_val (B,T[,A]) as score_targets,
@@ -639,33 +612,13 @@ class HipEngine(object):
         (logp (B,N,U), best (B,N,U), rank (B,N,U), nll float64 (B,N), count (B,N), align) with align = None, the dense rows (B,N,U,T)
         (want_align=True) or the window form (lo (B,N,U), w (B,N,U,K)) (want_align='sparse'); everything else as score_targets, whose
         results are this call's at N = 1."""
-        enc_idx = nv.carray(enc_idx, np.int32)
-        if enc_idx.ndim == 2:
-            enc_idx = np.ascontiguousarray(enc_idx[:, :, None])
-        B, T, A = enc_idx.shape
-        enc_val = None if enc_val is None else nv.carray(np.asarray(enc_val, np.float32).reshape(B, T, A), np.float32)
+        enc_idx, enc_val, (B, T, A) = self._encoder_batch(enc_idx, enc_val)
         dec_in = nv.carray(dec_in, np.int32)
         dec_out = nv.carray(dec_out, np.int32)
         assert dec_in.ndim == 3 and dec_in.shape == dec_out.shape and dec_in.shape[0] == B
         N, U = dec_in.shape[1:]
-        logp = np.empty((B, N, U), np.float32)
-        best = np.empty((B, N, U), np.int32)
-        rank = np.empty((B, N, U), np.int32)
-        nll = np.empty((B, N), np.float64)
-        count = np.empty((B, N), np.int32)
-        sparse = want_align == 'sparse'
-        align = np.empty((B, N, U, T), np.float32) if want_align and not sparse else None
-        nv.check(self.lib.casv_score_candidates(self.handle, B, N, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in),
-                                                nv.ptr(dec_out), nv.ptr(logp), nv.ptr(best), nv.ptr(rank), nv.ptr(nll), nv.ptr(count),
-                                                nv.ptr(align)))
-        self._score_shape = (B * N, U)
-        if sparse:
-            K = 2 * self.window_width + 1
-            lo = np.empty((B, N, U), np.int32)
-            w = np.empty((B, N, U, K), np.float32)
-            nv.check(self.lib.casv_score_get_alignments_sparse(self.handle, K, nv.ptr(lo), nv.ptr(w)))
-            align = (lo, w)
-        return logp, best, rank, nll, count, align
+        head = (B, N, T, U, A, nv.ptr(enc_idx), nv.ptr(enc_val), nv.ptr(dec_in), nv.ptr(dec_out))
+        return self._score_call(self.lib.casv_score_candidates, (B, N), U, T, head, want_align)
 
     def score_alternatives(self, K, want_entropy=True):
         """The K likeliest characters and the entropy of every position of the LAST score_targets / score_candidates call

@@ -1,4 +1,4 @@
-"""Cases, references and bounds of sampling (csrc/sample_kernels.hip: sample_kernel; csrc/decode.hip: casv_decode_sample; csrc/score.hip:
+"""Cases, references and bounds of sampling (csrc/sample_kernels.hip: sample_kernel; csrc/decode.hip: casv_decode_sample; csrc/debug_rows.hip:
 casv_debug_sample_rows) -- helpers, no test.  Held on the CPU by tests/test_sample_cases.py, used on the device
 by tests/test_gpu_sample.py.
 

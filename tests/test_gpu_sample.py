@@ -1,4 +1,4 @@
-"""Sampling on the device (csrc/sample_kernels.hip: sample_kernel; csrc/decode.hip: casv_decode_sample; csrc/score.hip: casv_debug_sample_rows;
+"""Sampling on the device (csrc/sample_kernels.hip: sample_kernel; csrc/decode.hip: casv_decode_sample; csrc/debug_rows.hip: casv_debug_sample_rows;
 DESIGN.md section 4.8): the kernel alone against the float64 restatement and the scoring head's bits, the model against the oracle
 forced along the device's own sequence, a row's bits whatever the batch, the edges and errors, and the facade.  Cases, references and
 bounds: tests/sample_cases.py, held on the CPU by tests/test_sample_cases.py.  Runs with and without CASV_POISON=1."""
