@@ -46,6 +46,12 @@ class SampleCut(Structure):
     _fields_ = [('top_k', c_int32), ('top_p', c_float)]
 
 
+class EditCosts(Structure):
+    """casv_edit_costs: what an insertion or deletion, a substitution and a substitution within one key cost, and the cost of one
+    full edit that mode 1 divides by"""
+    _fields_ = [('gap', c_int32), ('sub', c_int32), ('near', c_int32), ('unit', c_int32)]
+
+
 class SchedParams(Structure):
     _fields_ = [('seed', c_uint64), ('step_id', c_uint64), ('ratio', c_float), ('temperature', c_float), ('pick', c_int32),
                 ('passes', c_int32)]
@@ -126,6 +132,8 @@ SIGNATURES = {
     'casv_score_release': (c_int, [c_void_p]),
     'casv_consensus': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6),
     'casv_consensus_align': (c_int, [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 5),
+    'casv_consensus_costed': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 4 + [POINTER(EditCosts)] + [c_void_p] * 3),
+    'casv_consensus_align_costed': (c_int, [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 4 + [POINTER(EditCosts)] + [c_void_p] * 2),
     'casv_consensus_vote': (c_int, [c_void_p, c_int32] + [c_void_p] * 4),
     'casv_debug_set_align_budget': (c_int, [c_void_p, c_int64]),
     'casv_train_step_soft': (c_int, _STEP + [c_int32] + [c_void_p] * 6 + [POINTER(c_double)] * 2),

@@ -257,16 +257,33 @@ void launch_spread_rows(const float* src, float* dst, int lines, int rows_per_li
 // The vote over N candidates per source (consensus_kernels.hip).  sym [B][N][L] arbitrary int32 symbols
 // compared for equality only, len [B][N] in -1 .. L (-1: a padding candidate), weight [B][N] or nullptr (all 1.0);
 // dist [B][N][N], risk [B][N], pick [B].
+// The costed calls (casv_edit_costs): key [B][N][L] beside sym -- never nullptr there: a call without keys
+// passes sym itself, under which keys are equal exactly where symbols are -- and the costs; key == nullptr takes the plain kernels,
+// which read of `costs` only the risk kernel's unit = 1.
+struct EditCosts { int gap, sub, near, unit; };
 struct ConsensusArgs {
     const int* sym; const int* len; const double* weight;
     int* dist; double* risk; int* pick;
     int B, N, L, mode;
+    const int* key; EditCosts costs;
 };
 constexpr int CONSENSUS_MAX_N = 256, CONSENSUS_MAX_L = 8192;
+constexpr int CONSENSUS_COSTED_MAX_L = 2048, EDIT_COST_MAX = 255;
+// nullptr, or what is wrong with a cost set: 1 <= gap, 0 <= near <= sub, 1 <= unit, all at most 255
+inline const char* edit_costs_refused(const EditCosts& c) {
+    if (c.gap < 1 || c.gap > EDIT_COST_MAX) return "gap outside 1..255";
+    if (c.sub < 0 || c.sub > EDIT_COST_MAX) return "sub outside 0..255";
+    if (c.near < 0 || c.near > c.sub) return "near outside 0..sub";
+    if (c.unit < 1 || c.unit > EDIT_COST_MAX) return "unit outside 1..255";
+    return nullptr;
+}
 // a wave's LDS at the longest pair: one string's symbols, and per column the other's symbol and one DP row's entry, with
 // CONSENSUS_GUARD columns in front and behind for the lanes that stand outside the matrix (consensus_pair)
 constexpr int CONSENSUS_GUARD = 64;
 inline int consensus_lds_bytes(int max_len) { return (3 * max_len + 4 * CONSENSUS_GUARD) * 4; }
+// the costed form's: per column {symbol, DP entry, key, unused} with the guards on both sides -- 34 KiB at CONSENSUS_COSTED_MAX_L
+// (the row string stays in registers)
+inline int consensus_costed_lds_bytes(int max_len) { return (max_len + 2 * CONSENSUS_GUARD) * 16; }
 // sources a launch takes side by side (the blocks of a pair loop over the rest): at most 2^20 blocks in all
 inline int consensus_grid_z(int B, int N) { return std::max(1, std::min(std::min(B, 65535), (1 << 20) / (N * N))); }
 // false: the runtime refused consensus_dist_kernel's dynamic LDS at the longest strings (nothing may be launched then)
@@ -287,6 +304,7 @@ struct AlignArgs {
     uint2* dir;
     unsigned long long* stamps;     // nullptr, or two sums over the waves of s_memtime clocks: [0] in the fill, [1] in the walk
     int B, N, L, stride, rows, wpr, b0, b1;
+    const int* key; EditCosts costs;   // as in ConsensusArgs: nullptr takes the plain kernel
 };
 // src / mass [B][C][N], best [B][C] (include/cor_asv_ann_hip.h, casv_consensus_vote)
 struct VoteArgs {

@@ -1,13 +1,15 @@
-// Host side of casv_consensus_align / casv_consensus_vote (include/cor_asv_ann_hip.h): the checks, the
+// Host side of casv_consensus_align, casv_consensus_align_costed and casv_consensus_vote (include/cor_asv_ann_hip.h): the checks, the
 // handle's buffers, the rounds of consensus_align_kernel under the direction-word budget, the layout and the vote launches of
 // consensus_kernels.hip on the handle's stream.  The pair owns the al_* buffers of the handle: no buffer of casv_consensus or of an
 // encode, decode, score or train session is read or written.
 #include "engine.h"
 #include <cmath>
 
-extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t L, const int32_t* sym, const int32_t* len,
-                                    const int32_t* pivot, int32_t* out_where, int32_t* out_ncol) {
+// Both align entry points: costs == nullptr is the plain call (key is not looked at), else the costed one
+static int align_call(casv_model* m, int32_t B, int32_t N, int32_t L, const int32_t* sym, const int32_t* key, const int32_t* len,
+                      const int32_t* pivot, const EditCosts* costs, int32_t* out_where, int32_t* out_ncol) {
     if (!m || !len || !pivot || !out_ncol || (L > 0 && (!sym || !out_where))) return fail(CASV_ERR_ARG, "null argument");
+    if (costs) if (const char* why = edit_costs_refused(*costs)) return fail(CASV_ERR_ARG, "costs {%d, %d, %d, %d}: %s", costs->gap, costs->sub, costs->near, costs->unit, why);
     if (B < 1) return fail(CASV_ERR_ARG, "B=%d: need at least one source", B);
     if (N < 1 || N > CONSENSUS_MAX_N) return fail(CASV_ERR_ARG, "N=%d out of range 1..%d", N, CONSENSUS_MAX_N);
     if (L < 0 || L > CONSENSUS_ALIGN_MAX_L) return fail(CASV_ERR_ARG, "L=%d out of range 0..%d", L, CONSENSUS_ALIGN_MAX_L);
@@ -33,6 +35,8 @@ extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t
     m->al_valid = false;                         // (from here on the buffers no longer hold the call before)
     if (int rc = m->al_sym.ensure(std::max(nsym, (size_t)1) * 4)) return rc;
     if (int rc = m->al_where.ensure(std::max(nsym, (size_t)1) * 4)) return rc;
+    const bool keyed = costs && key && nsym;
+    if (keyed) if (int rc = m->al_key.ensure(nsym * 4)) return rc;
     if (int rc = m->al_len.ensure(rows * 4)) return rc;
     if (int rc = m->al_pivot.ensure((size_t)B * 4)) return rc;
     if (int rc = m->al_ncol.ensure((size_t)B * 4)) return rc;
@@ -40,6 +44,7 @@ extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t
     if (int rc = m->al_start.ensure((size_t)B * stride * 4)) return rc;
     if (int rc = m->al_dir.ensure(source * per_round)) return rc;
     if (nsym) HIPCHK(hipMemcpyAsync(m->al_sym.p, sym, nsym * 4, hipMemcpyHostToDevice, m->stream));
+    if (keyed) HIPCHK(hipMemcpyAsync(m->al_key.p, key, nsym * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->al_len.p, len, rows * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->al_pivot.p, pivot, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemsetAsync(m->al_ins.p, 0, (size_t)B * stride * 4, m->stream));
@@ -52,6 +57,8 @@ extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t
     a.where = m->al_where.as<int>(); a.ins = m->al_ins.as<int>(); a.start = m->al_start.as<int>(); a.ncol = m->al_ncol.as<int>();
     a.dir = m->al_dir.as<uint2>(); a.stamps = m->align_stamps ? m->al_stamps.as<unsigned long long>() : nullptr;
     a.B = B; a.N = N; a.L = L; a.stride = (int)stride; a.rows = max_pivot; a.wpr = consensus_align_wpr(max_len);
+    a.key = !costs ? nullptr : keyed ? m->al_key.as<int>() : a.sym;      // (no keys: the symbols as keys -- equal only where those are)
+    a.costs = costs ? *costs : EditCosts{1, 1, 1, 1};
     hipEvent_t ev{};
     m->prof_begin(PC_CONSENSUS, 0.0, 8.0 * (double)nsym + 2.0 * (double)pair * (double)rows, ev);
     m->stat_align_rounds = 0;
@@ -74,6 +81,19 @@ extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t
     for (int b = 0; b < B; ++b) m->al_max_ncol = std::max(m->al_max_ncol, out_ncol[b]);
     m->al_valid = true;
     return CASV_OK;
+}
+
+extern "C" int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t L, const int32_t* sym, const int32_t* len,
+                                    const int32_t* pivot, int32_t* out_where, int32_t* out_ncol) {
+    return align_call(m, B, N, L, sym, nullptr, len, pivot, nullptr, out_where, out_ncol);
+}
+
+extern "C" int casv_consensus_align_costed(casv_model* m, int32_t B, int32_t N, int32_t L, const int32_t* sym, const int32_t* key,
+                                           const int32_t* len, const int32_t* pivot, const casv_edit_costs* costs, int32_t* out_where,
+                                           int32_t* out_ncol) {
+    if (!costs) return fail(CASV_ERR_ARG, "null argument");
+    const EditCosts ec{costs->gap, costs->sub, costs->near, costs->unit};
+    return align_call(m, B, N, L, sym, key, len, pivot, &ec, out_where, out_ncol);
 }
 
 extern "C" int casv_consensus_vote(casv_model* m, int32_t C, const double* weight, int32_t* out_src, double* out_mass, int32_t* out_best) {

@@ -21,12 +21,28 @@ __device__ __forceinline__ int lane_below(int v) { return __builtin_amdgcn_updat
 // ahead (what it holds depends on t and the lane alone, so the read is off the chain cur -> cur).  CONSENSUS_GUARD entries in front
 // of col[0] and behind col[lb - 1] take the reads of the lanes that stand outside the matrix; such a lane (a row beyond la, a
 // column outside 1 .. lb) throws the value away, keeps its registers and stores nothing.  Nothing beyond la / lb symbols is loaded.
-__device__ __forceinline__ int consensus_pair(const int* __restrict__ ga, int la, const int* __restrict__ gb, int lb, int* lds, int lane) {
-    int2* col = reinterpret_cast<int2*>(lds) + CONSENSUS_GUARD;
-    int* sa = lds + 2 * (lb + 2 * CONSENSUS_GUARD);
+//   The costed form (include/cor_asv_ann_hip.h, casv_edit_costs) is the same sweep with gap for the 1 of an
+// insertion or deletion and c(x, y) for the substitution.  Its column entry is {b[k], D, key of b[k], unused}: 16 bytes, still one
+// aligned LDS read per lane and step (ds_read_b128; a 12-byte entry would need two, as a b96 read wants 16-byte alignment); a's
+// symbols and keys do not pass through LDS -- a lane loads those of its own row from global memory, coalesced, once per strip.
+template <bool COSTED> struct PairForm { using Entry = int2; };
+template <> struct PairForm<true> { using Entry = int4; };
+__device__ __forceinline__ int2 pair_entry(int2*, int sym, int d, int) { return make_int2(sym, d); }
+__device__ __forceinline__ int4 pair_entry(int4*, int sym, int d, int key) { return make_int4(sym, d, key, 0); }
+// c(x, y) of the costed form: 0 for equal symbols whatever the keys, else near for equal keys, else sub
+__device__ __forceinline__ int edit_cost(int x, int kx, const int4& y, const EditCosts& ec) { return x == y.x ? 0 : (kx == y.z ? ec.near : ec.sub); }
+
+template <bool COSTED>
+__device__ __forceinline__ int consensus_pair(const int* __restrict__ ga, const int* __restrict__ gka, int la, const int* __restrict__ gb,
+                                              const int* __restrict__ gkb, int lb, int* lds, int lane, const EditCosts& ec) {
+    using Entry = typename PairForm<COSTED>::Entry;
+    Entry* col = reinterpret_cast<Entry*>(lds) + CONSENSUS_GUARD;
+    int* sa = lds + 2 * (lb + 2 * CONSENSUS_GUARD);      // (the plain form only)
+    const int gap = COSTED ? ec.gap : 1;
     wave_lds_handover();                         // (the pair before this one has read its last LDS word)
-    for (int k = lane; k < la; k += 64) sa[k] = ga[k];
-    for (int k = lane; k < lb; k += 64) col[k] = make_int2(gb[k], k + 1);
+    if constexpr (!COSTED)
+        for (int k = lane; k < la; k += 64) sa[k] = ga[k];
+    for (int k = lane; k < lb; k += 64) col[k] = pair_entry(col, gb[k], (k + 1) * gap, COSTED ? gkb[k] : 0);
     wave_lds_handover();
     const int strips = (la + 63) >> 6;
     int cur = 0;
@@ -34,20 +50,25 @@ __device__ __forceinline__ int consensus_pair(const int* __restrict__ ga, int la
         const int rows = min(64, la - s * 64);   // rows of this strip: only the last one may be short
         const int r = s * 64 + lane + 1;
         const bool row = lane < rows;
-        const int ca = row ? sa[r - 1] : 0;
-        int diag = r - 1;                        // D[r-1][0]
-        cur = r;                                 // D[r][0]
+        int ca, ka = 0;
+        if constexpr (COSTED) { ca = row ? ga[r - 1] : 0; ka = row ? gka[r - 1] : 0; }
+        else ca = row ? sa[r - 1] : 0;
+        int diag = (r - 1) * gap;                // D[r-1][0]
+        cur = r * gap;                           // D[r][0]
         const int steps = lb + rows - 1;
-        const int2* p = col - lane;              // col[t - lane] of step t = 0
-        int2 next = *p;
+        const Entry* p = col - lane;             // col[t - lane] of step t = 0
+        Entry next = *p;
         for (int t = 0; t < steps; ++t) {
             const int k = t - lane;              // column k + 1
             const bool on = row && (unsigned)k < (unsigned)lb;
-            const int2 now = next;
+            const Entry now = next;
             next = *++p;                         // (lane 0 reads col[t + 1] here; lane 63 writes col[t - 63] below)
             const int below = lane_below(cur);   // (by all lanes: a lane that is switched off is not read)
             const int up = lane == 0 ? now.y : below;
-            const int best = min(min(up, cur) + 1, diag + (ca != now.x ? 1 : 0));
+            int c;
+            if constexpr (COSTED) c = edit_cost(ca, ka, now, ec);
+            else c = ca != now.x ? 1 : 0;
+            const int best = min(min(up, cur) + gap, diag + c);
             if (on) { cur = best; diag = up; }
             if (on && lane == 63) col[k].y = best;
         }
@@ -57,8 +78,8 @@ __device__ __forceinline__ int consensus_pair(const int* __restrict__ ga, int la
 }
 
 // Grid (N, N, consensus_grid_z(B, N)), 64 threads: the block (j, i) with i <= j owns the pair of every source b = z, z + gridDim.z, ...
-__global__ __launch_bounds__(64) void consensus_dist_kernel(ConsensusArgs a) {
-    extern __shared__ __align__(16) int consensus_lds[];
+template <bool COSTED>
+__device__ __forceinline__ void consensus_dist_body(const ConsensusArgs& a, int* lds) {
     const int i = blockIdx.y, j = blockIdx.x, lane = threadIdx.x, N = a.N;
     if (i > j) return;
     for (int b = blockIdx.z; b < a.B; b += gridDim.z) {
@@ -67,13 +88,17 @@ __global__ __launch_bounds__(64) void consensus_dist_kernel(ConsensusArgs a) {
         int d;
         if (li < 0 || lj < 0) d = -1;            // a padding row or column
         else if (i == j) d = 0;
-        else if (li == 0 || lj == 0) d = max(li, lj);
+        else if (li == 0 || lj == 0) d = max(li, lj) * (COSTED ? a.costs.gap : 1);
         else {
-            const int* si = a.sym + ((long long)b * N + i) * a.L;
-            const int* sj = a.sym + ((long long)b * N + j) * a.L;
+            const long long at_i = ((long long)b * N + i) * a.L, at_j = ((long long)b * N + j) * a.L;
+            const int* si = a.sym + at_i;
+            const int* sj = a.sym + at_j;
+            const int* ki = COSTED ? a.key + at_i : nullptr;
+            const int* kj = COSTED ? a.key + at_j : nullptr;
             // (the distance is symmetric: the rows go to the string that makes fewer steps of it)
             const bool rows_i = ((li + 63) >> 6) * (lj + 63) <= ((lj + 63) >> 6) * (li + 63);
-            d = consensus_pair(rows_i ? si : sj, rows_i ? li : lj, rows_i ? sj : si, rows_i ? lj : li, consensus_lds, lane);
+            d = consensus_pair<COSTED>(rows_i ? si : sj, rows_i ? ki : kj, rows_i ? li : lj, rows_i ? sj : si, rows_i ? kj : ki, rows_i ? lj : li,
+                                       lds, lane, a.costs);
         }
         if (lane == 0) {
             int* D = a.dist + (long long)b * N * N;
@@ -83,8 +108,19 @@ __global__ __launch_bounds__(64) void consensus_dist_kernel(ConsensusArgs a) {
     }
 }
 
+__global__ __launch_bounds__(64) void consensus_dist_kernel(ConsensusArgs a) {
+    extern __shared__ __align__(16) int consensus_lds[];
+    consensus_dist_body<false>(a, consensus_lds);
+}
+
+// The costed form (casv_consensus_costed): a.key and a.costs are read, the LDS is consensus_costed_lds_bytes
+__global__ __launch_bounds__(64) void consensus_dist_costed_kernel(ConsensusArgs a) {
+    extern __shared__ __align__(16) int consensus_lds[];
+    consensus_dist_body<true>(a, consensus_lds);
+}
+
 // One workgroup of 256 threads per source (b = blockIdx.x, + gridDim.x, ...); thread c < N owns candidate c.  risk[c] = the sum
-// over the live candidates k in ascending order of w[k] * d (mode 0) or w[k] * (d / max(len[c], len[k], 1)) (mode 1),
+// over the live candidates k in ascending order of w[k] * d (mode 0) or w[k] * (d / (unit * max(len[c], len[k], 1))) (mode 1),
 // d = (double)D[c][k], one rounding per operation; then thread 0 takes the first live candidate of the smallest risk.
 __global__ __launch_bounds__(256) void consensus_risk_kernel(ConsensusArgs a) {
 #pragma clang fp contract(off)
@@ -106,7 +142,7 @@ __global__ __launch_bounds__(256) void consensus_risk_kernel(ConsensusArgs a) {
                     const int lk = s_len[k];
                     if (lk < 0) continue;
                     double d = (double)D[k * N + c];         // (= D[c][k]: the kernel above wrote both; this one is coalesced)
-                    if (a.mode == 1) d = d / (double)max(max(lc, lk), 1);
+                    if (a.mode == 1) d = d / (double)(a.costs.unit * max(max(lc, lk), 1));     // (unit = 1 in the plain call: the same double)
                     const double term = (w ? w[k] : 1.0) * d;
                     risk = risk + term;
                 }
@@ -134,39 +170,50 @@ __global__ __launch_bounds__(256) void consensus_risk_kernel(ConsensusArgs a) {
 // D[i][j] == D[i-1][j] + 1.  A lane collects the bits of its row in two registers, bit (j - 1) & 31 each, and stores them as one
 // 8-byte word {diagonal, gap} per 32 columns (and at the row's end) to dir[(i - 1) * wpr + ((j - 1) >> 5)]: every word the walk can
 // read is written, whole, by one vector store.
-__device__ __forceinline__ void consensus_align_fill(const int* __restrict__ gp, int lp, const int* __restrict__ gc, int lc, int* lds, int lane,
-                                                     uint2* dir, int wpr) {
-    int2* col = reinterpret_cast<int2*>(lds) + CONSENSUS_GUARD;
-    int* sa = lds + 2 * (lc + 2 * CONSENSUS_GUARD);
+//   The costed form as in consensus_pair: the bits are "D[i][j] == D[i-1][j-1] + c(p[i-1], c[j-1])" and "D[i][j] == D[i-1][j] + gap".
+template <bool COSTED>
+__device__ __forceinline__ void consensus_align_fill(const int* __restrict__ gp, const int* __restrict__ gkp, int lp, const int* __restrict__ gc,
+                                                     const int* __restrict__ gkc, int lc, int* lds, int lane, uint2* dir, int wpr,
+                                                     const EditCosts& ec) {
+    using Entry = typename PairForm<COSTED>::Entry;
+    Entry* col = reinterpret_cast<Entry*>(lds) + CONSENSUS_GUARD;
+    int* sa = lds + 2 * (lc + 2 * CONSENSUS_GUARD);      // (the plain form only)
+    const int gap = COSTED ? ec.gap : 1;
     wave_lds_handover();                         // (the pair before this one has read its last LDS word)
-    for (int k = lane; k < lp; k += 64) sa[k] = gp[k];
-    for (int k = lane; k < lc; k += 64) col[k] = make_int2(gc[k], k + 1);
+    if constexpr (!COSTED)
+        for (int k = lane; k < lp; k += 64) sa[k] = gp[k];
+    for (int k = lane; k < lc; k += 64) col[k] = pair_entry(col, gc[k], (k + 1) * gap, COSTED ? gkc[k] : 0);
     wave_lds_handover();
     const int strips = (lp + 63) >> 6;
     for (int s = 0; s < strips; ++s) {
         const int rows = min(64, lp - s * 64);
         const int r = s * 64 + lane + 1;
         const bool row = lane < rows;
-        const int ca = row ? sa[r - 1] : 0;
+        int ca, ka = 0;
+        if constexpr (COSTED) { ca = row ? gp[r - 1] : 0; ka = row ? gkp[r - 1] : 0; }
+        else ca = row ? sa[r - 1] : 0;
         uint2* words = dir + (size_t)(row ? r - 1 : 0) * wpr;
-        int diag = r - 1, cur = r;
+        int diag = (r - 1) * gap, cur = r * gap;
         unsigned wd = 0, wu = 0;
         const int steps = lc + rows - 1;
-        const int2* p = col - lane;
-        int2 next = *p;
+        const Entry* p = col - lane;
+        Entry next = *p;
         for (int t = 0; t < steps; ++t) {
             const int k = t - lane;              // column k + 1
             const bool on = row && (unsigned)k < (unsigned)lc;
-            const int2 now = next;
+            const Entry now = next;
             next = *++p;
             const int below = lane_below(cur);
             const int up = lane == 0 ? now.y : below;
-            const int sub = diag + (ca != now.x ? 1 : 0);
-            const int best = min(min(up, cur) + 1, sub);
+            int c;
+            if constexpr (COSTED) c = edit_cost(ca, ka, now, ec);
+            else c = ca != now.x ? 1 : 0;
+            const int sub = diag + c;
+            const int best = min(min(up, cur) + gap, sub);
             if (on) {
                 const unsigned bit = 1u << (k & 31);
                 if (best == sub) wd |= bit;
-                if (best == up + 1) wu |= bit;
+                if (best == up + gap) wu |= bit;
                 cur = best; diag = up;
                 if ((k & 31) == 31 || k == lc - 1) { words[k >> 5] = make_uint2(wd, wu); wd = 0; wu = 0; }
             }
@@ -199,8 +246,8 @@ __device__ __forceinline__ void consensus_align_walk(const uint2* dir, int wpr, 
 // Grid (N, sources side by side), 64 threads: the wave of block (c, y) owns candidate c of the sources b = b0 + y, + gridDim.y, ...
 // below b1 -- its row of `where` whole (CASV_ALIGN_NONE beyond the length, the identity for the pivot itself), and for a live
 // candidate other than the pivot the fill into the pair's own direction words, then the walk.
-__global__ __launch_bounds__(64) void consensus_align_kernel(AlignArgs a) {
-    extern __shared__ __align__(16) int consensus_lds[];
+template <bool COSTED>
+__device__ __forceinline__ void consensus_align_body(const AlignArgs& a, int* consensus_lds) {
     const int c = blockIdx.x, lane = threadIdx.x, N = a.N;
     for (int b = a.b0 + blockIdx.y; b < a.b1; b += gridDim.y) {
         const int piv = a.pivot[b];
@@ -217,7 +264,9 @@ __global__ __launch_bounds__(64) void consensus_align_kernel(AlignArgs a) {
         uint2* dir = a.dir + ((size_t)(b - a.b0) * N + c) * ((size_t)a.rows * a.wpr);
         const long long t0 = a.stamps ? clock64() : 0;
         if (lp > 0 && lc > 0) {
-            consensus_align_fill(a.sym + ((long long)b * N + piv) * a.L, lp, a.sym + ((long long)b * N + c) * a.L, lc, consensus_lds, lane, dir, a.wpr);
+            const long long at_p = ((long long)b * N + piv) * a.L, at_c = ((long long)b * N + c) * a.L;
+            consensus_align_fill<COSTED>(a.sym + at_p, COSTED ? a.key + at_p : nullptr, lp, a.sym + at_c, COSTED ? a.key + at_c : nullptr, lc,
+                                         consensus_lds, lane, dir, a.wpr, a.costs);
             __threadfence();                     // the lanes' direction words -> lane 0's reads
             __builtin_amdgcn_wave_barrier();
         }
@@ -228,6 +277,17 @@ __global__ __launch_bounds__(64) void consensus_align_kernel(AlignArgs a) {
             atomicAdd(a.stamps + 1, (unsigned long long)(clock64() - t1));
         }
     }
+}
+
+__global__ __launch_bounds__(64) void consensus_align_kernel(AlignArgs a) {
+    extern __shared__ __align__(16) int consensus_lds[];
+    consensus_align_body<false>(a, consensus_lds);
+}
+
+// The costed form (casv_consensus_align_costed): a.key and a.costs are read, the LDS is consensus_costed_lds_bytes
+__global__ __launch_bounds__(64) void consensus_align_costed_kernel(AlignArgs a) {
+    extern __shared__ __align__(16) int consensus_lds[];
+    consensus_align_body<true>(a, consensus_lds);
 }
 
 // One wave per source (b = blockIdx.x, + gridDim.x, ...): start[g] = g + ins[0] + ... + ins[g-1], the first column of slot g
@@ -347,7 +407,9 @@ bool consensus_ready() {
 }
 
 void launch_consensus_dist(const ConsensusArgs& a, int max_len, hipStream_t stream) {
-    hipLaunchKernelGGL(consensus_dist_kernel, dim3(a.N, a.N, consensus_grid_z(a.B, a.N)), dim3(64), (size_t)consensus_lds_bytes(max_len), stream, a);
+    const dim3 grid(a.N, a.N, consensus_grid_z(a.B, a.N));
+    if (a.key) hipLaunchKernelGGL(consensus_dist_costed_kernel, grid, dim3(64), (size_t)consensus_costed_lds_bytes(max_len), stream, a);
+    else hipLaunchKernelGGL(consensus_dist_kernel, grid, dim3(64), (size_t)consensus_lds_bytes(max_len), stream, a);
 }
 
 void launch_consensus_risk(const ConsensusArgs& a, hipStream_t stream) {
@@ -356,7 +418,9 @@ void launch_consensus_risk(const ConsensusArgs& a, hipStream_t stream) {
 
 // max_len: the longest live candidate of the call (at most CONSENSUS_ALIGN_MAX_L: within the LDS every kernel may have unasked)
 void launch_consensus_align(const AlignArgs& a, int max_len, hipStream_t stream) {
-    hipLaunchKernelGGL(consensus_align_kernel, dim3(a.N, std::min(a.b1 - a.b0, 65535)), dim3(64), (size_t)consensus_lds_bytes(max_len), stream, a);
+    const dim3 grid(a.N, std::min(a.b1 - a.b0, 65535));
+    if (a.key) hipLaunchKernelGGL(consensus_align_costed_kernel, grid, dim3(64), (size_t)consensus_costed_lds_bytes(max_len), stream, a);
+    else hipLaunchKernelGGL(consensus_align_kernel, grid, dim3(64), (size_t)consensus_lds_bytes(max_len), stream, a);
 }
 
 void launch_consensus_layout(const AlignArgs& a, hipStream_t stream) {

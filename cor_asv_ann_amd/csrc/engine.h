@@ -160,10 +160,10 @@ struct casv_model {
     DevBuf st_a, st_p, ctx, wq, logits, prev, pin, apos, amax1, d_step, d_line, d_nan;
     DevBuf st_q;                                          // beam search: the attention query of every expansion, [(S+1)*R][W] (decode.hip, launch_step)
     DevBuf o_idx, o_prob, o_align, st_win, sp_lo, sp_w;
-    DevBuf cs_sym, cs_len, cs_weight, cs_dist, cs_risk, cs_pick;   // casv_consensus: its own scratch, nothing of a session (consensus.hip)
+    DevBuf cs_sym, cs_key, cs_len, cs_weight, cs_dist, cs_risk, cs_pick;   // casv_consensus(_costed): its own scratch, nothing of a session (consensus.hip)
     // casv_consensus_align / casv_consensus_vote (consensus_align.hip): what the last align left on the device for the votes after
     // it -- symbols, lengths, pivots, where, the layout -- the direction words of one round, and the vote's own inputs and results
-    DevBuf al_sym, al_len, al_pivot, al_where, al_ins, al_start, al_ncol, al_dir, al_weight, al_src, al_mass, al_best;
+    DevBuf al_sym, al_key, al_len, al_pivot, al_where, al_ins, al_start, al_ncol, al_dir, al_weight, al_src, al_mass, al_best;
     int al_B = 0, al_N = 0, al_L = 0, al_stride = 0, al_max_ncol = 0; bool al_valid = false;
     size_t align_budget = 0; int stat_align_rounds = 0;   // test support (casv_debug_set_align_budget; 0: CONSENSUS_ALIGN_BUDGET); launches of the last align
     bool align_stamps = false; DevBuf al_stamps; long long stat_align_ticks[2] = {0, 0};   // option "align_stamps": the last align's clocks in fill / walk, summed over its waves

@@ -644,13 +644,25 @@ class HipEngine(object):
         """Drop the forward-only state score_targets keeps outside a training session (allowed when there is none)."""
         nv.check(self.lib.casv_score_release(self.handle))
 
-    def consensus(self, sym, length, weights=None, mode=0, want_dist=False):
+    @staticmethod
+    def _edit_costs(sym, key, costs):
+        """(key int32 like sym or None, nv.EditCosts) of a costed call: costs is an `edit_costs.EditCosts` or (gap, sub, near, unit)."""
+        if key is not None:
+            key = nv.carray(key, np.int32)
+            assert key.shape == sym.shape
+        return key, nv.EditCosts(*(costs.as_tuple() if hasattr(costs, 'as_tuple') else costs))
+
+    def consensus(self, sym, length, weights=None, mode=0, want_dist=False, key=None, costs=None):
         """The vote over N candidates per source (casv_consensus): sym (B,N,L) int32 symbols compared for equality only, length
         (B,N) in -1 .. L (-1: a padding candidate), weights (B,N) float64, not negative and finite, or None (all 1.0); mode 0 sums
         weight * distance, mode 1 weight * distance / max(the two lengths, 1).  Returns (risk float64 (B,N), pick int32 (B), dist
         int32 (B,N,N) or None): the unit-cost Levenshtein distances, each candidate's risk summed over the live candidates in
         ascending order (+inf for padding), and the live candidate of smallest risk, the lowest index among equals (-1: none).
-        Needs no weights and no encoded batch, and changes nothing another call reads."""
+        Needs no weights and no encoded batch, and changes nothing another call reads.  costs: None, or an
+        `edit_costs.EditCosts` or (gap, sub, near, unit) -- then casv_consensus_costed: the distances are those under the costs,
+        key (B,N,L) int32 or None names the characters that are near each other, mode 1 divides by unit x the longer length as
+        well, and L is at most 2048."""
+        assert costs is not None or key is None
         sym = nv.carray(sym, np.int32)
         length = nv.carray(length, np.int32)
         assert sym.ndim == 3 and length.shape == sym.shape[:2]
@@ -661,15 +673,22 @@ class HipEngine(object):
         risk = np.empty((B, N), np.float64)
         pick = np.empty((B,), np.int32)
         dist = np.empty((B, N, N), np.int32) if want_dist else None
-        nv.check(self.lib.casv_consensus(self.handle, B, N, L, int(mode), nv.ptr(sym), nv.ptr(length), nv.ptr(weights), nv.ptr(dist),
-                                         nv.ptr(risk), nv.ptr(pick)))
+        if costs is None:
+            nv.check(self.lib.casv_consensus(self.handle, B, N, L, int(mode), nv.ptr(sym), nv.ptr(length), nv.ptr(weights), nv.ptr(dist),
+                                             nv.ptr(risk), nv.ptr(pick)))
+        else:
+            key, c = self._edit_costs(sym, key, costs)
+            nv.check(self.lib.casv_consensus_costed(self.handle, B, N, L, int(mode), nv.ptr(sym), nv.ptr(key), nv.ptr(length), nv.ptr(weights),
+                                                    ctypes.byref(c), nv.ptr(dist), nv.ptr(risk), nv.ptr(pick)))
         return risk, pick, dist
 
-    def consensus_align(self, sym, length, pivot):
+    def consensus_align(self, sym, length, pivot, key=None, costs=None):
         """Every candidate of a source aligned to its pivot (casv_consensus_align): sym (B,N,L) int32 symbols, L at most 2048,
         length (B,N) in -1 .. L, pivot (B) the index of a live candidate or -1 to skip the source.  Returns (where int32 (B,N,L),
         ncol int32 (B)): per candidate symbol the pivot symbol it stands against (>= 0) or -1 - slot of its insertion, ALIGN_NONE
-        beyond a length, and the columns of the source's confusion network.  The device keeps what `consensus_vote` reads."""
+        beyond a length, and the columns of the source's confusion network.  The device keeps what `consensus_vote` reads.
+        key, costs as in `consensus` -- then casv_consensus_align_costed: the path under the costs."""
+        assert costs is not None or key is None
         sym = nv.carray(sym, np.int32)
         length = nv.carray(length, np.int32)
         pivot = nv.carray(pivot, np.int32)
@@ -677,7 +696,12 @@ class HipEngine(object):
         B, N, L = sym.shape
         where = np.empty((B, N, L), np.int32)
         ncol = np.empty((B,), np.int32)
-        nv.check(self.lib.casv_consensus_align(self.handle, B, N, L, nv.ptr(sym), nv.ptr(length), nv.ptr(pivot), nv.ptr(where), nv.ptr(ncol)))
+        if costs is None:
+            nv.check(self.lib.casv_consensus_align(self.handle, B, N, L, nv.ptr(sym), nv.ptr(length), nv.ptr(pivot), nv.ptr(where), nv.ptr(ncol)))
+        else:
+            key, c = self._edit_costs(sym, key, costs)
+            nv.check(self.lib.casv_consensus_align_costed(self.handle, B, N, L, nv.ptr(sym), nv.ptr(key), nv.ptr(length), nv.ptr(pivot),
+                                                          ctypes.byref(c), nv.ptr(where), nv.ptr(ncol)))
         self._align_shape = (B, N)
         return where, ncol
 

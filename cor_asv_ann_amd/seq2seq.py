@@ -899,7 +899,7 @@ class Sequence2Sequence(object):
             self._vote_engine = HipEngine(1, 32, 2, device=self.device)
         return self._vote_engine
 
-    def consensus_of(self, candidates, weights=None, normalise=False, distances=False):
+    def consensus_of(self, candidates, weights=None, normalise=False, distances=False, costs=None):
         """The line that a list of candidate lines agrees on: per source the candidate with the smallest expected edit distance to
         the others -- the minimum-Bayes-risk pick, the medoid under Levenshtein distance (`HipEngine.consensus`; DESIGN.md section
         4.9).  `candidates[j]` is the list of candidate strings of source j, in `score_candidates`' nesting (what `sample_lines`
@@ -913,8 +913,11 @@ class Sequence2Sequence(object):
         Needs a device but no weights: it works at any `status`.  At most 256 candidates per source and 8192 code points per
         candidate (ValueError).  The sources are taken in order into chunks as `score_candidates` takes them: a chunk grows while
         sources x the largest candidate count stays within max(`batch_size`, that count) rows, and shorter lists are filled with
-        padding candidates; a source's result does not depend on its chunk."""
-        points, rows_w = self._vote_inputs(candidates, weights, 8192)
+        padding candidates; a source's result does not depend on its chunk.  `costs` is None -- unit costs, as above -- or an
+        `edit_costs.EditCosts`: the distances are then those under its costs and keys (`HipEngine.consensus(key=, costs=)`; DESIGN.md
+        section 4.11), `normalise` divides by `costs.unit` x the longer line, and a candidate has at most 2048 code points."""
+        points, rows_w = self._vote_inputs(candidates, weights, 8192 if costs is None else 2048)
+        keys = None if costs is None else costs.keys_of(points)
         picks, risks = [None] * len(candidates), [[] for _ in candidates]
         dists = [[] for _ in candidates]
         if not any(candidates):
@@ -922,7 +925,8 @@ class Sequence2Sequence(object):
         eng = self._consensus_engine()
         for chunk, N in self._vote_chunks(candidates):
             sym, length, w = self._vote_arrays(chunk, N, points, rows_w)
-            risk, pick, dist = eng.consensus(sym, length, weights=w, mode=1 if normalise else 0, want_dist=bool(distances))
+            costed = {} if costs is None else {'key': self._vote_keys(chunk, N, keys), 'costs': costs}
+            risk, pick, dist = eng.consensus(sym, length, weights=w, mode=1 if normalise else 0, want_dist=bool(distances), **costed)
             for b, j in enumerate(chunk):
                 n = len(points[j])
                 picks[j] = int(pick[b])
@@ -989,7 +993,12 @@ class Sequence2Sequence(object):
                 w[b, :len(rows_w[j])] = rows_w[j]
         return sym, length, w
 
-    def confusion_of(self, candidates, weights=None, pivots=None, normalise=False, floor=0.0):
+    @classmethod
+    def _vote_keys(cls, chunk, N, keys):
+        """The chunk's keys (B,N,L) int32 beside `_vote_arrays`' symbols; None without keys."""
+        return None if keys is None else cls._vote_arrays(chunk, N, keys, [None] * (max(chunk) + 1))[0]
+
+    def confusion_of(self, candidates, weights=None, pivots=None, normalise=False, floor=0.0, costs=None):
         """The confusion network that a list of candidate lines votes: per source every candidate is aligned to one of them, the
         pivot, by unit-cost edit distance; the pivot's symbols and the insertions in front of, between and behind them are the
         columns, and in each column the candidates that put the same character there (or none: a gap) pool their weights
@@ -1005,8 +1014,11 @@ class Sequence2Sequence(object):
         columns -- per column the same classes before the floor as (char or '', mass, [indices of the voters]).
         A source without candidates gives '', [], None, [].  ValueError, before anything runs: what `consensus_of` refuses, a
         candidate longer than 2048, weights of a source that sum to 0, a pivot that names no candidate.  Chunks as `consensus_of`;
-        a source's result does not depend on its chunk."""
+        a source's result does not depend on its chunk.  `costs` as in `consensus_of`: the alignment, and the `consensus_of` that
+        finds the pivots, run under these costs -- two characters of one key are drawn into one column, where they still are two
+        classes."""
         points, rows_w = self._vote_inputs(candidates, weights, 2048)
+        keys = None if costs is None else costs.keys_of(points)
         n_src = len(candidates)
         if pivots is not None:
             if len(pivots) != n_src:
@@ -1026,7 +1038,7 @@ class Sequence2Sequence(object):
                 raise ValueError('the weights of source %d sum to 0' % j)
             totals.append(total)
         if pivots is None:
-            pivots = self.consensus_of(candidates, weights=weights, normalise=normalise)[0]
+            pivots = self.consensus_of(candidates, weights=weights, normalise=normalise, **({} if costs is None else {'costs': costs}))[0]
         pivots = [None if p is None else int(p) for p in pivots]
         lines, confmats, columns = [''] * n_src, [[] for _ in candidates], [[] for _ in candidates]
         if not any(candidates):
@@ -1034,7 +1046,8 @@ class Sequence2Sequence(object):
         eng = self._consensus_engine()
         for chunk, N in self._vote_chunks(candidates):
             sym, length, w = self._vote_arrays(chunk, N, points, rows_w)
-            _, ncol = eng.consensus_align(sym, length, np.array([pivots[j] for j in chunk], np.int32))
+            costed = {} if costs is None else {'key': self._vote_keys(chunk, N, keys), 'costs': costs}
+            _, ncol = eng.consensus_align(sym, length, np.array([pivots[j] for j in chunk], np.int32), **costed)
             src, mass, best = eng.consensus_vote(max(1, int(ncol.max())), weights=w)
             for b, j in enumerate(chunk):
                 n, nc = len(points[j]), int(ncol[b])
@@ -1058,12 +1071,13 @@ class Sequence2Sequence(object):
         return lines, confmats, pivots, columns
 
     def correct_candidates(self, candidates, weights=None, pivots=None, normalise=False, floor=0.0, fast=True, greedy=True,
-                           alignments=True):
+                           alignments=True, costs=None):
         """`confusion_of(candidates, weights, pivots, normalise, floor)`, then the model's correction of the voted network:
         `correct_lines(voted lines, conf=the networks, fast, greedy, alignments)` over the sources whose network has at least one
-        column.  Returns what `correct_lines` returns, one entry per source; a source without columns (no candidates, or nothing
+        column; `costs` goes to `confusion_of`.  Returns what `correct_lines` returns, one entry per source; a source without columns (no candidates, or nothing
         but empty ones) gives '', [], 0.0, [].  Characters outside the model's mapping behave as in any `conf=` input."""
-        voted, confmats, _, _ = self.confusion_of(candidates, weights=weights, pivots=pivots, normalise=normalise, floor=floor)
+        voted, confmats, _, _ = self.confusion_of(candidates, weights=weights, pivots=pivots, normalise=normalise, floor=floor,
+                                                  **({} if costs is None else {'costs': costs}))
         out = ([''] * len(voted), [[] for _ in voted], [0.0] * len(voted), [[] for _ in voted])
         live = [j for j in range(len(voted)) if confmats[j]]
         if live:
@@ -1075,13 +1089,13 @@ class Sequence2Sequence(object):
         return out
 
     def consensus_lines(self, lines, conf=None, n=16, temperature=1.0, top_k=0, top_p=1.0, seed=None, streams=None,
-                        include_greedy=True, weights='uniform', normalise=False):
+                        include_greedy=True, weights='uniform', normalise=False, costs=None):
         """Sampling as a decoder: `n` lines drawn per source by `sample_lines` (same arguments, same draws), with `include_greedy`
         the `correct_lines(fast=True)` result in front of them as candidate 0, and of these the one `consensus_of` picks -- the
         candidate closest to all the others.  `weights` is 'uniform' (every candidate counts 1) or 'importance': sampled line k
         counts w_k = e_k / (e_1 + ... + e_n) with e_k = exp(s_k - max s) and s_k the sum over its characters of log p - log q as
         `sample_lines` returns them, all in float64 on the host and summed in order; the greedy candidate counts the mean of the
-        w_k.  `normalise` as in `consensus_of`.  Returns (lines, risks, candidates, picks), one entry per source: the chosen
+        w_k.  `normalise` and `costs` as in `consensus_of`.  Returns (lines, risks, candidates, picks), one entry per source: the chosen
         line, its risk, the list of candidates that voted and the index of the chosen one.  An empty source gives '', 0.0, [],
         None.  What `sample_lines` says about seeds, streams and chunks holds here."""
         if weights not in ('uniform', 'importance'):
@@ -1106,7 +1120,8 @@ class Sequence2Sequence(object):
                     w = [sum(w) / len(w)] + w
             candidates.append(([greedy[j]] if greedy is not None else []) + list(sampled[j]))
             votes.append(w)
-        picks, risks, _ = self.consensus_of(candidates, weights=None if weights == 'uniform' else votes, normalise=normalise)
+        picks, risks, _ = self.consensus_of(candidates, weights=None if weights == 'uniform' else votes, normalise=normalise,
+                                            **({} if costs is None else {'costs': costs}))
         chosen = ['' if picks[j] is None else candidates[j][picks[j]] for j in range(len(lines))]
         return chosen, [0.0 if picks[j] is None else risks[j][picks[j]] for j in range(len(lines))], candidates, picks
 
@@ -1475,7 +1490,7 @@ class Sequence2Sequence(object):
 
     def train(self, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
               sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0,
-              risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None):
+              risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None, risk_costs=None):
         """seq2seq.py:590-649.  resume: a per-epoch checkpoint written with `checkpoint_training_state` on -- training goes on
         from the epoch after it with weights, Adam's state, random generator, validation split, EarlyStopping and history
         restored (epoch boundaries only: a run stopped inside an epoch resumes from its last checkpoint).
@@ -1507,12 +1522,18 @@ class Sequence2Sequence(object):
         `history` is then the mean expected cost; validation stays the hard loss.  The candidates' seed is drawn once from the
         model's generator, the stream ids are the lines' running numbers; the settings and the seed go into the state checkpoints
         and `resume` refuses other values; a run without `risk_samples` writes the checkpoints it always wrote.  Not together
-        with `teacher` or `sample_schedule` (ValueError, before anything runs)."""
+        with `teacher` or `sample_schedule` (ValueError, before anything runs).  risk_costs: None, or `EditCosts.historic_latin()`,
+        `EditCosts.graded()` or an `EditCosts` without a key -- a candidate's cost is then its distance to the gold line under these
+        costs over `unit` x the gold line's length, so that what `evaluate()` counts as equal costs nothing; the costs and the
+        preset's name join the recorded settings (a key that has no name cannot be recorded: ValueError), and a run without
+        them writes the checkpoints it always wrote."""
         from .training import train_files, cut_is_set
         cut = {'sample_top_k': sample_top_k, 'sample_top_p': sample_top_p} if cut_is_set(sample_top_k, sample_top_p) else {}
         if risk_samples or proposal is not None:
             cut.update(risk_samples=risk_samples, risk_alpha=risk_alpha, risk_temperature=risk_temperature, risk_top_k=risk_top_k,
                        risk_top_p=risk_top_p, proposal=proposal)
+        if risk_costs is not None:
+            cut.update(risk_costs=risk_costs)
         return train_files(self, filenames, val_filenames, resume=resume, teacher=teacher, distill_k=distill_k,
                            distill_alpha=distill_alpha, sample_schedule=sample_schedule, sample_pick=sample_pick,
                            sample_passes=sample_passes, sample_temperature=sample_temperature, **cut)

@@ -376,7 +376,7 @@ def check_risk_resume(state, filename, settings):
         raise ValueError('cannot resume from "%s": it was trained without risk_samples' % filename)
     if settings is None:
         raise ValueError('cannot resume from "%s": it was trained with risk_samples=%r' % (filename, theirs['samples']))
-    for key in ('samples', 'alpha', 'temperature', 'top_k', 'top_p', 'own_proposal'):
+    for key in ('samples', 'alpha', 'temperature', 'top_k', 'top_p', 'own_proposal', 'costs'):
         if theirs.get(key) != settings.get(key):
             raise ValueError('cannot resume from "%s": risk %s differs (file %r, now %r)' % (filename, key, theirs.get(key), settings.get(key)))
 
@@ -400,17 +400,20 @@ def risk_candidates(proposal, src, conf, tgt, settings, first_stream):
     proposal (stream ids first_stream + the source's index).  Returns (candidates, cost): the lists per source and the float32
     costs in row order g * samples + i -- the candidate's edit distance to the gold line over max(len(gold), 1), and -1 for an
     exact duplicate of an earlier candidate of the same source (not a member of its set).  The distances are one row of the
-    N x N matrix that `consensus_of` computes on the device."""
+    N x N matrix that `consensus_of` computes on the device; with settings['edit_costs'] (an `EditCosts`) it is the distance under
+    those costs over unit x max(len(gold), 1).  A duplicate is an equal string, whatever the costs."""
     n = settings['samples']
     drawn = proposal.sample_lines(src, conf, n=n - 1, temperature=settings['temperature'], top_k=settings['top_k'], seed=settings['seed'],
                                   streams=[first_stream + j for j in range(len(src))], top_p=settings['top_p'])[0]
     candidates = [[gold] + list(lines) for gold, lines in zip(tgt, drawn)]
-    dists = proposal.consensus_of(candidates, distances=True)[2]
+    costs = settings.get('edit_costs')       # (the EditCosts of a run with risk_costs; its recorded form is settings['costs'])
+    unit = 1 if costs is None else costs.unit
+    dists = proposal.consensus_of(candidates, distances=True, **({} if costs is None else {'costs': costs}))[2]
     cost = np.empty((len(src) * n,), np.float32)
     for g, cands in enumerate(candidates):
         assert len(cands) == n, 'source %d has %d candidates, not %d' % (g, len(cands), n)
         for i, line in enumerate(cands):
-            cost[g * n + i] = -1.0 if line in cands[:i] else dists[g][0][i] / max(len(cands[0]), 1)
+            cost[g * n + i] = -1.0 if line in cands[:i] else dists[g][0][i] / (unit * max(len(cands[0]), 1))
     return candidates, cost
 
 
@@ -444,14 +447,20 @@ def risk_step(engine, proposal, batch, settings, rng):
 
 def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, distill_k=8, distill_alpha=0.5,
                 sample_schedule=None, sample_pick='greedy', sample_passes=1, sample_temperature=1.0, sample_top_k=0, sample_top_p=1.0,
-                risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None):
+                risk_samples=0, risk_alpha=1.0, risk_temperature=1.0, risk_top_k=0, risk_top_p=1.0, proposal=None, risk_costs=None):
     risk = None                              # minimum-risk training: what the checkpoints record (the seed joins below)
     if risk_samples:
         check_risk(s2s, risk_samples, risk_alpha, risk_temperature, risk_top_k, risk_top_p, None, teacher, sample_schedule)
         risk = {'samples': int(risk_samples), 'alpha': float(risk_alpha), 'temperature': float(risk_temperature),
                 'top_k': int(risk_top_k), 'top_p': float(risk_top_p), 'own_proposal': proposal is None}
+        if risk_costs is not None:           # (only where set: a run without costs writes the checkpoints it always wrote)
+            if not hasattr(risk_costs, 'settings'):
+                raise ValueError('risk_costs=%r: None or an EditCosts' % (risk_costs,))
+            risk['costs'] = risk_costs.settings()
     elif proposal is not None:
         raise ValueError('proposal without risk_samples: there is nothing to propose for')
+    elif risk_costs is not None:
+        raise ValueError('risk_costs without risk_samples: there is no candidate to cost')
     sampling = None                          # scheduled sampling: what the checkpoints record (the seed joins below)
     if sample_schedule is not None:
         check_sampling(sample_schedule, sample_pick, sample_passes, sample_temperature, teacher, sample_top_k, sample_top_p)
@@ -537,7 +546,7 @@ def train_files(s2s, filenames, val_filenames=None, resume=None, teacher=None, d
                 # lines' running numbers start at epoch * 2^32, so that a resumed run draws what the uninterrupted one drew
                 if own_proposal is not None:
                     own_proposal.set_weights(engine.train_weights())
-                settings = dict(risk, model=s2s, batch_size=s2s.batch_size, stream=epoch << 32)
+                settings = dict(risk, model=s2s, batch_size=s2s.batch_size, stream=epoch << 32, edit_costs=risk_costs)
                 for batch in prefetch(line_batches(s2s, filenames, split_rand)):
                     losses = risk_step(engine, proposal, batch, settings, rng)
                     if not all(np.isfinite(losses)):

@@ -515,6 +515,37 @@ int casv_consensus_align(casv_model* m, int32_t B, int32_t N, int32_t L,
                          int32_t* out_where, int32_t* out_ncol);
 int casv_consensus_vote(casv_model* m, int32_t C, const double* weight,
                         int32_t* out_src, double* out_mass, int32_t* out_best);
+/* Weighted edit costs for the vote, the confusion network and the risk.  casv_consensus_costed and
+ * casv_consensus_align_costed are casv_consensus and casv_consensus_align with a cost set and, beside sym (B,N,L), key (B,N,L) or
+ * NULL: per symbol a second, coarser name.  Keys are arbitrary int32 values compared for equality only; a key at or beyond a
+ * candidate's length influences nothing.  For symbols x, y with keys kx, ky:
+ *   c(x, y) = 0 if x == y, whatever the keys; otherwise `near` if key is not NULL and kx == ky; otherwise `sub`;
+ *   an insertion or a deletion costs `gap`.
+ * The matrix of p against c: D[0][j] = j * gap, D[i][0] = i * gap,
+ *   D[i][j] = min(D[i-1][j] + gap, D[i][j-1] + gap, D[i-1][j-1] + c(p[i-1], c[j-1])),
+ * so an empty string against one of length n gives n * gap; the costs are symmetric, and so is D.  casv_consensus_costed's D[i][j]
+ * is that of candidates i and j (-1 for padding, D[i][i] = 0, as in casv_consensus); its risk is
+ *   mode 0: the sum of weight[k] * (double)D[i][k];
+ *   mode 1: the sum of weight[k] * ((double)D[i][k] / (double)(unit * max(len[i], len[k], 1))), the product formed in int32 and
+ *           converted once -- `unit` is the caller's statement of what one full edit costs;
+ * in casv_consensus's order and rounding, with its pick.  casv_consensus_align_costed's path follows casv_consensus_align's rule
+ * with the costs put in: the diagonal where D[i][j] == D[i-1][j-1] + c(p[i-1], c[j-1]); else up where D[i][j] == D[i-1][j] + gap;
+ * else left.  where, ins, the columns, src, mass and best keep their meaning, and a vote class is still "a gap, or equal SYMBOLS":
+ * keys never pool votes.  casv_consensus_vote is unchanged and votes on what the last align of the handle left, costed or not.
+ * Costs {1, 1, 1, 1} with key NULL give casv_consensus's and casv_consensus_align's results.
+ *   Accepted: 1 <= gap <= 255, 0 <= near <= sub <= 255, 1 <= unit <= 255 (casv_consensus_align_costed does not read unit but
+ * checks it); L at most 2048 in BOTH costed calls (a wave keeps symbol, key and DP entry of every column of the longer string in
+ * LDS, 16 bytes each).  Every refusal of the plain calls applies; NULL costs, a cost outside these ranges and L beyond 2048 are
+ * refused too: CASV_ERR_ARG before anything is enqueued, nothing written, the kept align state untouched.  Scratch (the keys in a
+ * buffer of their own beside the symbols'), stream, the rounds under the workspace budget, "may stand between any two other
+ * calls, before the weights are committed too" and the profile class "consensus" are those of the plain calls. */
+typedef struct { int32_t gap, sub, near, unit; } casv_edit_costs;
+int casv_consensus_costed(casv_model* m, int32_t B, int32_t N, int32_t L, int32_t mode,
+                          const int32_t* sym, const int32_t* key, const int32_t* len, const double* weight,
+                          const casv_edit_costs* costs, int32_t* out_dist, double* out_risk, int32_t* out_pick);
+int casv_consensus_align_costed(casv_model* m, int32_t B, int32_t N, int32_t L,
+                                const int32_t* sym, const int32_t* key, const int32_t* len, const int32_t* pivot,
+                                const casv_edit_costs* costs, int32_t* out_where, int32_t* out_ncol);
 /* Test support: the workspace budget of casv_consensus_align in bytes (0: the default), so that small calls take several rounds;
  * casv_get_stat "align_rounds" reports the rounds of the last call. */
 int casv_debug_set_align_budget(casv_model* m, int64_t bytes);
